@@ -16,8 +16,21 @@ step: weak scaling, value = world * K / max-over-ranks(time).  Inputs are reside
 Prints ONE JSON line on rank 0, with
   roofline     : the dominant kernel (by HIP-event time inside the timed region) against the
                  8 TB/s HBM peak, algorithmic bytes from SURVEY.md §8d with the measured V and I;
+  kernels      : the per-kernel table of the last (up to 3) warm-up steps, event-bracketed;
+and, with --full only (everything that runs steps or passes of its own, after the timed region):
   cpu_baseline : the CPU oracle (oracle/, "port") timed on this box's host cores for ONE training
-                 image of the same workload (rank 0, N=1 only).
+                 image of the same workload (rank 0, N=1 only), with its parity against the HIP step;
+  ops_route, sh_sharded, replicated_other_exchange, config4, config.refine_step_ms : the side lines.
+
+--dump-outputs DIR writes what the last timed step hands its caller: the loss trainer.train_step returns
+(DIR/loss.npy, float32; rank 0's share with N ranks). The inputs are seeded; two runs of one build agree
+in it to 1e-6 after 20 steps, 2e-6 after 500 and 1e-5 after 3000 (relative, SYN-B: the trajectory spreads
+slowly, see below). The parameters the steps leave behind are not written: the backward accumulates
+with float atomics in a run-dependent order, and Adam's normalised update turns the rounding of near-zero
+gradients into steps of a whole learning rate, so two runs of one build - or two builds that round one sum
+differently - end up far apart in a few per cent of them (SYN-B, 5 + 20 steps: 6 % of the opacity logits
+differ by more than 1e-4, by up to 0.18). LFS_DEBUG_FLAGS=16 (fixed-point accumulation, tools/step_bits.py)
+makes them reproducible bit for bit, at 1.85 instead of 1.24 ms per step.
 """
 from __future__ import annotations
 
@@ -174,6 +187,15 @@ def hip_reference_step(trainer, view: int, target_dev) -> dict:
     return res
 
 
+def dump_outputs(loss, out_dir: str) -> None:
+    """--dump-outputs: the loss the last timed step returned (module docstring)."""
+    import numpy as np
+    if loss is None:
+        raise SystemExit("--dump-outputs: no timed step ran (--steps 0)")
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), torch.as_tensor(loss).detach().reshape(-1).float().cpu().numpy())
+
+
 def measure(trainer, targets, args, world: int, device, profile: bool) -> dict:
     """W warm-up steps (the last up to 3 with every kernel scope timed: the per-kernel table, which names the dominant kernel), then exactly K timed steps
     bracketed by barrier + synchronize, max over ranks. Inside the timed region only the dominant kernel is bracketed with events (two hipEventRecord per
@@ -216,8 +238,9 @@ def measure(trainer, targets, args, world: int, device, profile: bool) -> dict:
         capi.profile_filter(dom)
         capi.profile_enable(True)
     t0 = time.perf_counter()
+    loss = None
     for _ in range(args.steps):
-        trainer.train_step(targets)
+        loss = trainer.train_step(targets)
     lfs_dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
@@ -230,7 +253,7 @@ def measure(trainer, targets, args, world: int, device, profile: bool) -> dict:
         capi.profile_filter(None)
     elapsed = lfs_dist.max_over_ranks(elapsed, device)
     coll = lfs_dist.stats_collect()   # this rank's collectives inside the timed steps: calls, payload bytes (device ms: from the profiled warm-up steps above)
-    return dict(elapsed=elapsed, table=table, table_steps=table_steps, kernels=kernels, dom=dom, coll=coll, coll_ms=coll_ms, seen=seen)
+    return dict(elapsed=elapsed, table=table, table_steps=table_steps, kernels=kernels, dom=dom, coll=coll, coll_ms=coll_ms, seen=seen, loss=loss)
 
 
 def main() -> None:
@@ -263,11 +286,16 @@ def main() -> None:
                                                                  "lfs_gut_train_step_ex (round 6: one launch for all three, the next view's colours from the rows in registers)")
     ap.add_argument("--pipeline", action="store_true", help="single-GPU MSE step: lfs_gut_train_step_pipelined (round 6: the SH Adam pass and the SH colours on the library's side stream, "
                                                             "under the next step's projection / tile lists / culling; measured -4.5 % at best, profiles/r06/pipeline/README.md)")
+    ap.add_argument("--full", action="store_true", help="besides the headline, everything the bench measures in runs of its own: HIP-vs-oracle parity and the CPU baselines, "
+                                                        "the drop-in route, the multi-GPU side lines, MCMC's refinement step (the --no-* options below thin it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the loss the last timed step returned as DIR/loss.npy (module docstring)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ops-route", action="store_true", help="skip the 16 extra steps of the drop-in route (the `ops_route` block of the line)")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0)
     args = ap.parse_args()
+    if not args.full:   # a plain run: the headline (its kernel table and roofline ride on the warm-up and timed steps), none of the legs with runs of their own
+        args.no_cpu_baseline = args.no_ops_route = True
 
     import lichtfeld_studio_amd as lfs
     from lichtfeld_studio_amd import capi, scenes
@@ -374,6 +402,8 @@ def main() -> None:
     profile = not args.no_profile
     m = measure(trainer, targets, args, world, device, profile)
     elapsed, table, table_steps, kernels, dom, coll, coll_ms, seen = (m[k] for k in ("elapsed", "table", "table_steps", "kernels", "dom", "coll", "coll_ms", "seen"))
+    if args.dump_outputs and rank == 0:   # before anything else can step this trainer
+        dump_outputs(m["loss"], args.dump_outputs)
 
     def side_line(name, sh_sharded, factored, sc=None, vpr=None):
         """one trial step of another layout / configuration; if the collective library refuses one of its collectives on this node the side line says so instead of
@@ -402,7 +432,7 @@ def main() -> None:
         return line
 
     sharded_line = factored_line = config4_line = None
-    multi_default = world > 1 and not args.replicated and not args.sh_sharded and not args.factored and args.rasterizer == "gut" and args.strategy == "none" and args.path == "step"
+    multi_default = args.full and world > 1 and not args.replicated and not args.sh_sharded and not args.factored and args.rasterizer == "gut" and args.strategy == "none" and args.path == "step"
     if multi_default:
         # the OTHER exchange of the replicated layout, then the SH-sharded layout
         factored_line = side_line(f"dp{world}-replicated-flat-all-reduce", False, False) if headline_factored else side_line(f"dp{world}-replicated-factored-sh", False, True)
@@ -459,7 +489,7 @@ def main() -> None:
                 pass
 
     refine_ms = None
-    if args.strategy == "mcmc" and world == 1:   # one refinement step on its own (relocation of the dead Gaussians + the step around it)
+    if args.full and args.strategy == "mcmc" and world == 1:   # one refinement step on its own (relocation of the dead Gaussians + the step around it)
         trainer.iteration = (trainer.iteration // 100 + 1) * 100 - 1
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -554,7 +584,7 @@ def main() -> None:
     out = {
         "metric": f"train-images/sec (fwd+bwd+Adam), {N / 1e6:g}M Gaussians @{scene.width}x{scene.height}",
         "value": round(images / elapsed, 3), "unit": "train-images/sec",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": bool(args.full),
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",

@@ -20,9 +20,9 @@ PORT=29731
 for N in 1 2 4 8; do
   [ $N -le $NG ] || continue
   if [ $N = 1 ]; then
-    timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_n$N.json 2> $OUT/bench_n$N.err
+    timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_n$N.json 2> $OUT/bench_n$N.err
   else
-    timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus $N --steps 20 --warmup 5 > $OUT/bench_n$N.json 2> $OUT/bench_n$N.err
+    timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $PORT bench.py --full --gpus $N --steps 20 --warmup 5 > $OUT/bench_n$N.json 2> $OUT/bench_n$N.err
   fi
   echo "bench --gpus $N rc $?" | tee -a $OUT/summary.txt
   PORT=$((PORT + 1))
