@@ -146,20 +146,14 @@ __global__ void __launch_bounds__(64) fg_blend_fwd_kernel(
     }
 }
 
-#ifndef LFS_FG_LDS_REDUCE
-#define LFS_FG_LDS_REDUCE 1   // the nine wave sums through an LDS transpose (lfs_raster_common.cuh), as the 3DGUT backward does with its sixteen. Same-box A/B x2
-                              // (profiles/r03/fastgs_blend_bwd_lds_reduce_ab.txt): fastgs_blend_bwd 0.452 - 0.457 -> 0.391 - 0.395 ms; 0 = register swaps + DPP
-#endif
 __global__ void __launch_bounds__(64) fg_blend_bwd_kernel(
     const uint32_t gw, const uint32_t gh, const uint32_t width, const uint32_t height,
     const GaussRec* __restrict__ recs, const int32_t* __restrict__ offsets, const int32_t* __restrict__ cell_count, const int2* __restrict__ cell_list,
     const float* __restrict__ alpha_map, const int32_t* __restrict__ n_contrib, const float* __restrict__ g_image, const float* __restrict__ g_alpha,
     float* __restrict__ acc) {
     const uint32_t total_tiles = gw * gh;
-#if LFS_FG_LDS_REDUCE
     __shared__ __attribute__((aligned(16))) float s_red[RED9_SCRATCH_FLOATS]; // this wavefront's transpose block (wave_sum9_atomic_lds)
     float* const red_scratch = s_red;
-#endif
     const CellCtx cc = cell_ctx(total_tiles, total_tiles, gw, TILE, WPT, 1);
     if (!cc.in_grid) return;
     const uint32_t lane = threadIdx.x & 63;
@@ -204,15 +198,8 @@ __global__ void __launch_bounds__(64) fg_blend_bwd_kernel(
         // accumulator row: {sum hx, sum hy, sum hx dx, sum hx dy | sum hy dy, dc.r, dc.g, dc.b | sum alpha dL/dalpha}
         //   dL/dmean2d = conic . (sum hx, sum hy), dL/dconic = 0.5 (sum hx dx, sum hx dy, sum hy dy)   (fastgs_prep.hip)
         float* row = acc + size_t(e.x) * ACC_STRIDE;
-#if LFS_FG_LDS_REDUCE
         const float v[9] = {hx, hy, hx * f.dx, hx * f.dy, hy * f.dy, w * gc0, w * gc1, w * gc2, aD};
         wave_sum9_atomic_lds(v, row, lane, red_scratch);
-#else
-        const float v[8] = {hx, hy, hx * f.dx, hx * f.dy, hy * f.dy, w * gc0, w * gc1, w * gc2};
-        wave_sum8_atomic(v, row, lane);
-        const float tot = wave_sum1(aD);
-        if (lane == 0) unsafeAtomicAdd(row + 8, tot);
-#endif
     };
     walk_cell_list<-1>(cl, recs, lo - 1, lo, eval, []() { return true; });
 }

@@ -48,7 +48,6 @@ LFS_DI void pack_gaussian(const CamDev& cam, const f3 mu, const float4 q, const 
 #pragma unroll
             for (int c = 0; c < 3; ++c) Mr.m[r][c] = M.m[r][0] * Ri.m[0][c] + M.m[r][1] * Ri.m[1][c] + M.m[r][2] * Ri.m[2][c];
     }
-#if LFS_REC_LOG2
     // The record in the form the per-pixel evaluation wants (lfs_raster_common.cuh, REC_SCALE): matrix (and, global shutter, g) times sqrt(0.5 log2 e), and
     // log2(opacity) - alpha = exp2(log2(opac) - |w'|^2) is then three fused multiply-adds and one v_exp_f32 (opacity 0: -inf -> alpha 0, never composited)
 #pragma unroll
@@ -57,9 +56,6 @@ LFS_DI void pack_gaussian(const CamDev& cam, const f3 mu, const float4 q, const 
         for (int c = 0; c < 3; ++c) Mr.m[r][c] *= REC_SCALE;
     if (UNIFORM_ORIGIN) g = {g.x * REC_SCALE, g.y * REC_SCALE, g.z * REC_SCALE};
     const float opac_field = __builtin_amdgcn_logf(opac);   // v_log_f32 = log2
-#else
-    const float opac_field = opac;
-#endif
 #if LFS_REC_ROT
     if (UNIFORM_ORIGIN) { // the record in the frame in which g lies on the third axis (lfs_raster_common.cuh, LFS_REC_ROT): rows of U M' (one rounding, from double), G^2, G
         RotFrame F;
@@ -72,16 +68,8 @@ LFS_DI void pack_gaussian(const CamDev& cam, const f3 mu, const float4 q, const 
         g = {G * G, 0.f, G};
     }
 #endif
-#if LFS_REC_PKQ
-    if (UNIFORM_ORIGIN) { // rows 0 and 1 of U M' interleaved by column: (q.x, q.y) is then a chain of three packed operations on aligned SGPR pairs (raster.hip, ray_eval)
-        rec.r0 = make_float4(Mr.m[0][0], Mr.m[1][0], Mr.m[0][1], Mr.m[1][1]);
-        rec.r1 = make_float4(Mr.m[0][2], Mr.m[1][2], g.x, g.y);
-    } else
-#endif
-    {
     rec.r0 = make_float4(Mr.m[0][0], Mr.m[0][1], Mr.m[0][2], g.x);
     rec.r1 = make_float4(Mr.m[1][0], Mr.m[1][1], Mr.m[1][2], g.y);
-    }
     rec.r2 = make_float4(Mr.m[2][0], Mr.m[2][1], Mr.m[2][2], g.z);
     rec.r3 = make_float4(opac_field, c0, c1, c2);
     ConicRec k = conic_never();

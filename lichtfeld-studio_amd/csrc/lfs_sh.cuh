@@ -82,8 +82,8 @@ LFS_DI void sh_basis(const int degree, const float x, const float y, const float
     }
 }
 
-// Sum over the LPG lanes of a group, result in every lane. Default: xor butterfly through ds_bpermute (LDS pipe). LFS_SH_DPP_SUM (compile-time,
-// off until it has run on a GPU - DESIGN.md §6b): the same additions as DPP operands - row_ror:8 is lane^8; after that step the values are
+// Sum over the LPG lanes of a group, result in every lane. Without the define: xor butterfly through ds_bpermute (LDS pipe; the emulator). LFS_SH_DPP_SUM
+// (compile-time, set by build.py for sh.hip and raster.hip since round 2): the same additions as DPP operands - row_ror:8 is lane^8; after that step the values are
 // symmetric under ^8, so row_ror:4 delivers the lane^4 partner (in either rotation direction); quad_perm for lane^2 and lane^1. Bit-identical
 // sums, no LDS traffic. LPG is 1, 4, 16 or 32 (lanes_for): only the lane^16 step of LPG = 32 crosses a DPP row.
 #ifdef LFS_SH_DPP_SUM

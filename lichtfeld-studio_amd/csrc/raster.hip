@@ -46,9 +46,6 @@
 #ifndef LFS_EMULATE
 #include <hip/hip_ext.h>
 #endif
-#ifndef LFS_PROF_EXT_LAUNCH
-#define LFS_PROF_EXT_LAUNCH 1   // 0: two hipEventRecord around the backward's launch (rounds 1 - 6)
-#endif
 #include "lfs_raster_common.cuh"
 #include "lfs_cull_conic.cuh"
 #include "lfs_raster_pack.cuh"
@@ -60,15 +57,6 @@
 // re-orthogonalises the foot vector against the ray direction before it is used in a gradient - K8's gradients for FLAT Gaussians (tools/aniso_probe.py).
 #ifndef LFS_BWD_REORTH
 #define LFS_BWD_REORTH 1
-#endif
-#if LFS_SEL_E64 && !LFS_REC_LOG2
-#error "LFS_SEL_E64 is written for the LFS_REC_LOG2 records"
-#endif
-#ifndef LFS_FWD_MARK
-#define LFS_FWD_MARK 0   // 1: the forward marks the cell-list entries nothing composited and the backward skips them. Measured (round 6, profiles/r06/lease18_fwd_marks_projfast_ab.txt,
-#endif                   // same box, 4 x 200 steps): raster_fwd 0.233 -> 0.256 ms, raster_bwd 0.4856 -> 0.4845 ms, 734 -> 722 img/s: off.
-#ifndef LFS_FINISH_LDS_ROWS
-#define LFS_FINISH_LDS_ROWS 1 // (round 3, same box: finish_adam 0.106 / 0.102 -> 0.102 / 0.097 ms; 0 = four 16-byte loads per lane at a 64-byte stride)
 #endif
 // Host build on the wavefront emulator (tests/emul) only: wave-evaluation counters [fwd, fwd that composited, bwd, bwd that accumulated]
 #ifdef LFS_EMULATE
@@ -142,9 +130,6 @@ __global__ void __launch_bounds__(256) raster_pack_kernel(
 // pairs in list order, stored in the cell's slice of a [cells_per_tile * n_isects] array.
 // ---------------------------------------------------------------------------
 
-#ifndef LFS_CULL_DEPTH
-#define LFS_CULL_DEPTH 1   // batches of look-ahead per thread in raster_cull_kernel; 2 and 4 measured: no gain (0.072 -> 0.073 / 0.078 ms on SYN-B) - the kernel is
-#endif                     // bound by the gather throughput (L2 / texture-address unit), not by the latency of a workgroup's dependent loads
 template <bool UNIFORM_ORIGIN>
 __global__ void __launch_bounds__(256) raster_cull_kernel(
     const uint32_t C, const uint32_t tw, const uint32_t th, const uint32_t W, const uint32_t H,
@@ -217,8 +202,10 @@ __global__ void __launch_bounds__(256) raster_cull_kernel(
         g = i < end ? ids[i] : 0;
         if (need_recs) cr = cull[g];
     };
-    // DEPTH batches are in flight per thread (id load -> dependent record gather: two memory round trips each)
-    constexpr int DEPTH = LFS_CULL_DEPTH;
+    // DEPTH batches are in flight per thread (id load -> dependent record gather: two memory round trips each). 2 and 4 measured: no gain (0.072 -> 0.073 / 0.078 ms on SYN-B) -
+    // the kernel is bound by the gather throughput (L2 / texture-address unit), not by the latency of a workgroup's dependent loads. (The loop keeps its DEPTH form: written
+    // for one batch without it, the compiler lays the kernel out differently, and this change leaves the measured code as it is.)
+    constexpr int DEPTH = 1;
     int32_t g_reg[DEPTH]; CullRec cr_reg[DEPTH];
 #pragma unroll
     for (int d = 0; d < DEPTH; ++d) {
@@ -271,24 +258,16 @@ constexpr int RAY_ROLLING = 0, RAY_GLOBAL = 1;
 // Distance of the Gaussian centre to the ray line in the Gaussian's normalised frame. With q = M d (un-normalised),
 // t = (gro . q) / |q|^2 and the foot vector w = gro - t q:  |w| equals the reference's |normalize(q) x gro|, and the
 // backward collapses to dL/dgro = -s w, dL/dq = t s w (s = vis * dL/dvis): no normalisation, no cross products.
-struct RayEval { f3 om, w, q; float t, vis, rl; }; // LFS_REC_LOG2: w = c w_true and `vis` is alpha_raw = opac * vis_true (see lfs_raster_common.cuh)
+struct RayEval { f3 om, w, q; float t, vis, rl; }; // w = c w_true and `vis` is alpha_raw = opac * vis_true (see lfs_raster_common.cuh)
 template <int MODE>
 LFS_DI void ray_eval(const GaussRec& rec, const f3& ro, const f3& d, RayEval& e) {
     e.om = {0.f, 0.f, 0.f};
 #if LFS_REC_ROT
     if (MODE == RAY_GLOBAL) { // the record lives in the frame in which g = (0, 0, G) (lfs_raster_common.cuh, LFS_REC_ROT): |w|^2 = G^2 m / l, no difference of large numbers anywhere
-#if LFS_REC_PKQ
-        v2f qxy = v2f{rec.r0.x, rec.r0.y} * v2f{d.x, d.x};
-        qxy = __builtin_elementwise_fma(v2f{rec.r0.z, rec.r0.w}, v2f{d.y, d.y}, qxy);
-        qxy = __builtin_elementwise_fma(v2f{rec.r1.x, rec.r1.y}, v2f{d.z, d.z}, qxy);
-        const f3 q{qxy.x, qxy.y, fma3(rec.r2.x, d.x, rec.r2.y, d.y, rec.r2.z, d.z)};
-        const float rec_k = rec.r1.z;
-#else
         const f3 q{fma3(rec.r0.x, d.x, rec.r0.y, d.y, rec.r0.z, d.z),
                    fma3(rec.r1.x, d.x, rec.r1.y, d.y, rec.r1.z, d.z),
                    fma3(rec.r2.x, d.x, rec.r2.y, d.y, rec.r2.z, d.z)};
         const float rec_k = rec.r0.w;
-#endif
         const float m = __builtin_fmaf(q.y, q.y, q.x * q.x);
         const float l = __builtin_fmaf(q.z, q.z, m);
         const float rl = fast_rcp(l);      // l == 0 (inactive lane: d = 0; degenerate record): inf, and m = q.z = 0 - the two products below are v_mul_legacy_f32 (0 * inf = 0): u = 0, t = 0, w = 0
@@ -315,21 +294,12 @@ LFS_DI void ray_eval(const GaussRec& rec, const f3& ro, const f3& d, RayEval& e)
                fma3(rec.r1.x, d.x, rec.r1.y, d.y, rec.r1.z, d.z),
                fma3(rec.r2.x, d.x, rec.r2.y, d.y, rec.r2.z, d.z)};
     const float l = fma3(q.x, q.x, q.y, q.y, q.z, q.z);
-#if LFS_REC_LOG2
     // l == 0 (inactive lane: d = 0; degenerate record: M = 0): q = 0 as well, so t = 0 * FLT_MAX = 0 and w = gro - one v_min instead of compare + select
     const float rl = fminf(fast_rcp(l), 3.402823466e38f);
     e.t = fma3(gro.x, q.x, gro.y, q.y, gro.z, q.z) * rl;
     e.q = q; e.rl = rl;
     e.w = {__builtin_fmaf(-e.t, q.x, gro.x), __builtin_fmaf(-e.t, q.y, gro.y), __builtin_fmaf(-e.t, q.z, gro.z)};
     e.vis = __builtin_amdgcn_exp2f(__builtin_fmaf(-e.w.z, e.w.z, __builtin_fmaf(-e.w.y, e.w.y, __builtin_fmaf(-e.w.x, e.w.x, rec.r3.x))));
-#else
-    const float rl = l > 0.f ? fast_rcp(l) : 0.f; // l == 0: no direction (inactive lane / degenerate record), w = gro
-    e.t = fma3(gro.x, q.x, gro.y, q.y, gro.z, q.z) * rl;
-    e.q = q; e.rl = rl;
-    e.w = {__builtin_fmaf(-e.t, q.x, gro.x), __builtin_fmaf(-e.t, q.y, gro.y), __builtin_fmaf(-e.t, q.z, gro.z)};
-    // exp(-0.5 |w|^2) as one exp2: -0.5 * log2(e) = -0.72134752
-    e.vis = __builtin_amdgcn_exp2f(-0.72134752044448170f * fma3(e.w.x, e.w.x, e.w.y, e.w.y, e.w.z, e.w.z));
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -354,7 +324,8 @@ __global__ void __launch_bounds__(256) raster_fwd_kernel(
     const CamDev* __restrict__ cams, const GaussRec* __restrict__ recs, const float* __restrict__ colors,
     const float* __restrict__ backgrounds, const uint8_t* __restrict__ masks,
     const int32_t* __restrict__ offsets, const int32_t* __restrict__ cell_count, const int2* __restrict__ cell_list, const int32_t n_isects,
-    float* __restrict__ render_colors, float* __restrict__ render_alphas, int32_t* __restrict__ last_ids, int32_t* __restrict__ cell_marks) {
+    float* __restrict__ render_colors, float* __restrict__ render_alphas, int32_t* __restrict__ last_ids,
+    int32_t* __restrict__ /* unused since the forward's entry marks were removed; dropping it changes the kernel's signature: left for the next change of this kernel */) {
     const uint32_t n_tiles = tw * th, total_tiles = C * n_tiles;
     const CellCtx cc = cell_ctx(n_tiles, total_tiles, tw, tile_size, blocks_per_tile, waves_per_block);
     if (!cc.in_grid) return;
@@ -387,20 +358,8 @@ __global__ void __launch_bounds__(256) raster_fwd_kernel(
     const int32_t end = (cc.tile_global == total_tiles - 1 && n_isects >= 0) ? n_isects : offsets[cc.tile_global + 1]; // n_isects < 0: offsets has T + 1 entries (guarded step)
     const int2* __restrict__ cl = cell_list + (size_t(wpt) * size_t(start) + size_t(cc.wl) * size_t(end - start));
     const int32_t cnt = cell_count[size_t(cc.tile_global) * wpt + cc.wl];
-#if LFS_FWD_MARK
-    // Round 6: an entry whose alpha stays below 1/255 on every live ray of this cell (the culling in front is conservative) cannot pass the backward's test either (a lane valid there composited here: e.y <= its last contributor and alpha >= 1/255, the same
-    // bits). The forward says so in the list itself - the sign bit of the entry's Gaussian index, one 4-byte store by one lane - and the backward skips the entry before
-    // it evaluates anything (14 % of its evaluations on the dense SYN-B window of profiles/r05/quarter_histogram.txt: 31 VALU instructions each). The record address of
-    // a marked entry is unchanged: the walker forms it as uint32(index) << 6 and the bit falls off the top. Entries the forward never reaches lie behind the last
-    // contributor, where the backward does not walk.
-    // cell_marks IS the cell list (host: the same pointer), handed over as a second __restrict__ argument: a store through cell_list itself makes the list "written in
-    // this kernel" for the compiler, and the walker's entry loads stop being scalar loads (measured: raster_fwd 0.238 -> 0.399 ms). A position is never read again
-    // once it is marked (the walker runs ahead of the evaluation), so the two views of the memory never meet.
-    int32_t* const cl_mark = cell_marks + 2 * (size_t(wpt) * size_t(start) + size_t(cc.wl) * size_t(end - start));
-    const bool marker = (threadIdx.x & 63u) == 0u;
-    int32_t pos = 0;   // (uniform) the evaluations run over positions 0, 1, 2, ... of the list
-    auto mark = [&](const int32_t p, const int32_t g) { if (marker) cl_mark[2 * p] = g | int32_t(0x80000000u); };
-#endif
+    // (Measured and removed: the forward marking the entries nothing composited, for the backward to skip - raster_fwd 0.233 -> 0.256 ms, raster_bwd 0.4856 -> 0.4845 ms,
+    // 734 -> 722 img/s: profiles/r06/lease18_fwd_marks_projfast_ab.txt.)
 
     float T = 1.f;
     float pix[CDIM];
@@ -412,43 +371,10 @@ __global__ void __launch_bounds__(256) raster_fwd_kernel(
     auto eval = [&](const GaussRec& rec, const int2 e) {
         RayEval re;
         ray_eval<MODE>(rec, ro, rd, re);
-        const float alpha = fminf(0.999f, LFS_REC_LOG2 ? re.vis : rec.r3.x * re.vis);
-#if LFS_SEL_E64
-        // lane-mask form (lfs_raster_common.cuh): the same compares and selects, no VCC / EXEC round trips. A lane that does not composite adds fma(c, 0, pix) = pix.
-        const lmask_t pass = mask_nlt_f32(alpha, thr); // live pixel and alpha >= 1/255 (a NaN alpha passes, as in the reference's `if (alpha < 1/255) continue`)
-        LFS_EMUL_COUNT(0);
-#if LFS_FWD_MARK
-        const int32_t my_pos = pos; pos += 1;
-        if (pass == 0ull) { mark(my_pos, e.x); return; }
-#else
-        if (pass == 0ull) return;
-#endif
-        LFS_EMUL_COUNT(1);
-        const float next_T = T * (1.f - alpha);
-        const lmask_t fin = pass & mask_le_f32(next_T, 1e-4f); // the terminating Gaussian is not composited
-        const lmask_t contrib = pass & ~fin;
-        const float vis = sel_mask(contrib, alpha * T, 0.f);
-        if (CDIM <= 3) {
-            pix[0] = __builtin_fmaf(rec.r3.y, vis, pix[0]);
-            if (CDIM > 1) pix[1] = __builtin_fmaf(rec.r3.z, vis, pix[1]);
-            if (CDIM > 2) pix[2] = __builtin_fmaf(rec.r3.w, vis, pix[2]);
-        } else {
-            const float* cp = colors + size_t(e.x) * CDIM;
-#pragma unroll
-            for (int k = 0; k < CDIM; ++k) pix[k] = __builtin_fmaf(cp[k], vis, pix[k]);
-        }
-        cur_idx = sel_mask_i32(contrib, e.y, cur_idx);
-        T = sel_mask(contrib, next_T, T);
-        thr = sel_mask(fin, INF, thr);
-#else
+        const float alpha = fminf(0.999f, re.vis);
         const bool pass = !(alpha < thr); // live pixel and alpha >= 1/255 (a NaN alpha passes, as in the reference's `if (alpha < 1/255) continue`)
         LFS_EMUL_COUNT(0);
-#if LFS_FWD_MARK
-        const int32_t my_pos = pos; pos += 1;
-        if (__ballot(pass) == 0ull) { mark(my_pos, e.x); return; }
-#else
         if (__ballot(pass) == 0ull) return;
-#endif
         LFS_EMUL_COUNT(1);
         const float next_T = T * (1.f - alpha);
         const bool fin = pass && next_T <= 1e-4f; // the terminating Gaussian is not composited
@@ -468,7 +394,6 @@ __global__ void __launch_bounds__(256) raster_fwd_kernel(
             T = next_T;
         }
         thr = fin ? INF : thr;
-#endif
     };
     walk_cell_list<1>(cl, recs, 0, cnt, eval, [&]() { return __ballot(thr < INF) != 0ull; });
 
@@ -489,22 +414,6 @@ __global__ void __launch_bounds__(256) raster_fwd_kernel(
 // pass over the image disappears.
 struct MseFuse { const float* render; const float* target; float scale; float* loss; unsigned long long* det64; };
 
-#ifndef LFS_RASTER_WAVE_BLOCKS
-#define LFS_RASTER_WAVE_BLOCKS 1   // fwd / bwd launched with ONE wavefront per workgroup (wave_geom below). Same-box A/B x3 (profiles/r03/raster_wave_blocks_ab.txt):
-                                   // raster_bwd 0.532 - 0.537 -> 0.514 - 0.526 ms, raster_fwd 0.241 - 0.247 -> 0.237 - 0.241 ms; 0 = the tile's four cells as one workgroup
-#endif
-#ifndef LFS_BWD_LDS_REDUCE
-#define LFS_BWD_LDS_REDUCE 1   // the 16-value wave reduction through an LDS transpose instead of register swaps (lfs_raster_common.cuh). Measured on SYN-B, same box,
-#endif                         // 3 pairs (profiles/r03/raster_bwd_lds_reduce_ab.txt): raster_bwd 0.621 - 0.624 -> 0.534 - 0.541 ms; 0 = the register transpose of rounds 1 - 2
-#ifndef LFS_BWD_ALPHA0
-#define LFS_BWD_ALPHA0 1   // (round 6) invalid lanes of a backward evaluation carry alpha = 0 instead of selects on T and fac, and the running tail - B is ONE variable: -2 VALU per evaluation
-#endif
-#if LFS_BWD_ALPHA0 && LFS_SEL_E64
-#error "LFS_BWD_ALPHA0 is written for the bool form of the conditions"
-#endif
-#ifndef LFS_BWD_PK
-#define LFS_BWD_PK 1   // the backward's gradient products and the first two levels of its 16-value reduction on register pairs (v_pk_mul_f32 / v_pk_add_f32): 47 fewer
-#endif                 // VALU instructions in the kernel (-12 per evaluation), bit-identical sums; measured 0.621 - 0.631 -> 0.611 - 0.617 ms (same box, 3 pairs)
 template <int CDIM, int MODE, bool LOSS = false, int ACC = 0>
 __global__ void __launch_bounds__(256) raster_bwd_kernel(
     const uint32_t C, const uint32_t N, const uint32_t tw, const uint32_t th, const uint32_t W, const uint32_t H,
@@ -516,22 +425,16 @@ __global__ void __launch_bounds__(256) raster_bwd_kernel(
     const float* __restrict__ v_render_colors, const float* __restrict__ v_render_alphas,
     float* __restrict__ acc, float* __restrict__ v_colors_extra, const MseFuse mse = MseFuse{}) {
     const uint32_t n_tiles = tw * th, total_tiles = C * n_tiles;
-#if LFS_BWD_LDS_REDUCE
     constexpr int RED_BLOCK = (LFS_RED_QUAD_ASM && RED_QUAD_SCRATCH_FLOATS > RED_SCRATCH_FLOATS) ? RED_QUAD_SCRATCH_FLOATS : RED_SCRATCH_FLOATS;
-    __shared__ __attribute__((aligned(16))) float s_red[(LFS_RASTER_WAVE_BLOCKS ? 1 : 4) * RED_BLOCK]; // one transpose block per wavefront (wave_sum16_atomic_lds / _quad)
+    __shared__ __attribute__((aligned(16))) float s_red[RED_BLOCK]; // the wavefront's transpose block (wave_sum16_atomic_lds / _quad; one wavefront per workgroup: wave_geom)
     float* const red_scratch = s_red + (threadIdx.x >> 6) * RED_BLOCK;
 #if LFS_RED_QUAD_ASM
     const uint32_t red_base = __builtin_amdgcn_readfirstlane(uint32_t(reinterpret_cast<uintptr_t>(red_scratch)));   // LDS byte address of the block (low half of the flat address)
-#if LFS_RED_M0_ONCE
-    asm volatile("s_mov_b32 m0, %0" ::"s"(red_base));   // the one write of M0 in this kernel (lfs_raster_common.cuh, LFS_RED_M0_ONCE)
-#endif
+    asm volatile("s_mov_b32 m0, %0" ::"s"(red_base));   // the one write of M0 in this kernel (lfs_raster_common.cuh, wave_sum16_atomic_quad)
     const float4* const red_rd = reinterpret_cast<const float4*>(red_scratch + ((threadIdx.x & 63u) >> 2) * RED_QROW + 4u * (threadIdx.x & 3u));
     constexpr bool RED_SKIP = LFS_ACC_SYM && MODE == RAY_GLOBAL && CDIM == 3;   // (slots 9 .. 11 of the LFS_ACC_SYM row are empty)
     const bool red_atomic_lane = (threadIdx.x & 3u) == 0u && !(RED_SKIP && ((threadIdx.x & 63u) >> 2) >= 9u && ((threadIdx.x & 63u) >> 2) <= 11u);
-#if LFS_RED_BUF_ATOMIC
     const RedBuf red_buf = red_buf_make(acc, uint64_t(C) * N, threadIdx.x & 63u, red_atomic_lane);   // (ACC == 0: the totals leave through a buffer atomic, lfs_raster_common.cuh)
-#endif
-#endif
 #endif
     const CellCtx cc = cell_ctx(n_tiles, total_tiles, tw, tile_size, blocks_per_tile, waves_per_block);
     if (!cc.in_grid) return;
@@ -555,7 +458,7 @@ __global__ void __launch_bounds__(256) raster_bwd_kernel(
 
     float T_final = 1.f, v_ra = 0.f;
     int32_t bin_final = -1; // Bwd.cu:183 uses 0 for inactive pixels; -1 keeps them out of entry 0 as well
-    float vc[CDIM], Bsum = 0.f;
+    float vc[CDIM];
 #pragma unroll
     for (int k = 0; k < CDIM; ++k) vc[k] = 0.f;
     if (active) {
@@ -610,9 +513,6 @@ __global__ void __launch_bounds__(256) raster_bwd_kernel(
     if (n_walk <= 0) return;
 
     auto eval = [&](const GaussRec& rec, const int2 e) {
-#if LFS_FWD_MARK
-        if (e.x < 0) return;   // (uniform) marked by the forward: no pixel of this cell composited the entry - nothing to accumulate (see raster_fwd_kernel)
-#endif
         RayEval re;
         ray_eval<MODE>(rec, ro, rd, re);
 #if LFS_BWD_REORTH
@@ -625,49 +525,23 @@ __global__ void __launch_bounds__(256) raster_bwd_kernel(
             re.w = {__builtin_fmaf(-c, re.q.x, re.w.x), __builtin_fmaf(-c, re.q.y, re.w.y), __builtin_fmaf(-c, re.q.z, re.w.z)};
         }
 #endif
-#if LFS_REC_LOG2
         const float araw = re.vis;
-#else
-        const float vis = re.vis, opac = rec.r3.x;
-        const float araw = opac * vis;
-#endif
         const float alpha = fminf(0.999f, araw);
         LFS_EMUL_COUNT(2);
-#if LFS_SEL_E64
-        const lmask_t vmask = mask_le_i32_uniform(e.y, bin_final) & mask_nlt_f32(alpha, 1.f / 255.f); // (lane-mask form: lfs_raster_common.cuh)
-        if (vmask == 0ull) return;
-#else
         const bool valid = e.y <= bin_final && !(alpha < (1.f / 255.f)); // (inactive lanes carry bin_final = -1; vis > 1 cannot happen)
         if (__ballot(valid) == 0ull) return;
-#endif
         LFS_EMUL_COUNT(3);
-#if LFS_SEL_E64
-        LFS_EMUL_LANES(vmask);
-#else
         LFS_EMUL_LANES(__ballot(valid));
-#endif
 
         // Invalid lanes are masked by zeroing three scalars (fac, v_op, and through it s): every reduced value below is
         // a product with one of them. (All factors are finite for an inactive lane: its direction is 0, so w = gro, t = 0.)
-#if LFS_BWD_ALPHA0
-        // an invalid lane takes part with alpha = 0: 1 / (1 - 0) = 1 exactly (v_rcp_f32 is exact at 1: tests/test_gpu_raster.py), so its T is multiplied by 1 and its
+        // (round 6: -2 VALU per evaluation) an invalid lane takes part with alpha = 0: 1 / (1 - 0) = 1 exactly (v_rcp_f32 is exact at 1: tests/test_gpu_raster.py), so its T is multiplied by 1 and its
         // fac is 0 * T - one select instead of the two on T and fac
         const float alpha_v = valid ? alpha : 0.f;
         const float ra = fast_rcp(1.f - alpha_v);
         const float Tn = T * ra;
         T = Tn;
         const float fac = alpha_v * Tn;
-#else
-        const float ra = fast_rcp(1.f - alpha);
-        const float Tn = T * ra;
-#if LFS_SEL_E64
-        T = sel_mask(vmask, Tn, T);
-        const float fac = sel_mask(vmask, alpha * Tn, 0.f);
-#else
-        T = valid ? Tn : T;
-        const float fac = valid ? alpha * Tn : 0.f;
-#endif
-#endif
         float v[16], v_extra = 0.f, cv;
         if (CDIM <= 3) {
             cv = rec.r3.y * vc[0];
@@ -680,13 +554,8 @@ __global__ void __launch_bounds__(256) raster_bwd_kernel(
             for (int k = 1; k < CDIM; ++k) cv = __builtin_fmaf(cp[k], vc[k], cv);
         }
         // dL/dalpha = (tail - B) / (1 - alpha) + T (c . v_c), B = sum over the entries behind of fac_j (c_j . v_c)
-#if LFS_BWD_ALPHA0
         const float v_alpha = __builtin_fmaf(ra, tail, Tn * cv);   // `tail` carries tail - B: one fma per entry instead of a subtraction and an fma
         tail = __builtin_fmaf(-fac, cv, tail);
-#else
-        const float v_alpha = __builtin_fmaf(ra, tail - Bsum, Tn * cv);
-        Bsum = __builtin_fmaf(fac, cv, Bsum);
-#endif
 #pragma unroll
         for (int k = 0; k < CDIM; ++k) {
             const float vrgb = fac * vc[k];
@@ -695,21 +564,10 @@ __global__ void __launch_bounds__(256) raster_bwd_kernel(
 #pragma unroll
         for (int k = CDIM; k < 3; ++k) v[13 + k] = 0.f;
         // through alpha = min(0.999, opac * vis): no gradient on the clamped side
-#if LFS_REC_LOG2
-#if LFS_SEL_E64
-        const float sgeo = sel_mask(vmask & mask_le_f32(araw, 0.999f), araw * v_alpha, 0.f);
-#else
         const float sgeo = (valid && araw <= 0.999f) ? araw * v_alpha : 0.f; // s = alpha_raw * dL/dalpha = opac * dL/dopacity = vis * dL/dvis
-#endif
         const float v_op = sgeo;                                            // (slot 12 holds opac * dL/dopacity: the finish kernels divide)
         v[12] = v_op;
-#else
-        const float v_op = (valid && araw <= 0.999f) ? vis * v_alpha : 0.f; // dL/dopacity
-        v[12] = v_op;
-        const float sgeo = opac * v_op;                                     // s = vis * dL/dvis
-#endif
-#if LFS_BWD_PK
-        if (CDIM == 3 && MODE == RAY_GLOBAL) { // the 18 products and the first two reduction levels on register PAIRS (v_pk_mul_f32 / v_pk_add_f32)
+        if (CDIM == 3 && MODE == RAY_GLOBAL) { // the 18 products on register PAIRS (v_pk_mul_f32): -12 VALU per evaluation, bit-identical sums; 0.621 - 0.631 -> 0.611 - 0.617 ms (same box, 3 pairs)
             v2f V[8];
 #if LFS_ACC_SYM
             // B'' = a (x) w (symmetric: six products) and a = s w - lfs_raster_common.cuh, LFS_ACC_SYM. Slots: xx, yy | xz, yz | xy, zz | ax, ay | az
@@ -750,21 +608,14 @@ __global__ void __launch_bounds__(256) raster_bwd_kernel(
 #endif
             V[6] = v2f{v_op, fac * vc[0]};
             V[7] = v2f{vc[1], vc[2]} * fac;
-#if LFS_BWD_LDS_REDUCE && LFS_RED_QUAD_ASM
-#if LFS_RED_BUF_ATOMIC
+#if LFS_RED_QUAD_ASM
             wave_sum16_atomic_quad<ACC, RED_SKIP>(V, acc + size_t(uint32_t(e.x)) * ACC_STRIDE, lane, red_base, red_rd, red_atomic_lane, ACC == 2 ? mse.det64 + size_t(e.x) * ACC_STRIDE : nullptr,
                                                   &red_buf, uint32_t(e.x) << 6);
 #else
-            wave_sum16_atomic_quad<ACC, RED_SKIP>(V, acc + size_t(uint32_t(e.x)) * ACC_STRIDE, lane, red_base, red_rd, red_atomic_lane, ACC == 2 ? mse.det64 + size_t(e.x) * ACC_STRIDE : nullptr);
-#endif
-#elif LFS_BWD_LDS_REDUCE
             wave_sum16_atomic_lds<ACC>(V, acc + size_t(e.x) * ACC_STRIDE, lane, red_scratch, ACC == 2 ? mse.det64 + size_t(e.x) * ACC_STRIDE : nullptr);
-#else
-            wave_sum16_atomic_pk<ACC>(V, acc + size_t(e.x) * ACC_STRIDE, lane, ACC == 2 ? mse.det64 + size_t(e.x) * ACC_STRIDE : nullptr);
 #endif
             return;
         }
-#endif
         const f3 a = re.w * sgeo;                                           // = -dL/dgro (the sign is undone in raster_finish_kernel)
         if (LFS_ACC_SYM && MODE == RAY_GLOBAL) { // the symmetric row (see the packed form above): B'' xx, yy, xz, yz, xy, zz | a | - - -
             v[0] = a.x * re.w.x; v[1] = a.y * re.w.y; v[2] = a.x * re.w.z; v[3] = a.y * re.w.z; v[4] = a.x * re.w.y; v[5] = a.z * re.w.z;
@@ -952,14 +803,12 @@ __global__ void __launch_bounds__(256) raster_finish_kernel(
         const size_t idx = size_t(cid) * N + gid;
         const float4* a4 = reinterpret_cast<const float4*>(acc + idx * ACC_STRIDE);
         float4 a0 = a4[0], a1 = a4[1], a2 = a4[2], a3 = a4[3];
-#if LFS_REC_LOG2
         { // the row was accumulated against the scaled record (lfs_raster_common.cuh): A' = c A, G' = c G, slot 12 = opac * dL/dopac
             a0.x *= REC_UNSCALE; a0.y *= REC_UNSCALE; a0.z *= REC_UNSCALE; a0.w *= REC_UNSCALE; a1.x *= REC_UNSCALE; a1.y *= REC_UNSCALE; a1.z *= REC_UNSCALE;
             a1.w *= REC_UNSCALE; a2.x *= REC_UNSCALE; a2.y *= REC_UNSCALE; a2.z *= REC_UNSCALE; a2.w *= REC_UNSCALE;
             const float op = opacities[idx];
             a3.x = a3.x != 0.f ? a3.x / op : 0.f;
         }
-#endif
         v_opacities[idx] = a3.x;
         float* vcol = v_colors + idx * channels;
         vcol[0] = a3.y;
@@ -995,25 +844,17 @@ struct FinishAdam { float* m[4]; float* v[4]; AdamScalars s[4]; float scale_reg,
 // `accumulate`) to g_* instead of being consumed - raster_finish_kernel + activations_bwd_kernel + the copy of dL/dmeans in one launch; dL/dcolour goes
 // to v_colors for the SH backward, which adds dL/d(dirs) onto g_means afterwards. *loss += the fused MSE (as raster_finish_kernel).
 struct FinishGrads { float* g_means; float* g_scales; float* g_quats; float* g_opac; float* v_colors; int accumulate; };
-#ifndef LFS_FINISH_ONE_TRIP
-#define LFS_FINISH_ONE_TRIP 1   // (round 6) every load of raster_finish_adam_kernel in one round trip; 0 = the round-5 form (four dependent trips), kept for the A/B
-#endif
-#if LFS_FINISH_ONE_TRIP && (!LFS_REC_LOG2 || !LFS_FINISH_LDS_ROWS)
-#error "LFS_FINISH_ONE_TRIP is written for the LFS_REC_LOG2 records and the LDS row hand-over"
-#endif
-#ifndef LFS_FINISH_BLOCK
-#define LFS_FINISH_BLOCK 256   // threads per workgroup of raster_finish_adam_kernel (A/B hook: 512 / 1024 = a larger contiguous chunk per stream and CU for the 29-stream pass)
-#endif
+constexpr int FINISH_BLOCK = 256;   // threads per workgroup of raster_finish_adam_kernel
 // the fused-loss fold reads LOSS_SLOTS = 256 partial sums with the first four wavefronts of workgroup 0 and adds wave_sum[0..3]: smaller workgroups would drop slots
-static_assert(LFS_FINISH_BLOCK >= 256 && LFS_FINISH_BLOCK % 64 == 0 && LFS_FINISH_BLOCK <= 1024, "LFS_FINISH_BLOCK: 256, 320, ..., 1024");
+static_assert(FINISH_BLOCK >= 256 && FINISH_BLOCK % 64 == 0 && FINISH_BLOCK <= 1024, "FINISH_BLOCK: 256, 320, ..., 1024");
 template <bool ADAM>
-__global__ void __launch_bounds__(LFS_FINISH_BLOCK) raster_finish_adam_kernel(
+__global__ void __launch_bounds__(FINISH_BLOCK) raster_finish_adam_kernel(
     const uint32_t N, float* __restrict__ means, float* __restrict__ raw_scales, float* __restrict__ raw_quats, float* __restrict__ raw_opacities,
     const float* __restrict__ quats, const float* __restrict__ scales, const float* __restrict__ opacities,
     const CamDev* __restrict__ cams, const float* __restrict__ acc, const float* __restrict__ v_dirs, const FinishAdam ad, const FinishGrads gr,
     const float* __restrict__ loss_slots, float* __restrict__ loss, const int32_t* __restrict__ abort_flag = nullptr) {
-#if LFS_FINISH_ONE_TRIP && !defined(LFS_EMULATE)   // (the emulator has no wave-private LDS hand-over: it runs the round-5 form below)
-    // Round 6: ONE memory round trip per wavefront. The round-5 form had four in series - abort-flag pointer -> flag -> the accumulator rows (their LDS hand-over
+#ifndef LFS_EMULATE
+    // ONE memory round trip per wavefront (round 6). The form before had four in series - abort-flag pointer -> flag -> the accumulator rows (their LDS hand-over
     // sits behind a scheduling barrier no load may cross) -> the other 21 loads (two of them issued late, behind the first arithmetic) - in a kernel whose 29 streams
     // reach 5.1 TB/s in a trivial pass (tools/hbm_stream.hip: multi_rmw_32_streams) and that ran at 3.1 - 3.7. Here every load of the pass is issued before the first
     // wait, through (SGPR base, 32-bit byte offset) addresses - three offset registers instead of a 64-bit address pair per stream - and the abort flag is looked at
@@ -1029,7 +870,9 @@ __global__ void __launch_bounds__(LFS_FINISH_BLOCK) raster_finish_adam_kernel(
     int32_t aborted = 0;
     if (ADAM && abort_flag != nullptr) aborted = *abort_flag; // (scalar load: in flight with everything else)
     // the 64 accumulator rows of a wavefront (4 KB contiguous) as four fully coalesced 1-KB loads, handed to their lanes through a wave-private LDS block below
-    __shared__ float4 s_rows[LFS_FINISH_BLOCK / 64][64 * 5];
+    // (row stride 20 floats: 16-byte aligned, conflict-free on the read side) instead of four 16-byte loads per lane at a 64-byte stride: finish_adam 0.106 / 0.102 -> 0.102 / 0.097 ms
+    // (round 3, profiles/r03/finish_lds_rows_ab.txt)
+    __shared__ float4 s_rows[FINISH_BLOCK / 64][64 * 5];
     float4* const rows = s_rows[threadIdx.x >> 6];
     const uint32_t lane = threadIdx.x & 63, g0 = (blockIdx.x * blockDim.x + threadIdx.x) - lane;
     float4 t_rows[4];
@@ -1058,7 +901,7 @@ __global__ void __launch_bounds__(LFS_FINISH_BLOCK) raster_finish_adam_kernel(
     for (int i = 0; i < 4; ++i) { const uint32_t idx = i * 64 + lane; rows[(idx >> 2) * 5 + (idx & 3)] = t_rows[i]; }
     __builtin_amdgcn_wave_barrier();
     if (loss_slots != nullptr && blockIdx.x == 0) { // *loss = the fused MSE (a store in a fixed order: the step needs no zeroed accumulator)
-        __shared__ float wave_sum[LFS_FINISH_BLOCK / 64];
+        __shared__ float wave_sum[FINISH_BLOCK / 64];
         float v = loss_v;
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
@@ -1083,10 +926,10 @@ __global__ void __launch_bounds__(LFS_FINISH_BLOCK) raster_finish_adam_kernel(
     auto st3a = [&](float* base, const float (&src)[3]) { V3f t; t.a[0] = src[0]; t.a[1] = src[1]; t.a[2] = src[2]; *reinterpret_cast<V3f*>(const_cast<char*>(at(base, o12))) = t; };
     auto ld3a = [&](const float* base, float (&dst)[3]) { ld3o(base, dst); };
     const float v_opac = a3.x != 0.f ? a3.x / o : 0.f;
-#else
+#else   // LFS_EMULATE: the emulator switches lanes only at cross-lane operations, so it has no wave-private LDS hand-over - the same pass with plain per-lane loads
     if (ADAM && abort_flag != nullptr && *abort_flag != 0) return; // (uniform) speculative step that did not fit its buffers: no update, the host runs it again
     if (loss_slots != nullptr && blockIdx.x == 0) { // *loss = the fused MSE (a store in a fixed order: the step needs no zeroed accumulator)
-        __shared__ float wave_sum[LFS_FINISH_BLOCK / 64];
+        __shared__ float wave_sum[FINISH_BLOCK / 64];
         float v = threadIdx.x < LOSS_SLOTS ? loss_slots[threadIdx.x] : 0.f;   // (LOSS_SLOTS = 256: the first four wavefronts carry the slots whatever the block size)
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
@@ -1098,40 +941,14 @@ __global__ void __launch_bounds__(LFS_FINISH_BLOCK) raster_finish_adam_kernel(
         }
     }
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-#if LFS_FINISH_LDS_ROWS && !defined(LFS_EMULATE)   // (the emulator switches lanes only at cross-lane operations: no wave-private LDS hand-over there)
-    // the 64 accumulator rows of a wavefront (4 KB contiguous) as four fully coalesced 1-KB loads, handed to their lanes through a wave-private LDS block
-    // (row stride 20 floats: 16-byte aligned, conflict-free on the read side) instead of four 16-byte loads per lane at a 64-byte stride
-    __shared__ float4 s_rows[LFS_FINISH_BLOCK / 64][64 * 5];
-    float4* const rows = s_rows[threadIdx.x >> 6];
-    {
-        const uint32_t lane = threadIdx.x & 63, g0 = gid - lane;
-        const float4* src = reinterpret_cast<const float4*>(acc + size_t(g0) * ACC_STRIDE);
-        float4 t[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { const uint32_t idx = i * 64 + lane; t[i] = (g0 + (idx >> 2) < N) ? src[idx] : make_float4(0.f, 0.f, 0.f, 0.f); }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { const uint32_t idx = i * 64 + lane; rows[(idx >> 2) * 5 + (idx & 3)] = t[i]; }
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (gid >= N) return;
-    float vm[3] = {0.f, 0.f, 0.f}, vq[4] = {0.f, 0.f, 0.f, 0.f}, vs[3] = {0.f, 0.f, 0.f};
-    const float4* a4 = rows + (threadIdx.x & 63) * 5;
-    const float4 a0 = a4[0], a1 = a4[1], a2 = a4[2], a3 = a4[3];
-#else
     if (gid >= N) return;
     float vm[3] = {0.f, 0.f, 0.f}, vq[4] = {0.f, 0.f, 0.f, 0.f}, vs[3] = {0.f, 0.f, 0.f};
     const float4* a4 = reinterpret_cast<const float4*>(acc + size_t(gid) * ACC_STRIDE);
     const float4 a0 = a4[0], a1 = a4[1], a2 = a4[2], a3 = a4[3];
-#endif
-#if LFS_REC_LOG2
     // the row was accumulated against the scaled record (lfs_raster_common.cuh): A' = c A, G' = c G, slot 12 = opac * dL/dopac (divided where `o` is loaded)
     const float A[9] = {a0.x * REC_UNSCALE, a0.y * REC_UNSCALE, a0.z * REC_UNSCALE, a0.w * REC_UNSCALE, a1.x * REC_UNSCALE, a1.y * REC_UNSCALE, a1.z * REC_UNSCALE,
                         a1.w * REC_UNSCALE, a2.x * REC_UNSCALE};
     const f3 G{-a2.y * REC_UNSCALE, -a2.z * REC_UNSCALE, -a2.w * REC_UNSCALE};
-#else
-    const float A[9] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, a2.x};
-    const f3 G{-a2.y, -a2.z, -a2.w};
-#endif
     bool any = G.x != 0.f || G.y != 0.f || G.z != 0.f;
 #pragma unroll
     for (int k = 0; k < 9; ++k) any |= A[k] != 0.f;
@@ -1148,7 +965,7 @@ __global__ void __launch_bounds__(LFS_FINISH_BLOCK) raster_finish_adam_kernel(
     const float4 q = reinterpret_cast<const float4*>(quats)[gid];
     const float4 rq = reinterpret_cast<const float4*>(raw_quats)[gid];
     const float o = opacities[gid];
-    const float v_opac = LFS_REC_LOG2 ? (a3.x != 0.f ? a3.x / o : 0.f) : a3.x;
+    const float v_opac = a3.x != 0.f ? a3.x / o : 0.f;
     float m0[3] = {0.f, 0.f, 0.f}, v0[3] = {0.f, 0.f, 0.f}, p1[3] = {0.f, 0.f, 0.f}, m1[3] = {0.f, 0.f, 0.f}, v1[3] = {0.f, 0.f, 0.f};
     float4 mq = make_float4(0.f, 0.f, 0.f, 0.f), vq4 = mq;
     float po = 0.f, mo = 0.f, vo = 0.f;
@@ -1157,7 +974,7 @@ __global__ void __launch_bounds__(LFS_FINISH_BLOCK) raster_finish_adam_kernel(
         mq = reinterpret_cast<const float4*>(ad.m[2])[gid]; vq4 = reinterpret_cast<const float4*>(ad.v[2])[gid];
         po = raw_opacities[gid]; mo = ad.m[3][gid]; vo = ad.v[3][gid];
     }
-#endif // LFS_FINISH_ONE_TRIP
+#endif // LFS_EMULATE
     { // exactly raster_finish_kernel<true> for C == 1 (selected by `any` at the end)
         const float is[3] = {1.f / sc[0], 1.f / sc[1], 1.f / sc[2]};
         finish_geometry<true>(q, is, A, G, mu, cams[0], vm, vq, vs);
@@ -1257,24 +1074,14 @@ struct GutTail {
     FinishAdam fin;
     const float* loss_slots; float* loss; const int32_t* abort_flag;
 };
-#ifndef LFS_TAIL_DEPTH
-#define LFS_TAIL_DEPTH 4   // coefficient rows (parameter + two moments) in flight per lane in phase 5
-#endif
-// Same-box A/B with the order rotated, 4 rounds of 200 steps, SYN-B (profiles/r06/lease16_count_scan_tail_ab.txt; lease 15 before it: the same ranking on another box):
+// Phase 5 of gut_tail_kernel: the coefficient rows phase 2 fetches stay in registers for it (KEEP: same lane, same rows - 3 x LPG VGPRs, 196 - 224 in all: two wavefronts
+// per SIMD, each with 16 rows x 12 B per lane in flight in phase 2), and its first TAIL_DEPTH moment rows (parameter + two moments in flight per lane) are requested in
+// front of phase 3 (EARLY). Same-box A/B with the order rotated, 4 rounds of 200 steps, SYN-B (profiles/r06/lease16_count_scan_tail_ab.txt):
 //   KEEP EARLY DEPTH   img/s (median)            KEEP EARLY DEPTH   img/s
-//    0     0     4      670.3                     1     1     4      687.3   <- default
-//    0     1     4      681.7                     1     1     8      687.9
-//    0     0     8      686.2                     1     1     4 NT   686.8
-//    0     1     8      682.7                     1     0     4      lease 15: below 0 / 0
-#ifndef LFS_TAIL_KEEP
-#define LFS_TAIL_KEEP 1    // 1: the coefficient rows phase 2 fetches stay in registers for phase 5 (same lane, same rows: 3 x LPG VGPRs; every row is then fetched in phase 2;
-#endif                     //    196 - 224 VGPRs: two wavefronts per SIMD, each with 16 rows x 12 B per lane in flight in phase 2)
-#ifndef LFS_TAIL_EARLY
-#define LFS_TAIL_EARLY 1   // 1: the first LFS_TAIL_DEPTH moment rows of phase 5 are requested in front of phase 3 (they land under the finish arithmetic)
-#endif
-#ifndef LFS_TAIL_NT
-#define LFS_TAIL_NT 0      // 1: the moments leave with non-temporal stores (nothing reads them for a whole step) - no difference measured
-#endif
+//    0     0     4      670.3                     1     1     4      687.3   <- this form
+//    0     0     8      686.2                     1     1     8      687.9
+//    0     1     4      681.7                     1     1     4      686.8   with non-temporal stores of the moments
+constexpr int TAIL_DEPTH = 4;
 template <int LPG, bool NEXT>
 __global__ void __launch_bounds__(64) gut_tail_kernel(const GutTail t, const CamDev* __restrict__ cams) {
     __shared__ float lds_b[64 * (LPG + 1)];
@@ -1345,7 +1152,7 @@ __global__ void __launch_bounds__(64) gut_tail_kernel(const GutTail t, const Cam
     __syncthreads();
     // ---- phase 2: s_k ------------------------------------------------------------------------------------------------------------------------------------
     const uint32_t lane_el = ((lane / LPG) * KK + uint32_t(k - 1)) * 3u;   // (k == 0 lanes never use it)
-    // phase 5's row addressing (the same lane meets the same rows in phase 2: LFS_TAIL_KEEP)
+    // phase 5's row addressing (the same lane meets the same rows in phase 2, whose fetches stay in registers for phase 5: PK)
     const bool row_k = uint32_t(k) < K;
     float* const pbase = (k == 0) ? t.sh0 : t.shN;
     float* const mbase = (k == 0) ? t.m0 : t.mN;
@@ -1355,59 +1162,38 @@ __global__ void __launch_bounds__(64) gut_tail_kernel(const GutTail t, const Cam
         return (k == 0) ? gg * 3 : (gg * KK + uint32_t(k - 1)) * 3;
     };
     auto row_ok = [&](const int it) { return row_k && (g0 + uint32_t(it) * GPI + lane / LPG) < N; };
-#if LFS_TAIL_KEEP
     V3f PK[LPG];
 #pragma unroll
     for (int it = 0; it < LPG; ++it) {
         PK[it].a[0] = PK[it].a[1] = PK[it].a[2] = 0.f;
         if (row_ok(it)) PK[it] = *reinterpret_cast<const V3f*>(pbase + row_el(it));
     }
-#endif
     {
 #pragma clang fp contract(off)
-#if LFS_TAIL_KEEP
 #pragma unroll
-#else
-#pragma unroll 4
-#endif
         for (int it = 0; it < LPG; ++it) {
             const uint32_t gl = it * GPI + lane / LPG;
             const float w0 = ldv[gl * 3], w1 = ldv[gl * 3 + 1], w2 = ldv[gl * 3 + 2];
             float sk = 0.f;
             // a zero gradient gives 0 x (finite) = 0 whatever the row holds: its 12 bytes are not fetched (sh_pipe_dirs_kernel, sh.hip)
             if (g0 + gl < N && k >= 1 && k < Kd && uint32_t(k) < K && (w0 != 0.f || w1 != 0.f || w2 != 0.f)) {
-#if LFS_TAIL_KEEP
                 const V3f p = PK[it];
-#else
-                const V3f p = *reinterpret_cast<const V3f*>(t.shN + size_t(g0 + uint32_t(it) * GPI) * KK * 3u + lane_el);
-#endif
                 sk = p.a[0] * w0 + p.a[1] * w1 + p.a[2] * w2;
             }
             lds_s[gl * (LPG + 1) + k] = sk;
         }
     }
-    // phase 5's moment rows: LFS_TAIL_DEPTH of them per lane in flight
-    constexpr int D = (LPG < LFS_TAIL_DEPTH) ? LPG : LFS_TAIL_DEPTH;
-#if !LFS_TAIL_KEEP
-    V3f P[D];
-#endif
+    // phase 5's moment rows: TAIL_DEPTH of them per lane in flight, requested in front of phase 3 (they land under the finish arithmetic)
+    constexpr int D = (LPG < TAIL_DEPTH) ? LPG : TAIL_DEPTH;
     V3f M[D], Q[D];
     auto load = [&](const int it, const int slot) {
-#if !LFS_TAIL_KEEP
-        P[slot].a[0] = P[slot].a[1] = P[slot].a[2] = 0.f;
-#endif
         if (row_ok(it)) {
             const size_t e = row_el(it);
-#if !LFS_TAIL_KEEP
-            P[slot] = *reinterpret_cast<const V3f*>(pbase + e);
-#endif
             M[slot] = *reinterpret_cast<const V3f*>(mbase + e); Q[slot] = *reinterpret_cast<const V3f*>(vbase + e);
         }
     };
-#if LFS_TAIL_EARLY
 #pragma unroll
     for (int it = 0; it < D; ++it) load(it, it);
-#endif
     __syncthreads();
     // ---- phase 3: dL/d(dirs), then the finish pass ------------------------------------------------------------------------------------------------------------
     float vd[3] = {0.f, 0.f, 0.f};
@@ -1501,31 +1287,15 @@ __global__ void __launch_bounds__(64) gut_tail_kernel(const GutTail t, const Cam
 #pragma clang fp contract(off)
         const AdamScalars as = (k == 0) ? t.s0 : t.sN;
         auto st_mom = [&](float* q, const V3f& x) {
-#if LFS_TAIL_NT
-            __builtin_nontemporal_store(x.a[0], q); __builtin_nontemporal_store(x.a[1], q + 1); __builtin_nontemporal_store(x.a[2], q + 2);
-#else
             *reinterpret_cast<V3f*>(q) = x;
-#endif
         };
-#if !LFS_TAIL_EARLY
 #pragma unroll
-        for (int it = 0; it < D; ++it) load(it, it);
-#endif
-#if LFS_TAIL_KEEP
-#pragma unroll
-#else
-#pragma unroll 1
-#endif
         for (int it0 = 0; it0 < LPG; it0 += D) {
 #pragma unroll
             for (int u = 0; u < D; ++u) {
                 const int it = it0 + u;
                 const uint32_t gl = it * GPI + lane / LPG;
-#if LFS_TAIL_KEEP
                 V3f p = PK[it];
-#else
-                V3f p = P[u];
-#endif
                 if (row_ok(it)) {
                     const float bk = lds_b[gl * (LPG + 1) + k];
                     const float o0 = bk * ldv[gl * 3], o1 = bk * ldv[gl * 3 + 1], o2 = bk * ldv[gl * 3 + 2];
@@ -1581,16 +1351,13 @@ static bool raster_geom(const lfs_cameras* cams, uint32_t tile_size, RasterGeom&
     return true;
 }
 // fwd / bwd never cooperate across the wavefronts of a workgroup (only the cull kernel shares its gathers through LDS): with one wavefront per workgroup a
-// finished cell frees its slot at once instead of waiting for the slowest of its tile's four
+// finished cell frees its slot at once instead of waiting for the slowest of its tile's four (profiles/r03/raster_wave_blocks_ab.txt: raster_bwd 0.532 - 0.537 -> 0.514 - 0.526 ms,
+// raster_fwd 0.241 - 0.247 -> 0.237 - 0.241 ms)
 static RasterGeom wave_geom(const lfs_cameras* cams, const RasterGeom& g) {
     RasterGeom w = g;
-#if LFS_RASTER_WAVE_BLOCKS
     w.waves_per_block = 1; w.blocks_per_tile = g.wpt; w.threads = 64;
     const uint64_t nb = uint64_t(cams->C) * g.tw * g.th * w.blocks_per_tile;
     w.grid = cell_grid_blocks(nb, w.blocks_per_tile);
-#else
-    (void)cams;
-#endif
     return w;
 }
 
@@ -1625,9 +1392,7 @@ static int raster_check(uint32_t N, uint32_t channels, const lfs_cameras* cams, 
     if (channels < 1 || channels > 4) return LFS_E_UNSUPPORTED; // Rasterization.cpp:65 asserts 3; depth modes need 1 and 4
     if (!raster_geom(cams, tile_size, g)) return LFS_E_UNSUPPORTED;
     if (uint64_t(cams->C) * N >= (1ull << 26)) return LFS_E_UNSUPPORTED; // 32-bit byte offsets of the record walker (4 GB of 64-B records)
-#if LFS_RED_BUF_ATOMIC
-    if (uint64_t(cams->C) * N >= (1ull << 25)) return LFS_E_UNSUPPORTED; // the backward's buffer atomic: accumulator rows below RED_BUF_DEAD = 2 GB (lfs_raster_common.cuh)
-#endif
+    if (uint64_t(cams->C) * N >= RED_MAX_ROWS) return LFS_E_UNSUPPORTED; // accumulator rows stay below the dead-lane offset of the backward's buffer atomic (lfs_raster_common.cuh)
     return LFS_OK;
 }
 
@@ -1689,7 +1454,7 @@ static int raster_fwd_impl(
     hipLaunchKernelGGL((raster_fwd_kernel<CD, MODE>), dim3(gw.grid), dim3(gw.threads), 0, s, C, N, g.tw, g.th,     \
                        cams->image_width, cams->image_height, tile_size, gw.blocks_per_tile, gw.waves_per_block, \
                        w.cams, w.recs, colors, backgrounds, masks, tile_offsets, w.cell_count, w.cell_list, ic.arg(), \
-                       render_colors, render_alphas, last_ids, reinterpret_cast<int32_t*>(w.cell_list))
+                       render_colors, render_alphas, last_ids, (int32_t*)nullptr)
     switch (channels * 2 + raster_mode(cams)) {
     case 2: LFS_FWD(1, 0); break; case 3: LFS_FWD(1, 1); break;
     case 4: LFS_FWD(2, 0); break; case 5: LFS_FWD(2, 1); break;
@@ -1769,10 +1534,10 @@ static int raster_bwd_impl(
     if (!prepared) raster_prepare(w, g, N, channels, means, quats, scales, colors, opacities, masks, cams, tile_size, tile_offsets, flatten_ids, ic, s);
     if (n_sized > 0) {
         // One launch (every mode but the deterministic one): timed, when asked for, through the dispatch packet's own signal (lfs_prof.h, prof_kernel_events) - no
-        // event-record packets around the dominant kernel inside bench.py's timed region. The deterministic mode's two passes + resolve keep the event scope.
+        // event-record packets around the dominant kernel inside bench.py's timed region (profiles/r06/lease33_ext_launch_timing_ab.txt). The deterministic mode's two passes + resolve keep the event scope.
         hipEvent_t pe0 = nullptr, pe1 = nullptr;
 #ifndef LFS_EMULATE
-        const bool ext_timed = !det && LFS_PROF_EXT_LAUNCH && lfs::prof_kernel_events("raster_bwd", &pe0, &pe1);
+        const bool ext_timed = !det && lfs::prof_kernel_events("raster_bwd", &pe0, &pe1);
 #else
         const bool ext_timed = false;
 #endif
@@ -1944,7 +1709,7 @@ int lfs::gut_finish_grads_impl(
     ad.scale_reg = scale_reg / (3.f * float(N)); ad.opacity_reg = opacity_reg / float(N);
     const FinishGrads gr{g_means, g_raw_scales, g_raw_quats, g_raw_opacities, v_colors, accumulate};
     lfs::ProfScope prof("finish_grads", s);
-    hipLaunchKernelGGL(raster_finish_adam_kernel<false>, dim3((N + LFS_FINISH_BLOCK - 1) / LFS_FINISH_BLOCK), dim3(LFS_FINISH_BLOCK), 0, s, N, const_cast<float*>(means), (float*)nullptr, const_cast<float*>(raw_quats),
+    hipLaunchKernelGGL(raster_finish_adam_kernel<false>, dim3((N + FINISH_BLOCK - 1) / FINISH_BLOCK), dim3(FINISH_BLOCK), 0, s, N, const_cast<float*>(means), (float*)nullptr, const_cast<float*>(raw_quats),
                        (float*)nullptr, quats, scales, opacities, w.cams, w.acc, v_dirs, ad, gr, loss ? w.acc + ACC_STRIDE * size_t(N) : nullptr, loss, (const int32_t*)nullptr);
     return (int)hipGetLastError();
 }
@@ -1977,7 +1742,7 @@ int lfs::gut_finish_adam_impl(
     // regularisers of trainer.cpp:132-158 (as lfs_activations_bwd): scale_reg * mean(scales) over 3N values, opacity_reg * mean(opacities)
     ad.scale_reg = scale_reg / (3.f * float(N)); ad.opacity_reg = opacity_reg / float(N);
     lfs::ProfScope prof("finish_adam", s);
-    hipLaunchKernelGGL(raster_finish_adam_kernel<true>, dim3((N + LFS_FINISH_BLOCK - 1) / LFS_FINISH_BLOCK), dim3(LFS_FINISH_BLOCK), 0, s, N, means, raw_scales, raw_quats, raw_opacities, quats, scales, opacities,
+    hipLaunchKernelGGL(raster_finish_adam_kernel<true>, dim3((N + FINISH_BLOCK - 1) / FINISH_BLOCK), dim3(FINISH_BLOCK), 0, s, N, means, raw_scales, raw_quats, raw_opacities, quats, scales, opacities,
                        w.cams, w.acc, v_dirs, ad, FinishGrads{}, loss ? w.acc + ACC_STRIDE * size_t(N) : nullptr, loss, abort_flag);
     return (int)hipGetLastError();
 }

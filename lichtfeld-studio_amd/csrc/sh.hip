@@ -61,15 +61,8 @@ template <bool MODEL, class T> LFS_DI T* sh_coef(T* coeffs, T* sh0, T* shN, uint
 //   3. (bwd) lane = Gaussian : dL/d(dir) = sum_k s_k grad b_k, evaluated once per Gaussian.
 // The previous layout evaluated the polynomial in every one of the LPG lanes of a Gaussian and was VALU-bound
 // (rocprof: 8.1e7 VALU instructions = 0.13 ms of the 0.20 ms backward at 1M Gaussians, K = 16).
-// LFS_SH_FWD_UNCOND (round 6): the coefficient rows are requested for EVERY Gaussian of the wavefront, together with the visibility word and the direction - one
-// memory round trip per wavefront instead of two in series (visibility -> ballot -> rows); the rows of an invisible Gaussian are read and dropped. Pays when most
-// Gaussians are visible (SYN-B: 95 %); a view that sees a small part of a scene reads (1 - visible fraction) x 180 B per Gaussian more than it needs.
-#ifndef LFS_SH_FWD_UNCOND
-#define LFS_SH_FWD_UNCOND 0
-#endif
-#ifndef LFS_SH_FWD_SPLIT
-#define LFS_SH_FWD_SPLIT 1
-#endif
+// (Tried in round 6 and removed, no A/B file kept: the coefficient rows requested for EVERY Gaussian in one round trip with the visibility word - a view that sees a small
+// part of a scene then reads (1 - visible fraction) x 180 B per Gaussian more than it needs.)
 template <int LPG, bool MODEL>
 LFS_DI void sh_fwd_block(const ShArgs& a, float* __restrict__ colors, const uint32_t g0 /* first of the workgroup's 64 Gaussians */) {
     __shared__ float lds[64 * (LPG + 1)];
@@ -92,11 +85,11 @@ LFS_DI void sh_fwd_block(const ShArgs& a, float* __restrict__ colors, const uint
     const unsigned long long vis = __ballot(on);
     constexpr int GPI = 64 / LPG; // Gaussians per iteration
     const int k = lane % LPG;
-    // Coefficient loads: masked-out Gaussians get colour 0 and their coefficients are not fetched. LFS_SH_FWD_SPLIT (round 5): the LPG row loads of a lane are issued
+    // Coefficient loads: masked-out Gaussians get colour 0 and their coefficients are not fetched. The LPG row loads (round 5) of a lane are issued
     // in TWO halves - the first before the basis polynomial is evaluated (it hides the direction's latency and the polynomial), the second once the basis sits in LDS and
     // its ~30 temporaries are dead - so that at most LPG/2 x 3 prefetch registers are live next to the polynomial: 100 -> <= 64 VGPRs = 8 instead of 5 wavefronts per SIMD
-    // (round 4 measured the streaming kernels that run 8 at 5.1 - 5.8 TB/s and this one at 3.6). 0 = all LPG loads up front (rounds 3 - 4).
-    constexpr int HALF = (LFS_SH_FWD_SPLIT && LPG >= 8) ? LPG / 2 : LPG;
+    // (round 4 measured the streaming kernels that run 8 at 5.1 - 5.8 TB/s and this one at 3.6).
+    constexpr int HALF = (LPG >= 8) ? LPG / 2 : LPG;
     float c0[LPG], c1[LPG], c2[LPG];
     // Addresses: one wave-uniform 64-bit row base per iteration (SGPRs) + ONE 32-bit per-lane element offset shared by all iterations (global_load with an SGPR base),
     // instead of a 64-bit VGPR address pair per iteration (32 VGPRs of the 98 the model form needed). The model form's k == 0 lanes take their row from sh0 - another
@@ -107,7 +100,7 @@ LFS_DI void sh_fwd_block(const ShArgs& a, float* __restrict__ colors, const uint
     auto fetch = [&](const int it) {
         const uint32_t gl = it * GPI + lane / LPG;
         c0[it] = c1[it] = c2[it] = 0.f;
-        if (k < Kd && (!MODEL || k >= 1) && (LFS_SH_FWD_UNCOND || ((vis >> gl) & 1ull))) {
+        if (k < Kd && (!MODEL || k >= 1) && ((vis >> gl) & 1ull)) {
             const float* row = walk + size_t(g0 + uint32_t(it) * GPI) * KK * 3u;   // (uniform)
             const V3f t3 = *reinterpret_cast<const V3f*>(row + lane_el);   // ONE 12-byte load (global_load_dwordx3): written element by element the compiler emits three
             c0[it] = t3.a[0]; c1[it] = t3.a[1]; c2[it] = t3.a[2];          // dword loads at a 12-byte lane stride - 48 instead of 16 trips through the address unit per wavefront
@@ -141,7 +134,6 @@ LFS_DI void sh_fwd_block(const ShArgs& a, float* __restrict__ colors, const uint
         float r0 = bk * c0[it], r1 = bk * c1[it], r2 = bk * c2[it];
         r0 = group_sum<LPG>(r0); r1 = group_sum<LPG>(r1); r2 = group_sum<LPG>(r2);
         if (k == 0 && g < a.n) {
-            if (LFS_SH_FWD_UNCOND && !((vis >> gl) & 1ull)) { r0 = 0.f; r1 = 0.f; r2 = 0.f; } // (0 x an un-masked non-finite coefficient would be NaN)
             if (MODEL) { r0 = fmaxf(r0 + 0.5f, 0.f); r1 = fmaxf(r1 + 0.5f, 0.f); r2 = fmaxf(r2 + 0.5f, 0.f); }
             const size_t cs = (MODEL && a.cs) ? a.cs : 3;
             colors[cs * g] = r0; colors[cs * g + 1] = r1; colors[cs * g + 2] = r2;
@@ -382,17 +374,9 @@ __global__ void __launch_bounds__(64) sh_pipe_dirs_kernel(const ShArgs a, const 
 // lane = (Gaussian, basis) phase walks ONE tensor triple: wave-uniform row bases in SGPRs + one 32-bit per-lane offset. 57 VGPRs: two of these wavefronts per SIMD leave
 // the main stream's kernels three quarters of the register file (the first form, double-buffered batches behind 64-bit per-lane addresses, took 131 each, and the
 // projection kernel - 94 VGPRs - ran at 2 instead of 5 wavefronts per SIMD beside it: 150 instead of 56 us, profiles/r06/pipeline/lease11_timelines.txt).
-#ifndef LFS_SH_PIPE_DEPTH
-#define LFS_SH_PIPE_DEPTH 4
-#endif
-constexpr int SH_PIPE_DEPTH = LFS_SH_PIPE_DEPTH;
-#if defined(LFS_PIPE_ADAM_WAVES) && !defined(LFS_EMULATE)
-#define LFS_PIPE_ADAM_ATTR __attribute__((amdgpu_waves_per_eu(LFS_PIPE_ADAM_WAVES)))   // (A/B hook: a register budget for the kernel - 8 = 64 VGPRs, with spills)
-#else
-#define LFS_PIPE_ADAM_ATTR
-#endif
+constexpr int SH_PIPE_DEPTH = 4;
 template <int LPG>
-__global__ void __launch_bounds__(64) LFS_PIPE_ADAM_ATTR sh_pipe_adam_kernel(const uint32_t n, const uint32_t K, const int degree, float* __restrict__ sh0, float* __restrict__ shN,
+__global__ void __launch_bounds__(64) sh_pipe_adam_kernel(const uint32_t n, const uint32_t K, const int degree, float* __restrict__ sh0, float* __restrict__ shN,
                                                           const float4* __restrict__ handover, const ShAdam adam, const int32_t* __restrict__ abort_snapshot) {
     __shared__ float lds[64 * (LPG + 1)];
     __shared__ float ldv[64 * 3];

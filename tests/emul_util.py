@@ -62,9 +62,6 @@ def build() -> str:
         return out
     os.makedirs(work, exist_ok=True)
     common = [CLANG, "-x", "c++", "-std=c++17", "-O1", "-DLFS_EMULATE", "-fPIC", "-I" + os.path.join(HERE, "emul"), "-I" + CSRC, "-Wno-unused-value", "-Wno-unknown-attributes"]
-    # the gfx950 build's default LFS_RED_BUF_ATOMIC = 1 (lfs_raster_common.cuh sets it inside the inline-asm reduction block, which LFS_EMULATE compiles out): the
-    # kernels here still take the compiler-generated reduction, the switch only reaches raster_check - the emulated entry points refuse the sizes the shipped ones refuse
-    common += ["-DLFS_RED_BUF_ATOMIC=1"]
     common += extra_defines
     if sanitize:
         common[1:1] = ["-fsanitize=address", "-shared-libasan", "-fno-omit-frame-pointer", "-g"]

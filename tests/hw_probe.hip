@@ -1,6 +1,6 @@
 // Test infrastructure (tests/test_gpu_raster.py compiles and runs it on the GPU box): two properties of gfx950 instructions that the rasterizer's backward relies on
 // since round 6 and that no product-level test can see directly.
-//   1. v_rcp_f32(1.0) == 1.0 exactly: an invalid lane of a backward evaluation carries alpha = 0 and multiplies its transmittance by 1 / (1 - 0) (LFS_BWD_ALPHA0).
+//   1. v_rcp_f32(1.0) == 1.0 exactly: an invalid lane of a backward evaluation carries alpha = 0 and multiplies its transmittance by 1 / (1 - 0) (raster_bwd_kernel).
 //      One ulp off would drift T by 6e-8 per evaluation - invisible to every parity bar, wrong all the same.
 //   2. v_mul_legacy_f32: 0 * inf = 0, 0 * NaN = 0 (mul_zero, lfs_raster_common.cuh: the reciprocal of a zero length meets a zero numerator without a clamp).
 #include <hip/hip_runtime.h>

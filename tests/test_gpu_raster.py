@@ -173,7 +173,7 @@ def test_raster_unsupported_channels_raises(lfs):
 
 def test_raster_refuses_more_rows_than_the_backward_can_address(lfs):
     """cameras x Gaussians >= 2^25: the backward's buffer atomic addresses 2 GB of accumulator rows and relies on 0x80000000 being out of range (lfs_raster_common.cuh,
-    LFS_RED_BUF_ATOMIC) - the entry points refuse such a call up front (raster_check: LFS_E_UNSUPPORTED -> RuntimeError) instead of running it; one row fewer is accepted."""
+    RED_BUF_DEAD / RED_MAX_ROWS) - the entry points refuse such a call up front (raster_check: LFS_E_UNSUPPORTED -> RuntimeError) instead of running it; one row fewer is accepted."""
     from lichtfeld_studio_amd import ops
     dev = "cuda:0"
     z = lambda *s: torch.zeros(*s, device=dev)
@@ -376,7 +376,7 @@ def test_deterministic_backward_mode_is_bit_reproducible(lfs, oracle_mod):
 
 def test_instruction_properties_the_backward_relies_on(tmp_path):
     """tests/hw_probe.hip, compiled and run here: v_rcp_f32 is exact at 1.0 (and on every power of two), v_mul_legacy_f32 gives 0 * inf = 0 * NaN = 0 - what
-    LFS_BWD_ALPHA0 and mul_zero (raster.hip / lfs_raster_common.cuh, round 6) assume and what no parity bar would notice."""
+    the alpha = 0 lanes of raster_bwd_kernel and mul_zero (raster.hip / lfs_raster_common.cuh, round 6) assume and what no parity bar would notice."""
     import json
     import shutil
     import subprocess

@@ -59,7 +59,7 @@ def test_streaming_kernels_register_budgets(table):
 
 
 def test_backward_rasterizer_writes_m0_exactly_once():
-    """LFS_RED_M0_ONCE (lfs_raster_common.cuh): the add-TID stores of the LDS reduction take their base from M0, which raster_bwd_kernel's prologue sets once. The
+    """wave_sum16_atomic_quad (lfs_raster_common.cuh): the add-TID stores of the LDS reduction take their base from M0, which raster_bwd_kernel's prologue sets once. The
     compiler is not told that the inline asm reads M0, so the statement "nothing else in the kernel touches it" is held here, against the disassembly of every
     shipped instantiation: one instruction mentions m0 (the prologue's s_mov_b32), and none of the forms that use it implicitly (LDS-direct loads, s_movrel /
     v_movrel, s_sendmsg with a payload, GDS) occurs."""
