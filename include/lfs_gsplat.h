@@ -440,6 +440,31 @@ LFS_API int lfs_gut_step_wait(const int64_t* host_counts, int64_t stamp, double 
  *      has written means / sh0 / shN since - the SH colour kernel is then not launched. Same results as lfs_gut_train_step. */
 LFS_API int lfs_gut_train_step_ex(const lfs_gut_step_args* args, const float* next_viewmat, int colors_ready, int64_t capacity, int64_t assumed_longest, void* workspace,
                                   size_t workspace_bytes, int64_t* host_counts, int64_t stamp, lfs_stream_t stream);
+/*   lfs_gut_train_step_opt: lfs_gut_train_step_ex for the configuration the reference trains - the photometric loss, the MCMC strategy's noise, shN frozen for the first
+ *      1000 iterations - as one enqueue without a host read or a gradient tensor. opts == NULL or an all-zero struct: lfs_gut_train_step_ex itself, bit for bit.
+ *      loss_kind 1 enqueues: the forward | memset(*loss) | the two photometric kernels on the workspace's render into loss_workspace (lfs_gut_step_loss_workspace_bytes;
+ *      no allocation) | the accumulator-rows backward with that dL/d(render) | the tail. *loss is stored, as in the MSE form (no regulariser term in it).
+ *      noise (device [N,3], standard normal) / noise_lr: what lfs_add_noise(raw_opacities, raw_scales, raw_quats, noise, means, noise_lr) would add is added to each mean
+ *      in front of its Adam update, computed from the raw values before THEIR updates; the gradients are those of the un-noised mean the forward rendered (the order of
+ *      mcmc.cpp:362-393: post_backward, then the optimizer step). The next view's colours (next_viewmat) are evaluated from the noised, updated mean.
+ *      freeze_shN: FusedAdam group 2 is skipped (fused_adam.cpp:68-70): shN and its moments keep their bytes; exp_avg[2] / exp_avg_sq[2] may be NULL. (The step
+ *      COUNT of that group is the caller's: FusedAdam::step increments it before it skips the group, :66, and a caller that wants the reference's trajectory does too.)
+ *      AN ATTEMPT THAT DID NOT FIT (lfs_gut_step_fits == 0) updated no parameter and no moment and did NOT apply the noise; *loss then holds the loss of an empty render
+ *      and is to be ignored. The caller enlarges the workspace and calls again with the SAME noise tensor.
+ *      K > 16 (SH degree 4) with freeze_shN or noise: LFS_E_UNSUPPORTED before anything is enqueued (the three-pass tail has neither); with loss_kind 1 alone the
+ *      three passes run, as in lfs_gut_train_step_ex. colors_ready: the contract of lfs_gut_train_step_ex. */
+typedef struct lfs_gut_step_options {
+    uint32_t loss_kind;      /* 0: folded clamped MSE (= lfs_gut_train_step_ex); 1: (1-lambda) L1 + lambda (1 - SSIM) of clamp(render,0,1), trainer.cpp:122-125 */
+    float    lambda_dssim;
+    uint32_t freeze_shN;     /* group 2 not updated this step (iteration <= 1000) */
+    const float* noise;      /* device [N,3] or NULL: gsplat::add_noise folded in front of the means' Adam update */
+    float    noise_lr;       /* its current_lr */
+    void*    loss_workspace; size_t loss_workspace_bytes;   /* loss_kind 1: SSIM derivative maps + v_render */
+} lfs_gut_step_options;
+LFS_API size_t lfs_gut_step_loss_workspace_bytes(uint32_t image_width, uint32_t image_height);
+LFS_API int lfs_gut_train_step_opt(const lfs_gut_step_args* args, const lfs_gut_step_options* opts /* NULL = all zero */, const float* next_viewmat, int colors_ready,
+                                   int64_t capacity, int64_t assumed_longest, void* workspace, size_t workspace_bytes, int64_t* host_counts, int64_t stamp,
+                                   lfs_stream_t stream);
 /*   lfs_gut_train_step_pipelined (round 6): lfs_gut_train_step - same arguments, same results - with the step's HBM-bound SH kernels on a side stream of the library,
  *      UNDER the latency- / VALU-bound front end of the NEXT step: projection(k+1) (records without colours) | tile lists | culling run on `stream` while SH Adam(k)
  *      (1.1 GB of read-modify-write at 1 M Gaussians) and the SH colours(k+1) run beside them; `stream` waits for the colours in front of the forward kernel. The SH

@@ -17,6 +17,16 @@ struct AdamGroupState {   // one FusedAdam parameter group: moments + the scalar
     torch::Tensor exp_avg, exp_avg_sq;
     float lr = 0.f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-15f, bias_correction1_rcp = 1.f, bias_correction2_sqrt_rcp = 1.f;
 };
+// What step_opt adds to step (lfs_gut_step_options, include/lfs_gsplat.h): the configuration the reference itself trains.
+struct GutStepOptions {
+    uint32_t loss_kind = 0;             // 0: the folded clamped MSE of step(); 1: (1 - lambda) L1 + lambda (1 - SSIM) of clamp(render, 0, 1) (trainer.cpp:122-125)
+    float lambda_dssim = 0.2f;
+    bool freeze_shN = false;            // iteration <= 1000: FusedAdam skips the shN group (fused_adam.cpp:68-70); adam[2]'s moments may be undefined tensors.
+                                        // The caller still does `++step_count` for shN on such a step, as FusedAdam::step does before it skips the group (:66): the
+                                        // bias corrections of iteration 1001 are then the ones the reference's own sequence computes.
+    at::optional<torch::Tensor> noise;  // [N,3] standard normal deviates: gsplat::add_noise (mcmc.cpp:349-360) folded in front of the means' Adam update ...
+    float noise_lr = 0.f;               // ... with this current_lr (the means' lr * MCMC::noise_lr)
+};
 class GutTrainStep {
 public:
     explicit GutTrainStep(uint32_t tile_size = 16, int64_t initial_capacity = 0);
@@ -32,6 +42,13 @@ public:
                  const std::array<AdamGroupState, 6>& adam, uint32_t sh_degree, const torch::Tensor& viewmat, const torch::Tensor& K, uint32_t image_width,
                  uint32_t image_height, const at::optional<torch::Tensor>& background, const torch::Tensor& target_chw, float loss_weight, torch::Tensor& loss,
                  float scale_reg = 0.f, float opacity_reg = 0.f, const at::optional<torch::Tensor>& next_viewmat = at::nullopt);
+    // step() with options: same contract, same bookkeeping (an attempt that did not fit applied nothing - the noise included - and is re-run with the same noise
+    // tensor). Default-constructed options give step()'s results bit for bit. `loss` receives loss_weight * the selected loss. SH degree 4 (K > 16) takes loss_kind 1
+    // only (freeze_shN / noise: an error before anything is enqueued).
+    int64_t step_opt(torch::Tensor& means, torch::Tensor& sh0, torch::Tensor& shN, torch::Tensor& raw_scales, torch::Tensor& raw_quats, torch::Tensor& raw_opacities,
+                     const std::array<AdamGroupState, 6>& adam, uint32_t sh_degree, const torch::Tensor& viewmat, const torch::Tensor& K, uint32_t image_width,
+                     uint32_t image_height, const at::optional<torch::Tensor>& background, const torch::Tensor& target_chw, float loss_weight, torch::Tensor& loss,
+                     float scale_reg, float opacity_reg, const at::optional<torch::Tensor>& next_viewmat, const GutStepOptions& options);
     torch::Tensor render() const;   // [H,W,3] view of the last step's un-clamped image (valid until the next step)
     torch::Tensor alpha() const;    // [H,W]
     torch::Tensor radii() const;    // int32 [N,2]
@@ -39,6 +56,10 @@ public:
     int retries() const { return retries_; }
     int colour_launches_saved() const { return colours_saved_; }   // steps that found their SH colours prepared by the step before
 private:
+    int64_t run(torch::Tensor& means, torch::Tensor& sh0, torch::Tensor& shN, torch::Tensor& raw_scales, torch::Tensor& raw_quats, torch::Tensor& raw_opacities,
+                const std::array<AdamGroupState, 6>& adam, uint32_t sh_degree, const torch::Tensor& viewmat, const torch::Tensor& K, uint32_t image_width,
+                uint32_t image_height, const at::optional<torch::Tensor>& background, const torch::Tensor& target_chw, float loss_weight, torch::Tensor& loss,
+                float scale_reg, float opacity_reg, const at::optional<torch::Tensor>& next_viewmat, const GutStepOptions* options);
     void ensure(uint32_t N, uint32_t W, uint32_t H, const torch::Tensor& like);
     uint32_t tile_;
     int64_t capacity_, assumed_longest_ = 1024, stamp_ = 0, n_isects_ = 0, longest_ = 0;
@@ -52,5 +73,6 @@ private:
         uint32_t param_version[3] = {0, 0, 0}; uint32_t N = 0, K = 0, degree = 0;
     } colours_for_;
     int colours_saved_ = 0;
+    torch::Tensor loss_ws_;   // step_opt, loss_kind 1: SSIM derivative maps + dL/d(render) (lfs_gut_step_loss_workspace_bytes)
 };
 } // namespace lfs

@@ -196,6 +196,23 @@ int check_args(const lfs_gut_step_args* a, bool need_adam) {
     return LFS_OK;
 }
 
+// The tail as three per-Gaussian passes (SH backward + Adam on sh0 / shN, then finish + Adam on the other four tensors): lfs_gut_train_step, and what the fused-tail entry
+// points run for K > 16 (no colours for the next step). loss (nullable): receives the fused MSE of the backward.
+int three_pass_tail(const lfs_gut_step_args* a, const StepWs& w, float* loss, hipStream_t s) {
+    const float* acc_rows = reinterpret_cast<const float*>(static_cast<const char*>(w.raster_ws) + lfs_rasterize_workspace_acc_offset(1, a->N));
+    const int rc = sh_model_bwd_adam_all_impl(a->N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, w.radii, w.colors, acc_rows, w.v_dirs, a->exp_avg[1],
+                                              a->exp_avg_sq[1], a->adam[1], a->exp_avg[2], a->exp_avg_sq[2], a->adam[2], s, w.abort_flag);
+    if (rc) return rc;
+    // lfs_gut_finish_adam's order: means, raw_scales, raw_quats, raw_opacities = FusedAdam groups 0, 3, 4, 5
+    float* const m[4] = {a->exp_avg[0], a->exp_avg[3], a->exp_avg[4], a->exp_avg[5]};
+    float* const v[4] = {a->exp_avg_sq[0], a->exp_avg_sq[3], a->exp_avg_sq[4], a->exp_avg_sq[5]};
+    float sc[24];
+    const int grp[4] = {0, 3, 4, 5};
+    for (int k = 0; k < 4; ++k) for (int j = 0; j < 6; ++j) sc[6 * k + j] = a->adam[grp[k]][j];
+    return gut_finish_adam_impl(a->N, a->means, a->raw_scales, a->raw_quats, a->raw_opacities, w.quats, w.scales, w.opacities, w.v_dirs, m, v, sc, a->scale_reg,
+                                a->opacity_reg, loss, w.raster_ws, w.raster_ws_bytes, s, w.abort_flag);
+}
+
 } // namespace
 } // namespace lfs
 
@@ -237,18 +254,7 @@ extern "C" int lfs_gut_train_step(const lfs_gut_step_args* a, int64_t capacity, 
     rc = raster_bwd_mse_acc_guarded(a->N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &f.cams, a->tile_size, f.offsets, w.flatten_ids, capacity,
                                     w.render, w.alpha, w.last_ids, a->target_chw, a->loss_weight, w.raster_ws, w.raster_ws_bytes, s);
     if (rc) return rc;
-    const float* acc_rows = reinterpret_cast<const float*>(static_cast<const char*>(w.raster_ws) + lfs_rasterize_workspace_acc_offset(1, a->N));
-    rc = sh_model_bwd_adam_all_impl(a->N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, w.radii, w.colors, acc_rows, w.v_dirs, a->exp_avg[1], a->exp_avg_sq[1],
-                                    a->adam[1], a->exp_avg[2], a->exp_avg_sq[2], a->adam[2], s, w.abort_flag);
-    if (rc) return rc;
-    // lfs_gut_finish_adam's order: means, raw_scales, raw_quats, raw_opacities = FusedAdam groups 0, 3, 4, 5
-    float* const m[4] = {a->exp_avg[0], a->exp_avg[3], a->exp_avg[4], a->exp_avg[5]};
-    float* const v[4] = {a->exp_avg_sq[0], a->exp_avg_sq[3], a->exp_avg_sq[4], a->exp_avg_sq[5]};
-    float sc[24];
-    const int grp[4] = {0, 3, 4, 5};
-    for (int k = 0; k < 4; ++k) for (int j = 0; j < 6; ++j) sc[6 * k + j] = a->adam[grp[k]][j];
-    return gut_finish_adam_impl(a->N, a->means, a->raw_scales, a->raw_quats, a->raw_opacities, w.quats, w.scales, w.opacities, w.v_dirs, m, v, sc, a->scale_reg,
-                                a->opacity_reg, a->loss, w.raster_ws, w.raster_ws_bytes, s, w.abort_flag);
+    return three_pass_tail(a, w, a->loss, s);
 }
 
 // lfs_gut_train_step with its three per-Gaussian tail passes as ONE (round 6; raster.hip: gut_tail_kernel): SH backward + Adam(sh0, shN) + finish + Adam(means, scales,
@@ -280,17 +286,81 @@ extern "C" int lfs_gut_train_step_ex(const lfs_gut_step_args* a, const float* ne
                        next_viewmat, w.radii, w.colors, a->exp_avg, a->exp_avg_sq, a->adam, a->scale_reg, a->opacity_reg, a->loss, w.raster_ws, w.raster_ws_bytes, s, w.abort_flag);
     if (rc != LFS_E_UNSUPPORTED) return rc;
     // K > 16: the separate passes of lfs_gut_train_step (no colours for the next step: the caller's next call must pass colors_ready = 0 - GutStep checks K)
-    const float* acc_rows = reinterpret_cast<const float*>(static_cast<const char*>(w.raster_ws) + lfs_rasterize_workspace_acc_offset(1, a->N));
-    rc = sh_model_bwd_adam_all_impl(a->N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, w.radii, w.colors, acc_rows, w.v_dirs, a->exp_avg[1], a->exp_avg_sq[1],
-                                    a->adam[1], a->exp_avg[2], a->exp_avg_sq[2], a->adam[2], s, w.abort_flag);
+    return three_pass_tail(a, w, a->loss, s);
+}
+
+// lfs_gut_train_step_ex for what the reference actually trains (trainer.cpp:122-126, mcmc.cpp:349-386, fused_adam.cpp:68-70): the photometric loss L1 + D-SSIM instead of
+// the folded MSE, the MCMC strategy's noise in front of the means' Adam update, and shN frozen while iteration <= 1000 - still one enqueue, no host read, no gradient
+// tensor. loss_kind 1:
+//   forward | memset(*loss) | ssim_fwd + ssim_bwd on the workspace's render -> loss_workspace (derivative maps, then v_render [H,W,3]) | accumulator-rows backward with that
+//   v_render | tail (loss == NULL: *loss was written by the loss kernels)
+// An attempt that did not fit rendered empty lists: its loss kernels see the background, its backward accumulates nothing, its tail returns at the abort flag - no parameter,
+// no moment and no noise is applied, and *loss holds the loss of the empty render.
+// The loss kernels live in ssim.hip. This file is also linked WITHOUT it (tests/test_emulated_step_pack.py builds the step driver from a fixed list of sources), so the
+// two entry points are weak references here: absent -> loss_kind 1 is LFS_E_UNSUPPORTED, everything else works. In liblfs_gsplat.so they are always present.
+extern "C" __attribute__((weak)) size_t lfs_photometric_loss_workspace_bytes(uint32_t H, uint32_t W);
+extern "C" __attribute__((weak)) int lfs_photometric_loss_fwd_bwd(uint32_t H, uint32_t W, const float* render_hwc, const float* target_chw, float lambda_dssim, float weight,
+                                                                  float* v_render_hwc, float* loss, void* workspace, size_t workspace_bytes, lfs_stream_t stream);
+static bool have_loss_kernels() { return &lfs_photometric_loss_workspace_bytes != nullptr && &lfs_photometric_loss_fwd_bwd != nullptr; }
+
+extern "C" size_t lfs_gut_step_loss_workspace_bytes(uint32_t image_width, uint32_t image_height) {
+    if (!have_loss_kernels()) return 0;
+    return a256(lfs_photometric_loss_workspace_bytes(image_height, image_width)) + a256(size_t(12) * image_width * image_height);
+}
+
+extern "C" int lfs_gut_train_step_opt(const lfs_gut_step_args* a, const lfs_gut_step_options* opts, const float* next_viewmat, int colors_ready, int64_t capacity,
+                                      int64_t assumed_longest, void* workspace, size_t workspace_bytes, int64_t* host_counts, int64_t stamp, lfs_stream_t stream) {
+    const lfs_gut_step_options none{};
+    const lfs_gut_step_options& o = opts ? *opts : none;
+    const bool freeze = o.freeze_shN != 0, ssim = o.loss_kind == 1;
+    if (!ssim && !freeze && !o.noise) {
+        if (o.loss_kind != 0) return LFS_E_INVALID;
+        return lfs_gut_train_step_ex(a, next_viewmat, colors_ready, capacity, assumed_longest, workspace, workspace_bytes, host_counts, stamp, stream);
+    }
+    if (o.loss_kind > 1) return LFS_E_INVALID;
+    // (check_args(.., true) with shN's moments optional while the group is frozen)
+    int rc = check_args(a, false);
     if (rc) return rc;
-    float* const m[4] = {a->exp_avg[0], a->exp_avg[3], a->exp_avg[4], a->exp_avg[5]};
-    float* const v[4] = {a->exp_avg_sq[0], a->exp_avg_sq[3], a->exp_avg_sq[4], a->exp_avg_sq[5]};
-    float sc[24];
-    const int grp[4] = {0, 3, 4, 5};
-    for (int k = 0; k < 4; ++k) for (int j = 0; j < 6; ++j) sc[6 * k + j] = a->adam[grp[k]][j];
-    return gut_finish_adam_impl(a->N, a->means, a->raw_scales, a->raw_quats, a->raw_opacities, w.quats, w.scales, w.opacities, w.v_dirs, m, v, sc, a->scale_reg,
-                                a->opacity_reg, a->loss, w.raster_ws, w.raster_ws_bytes, s, w.abort_flag);
+    if (a->K < 2 || !a->target_chw || !a->loss) return LFS_E_INVALID;
+    for (int k = 0; k < 6; ++k) if ((!a->exp_avg[k] || !a->exp_avg_sq[k]) && !(freeze && k == 2)) return LFS_E_INVALID;
+    if (a->K > 16 && (freeze || o.noise)) return LFS_E_UNSUPPORTED;   // the three-pass tail of degree 4 has neither
+    if (!workspace) return LFS_E_INVALID;
+    StepWs w;
+    if (!step_ws(workspace, a->N, a->image_width, a->image_height, a->tile_size, capacity, w, nullptr)) return LFS_E_INVALID;
+    if (workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
+    if (ssim) {
+        if (!have_loss_kernels()) return LFS_E_UNSUPPORTED;
+        if (!o.loss_workspace) return LFS_E_INVALID;
+        if (o.loss_workspace_bytes < lfs_gut_step_loss_workspace_bytes(a->image_width, a->image_height)) return LFS_E_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    rc = auto_join(s);
+    if (rc) return rc;
+    Front f;
+    rc = enqueue_forward(a, w, capacity, assumed_longest, host_counts, stamp, s, f, nullptr, colors_ready != 0);
+    if (rc) return rc;
+    if (ssim) {
+        const size_t maps_bytes = lfs_photometric_loss_workspace_bytes(a->image_height, a->image_width);
+        float* v_render = reinterpret_cast<float*>(static_cast<char*>(o.loss_workspace) + a256(maps_bytes));
+        const hipError_t e = hipMemsetAsync(a->loss, 0, sizeof(float), s);
+        if (e != hipSuccess) return (int)e;
+        rc = lfs_photometric_loss_fwd_bwd(a->image_height, a->image_width, w.render, a->target_chw, o.lambda_dssim, a->loss_weight, v_render, a->loss, o.loss_workspace,
+                                          maps_bytes, stream);
+        if (rc) return rc;
+        rc = raster_bwd_acc_guarded(a->N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &f.cams, a->tile_size, f.offsets, w.flatten_ids, capacity, w.alpha,
+                                    w.last_ids, v_render, w.raster_ws, w.raster_ws_bytes, s);
+    } else {
+        rc = raster_bwd_mse_acc_guarded(a->N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &f.cams, a->tile_size, f.offsets, w.flatten_ids, capacity,
+                                        w.render, w.alpha, w.last_ids, a->target_chw, a->loss_weight, w.raster_ws, w.raster_ws_bytes, s);
+    }
+    if (rc) return rc;
+    float* const tail_loss = ssim ? nullptr : a->loss;
+    if (a->K <= 16)
+        return gut_tail_impl(a->N, a->K, a->sh_degree, a->means, a->sh0, a->shN, a->raw_scales, a->raw_quats, a->raw_opacities, w.quats, w.scales, w.opacities, a->viewmat,
+                             next_viewmat, w.radii, w.colors, a->exp_avg, a->exp_avg_sq, a->adam, a->scale_reg, a->opacity_reg, tail_loss, w.raster_ws, w.raster_ws_bytes, s,
+                             w.abort_flag, freeze, o.noise, o.noise_lr);
+    // K > 16 with loss_kind 1 alone: the separate passes of lfs_gut_train_step (no colours for the next step)
+    return three_pass_tail(a, w, tail_loss, s);
 }
 
 // lfs_gut_train_step with the step's HBM-bound SH kernels moved UNDER its latency- and VALU-bound front end (round 6). Same arguments, same results (bit for bit in

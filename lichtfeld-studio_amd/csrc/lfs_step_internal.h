@@ -76,7 +76,9 @@ int gut_finish_grads_impl(uint32_t N, const float* means, const float* raw_quats
 int gut_tail_impl(uint32_t N, uint32_t K, uint32_t degrees_to_use, float* means, float* sh0, float* shN, float* raw_scales, float* raw_quats, float* raw_opacities,
                   const float* quats, const float* scales, const float* opacities, const float* viewmat, const float* next_viewmat, const int32_t* radii, float* colors,
                   float* const* exp_avg, float* const* exp_avg_sq, const float (*scalars)[6], float scale_reg, float opacity_reg, float* loss, void* workspace,
-                  size_t workspace_bytes, hipStream_t s, const int32_t* abort_flag);
+                  size_t workspace_bytes, hipStream_t s, const int32_t* abort_flag,
+                  bool freeze_shN = false,                               // FusedAdam group 2 is not updated (iteration <= 1000); exp_avg[2] / exp_avg_sq[2] may be NULL
+                  const float* noise = nullptr, float noise_lr = 0.f);   // lfs_add_noise(noise [N,3], noise_lr) folded in front of the means' Adam update
 
 // pipelined training step (gut_step.hip): the SH backward in two kernels on two streams (sh.hip), and the SH colours written into the rasterizer's records
 int sh_pipe_dirs_impl(uint32_t n, uint32_t K, uint32_t degrees_to_use, const float* means, const float* viewmat, const float* shN, const int32_t* radii,

@@ -4,6 +4,7 @@
 // Small streaming kernels, one lane per Gaussian, vector loads where the layout
 // allows (quats are 16-byte rows).
 #include "lfs_math.cuh"
+#include "lfs_mcmc_noise.cuh"
 #include "../../include/lfs_gsplat.h"
 
 namespace lfs {
@@ -51,22 +52,12 @@ __global__ void __launch_bounds__(256) add_noise_kernel(
     const float* __restrict__ noise, float* __restrict__ means, const float current_lr) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
-    const float s2[3] = {__expf(2.f * raw_scales[3 * i]), __expf(2.f * raw_scales[3 * i + 1]), __expf(2.f * raw_scales[3 * i + 2])};
-    const float4 q = reinterpret_cast<const float4*>(raw_quats)[i];
-    const m3 R = quat_to_rotmat(q.x, q.y, q.z, q.w, 1e12f);
-    // covariance = R diag(s2) R^T ; transformed noise = covariance * noise
-    const f3 nz{noise[3 * i], noise[3 * i + 1], noise[3 * i + 2]};
-    m3 cov;
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            cov.m[r][c] = R.m[r][0] * s2[0] * R.m[c][0] + R.m[r][1] * s2[1] * R.m[c][1] + R.m[r][2] * s2[2] * R.m[c][2];
-    const f3 tn = mul(cov, nz);
-    const float opacity = 1.f / (1.f + __expf(-raw_opacities[i]));
-    const float op_sigmoid = 1.f / (1.f + __expf(100.f * opacity - 0.5f));
-    const float nf = current_lr * op_sigmoid;
-    means[3 * i] += nf * tn.x; means[3 * i + 1] += nf * tn.y; means[3 * i + 2] += nf * tn.z;
+    // the arithmetic lives in lfs_mcmc_noise.cuh: the training step's fused tail (raster.hip) applies the same update to the mean it holds in registers
+    const float rs[3] = {raw_scales[3 * i], raw_scales[3 * i + 1], raw_scales[3 * i + 2]};
+    const float nz[3] = {noise[3 * i], noise[3 * i + 1], noise[3 * i + 2]};
+    float m[3] = {means[3 * i], means[3 * i + 1], means[3 * i + 2]};
+    mcmc_add_noise(m, rs, reinterpret_cast<const float4*>(raw_quats)[i], raw_opacities[i], nz, current_lr);
+    means[3 * i] = m[0]; means[3 * i + 1] = m[1]; means[3 * i + 2] = m[2];
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

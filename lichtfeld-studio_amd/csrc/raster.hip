@@ -51,6 +51,7 @@
 #include "lfs_raster_pack.cuh"
 #include "lfs_adam.cuh"
 #include "lfs_sh.cuh"
+#include "lfs_mcmc_noise.cuh"
 #include "lfs_step_internal.h"
 
 // LFS_BWD_REORTH (default 1 since round 5; -DLFS_BWD_REORTH=0 = the rounds 1 - 4 backward, kept for A/B: tools/build_variant.py noreorth raster.hip -DLFS_BWD_REORTH=0): the backward
@@ -1073,6 +1074,7 @@ struct GutTail {
     float *m0, *v0, *mN, *vN; AdamScalars s0, sN;    // sh0 / shN moments
     FinishAdam fin;
     const float* loss_slots; float* loss; const int32_t* abort_flag;
+    const float* noise; float noise_lr;               // NOISE: the MCMC strategy's normal deviates [N,3] and its current_lr (lfs_add_noise's operands)
 };
 // Phase 5 of gut_tail_kernel: the coefficient rows phase 2 fetches stay in registers for it (KEEP: same lane, same rows - 3 x LPG VGPRs, 196 - 224 in all: two wavefronts
 // per SIMD, each with 16 rows x 12 B per lane in flight in phase 2), and its first TAIL_DEPTH moment rows (parameter + two moments in flight per lane) are requested in
@@ -1081,8 +1083,12 @@ struct GutTail {
 //    0     0     4      670.3                     1     1     4      687.3   <- this form
 //    0     0     8      686.2                     1     1     8      687.9
 //    0     1     4      681.7                     1     1     4      686.8   with non-temporal stores of the moments
+// FREEZE (iteration <= 1000: FusedAdam skips group 2, fused_adam.cpp:68-70): the lanes k >= 1 fetch their coefficient rows where phase 2 / phase 5 read them, but
+// neither load nor store a moment row and store no coefficient row; mN / vN may be NULL. NOISE (the MCMC strategy between refinements, mcmc.cpp:349-386): phase 3 adds
+// lfs_add_noise's update (lfs_mcmc_noise.cuh) to the mean in registers in front of its Adam update, from the raw scales / quaternion / opacity as loaded; the SH direction
+// and finish_geometry have used the mean as the forward saw it. Its three deviates are requested with the finish operands (3 VGPRs in flight under phase 2).
 constexpr int TAIL_DEPTH = 4;
-template <int LPG, bool NEXT>
+template <int LPG, bool NEXT, bool FREEZE = false, bool NOISE = false>
 __global__ void __launch_bounds__(64) gut_tail_kernel(const GutTail t, const CamDev* __restrict__ cams) {
     __shared__ float lds_b[64 * (LPG + 1)];
     __shared__ float lds_s[64 * (LPG + 1)];
@@ -1149,6 +1155,8 @@ __global__ void __launch_bounds__(64) gut_tail_kernel(const GutTail t, const Cam
     ld3o(ad.m[0], m0); ld3o(ad.v[0], v0m); ld3o(t.raw_scales, p1); ld3o(ad.m[1], m1); ld3o(ad.v[1], v1);
     float4 mq = ld4o(ad.m[2]), vq4 = ld4o(ad.v[2]);
     float po = ld1o(t.raw_opacities), mo = ld1o(ad.m[3]), vo = ld1o(ad.v[3]);
+    float nz[3] = {0.f, 0.f, 0.f};
+    if (NOISE) ld3o(t.noise, nz);
     __syncthreads();
     // ---- phase 2: s_k ------------------------------------------------------------------------------------------------------------------------------------
     const uint32_t lane_el = ((lane / LPG) * KK + uint32_t(k - 1)) * 3u;   // (k == 0 lanes never use it)
@@ -1186,8 +1194,9 @@ __global__ void __launch_bounds__(64) gut_tail_kernel(const GutTail t, const Cam
     // phase 5's moment rows: TAIL_DEPTH of them per lane in flight, requested in front of phase 3 (they land under the finish arithmetic)
     constexpr int D = (LPG < TAIL_DEPTH) ? LPG : TAIL_DEPTH;
     V3f M[D], Q[D];
+    const bool upd_k = !FREEZE || k == 0;   // FREEZE: only the sh0 lane has an Adam update
     auto load = [&](const int it, const int slot) {
-        if (row_ok(it)) {
+        if (row_ok(it) && upd_k) {
             const size_t e = row_el(it);
             M[slot] = *reinterpret_cast<const V3f*>(mbase + e); Q[slot] = *reinterpret_cast<const V3f*>(vbase + e);
         }
@@ -1247,6 +1256,7 @@ __global__ void __launch_bounds__(64) gut_tail_kernel(const GutTail t, const Cam
 #pragma unroll
             for (int kk = 0; kk < 3; ++kk) gs[kk] = (vs[kk] + ad.scale_reg) * sc[kk];
             const float go = (v_opac + ad.opacity_reg) * o * (1.f - o);
+            if (NOISE) mcmc_add_noise(pm, p1, rq, po, nz, t.noise_lr);   // lfs_add_noise, from the raw values as loaded (before their own updates below)
 #pragma unroll
             for (int kk = 0; kk < 3; ++kk) {
                 adam_elem(pm[kk], m0[kk], v0m[kk], gm[kk], ad.s[0]);
@@ -1296,7 +1306,7 @@ __global__ void __launch_bounds__(64) gut_tail_kernel(const GutTail t, const Cam
                 const int it = it0 + u;
                 const uint32_t gl = it * GPI + lane / LPG;
                 V3f p = PK[it];
-                if (row_ok(it)) {
+                if (row_ok(it) && upd_k) {
                     const float bk = lds_b[gl * (LPG + 1) + k];
                     const float o0 = bk * ldv[gl * 3], o1 = bk * ldv[gl * 3 + 1], o2 = bk * ldv[gl * 3 + 2];
                     V3f m = M[u], qq = Q[u];
@@ -1753,14 +1763,14 @@ int lfs::gut_tail_impl(
     uint32_t N, uint32_t K, uint32_t degrees_to_use, float* means, float* sh0, float* shN, float* raw_scales, float* raw_quats, float* raw_opacities,
     const float* quats, const float* scales, const float* opacities, const float* viewmat, const float* next_viewmat, const int32_t* radii, float* colors,
     float* const* exp_avg /* [6] host, FusedAdam group order */, float* const* exp_avg_sq, const float (*scalars)[6], float scale_reg, float opacity_reg, float* loss,
-    void* workspace, size_t workspace_bytes, hipStream_t s, const int32_t* abort_flag) {
+    void* workspace, size_t workspace_bytes, hipStream_t s, const int32_t* abort_flag, bool freeze_shN, const float* noise, float noise_lr) {
     if (N == 0) return LFS_OK;
     const uint32_t Kd = (degrees_to_use + 1) * (degrees_to_use + 1);
     if (degrees_to_use > 3 || Kd > K || K < 2) return LFS_E_INVALID;
     if (K > 16) return LFS_E_UNSUPPORTED;
     if (!means || !sh0 || !shN || !raw_scales || !raw_quats || !raw_opacities || !quats || !scales || !opacities || !viewmat || !radii || !colors || !exp_avg || !exp_avg_sq ||
         !scalars || !workspace) return LFS_E_INVALID;
-    for (int k = 0; k < 6; ++k) if (!exp_avg[k] || !exp_avg_sq[k]) return LFS_E_INVALID;
+    for (int k = 0; k < 6; ++k) if ((!exp_avg[k] || !exp_avg_sq[k]) && !(freeze_shN && k == 2)) return LFS_E_INVALID;
     const RasterWs w = raster_ws(workspace, 1, N, 0, 0);
     if (workspace_bytes < size_t(reinterpret_cast<const char*>(w.cull) - static_cast<const char*>(workspace))) return LFS_E_WORKSPACE;
     GutTail t{};
@@ -1774,14 +1784,15 @@ int lfs::gut_tail_impl(
     for (int j = 0; j < 4; ++j) { t.fin.m[j] = exp_avg[grp[j]]; t.fin.v[j] = exp_avg_sq[grp[j]]; t.fin.s[j] = sc(grp[j]); }
     t.fin.scale_reg = scale_reg / (3.f * float(N)); t.fin.opacity_reg = opacity_reg / float(N);   // (as gut_finish_adam_impl)
     t.loss_slots = loss ? w.acc + ACC_STRIDE * size_t(N) : nullptr; t.loss = loss; t.abort_flag = abort_flag;
+    t.noise = noise; t.noise_lr = noise_lr;
     const dim3 grid((N + 63) / 64), block(64);
     lfs::ProfScope prof("tail_sh_finish_adam", s);
     const bool next = next_viewmat != nullptr;
-    if (K <= 4) {
-        if (next) hipLaunchKernelGGL((gut_tail_kernel<4, true>), grid, block, 0, s, t, w.cams); else hipLaunchKernelGGL((gut_tail_kernel<4, false>), grid, block, 0, s, t, w.cams);
-    } else {
-        if (next) hipLaunchKernelGGL((gut_tail_kernel<16, true>), grid, block, 0, s, t, w.cams); else hipLaunchKernelGGL((gut_tail_kernel<16, false>), grid, block, 0, s, t, w.cams);
-    }
+    using TailKernel = void (*)(const GutTail, const CamDev*);
+#define LFS_TAIL_ROW(LPG, NEXT) {gut_tail_kernel<LPG, NEXT, false, false>, gut_tail_kernel<LPG, NEXT, false, true>, gut_tail_kernel<LPG, NEXT, true, false>, gut_tail_kernel<LPG, NEXT, true, true>}
+    static const TailKernel table[2][2][4] = {{LFS_TAIL_ROW(4, false), LFS_TAIL_ROW(4, true)}, {LFS_TAIL_ROW(16, false), LFS_TAIL_ROW(16, true)}};   // [LPG][NEXT][2 FREEZE + NOISE]
+#undef LFS_TAIL_ROW
+    hipLaunchKernelGGL(table[K <= 4 ? 0 : 1][next ? 1 : 0][(freeze_shN ? 2 : 0) + (noise != nullptr ? 1 : 0)], grid, block, 0, s, t, w.cams);
     return (int)hipGetLastError();
 }
 

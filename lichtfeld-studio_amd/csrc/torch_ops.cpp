@@ -403,6 +403,24 @@ int64_t GutTrainStep::step(torch::Tensor& means, torch::Tensor& sh0, torch::Tens
                            const torch::Tensor& K, uint32_t image_width, uint32_t image_height, const at::optional<torch::Tensor>& background,
                            const torch::Tensor& target_chw, float loss_weight, torch::Tensor& loss, float scale_reg, float opacity_reg,
                            const at::optional<torch::Tensor>& next_viewmat) {
+    return run(means, sh0, shN, raw_scales, raw_quats, raw_opacities, adam, sh_degree, viewmat, K, image_width, image_height, background, target_chw, loss_weight, loss,
+               scale_reg, opacity_reg, next_viewmat, nullptr);
+}
+
+int64_t GutTrainStep::step_opt(torch::Tensor& means, torch::Tensor& sh0, torch::Tensor& shN, torch::Tensor& raw_scales, torch::Tensor& raw_quats,
+                               torch::Tensor& raw_opacities, const std::array<AdamGroupState, 6>& adam, uint32_t sh_degree, const torch::Tensor& viewmat,
+                               const torch::Tensor& K, uint32_t image_width, uint32_t image_height, const at::optional<torch::Tensor>& background,
+                               const torch::Tensor& target_chw, float loss_weight, torch::Tensor& loss, float scale_reg, float opacity_reg,
+                               const at::optional<torch::Tensor>& next_viewmat, const GutStepOptions& options) {
+    return run(means, sh0, shN, raw_scales, raw_quats, raw_opacities, adam, sh_degree, viewmat, K, image_width, image_height, background, target_chw, loss_weight, loss,
+               scale_reg, opacity_reg, next_viewmat, &options);
+}
+
+int64_t GutTrainStep::run(torch::Tensor& means, torch::Tensor& sh0, torch::Tensor& shN, torch::Tensor& raw_scales, torch::Tensor& raw_quats,
+                          torch::Tensor& raw_opacities, const std::array<AdamGroupState, 6>& adam, uint32_t sh_degree, const torch::Tensor& viewmat,
+                          const torch::Tensor& K, uint32_t image_width, uint32_t image_height, const at::optional<torch::Tensor>& background,
+                          const torch::Tensor& target_chw, float loss_weight, torch::Tensor& loss, float scale_reg, float opacity_reg,
+                          const at::optional<torch::Tensor>& next_viewmat, const GutStepOptions* options) {
     LFS_DEVICE_GUARD(means);
     LFS_CHECK_INPUT(means); LFS_CHECK_INPUT(sh0); LFS_CHECK_INPUT(shN); LFS_CHECK_INPUT(raw_scales); LFS_CHECK_INPUT(raw_quats); LFS_CHECK_INPUT(raw_opacities);
     LFS_CHECK_INPUT(viewmat); LFS_CHECK_INPUT(K); LFS_CHECK_INPUT(target_chw); LFS_CHECK_INPUT(loss);
@@ -413,7 +431,9 @@ int64_t GutTrainStep::step(torch::Tensor& means, torch::Tensor& sh0, torch::Tens
     a.N = N; a.K = 1 + (uint32_t)shN.size(1); a.sh_degree = sh_degree; a.image_width = image_width; a.image_height = image_height; a.tile_size = tile_;
     a.means = means.data_ptr<float>(); a.sh0 = sh0.data_ptr<float>(); a.shN = shN.data_ptr<float>();
     a.raw_scales = raw_scales.data_ptr<float>(); a.raw_quats = raw_quats.data_ptr<float>(); a.raw_opacities = raw_opacities.data_ptr<float>();
+    const bool frozen = options != nullptr && options->freeze_shN;
     for (int k = 0; k < 6; ++k) {
+        if (frozen && k == 2 && !adam[k].exp_avg.defined()) continue;   // (the frozen group is not touched: its moments need not exist)
         LFS_CHECK_INPUT(adam[k].exp_avg); LFS_CHECK_INPUT(adam[k].exp_avg_sq);
         a.exp_avg[k] = adam[k].exp_avg.data_ptr<float>(); a.exp_avg_sq[k] = adam[k].exp_avg_sq.data_ptr<float>();
         const float sc[6] = {adam[k].lr, adam[k].beta1, adam[k].beta2, adam[k].eps, adam[k].bias_correction1_rcp, adam[k].bias_correction2_sqrt_rcp};
@@ -431,6 +451,25 @@ int64_t GutTrainStep::step(torch::Tensor& means, torch::Tensor& sh0, torch::Tens
         TORCH_CHECK(next_viewmat->numel() == 16, "next_viewmat must be [4,4]");
         next_vm = next_viewmat->data_ptr<float>();
     }
+    lfs_gut_step_options o{};
+    if (options != nullptr) {
+        TORCH_CHECK(options->loss_kind <= 1, "GutStepOptions::loss_kind: 0 (MSE) or 1 (L1 + D-SSIM)");
+        TORCH_CHECK(a.K <= 16 || (!options->freeze_shN && !options->noise.has_value()), "GutTrainStep::step_opt: freeze_shN / noise need SH degree <= 3");
+        o.loss_kind = options->loss_kind; o.lambda_dssim = options->lambda_dssim; o.freeze_shN = options->freeze_shN ? 1u : 0u;
+        if (options->noise.has_value() && options->noise->defined()) {
+            LFS_CHECK_INPUT(options->noise.value());
+            TORCH_CHECK(options->noise->numel() == 3 * int64_t(N), "noise must be [N,3]");
+            o.noise = options->noise->data_ptr<float>(); o.noise_lr = options->noise_lr;
+        }
+        if (o.loss_kind == 1) {
+            const size_t need = lfs_gut_step_loss_workspace_bytes(image_width, image_height);
+            if (!loss_ws_.defined() || (size_t)loss_ws_.numel() < need || loss_ws_.device() != means.device()) {
+                loss_ws_ = at::Tensor();
+                loss_ws_ = at::empty({(int64_t)need}, means.options().dtype(at::kByte));
+            }
+            o.loss_workspace = loss_ws_.data_ptr(); o.loss_workspace_bytes = (size_t)loss_ws_.numel();
+        }
+    }
     const torch::Tensor* const watched[3] = {&means, &sh0, &shN};
     auto describes = [&](const ColoursFor& c, const torch::Tensor& vm) {
         bool same = c.valid && c.viewmat == vm.data_ptr() && c.viewmat_version == (uint32_t)vm._version() && c.ws == ws_.data_ptr() && c.N == N && c.K == a.K && c.degree == sh_degree;
@@ -443,12 +482,15 @@ int64_t GutTrainStep::step(torch::Tensor& means, torch::Tensor& sh0, torch::Tens
         int64_t* counts = counts_.data_ptr<int64_t>();
         const bool ready = describes(colours_for_, viewmat);
         colours_for_.valid = false;   // whatever happens below, the colours of THIS view are consumed / overwritten
-        check_rc(lfs_gut_train_step_ex(&a, next_vm, ready ? 1 : 0, capacity_, assumed_longest_, ws_.data_ptr(), (size_t)ws_.numel(), counts, stamp_, cur_stream()), "gut_train_step_ex");
+        if (options != nullptr)
+            check_rc(lfs_gut_train_step_opt(&a, &o, next_vm, ready ? 1 : 0, capacity_, assumed_longest_, ws_.data_ptr(), (size_t)ws_.numel(), counts, stamp_, cur_stream()), "gut_train_step_opt");
+        else
+            check_rc(lfs_gut_train_step_ex(&a, next_vm, ready ? 1 : 0, capacity_, assumed_longest_, ws_.data_ptr(), (size_t)ws_.numel(), counts, stamp_, cur_stream()), "gut_train_step_ex");
         // the counts were written by the scan kernel early in the step: by now they have long arrived (no GPU idle time behind this wait)
         check_rc(lfs_gut_step_wait(counts, stamp_, 30.0, &n_isects_, &longest_), "gut_step_wait");
         if (lfs_gut_step_fits(n_isects_, longest_, capacity_, assumed_longest_)) {
             colours_saved_ += ready ? 1 : 0;
-            for (torch::Tensor* t : {&means, &sh0, &shN, &raw_scales, &raw_quats, &raw_opacities}) bump(*t);   // in-place updates through raw pointers: visible to autograd / the staging slot
+            for (torch::Tensor* t : {&means, &sh0, &shN, &raw_scales, &raw_quats, &raw_opacities}) if (!(frozen && t == &shN)) bump(*t);   // in-place updates through raw pointers: visible to autograd / the staging slot
             if (next_vm != nullptr) {
                 ColoursFor& c = colours_for_;
                 c.valid = true; c.viewmat = next_viewmat->data_ptr(); c.viewmat_version = (uint32_t)next_viewmat->_version(); c.ws = ws_.data_ptr();

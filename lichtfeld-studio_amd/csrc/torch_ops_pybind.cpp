@@ -81,6 +81,27 @@ PYBIND11_MODULE(_lfs_torch_ops, m) {
             return self.step(params[0], params[1], params[2], params[3], params[4], params[5], ad, sh_degree, viewmat, K, W, H, background, target, weight, loss,
                              scale_reg, opacity_reg);
         })
+        // step_opt: step + next_viewmat + lfs::GutStepOptions (loss_kind, lambda_dssim, freeze_shN, noise, noise_lr); exp_avg[2] / exp_avg_sq[2] may be None when frozen
+        .def("step_opt", [](lfs::GutTrainStep& self, std::vector<at::Tensor> params, std::vector<OptT> exp_avg, std::vector<OptT> exp_avg_sq,
+                            std::vector<std::vector<float>> scalars, uint32_t sh_degree, at::Tensor viewmat, at::Tensor K, uint32_t W, uint32_t H, OptT background,
+                            at::Tensor target, float weight, at::Tensor loss, float scale_reg, float opacity_reg, OptT next_viewmat, uint32_t loss_kind, float lambda_dssim,
+                            bool freeze_shN, OptT noise, float noise_lr) {
+            TORCH_CHECK(params.size() == 6 && exp_avg.size() == 6 && exp_avg_sq.size() == 6 && scalars.size() == 6, "six parameter groups");
+            std::array<lfs::AdamGroupState, 6> ad;
+            for (int k = 0; k < 6; ++k) {
+                TORCH_CHECK(scalars[k].size() == 6, "six Adam scalars per group");
+                ad[k] = lfs::AdamGroupState{exp_avg[k].has_value() ? *exp_avg[k] : at::Tensor(), exp_avg_sq[k].has_value() ? *exp_avg_sq[k] : at::Tensor(), scalars[k][0],
+                                            scalars[k][1], scalars[k][2], scalars[k][3], scalars[k][4], scalars[k][5]};
+            }
+            lfs::GutStepOptions o;
+            o.loss_kind = loss_kind; o.lambda_dssim = lambda_dssim; o.freeze_shN = freeze_shN; o.noise = noise; o.noise_lr = noise_lr;
+            return self.step_opt(params[0], params[1], params[2], params[3], params[4], params[5], ad, sh_degree, viewmat, K, W, H, background, target, weight, loss,
+                                 scale_reg, opacity_reg, next_viewmat, o);
+        }, py::arg("params"), py::arg("exp_avg"), py::arg("exp_avg_sq"), py::arg("scalars"), py::arg("sh_degree"), py::arg("viewmat"), py::arg("K"), py::arg("W"), py::arg("H"),
+           py::arg("background"), py::arg("target"), py::arg("weight"), py::arg("loss"), py::arg("scale_reg") = 0.f, py::arg("opacity_reg") = 0.f,
+           py::arg("next_viewmat") = py::none(), py::arg("loss_kind") = 0u, py::arg("lambda_dssim") = 0.2f, py::arg("freeze_shN") = false, py::arg("noise") = py::none(),
+           py::arg("noise_lr") = 0.f)
+        .def("colour_launches_saved", &lfs::GutTrainStep::colour_launches_saved)
         .def("render", &lfs::GutTrainStep::render).def("alpha", &lfs::GutTrainStep::alpha).def("radii", &lfs::GutTrainStep::radii)
         .def("retries", &lfs::GutTrainStep::retries).def("capacity", &lfs::GutTrainStep::capacity);
     m.def("fusedssim", [](float C1, float C2, at::Tensor a, at::Tensor b, bool train) { return fusedssim(C1, C2, a, b, train); });

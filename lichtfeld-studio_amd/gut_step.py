@@ -32,6 +32,14 @@ class StepLayout(C.Structure):  # lfs_gut_step_layout
                                           "tile_offsets", "flatten_ids", "isect_ids", "counts", "abort_flag")]
 
 
+class StepOptions(C.Structure):  # lfs_gut_step_options
+    _fields_ = [("loss_kind", C.c_uint32), ("lambda_dssim", C.c_float), ("freeze_shN", C.c_uint32), ("noise", C.c_void_p), ("noise_lr", C.c_float),
+                ("loss_workspace", C.c_void_p), ("loss_workspace_bytes", C.c_size_t)]
+
+
+LOSS_KINDS = {"mse": 0, "l1_ssim": 1}
+
+
 class GutStep:
     """One workspace + the capacity bookkeeping for steps of one (N, W, H, tile) shape on one device."""
 
@@ -53,6 +61,7 @@ class GutStep:
         self.colors_for = None    # fused tail (lfs_gut_train_step_ex): what the workspace's SH colours were evaluated for by the previous step - (viewmat pointer, N, K,
                                   # degree, workspace pointer) - or None; a step for exactly that skips its SH colour kernel
         self.colour_launches_saved = 0
+        self.loss_ws: Optional[torch.Tensor] = None   # lfs_gut_train_step_opt, loss "l1_ssim": the SSIM derivative maps + dL/d(render) (lfs_gut_step_loss_workspace_bytes)
 
     # ---- workspace --------------------------------------------------------------------------------------------------------------------------
     def _ensure(self, N: int, W: int, H: int) -> None:
@@ -139,16 +148,38 @@ class GutStep:
     # ---- the step -------------------------------------------------------------------------------------------------------------------------------
     def train_step(self, params: Sequence[torch.Tensor], adam: Dict[str, dict], sh_degree: int, W: int, H: int, viewmat: torch.Tensor, Kmat: torch.Tensor,
                    bg: Optional[torch.Tensor], target_chw: torch.Tensor, weight: float, loss_acc: torch.Tensor, scale_reg: float = 0.0,
-                   opacity_reg: float = 0.0, pipelined: bool = False, fused_tail: bool = False, next_viewmat: Optional[torch.Tensor] = None) -> int:
+                   opacity_reg: float = 0.0, pipelined: bool = False, fused_tail: bool = False, next_viewmat: Optional[torch.Tensor] = None,
+                   loss: str = "mse", lambda_dssim: float = 0.2, freeze_shN: bool = False, noise: Optional[torch.Tensor] = None, noise_lr: float = 0.0) -> int:
         """Forward + backward + Adam on all six parameter tensors, in place; *loss_acc = weight * mse. `adam[name]` = FusedAdam.prepare_inline(param) for
         the six names of GROUPS. Returns n_isects.
         pipelined: lfs_gut_train_step_pipelined - the SH Adam pass of this step and the SH colours of the next run on the library's side stream, under the next step's
         front end. Same results; sh0 / shN and their moments then belong to that stream until join() (every other method of this class joins by itself).
         fused_tail: lfs_gut_train_step_ex - SH backward, the six Adam updates and (next_viewmat: the view the NEXT step renders, a tensor that stays untouched until then)
-        the next step's SH colours in one launch; a following step for exactly that view (same tensor, same N / K / degree / workspace) skips its SH colour kernel."""
+        the next step's SH colours in one launch; a following step for exactly that view (same tensor, same N / K / degree / workspace) skips its SH colour kernel.
+        loss "l1_ssim" (with lambda_dssim), freeze_shN (iteration <= 1000: FusedAdam skips shN - `adam` then needs no "shN" entry) and noise [N,3] + noise_lr (the MCMC
+        strategy's draw and lr * noise_lr, added to the means in front of their Adam update as lfs_add_noise would) select lfs_gut_train_step_opt: the fused-tail form for
+        what the reference trains. An attempt that did not fit applied nothing, the noise included: the re-run takes the same noise tensor."""
         lib = load_library()
         N = params[0].shape[0]
         K = 1 + params[2].shape[1]
+        opts = None
+        if loss != "mse" or freeze_shN or noise is not None:
+            if pipelined or not fused_tail:
+                raise LfsError("gut_step: loss / freeze_shN / noise need the fused-tail form (fused_tail=True, pipelined=False)")
+            if loss not in LOSS_KINDS:
+                raise LfsError(f"gut_step: unknown loss {loss!r}")
+            opts = StepOptions()
+            opts.loss_kind, opts.lambda_dssim, opts.freeze_shN = LOSS_KINDS[loss], float(lambda_dssim), int(bool(freeze_shN))
+            if noise is not None:
+                if not noise.is_cuda or not noise.is_contiguous() or noise.dtype != torch.float32 or noise.numel() != 3 * N:
+                    raise LfsError("gut_step: noise must be a contiguous float32 CUDA (HIP) tensor [N,3]")
+                opts.noise, opts.noise_lr = noise.data_ptr(), float(noise_lr)
+            if opts.loss_kind == 1:
+                need = int(lib.lfs_gut_step_loss_workspace_bytes(C.c_uint32(W), C.c_uint32(H)))
+                if self.loss_ws is None or self.loss_ws.numel() < need:
+                    self.loss_ws = None
+                    self.loss_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+                opts.loss_workspace, opts.loss_workspace_bytes = self.loss_ws.data_ptr(), self.loss_ws.numel()
         fn, what = (lib.lfs_gut_train_step_pipelined, "gut_train_step_pipelined") if pipelined else (lib.lfs_gut_train_step, "gut_train_step")
         for attempt in range(4):
             self._ensure(N, W, H)
@@ -159,9 +190,14 @@ class GutStep:
                 ready = self.colors_for is not None and self.colors_for == key(viewmat)
                 nxt = next_viewmat if (next_viewmat is not None and K <= 16) else None
                 self.colors_for = None   # (whatever happens below, the colours of THIS view are consumed / overwritten)
-                check(lib.lfs_gut_train_step_ex(C.byref(a), C.c_void_p(nxt.data_ptr()) if nxt is not None else None, C.c_int(int(ready)), C.c_int64(self.capacity),
-                                                C.c_int64(self.assumed_longest), C.c_void_p(self.ws.data_ptr()), C.c_size_t(self.ws.numel()),
-                                                C.c_void_p(self.counts.data_ptr()), C.c_int64(self._stamp), stream()), "gut_train_step_ex")
+                if opts is not None:
+                    check(lib.lfs_gut_train_step_opt(C.byref(a), C.byref(opts), C.c_void_p(nxt.data_ptr()) if nxt is not None else None, C.c_int(int(ready)),
+                                                     C.c_int64(self.capacity), C.c_int64(self.assumed_longest), C.c_void_p(self.ws.data_ptr()), C.c_size_t(self.ws.numel()),
+                                                     C.c_void_p(self.counts.data_ptr()), C.c_int64(self._stamp), stream()), "gut_train_step_opt")
+                else:
+                    check(lib.lfs_gut_train_step_ex(C.byref(a), C.c_void_p(nxt.data_ptr()) if nxt is not None else None, C.c_int(int(ready)), C.c_int64(self.capacity),
+                                                    C.c_int64(self.assumed_longest), C.c_void_p(self.ws.data_ptr()), C.c_size_t(self.ws.numel()),
+                                                    C.c_void_p(self.counts.data_ptr()), C.c_int64(self._stamp), stream()), "gut_train_step_ex")
                 if self._wait():
                     if nxt is not None:
                         self.colors_for = key(nxt)

@@ -211,16 +211,28 @@ class MCMC(_StrategyBase):
         return n_new
 
     @torch.no_grad()
-    def inject_noise(self) -> None:  # mcmc.cpp:342-360
+    def draw_noise(self):
+        """This step's normal deviates [N,3] and the step size lr * noise_lr inject_noise applies them with - one draw from the strategy's generator, so a caller that
+        folds the update into its own kernel (the trainer's one-call step) consumes the same stream of draws as post_backward does."""
         m = self.model
         lr = float(self.optimizer.param_groups[0]["lr"]) * self.noise_lr
         noise = torch.randn(m.means.shape, device=self.device, dtype=m.means.dtype, generator=self.generator)
+        return noise, lr
+
+    @torch.no_grad()
+    def inject_noise(self) -> None:  # mcmc.cpp:342-360
+        m = self.model
+        noise, lr = self.draw_noise()
         ops.add_noise(m.raw_opacities.detach(), m.raw_scales.detach(), m.raw_quats.detach(), noise, m.means.data, lr)
+
+    def post_backward_schedule(self, it: int) -> None:
+        """The part of post_backward that is neither refinement nor noise: the SH-degree schedule (mcmc.cpp:366-368)."""
+        if it % self.params.sh_degree_interval == 0:
+            self.increment_sh_degree()
 
     @torch.no_grad()
     def post_backward(self, it: int) -> None:  # mcmc.cpp:362-384
-        if it % self.params.sh_degree_interval == 0:
-            self.increment_sh_degree()
+        self.post_backward_schedule(it)
         if self.is_refining(it):
             self.relocate_gs()
             self.add_new_gs()

@@ -25,11 +25,12 @@ class StepPlan:
     inline_shard: bool   # SH-sharded: the owners' multi-view SH backward applies the shard's Adam update
     multi: bool          # the multi-rank code path (world > 1, or LFS_DIST_FORCE_COLLECTIVES on one GPU)
     skip_deferred: bool  # the shN segment stays out of the flat all-reduce
+    freeze_shN: bool = False   # one-call form with options (plan_step(one_call=True)): FusedAdam skips shN this step (iteration <= 1000), the tail leaves it alone
 
 
 def plan_step(*, rasterizer: str, fused_l2: bool, world: int, force_collectives: bool, sh_sharded: bool, shard_rows: int, n_views: int, loss: str,
               strategy: Optional[str], refining: bool, iteration: int, has_shN: bool, optimizer_fused: bool, bilateral: bool, inline_shN_adam: bool = True,
-              inline_all_adam: bool = True, cxx_step: bool = True, batch_views: bool = True, factored_sh: bool = False) -> StepPlan:
+              inline_all_adam: bool = True, cxx_step: bool = True, batch_views: bool = True, factored_sh: bool = False, one_call: bool = False) -> StepPlan:
     """Pure function of the configuration -> the step form. The rules, in the order they are applied:
       * fastgs rasterizer -> its own step; fused_l2 off -> torch autograd over the op-by-op mirror.
       * shN's Adam update moves into the SH backward (inline_shN) when Adam reads shN anyway (iteration > 1000, fused_adam.cpp:68-70), there IS an shN, the
@@ -41,7 +42,10 @@ def plan_step(*, rasterizer: str, fused_l2: bool, world: int, force_collectives:
       * inline_all (no gradient tensor at all) = inline_shN on one view / one rank + MSE + no strategy + no bilateral grid.
       * C++ step driver (cxx_step): inline_all -> ONE call (cxx_all); otherwise its per-view form whenever the layout is replicated and the rank has one view
         or runs the multi-rank path (cxx_views). Several views on one rank without collectives -> batch_views. Everything else - SH-sharded ranks, cxx_step
-        off - -> the kernels enqueued from Python view by view (py_views)."""
+        off - -> the kernels enqueued from Python view by view (py_views).
+      * one_call (opt-in, GutTrainer(one_call=True)): one view on one rank ALSO takes the one-call form (cxx_all, lfs_gut_train_step_opt) for what the reference trains -
+        loss "mse" or "l1_ssim", no strategy or MCMC between refinements (its noise is folded into the tail), at ANY iteration (<= 1000: freeze_shN, the tail skips
+        shN as FusedAdam does) - given the fused optimizer, an shN, cxx_step and no bilateral grid. Everything else keeps the form it has with the keyword off."""
     multi = world > 1 or force_collectives
     if rasterizer == "fastgs":
         return StepPlan("fastgs", False, False, False, multi, iteration <= 1000)
@@ -53,6 +57,9 @@ def plan_step(*, rasterizer: str, fused_l2: bool, world: int, force_collectives:
     inline_all = inline_one and inline_all_adam and strategy is None and loss == "mse" and not bilateral
     inline_shard = inline_shN_adam and sh_sharded and n_views == 1 and adam_reads_shN and shard_rows > 0 and not refining
     skip_deferred = iteration <= 1000 or sh_sharded
+    if (one_call and cxx_step and not multi and not sh_sharded and n_views == 1 and strat_ok and has_shN and optimizer_fused and not bilateral
+            and loss in ("mse", "l1_ssim")):
+        return StepPlan("cxx_all", adam_reads_shN, True, False, multi, skip_deferred, freeze_shN=not adam_reads_shN)
     if factored_sh and multi and not sh_sharded:
         # replicated layout with the factored SH exchange (dist.ColorGradExchange): per view rasterizer backward + finish, rows gathered, ONE multi-view SH backward
         # over every rank's views with shN's Adam update inside whenever Adam reads shN and no refinement rewrites it first; sh0 / shN never enter the all-reduce
@@ -75,10 +82,14 @@ class GutTrainer:
                  views_per_rank: int = 1, fused_adam: bool = True, fused_l2: bool = True, loss: str = "mse", lambda_dssim: float = 0.2,
                  strategy: Optional[str] = None, opt_params=None, scene_scale: float = 1.0, seed: int = 0, rasterizer: str = "gut",
                  use_bilateral_grid: bool = False, bilateral_grid_dims=(16, 16, 8), bilateral_grid_lr: float = 2e-3, tv_loss_weight: float = 10.0,
-                 sh_sharded: Optional[bool] = None, factored_sh: bool = False):
+                 sh_sharded: Optional[bool] = None, factored_sh: bool = False, one_call: bool = False):
         """strategy: None (fixed set of Gaussians: the benchmark), "mcmc" (strategies.MCMC: relocation + growth + SGLD noise, with
         the scale / opacity regularisers of trainer.cpp:132-158) or "default" (ADC; needs densification_info, see strategies.py).
-        `seed` seeds the strategy's generator: the same on every rank, so replicas densify identically."""
+        `seed` seeds the strategy's generator: the same on every rank, so replicas densify identically.
+        one_call: one view per step on one rank takes the one-call C++ step (no host read, no gradient tensors) for loss "l1_ssim", for MCMC between refinements and
+        while iteration <= 1000 as well, not only for the MSE benchmark configuration (plan_step). Same trajectory as the default forms; off by default. A model with
+        SH degree 4 (more than 16 coefficients per channel) keeps the default forms: the switch has no effect there."""
+        self.one_call = bool(one_call)
         self.device, self.world, self.rank, self.views_per_rank = device, world, rank, views_per_rank
         sc = scene.to(device)
         self.scene = sc
@@ -390,7 +401,10 @@ class GutTrainer:
                          iteration=self.iteration, has_shN=self.model.shN.shape[1] > 0, optimizer_fused=bool(getattr(self.optimizer, "fused", False)),
                          bilateral=self.bilateral is not None, inline_shN_adam=self.inline_shN_adam, inline_all_adam=self.inline_all_adam,
                          cxx_step=self.cxx_step and self.rasterizer != "fastgs" and self.fused_l2 and self._cxx_supported(), batch_views=self.batch_views,
-                         factored_sh=self.factored_sh)
+                         factored_sh=self.factored_sh,
+                         # (a strategy stops updating at its last iteration, strategies._StrategyBase.step: those steps keep the split form; so does a model with
+                         #  SH degree 4 - K = 25 > 16: the fused tail, which carries the freeze and the noise, has no instantiation for it)
+                         one_call=self.one_call and (st is None or self.iteration < st.params.iterations) and 1 + self.model.shN.shape[1] <= 16)
 
     def _gut(self):
         from .gut_step import GutStep
@@ -399,14 +413,23 @@ class GutTrainer:
         return self._gut_step
 
     def _step_cxx_all(self, plan, targets, views, total_views) -> None:
-        """One view, one rank, MSE, iteration > 1000: forward + backward + Adam on all six tensors as ONE C++ call (csrc/gut_step.hip), no gradient tensors."""
-        inline_all = {name: self.optimizer.prepare_inline(getattr(self.model, name)) for name in ("shN", "means", "sh0", "raw_scales", "raw_quats", "raw_opacities")}
+        """One view, one rank, MSE, iteration > 1000: forward + backward + Adam on all six tensors as ONE C++ call (csrc/gut_step.hip), no gradient tensors.
+        With one_call=True also L1 + D-SSIM, MCMC between refinements (the step's noise is drawn HERE, from the strategy's generator, where post_backward would have
+        drawn it) and iteration <= 1000 (plan.freeze_shN: no inline state for shN - FusedAdam.step counts the skipped step itself, as in the split form)."""
+        names = ("means", "sh0", "raw_scales", "raw_quats", "raw_opacities") if plan.freeze_shN else ("shN", "means", "sh0", "raw_scales", "raw_quats", "raw_opacities")
+        inline_all = {name: self.optimizer.prepare_inline(getattr(self.model, name)) for name in names}
         gs, sc, v = self._gut(), self.scene, views[0]
         N = self.model.means.shape[0]
+        extra = {}
+        if self.one_call:
+            extra = dict(loss=self.loss_kind, lambda_dssim=self.lambda_dssim, freeze_shN=plan.freeze_shN)
+            if self.strategy is not None:
+                extra["noise"], extra["noise_lr"] = self.strategy.draw_noise()
+        opt_form = bool(extra) and (self.loss_kind != "mse" or plan.freeze_shN or "noise" in extra)   # lfs_gut_train_step_opt: always the fused-tail form
         self.last_n_isects = gs.train_step([p.detach() for p in self.model.parameters()], inline_all, self.model.get_active_sh_degree(), sc.width, sc.height,
                                            sc.viewmats[v], sc.Ks[v], self.bg, targets[0], 1.0 / total_views, self.loss_acc, self.scale_reg, self.opacity_reg,
-                                           pipelined=self.pipelined, fused_tail=self.fused_tail,
-                                           next_viewmat=None if self._next_view is None else sc.viewmats[self._next_view])
+                                           pipelined=self.pipelined and not opt_form, fused_tail=self.fused_tail or opt_form,
+                                           next_viewmat=None if self._next_view is None else sc.viewmats[self._next_view], **extra)
         self._last_radii = gs.view("radii", torch.int32, (1, N, 2))
 
     def join_pipeline(self) -> None:
@@ -547,7 +570,9 @@ class GutTrainer:
         for p, gv in zip(params, self.bucket.views):
             p.grad = gv
         if self.strategy is not None:  # trainer.cpp:741-760: post_backward (may replace the parameter tensors) then step
-            if self.sh_exchange is not None and self.strategy.is_refining(self.iteration):
+            if plan.path == "cxx_all":   # (one_call: the noise went into the tail - what is left of post_backward is the SH schedule)
+                self.strategy.post_backward_schedule(self.iteration)
+            elif self.sh_exchange is not None and self.strategy.is_refining(self.iteration):
                 self._refine_with_full_shN(lambda: self.strategy.post_backward(self.iteration))
             else:
                 self.strategy.post_backward(self.iteration)
