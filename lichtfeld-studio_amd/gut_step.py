@@ -58,8 +58,8 @@ class GutStep:
         self.longest = 0
         self.wait_poll_s = 5.0    # how long _wait spins on the pinned counts before it falls back to a stream synchronisation
         self.retries = 0          # attempts that did not fit (each one is re-run): a few right after start-up or a densification, none in steady state
-        self.colors_for = None    # fused tail (lfs_gut_train_step_ex): what the workspace's SH colours were evaluated for by the previous step - (viewmat pointer, N, K,
-                                  # degree, workspace pointer) - or None; a step for exactly that skips its SH colour kernel
+        self.colors_for = None    # fused tail (lfs_gut_train_step_ex): what the workspace's SH colours were evaluated for by the previous step - (viewmat pointer and version, N, K,
+                                  # degree, workspace pointer, pointers and versions of means / sh0 / shN) - or None; a step for exactly that skips its SH colour kernel
         self.colour_launches_saved = 0
         self.loss_ws: Optional[torch.Tensor] = None   # lfs_gut_train_step_opt, loss "l1_ssim": the SSIM derivative maps + dL/d(render) (lfs_gut_step_loss_workspace_bytes)
 
@@ -186,7 +186,11 @@ class GutStep:
             a = self._args(params, sh_degree, W, H, viewmat, Kmat, bg, target_chw, weight, scale_reg, opacity_reg, loss_acc, adam)
             self._stamp += 1
             if fused_tail and not pipelined:
-                key = lambda vm: (vm.data_ptr(), N, K, sh_degree, self.ws.data_ptr(), params[0].data_ptr(), params[1].data_ptr(), params[2].data_ptr())   # (replaced parameter tensors void the colours too)
+                # (replaced parameter tensors void the colours too - and so does an in-place write to the view matrix, means, sh0 or shN between the two steps: their
+                #  autograd version counters, which a detach() or an index view shares with its base, as the C++ GutTrainStep compares them. The step's own updates go
+                #  through raw pointers and leave the counters alone: the fast path stays.)
+                key = lambda vm: (vm.data_ptr(), vm._version, N, K, sh_degree, self.ws.data_ptr(), params[0].data_ptr(), params[1].data_ptr(), params[2].data_ptr(),
+                                  params[0]._version, params[1]._version, params[2]._version)
                 ready = self.colors_for is not None and self.colors_for == key(viewmat)
                 nxt = next_viewmat if (next_viewmat is not None and K <= 16) else None
                 self.colors_for = None   # (whatever happens below, the colours of THIS view are consumed / overwritten)

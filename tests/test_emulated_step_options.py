@@ -68,9 +68,12 @@ def _adam_scalars(k, t):
     return (LRS[k], 0.9, 0.999, 1e-15, 1.0 / (1.0 - 0.9 ** t), 1.0 / np.sqrt(1.0 - 0.999 ** t))
 
 
-def _train(lib, sc, form, steps, loss="mse", freeze=False, noise=False, shrink_on_step=None, capacity=None, opts_null=False):
+def _train(lib, sc, form, steps, loss="mse", freeze=False, noise=False, shrink_on_step=None, capacity=None, opts_null=False, on_step=None):
     """form: "opt" (lfs_gut_train_step_opt) | "ex" (lfs_gut_train_step_ex) | "ref" (the composition of the split entry points).
-    shrink_on_step: that step's FIRST attempt runs with a capacity of 8 entries; the state after it is recorded (`after_failed`) and the step is run again."""
+    shrink_on_step: that step's FIRST attempt runs with a capacity of 8 entries; the state after it is recorded (`after_failed`) and the step is run again.
+    A scene may name its own image size (sc["W"], sc["H"]) and have no background (sc["bg"] None); on_step(it, params, m, v, loss) is called after every step
+    (tests/test_emulated_step_reference.py looks at each step through it)."""
+    W, H = sc.get("W", globals()["W"]), sc.get("H", globals()["H"])
     ns = _defs()
     StepArgs, StepLayout, StepOptions = ns["StepArgs"], ns["StepLayout"], ns["StepOptions"]
     N = sc["means"].shape[0]
@@ -87,7 +90,8 @@ def _train(lib, sc, form, steps, loss="mse", freeze=False, noise=False, shrink_o
     v = [np.zeros_like(p) for p in params]
     grads = [np.zeros_like(p) for p in params]
     v_render = np.zeros((H, W, 3), np.float32)
-    Km, bg, target = [np.ascontiguousarray(sc[k], np.float32) for k in ("K", "bg", "target")]
+    Km, target = [np.ascontiguousarray(sc[k], np.float32) for k in ("K", "target")]
+    bg = None if sc["bg"] is None else np.ascontiguousarray(sc["bg"], np.float32)
     vms = sc["vms"]
     lossv = np.zeros(1, np.float32)
     out = dict(losses=[], fitted=[], rc=[], after_failed=None)
@@ -100,7 +104,7 @@ def _train(lib, sc, form, steps, loss="mse", freeze=False, noise=False, shrink_o
         for k in range(6):
             for j, val in enumerate(_adam_scalars(k, it + 1)):
                 a.adam[k][j] = val
-        a.viewmat, a.Kmat, a.background = vm.ctypes.data, Km.ctypes.data, bg.ctypes.data
+        a.viewmat, a.Kmat, a.background = vm.ctypes.data, Km.ctypes.data, (None if bg is None else bg.ctypes.data)
         a.loss_weight, a.scale_reg, a.opacity_reg = 1.0, 0.01, 0.01
         nz = sc["noise"][it] if noise else None
         attempts = [8, capacity] if shrink_on_step == it else [capacity]
@@ -162,6 +166,8 @@ def _train(lib, sc, form, steps, loss="mse", freeze=False, noise=False, shrink_o
             if not fit:
                 out["after_failed"] = dict(params=[p.copy() for p in params], m=[x.copy() for x in m], v=[x.copy() for x in v])
         out["losses"].append(float(lossv[0]))
+        if on_step is not None:
+            on_step(it, params, m, v, float(lossv[0]))
     return dict(out, params=params, m=m, v=v)
 
 

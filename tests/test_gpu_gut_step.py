@@ -349,3 +349,44 @@ def test_fused_tail_colours_are_dropped_when_the_next_step_is_another_one(lfs):
     assert a.model.active_sh_degree == 3
     assert 1 <= a._gut_step.colour_launches_saved <= 4
     _same_state(a, b, 7)
+
+
+@pytest.mark.parametrize("what", ["means", "sh0", "shN", "viewmat"])
+def test_fused_tail_colours_are_dropped_after_an_in_place_write(lfs, what):
+    """The tail evaluated the next view's colours; the caller then writes IN PLACE (same storage, same pointer: add_ / copy_) to means, sh0, shN or the next view's
+    matrix. Pointers and sizes cannot tell - the tensors' version counters do (the C++ GutTrainStep compares them as well): the next step must evaluate its own colours,
+    and the run stays, bit for bit, that of the three-pass step, which hands nothing over. The step's own raw-pointer updates do not count as writes: the steps before
+    and after the edit still skip their colour kernel."""
+    from lichtfeld_studio_amd import scenes
+    from lichtfeld_studio_amd.trainer import GutTrainer
+    sc = scenes._syn_box("SYN-T", 9, 2000, 320, 192, 260.0, 5, sh_degree=3)
+    target = torch.rand(3, sc.height, sc.width, generator=torch.Generator().manual_seed(8)).to(DEV) * 0.7
+    lib = lfs.load_library()
+    try:
+        lib.lfs_set_debug_flags(16)
+        a, b = GutTrainer(sc, DEV, iterations=7000), GutTrainer(sc, DEV, iterations=7000)
+        a.fused_tail, b.fused_tail = True, False
+        a.iteration = b.iteration = 3500
+        a.model.active_sh_degree = b.model.active_sh_degree = 3   # (at degree 0 the colours depend on neither the means nor the view)
+        for it in range(5):
+            if it == 3:
+                assert a._gut_step.colour_launches_saved == 2 and a._gut_step.colors_for is not None
+                for tr in (a, b):
+                    with torch.no_grad():
+                        if what == "viewmat":
+                            ptr = tr.scene.viewmats.data_ptr()
+                            tr.scene.viewmats[:, :3, 3].add_(0.05)
+                            assert tr.scene.viewmats.data_ptr() == ptr
+                        else:
+                            p = getattr(tr.model, what)
+                            ptr = p.data_ptr()
+                            p.copy_(p * 1.05 + 0.02) if what == "means" else p.add_(0.1)
+                            assert p.data_ptr() == ptr
+            la, lb = a.train_step([target]), b.train_step([target])
+            assert a.last_plan.path == b.last_plan.path == "cxx_all"
+        torch.cuda.synchronize()
+    finally:
+        lib.lfs_set_debug_flags(0)
+    assert a.last_n_isects == b.last_n_isects > 0
+    _same_state(a, b, 5)
+    assert a._gut_step.colour_launches_saved == 3 and b._gut_step.colour_launches_saved == 0   # steps 1, 2 and 4: not the one after the edit
