@@ -1,6 +1,6 @@
 // lfs::GutTrainStep - the extension a patched reference trainer includes BESIDE its own gsplat/Ops.h (this header declares nothing Ops.h declares, so both can be
 // included in one translation unit: oracle/ref_raster_shim.cpp does, under `make -C oracle reflink`, next to the reference's own FusedAdam / SplatData / Camera).
-// Implemented in lichtfeld-studio_amd/csrc/torch_ops.cpp (liblfs_gsplat_torch.so) over lfs_gut_train_step_ex (include/lfs_gsplat.h, csrc/gut_step.hip).
+// Implemented in lichtfeld-studio_amd/csrc/torch_ops.cpp (liblfs_gsplat_torch.so) over lfs_gut_train_step_opt (include/lfs_gsplat.h, csrc/gut_step.hip; NULL options = lfs_gut_train_step_ex).
 #pragma once
 #include <torch/torch.h>
 #include <array>

@@ -17,8 +17,15 @@
 #include "lfs_step_internal.h"
 #include "lfs_prof.h"
 #include <chrono>
-#include <cstdlib>
 #include <thread>
+
+// The photometric-loss kernels (loss kind 1) live in ssim.hip. This file is also linked WITHOUT it (tests/test_emulated_step_pack.py builds the step driver from a fixed
+// list of sources), so the two entry points are weak references here: absent -> loss_kind 1 is LFS_E_UNSUPPORTED, everything else works. In liblfs_gsplat.so they are
+// always present.
+extern "C" __attribute__((weak)) size_t lfs_photometric_loss_workspace_bytes(uint32_t H, uint32_t W);
+extern "C" __attribute__((weak)) int lfs_photometric_loss_fwd_bwd(uint32_t H, uint32_t W, const float* render_hwc, const float* target_chw, float lambda_dssim, float weight,
+                                                                  float* v_render_hwc, float* loss, void* workspace, size_t workspace_bytes, lfs_stream_t stream);
+static bool have_loss_kernels() { return &lfs_photometric_loss_workspace_bytes != nullptr && &lfs_photometric_loss_fwd_bwd != nullptr; }
 
 namespace lfs {
 namespace {
@@ -69,34 +76,26 @@ bool step_ws(void* base, uint32_t N, uint32_t W, uint32_t H, uint32_t tile, int6
 
 struct Front { lfs_cameras cams; const int32_t* offsets; };
 
+// the camera block and the tile offsets every guarded rasterizer call of a view takes
+void front_of(const lfs_gut_step_args* a, const StepWs& w, Front& f) {
+    const uint32_t tile = a->tile_size, tw = (a->image_width + tile - 1) / tile, th = (a->image_height + tile - 1) / tile;
+    f.cams = lfs_cameras{};
+    f.cams.C = 1; f.cams.image_width = a->image_width; f.cams.image_height = a->image_height; f.cams.camera_model = LFS_CAMERA_PINHOLE; f.cams.rs_type = LFS_SHUTTER_GLOBAL;
+    f.cams.viewmats0 = a->viewmat; f.cams.Ks = a->Kmat;
+    f.offsets = isect_workspace_offsets(w.isect_ws, 1, a->N, tw, th);
+}
+
 // ---- the pipelined step's side stream -------------------------------------------------------------------------------------------------------------------
 // One per process (one process per GPU). The SH colour kernel of step k + 1 and the SH Adam kernel of step k live on it; three events tie it to the caller's
-// stream (see lfs_gut_train_step_pipelined below). `done` is what lfs_gut_pipeline_join makes a stream wait for.
+// stream (see the pipelined form below). `done` is what lfs_gut_pipeline_join makes a stream wait for.
 struct Pipeline {
     hipStream_t side = nullptr;
     hipEvent_t projected = nullptr, colours = nullptr, dirs = nullptr, done = nullptr;
     bool pending = false;   // a side-stream update has been enqueued since the last join
-    bool start_after_finish = false;
     int init() {
         if (side != nullptr) return LFS_OK;
-        hipError_t e = hipSuccess;
-#ifndef LFS_EMULATE
-        // measurement knobs (tools/r6_lease10.sh): LFS_PIPE_PRIO = low | high (side stream priority), LFS_PIPE_CUMASK = n (side stream confined to every n-th CU),
-        // LFS_PIPE_START = finish (the SH Adam pass starts behind the finish pass instead of beside it)
-        const char* prio = getenv("LFS_PIPE_PRIO"); const char* cum = getenv("LFS_PIPE_CUMASK"); const char* st = getenv("LFS_PIPE_START");
-        start_after_finish = st != nullptr && st[0] == 'f';
-        if (cum != nullptr && atoi(cum) > 1) {
-            const int every = atoi(cum);
-            uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (int cu = 0; cu < 256; ++cu) if (cu % every == 0) mask[cu >> 5] |= 1u << (cu & 31);
-            e = hipExtStreamCreateWithCUMask(&side, 8, mask);
-        } else if (prio != nullptr) {
-            int lo = 0, hi = 0;
-            (void)hipDeviceGetStreamPriorityRange(&lo, &hi);   // (numerically: lo = least urgent, hi = most urgent)
-            e = hipStreamCreateWithPriority(&side, hipStreamNonBlocking, prio[0] == 'l' ? lo : hi);
-        } else
-#endif
-        e = hipStreamCreateWithFlags(&side, hipStreamNonBlocking);   // (non-blocking: no implicit ordering against the legacy default stream torch may hand in)
+        // a plain stream, the SH Adam pass beside the finish pass: stream priority, CU masks and start-behind-finish were measured and rejected (profiles/r06/pipeline/README.md)
+        hipError_t e = hipStreamCreateWithFlags(&side, hipStreamNonBlocking);   // (non-blocking: no implicit ordering against the legacy default stream torch may hand in)
         if (e != hipSuccess) { side = nullptr; return (int)e; }
         for (hipEvent_t* ev : {&projected, &colours, &dirs, &done}) {
             e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
@@ -114,15 +113,44 @@ int auto_join(hipStream_t s) {
     return LFS_OK;
 }
 
+// what a call needs of its argument block: the forward's tensors only; all six Adam states; or all six with shN's optional (FusedAdam skips the frozen group)
+enum class Need { Forward, Adam, AdamFrozenShN };
+
+int check_args(const lfs_gut_step_args* a, Need need) {
+    if (!a || !a->means || !a->sh0 || !a->raw_scales || !a->raw_quats || !a->raw_opacities || !a->viewmat || !a->Kmat) return LFS_E_INVALID;
+    if (a->N == 0 || a->K == 0 || a->K > 32 || (a->K > 1 && !a->shN)) return LFS_E_INVALID;
+    if ((a->sh_degree + 1) * (a->sh_degree + 1) > a->K || a->sh_degree > 4) return LFS_E_INVALID;
+    if (need != Need::Forward) {
+        if (a->K < 2 || !a->target_chw || !a->loss) return LFS_E_INVALID;   // (degree-0-only models take the gradient-tensor step: there is no shN to update)
+        for (int k = 0; k < 6; ++k) if ((!a->exp_avg[k] || !a->exp_avg_sq[k]) && !(need == Need::AdamFrozenShN && k == 2)) return LFS_E_INVALID;
+    }
+    return LFS_OK;
+}
+
+// What every entry point does before it enqueues anything: check the arguments (and, for the training step, its options `o`), lay the workspace out, check its size, and
+// - `join` - make the stream wait for a pending side-stream update: every form but the pipelined one reads / writes sh0 and shN on the caller's stream.
+int open_step(const lfs_gut_step_args* a, Need need, const lfs_gut_step_options* o, int64_t capacity, void* workspace, size_t workspace_bytes, hipStream_t s, bool join,
+              StepWs& w) {
+    const int rc = check_args(a, need);
+    if (rc) return rc;
+    if (o && a->K > 16 && (o->freeze_shN || o->noise)) return LFS_E_UNSUPPORTED;   // the three-pass tail of degree 4 has neither (enqueue_tail)
+    if (!workspace) return LFS_E_INVALID;
+    if (!step_ws(workspace, a->N, a->image_width, a->image_height, a->tile_size, capacity, w, nullptr)) return LFS_E_INVALID;
+    if (workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
+    if (o && o->loss_kind == 1) {
+        if (!have_loss_kernels()) return LFS_E_UNSUPPORTED;
+        if (!o->loss_workspace) return LFS_E_INVALID;
+        if (o->loss_workspace_bytes < lfs_gut_step_loss_workspace_bytes(a->image_width, a->image_height)) return LFS_E_WORKSPACE;
+    }
+    return join ? auto_join(s) : LFS_OK;
+}
+
 // everything up to and including the rasterizer forward; shared by the Adam-inline step and the gradient-tensor step
 int enqueue_forward(const lfs_gut_step_args* a, const StepWs& w, int64_t capacity, int64_t assumed_longest, int64_t* host_counts, int64_t stamp, hipStream_t s, Front& f,
                     Pipeline* pipe = nullptr, bool colors_ready = false) {   // colors_ready: w.colors holds this view's SH colours already (the previous step's fused tail wrote them)
     const uint32_t N = a->N, W = a->image_width, H = a->image_height, tile = a->tile_size;
     const uint32_t tw = (W + tile - 1) / tile, th = (H + tile - 1) / tile;
-    lfs_cameras& cams = f.cams;
-    cams = lfs_cameras{};
-    cams.C = 1; cams.image_width = W; cams.image_height = H; cams.camera_model = LFS_CAMERA_PINHOLE; cams.rs_type = LFS_SHUTTER_GLOBAL;
-    cams.viewmats0 = a->viewmat; cams.Ks = a->Kmat;
+    front_of(a, w, f);
     const lfs_ut_params ut{0.1f, 2.f, 0.f, 0.1f, 1};   // Cameras.h:27-61 defaults, as the trainer passes them (rasterizer_autograd.cpp:223-234)
     // trainer constants of rasterizer.cpp:176-181: eps2d 0.3, near 0.01, far 1e4, radius_clip 0
     // the projection kernel also clears the intersection stage's per-tile totals and writes the rasterizer's camera state (first block of the raster workspace):
@@ -130,17 +158,22 @@ int enqueue_forward(const lfs_gut_step_args* a, const StepWs& w, int64_t capacit
     // Round 4: the SH colours are evaluated FIRST (for every Gaussian - visibility is not known yet, 6 % more coefficient rows on SYN-B) so that the projection
     // kernel, which has the activated quaternion / scale / opacity in registers, can write the rasterizer's 64-byte record and the 32-byte culling record of every
     // visible Gaussian itself: raster_pack_kernel's second pass over the Gaussians (0.040 ms, 152 MB re-read) is gone. Debug bit 6: the round-3 order (A/B, tests).
+    // Pipelined: the projection goes FIRST and packs the records without colours; the SH colours (visible Gaussians only - the radii exist now) follow on the side
+    // stream, behind the previous step's SH Adam kernel, into `colors` and into the rgb slots of the records; the main stream carries on with the tile lists and
+    // waits for them in front of the forward kernel.
     const bool pack_here = pipe != nullptr || !(lfs_get_debug_flags() & 64u);
     void *recs = nullptr, *cull = nullptr;
     raster_workspace_parts(w.raster_ws, N, nullptr, &recs, &cull);
     int rc = LFS_OK;
-    if (pipe != nullptr) {
-        // Pipelined: the projection goes FIRST and packs the records without colours; the SH colours (visible Gaussians only - the radii exist now) follow on the side
-        // stream, behind the previous step's SH Adam kernel, into `colors` and into the rgb slots of the records; the main stream carries on with the tile lists and
-        // waits for them in front of the forward kernel.
-        rc = activations_project_ut_impl(N, a->means, a->raw_quats, a->raw_scales, a->raw_opacities, &cams, 0.3f, 0.01f, 10000.f, 0.f, &ut, w.quats, w.scales,
-                                         w.opacities, w.radii, w.means2d, w.depths, isect_workspace_totals(w.isect_ws, 1, N, tw, th), tw * th, w.raster_ws, s, recs, cull, nullptr);
+    if (pipe == nullptr && pack_here && !colors_ready) {
+        rc = sh_model_fwd_impl(N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, nullptr, w.colors, s);
         if (rc) return rc;
+    }
+    rc = activations_project_ut_impl(N, a->means, a->raw_quats, a->raw_scales, a->raw_opacities, &f.cams, 0.3f, 0.01f, 10000.f, 0.f, &ut, w.quats, w.scales,
+                                     w.opacities, w.radii, w.means2d, w.depths, isect_workspace_totals(w.isect_ws, 1, N, tw, th), tw * th, w.raster_ws, s,
+                                     pack_here ? recs : nullptr, pack_here ? cull : nullptr, pack_here && pipe == nullptr ? w.colors : nullptr);
+    if (rc) return rc;
+    if (pipe != nullptr) {
         hipError_t e = hipEventRecord(pipe->projected, s);
         if (e == hipSuccess) e = hipStreamWaitEvent(pipe->side, pipe->projected, 0);
         if (e != hipSuccess) return (int)e;
@@ -148,26 +181,7 @@ int enqueue_forward(const lfs_gut_step_args* a, const StepWs& w, int64_t capacit
         if (rc) return rc;
         e = hipEventRecord(pipe->colours, pipe->side);
         if (e != hipSuccess) return (int)e;
-        const IsectGuard guard{capacity, assumed_longest, w.abort_flag};
-        int64_t* counts = host_counts ? host_counts : w.dev_counts;
-        rc = isect_count_impl(1, N, w.means2d, w.radii, tile, tw, th, w.tiles_per_gauss, counts, counts + 1, nullptr, LFS_ISECT_COUNTERS_ZERO, counts + 2, stamp, w.isect_ws,
-                              w.isect_ws_bytes, s, &guard);
-        if (rc) return rc;
-        rc = isect_emit_impl(1, N, w.means2d, w.radii, w.depths, tile, tw, th, 1, -1, w.tiles_per_gauss, w.isect_ids, w.flatten_ids, nullptr, w.binned, -1, w.isect_ws,
-                             w.isect_ws_bytes, s, &guard);
-        if (rc) return rc;
-        f.offsets = isect_workspace_offsets(w.isect_ws, 1, N, tw, th);
-        return raster_fwd_guarded(N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &cams, tile, f.offsets, w.flatten_ids, capacity, w.render, w.alpha,
-                                  w.last_ids, w.raster_ws, w.raster_ws_bytes, s, /*cams_ready=*/true, /*records_ready=*/true, /*wait_before_fwd=*/pipe->colours);
     }
-    if (pack_here && !colors_ready) {
-        rc = sh_model_fwd_impl(N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, nullptr, w.colors, s);
-        if (rc) return rc;
-    }
-    rc = activations_project_ut_impl(N, a->means, a->raw_quats, a->raw_scales, a->raw_opacities, &cams, 0.3f, 0.01f, 10000.f, 0.f, &ut, w.quats, w.scales,
-                                     w.opacities, w.radii, w.means2d, w.depths, isect_workspace_totals(w.isect_ws, 1, N, tw, th), tw * th, w.raster_ws, s,
-                                     pack_here ? recs : nullptr, pack_here ? cull : nullptr, pack_here ? w.colors : nullptr);
-    if (rc) return rc;
     const IsectGuard guard{capacity, assumed_longest, w.abort_flag};
     int64_t* counts = host_counts ? host_counts : w.dev_counts;   // [n_isects, longest tile list, stamp]
     rc = isect_count_impl(1, N, w.means2d, w.radii, tile, tw, th, w.tiles_per_gauss, counts, counts + 1, nullptr, LFS_ISECT_COUNTERS_ZERO, counts + 2, stamp, w.isect_ws,
@@ -180,37 +194,144 @@ int enqueue_forward(const lfs_gut_step_args* a, const StepWs& w, int64_t capacit
     rc = isect_emit_impl(1, N, w.means2d, w.radii, w.depths, tile, tw, th, 1, -1, w.tiles_per_gauss, w.isect_ids, w.flatten_ids, nullptr, w.binned, -1, w.isect_ws,
                          w.isect_ws_bytes, s, &guard);
     if (rc) return rc;
-    f.offsets = isect_workspace_offsets(w.isect_ws, 1, N, tw, th);
-    return raster_fwd_guarded(N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &cams, tile, f.offsets, w.flatten_ids, capacity, w.render, w.alpha,
-                              w.last_ids, w.raster_ws, w.raster_ws_bytes, s, /*cams_ready=*/true, /*records_ready=*/pack_here);
+    return raster_fwd_guarded(N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &f.cams, tile, f.offsets, w.flatten_ids, capacity, w.render, w.alpha,
+                              w.last_ids, w.raster_ws, w.raster_ws_bytes, s, /*cams_ready=*/true, /*records_ready=*/pack_here,
+                              /*wait_before_fwd=*/pipe != nullptr ? pipe->colours : nullptr);
 }
 
-int check_args(const lfs_gut_step_args* a, bool need_adam) {
-    if (!a || !a->means || !a->sh0 || !a->raw_scales || !a->raw_quats || !a->raw_opacities || !a->viewmat || !a->Kmat) return LFS_E_INVALID;
-    if (a->N == 0 || a->K == 0 || a->K > 32 || (a->K > 1 && !a->shN)) return LFS_E_INVALID;
-    if ((a->sh_degree + 1) * (a->sh_degree + 1) > a->K || a->sh_degree > 4) return LFS_E_INVALID;
-    if (need_adam) {
-        if (a->K < 2 || !a->target_chw || !a->loss) return LFS_E_INVALID;   // (degree-0-only models take the gradient-tensor step: there is no shN to update)
-        for (int k = 0; k < 6; ++k) if (!a->exp_avg[k] || !a->exp_avg_sq[k]) return LFS_E_INVALID;
-    }
-    return LFS_OK;
+// accumulator-rows rasterizer backward of the view in the workspace. v_render NULL: args->target_chw is the loss target, the clamped MSE is folded in; otherwise
+// v_render [H,W,3] is dL/d(render)
+int enqueue_backward(const lfs_gut_step_args* a, const StepWs& w, const Front& f, int64_t capacity, const float* v_render, hipStream_t s) {
+    if (v_render == nullptr)
+        return raster_bwd_mse_acc_guarded(a->N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &f.cams, a->tile_size, f.offsets, w.flatten_ids, capacity,
+                                          w.render, w.alpha, w.last_ids, a->target_chw, a->loss_weight, w.raster_ws, w.raster_ws_bytes, s);
+    return raster_bwd_acc_guarded(a->N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &f.cams, a->tile_size, f.offsets, w.flatten_ids, capacity, w.alpha,
+                                  w.last_ids, v_render, w.raster_ws, w.raster_ws_bytes, s);
 }
 
-// The tail as three per-Gaussian passes (SH backward + Adam on sh0 / shN, then finish + Adam on the other four tensors): lfs_gut_train_step, and what the fused-tail entry
-// points run for K > 16 (no colours for the next step). loss (nullable): receives the fused MSE of the backward.
-int three_pass_tail(const lfs_gut_step_args* a, const StepWs& w, float* loss, hipStream_t s) {
-    const float* acc_rows = reinterpret_cast<const float*>(static_cast<const char*>(w.raster_ws) + lfs_rasterize_workspace_acc_offset(1, a->N));
-    const int rc = sh_model_bwd_adam_all_impl(a->N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, w.radii, w.colors, acc_rows, w.v_dirs, a->exp_avg[1],
-                                              a->exp_avg_sq[1], a->adam[1], a->exp_avg[2], a->exp_avg_sq[2], a->adam[2], s, w.abort_flag);
-    if (rc) return rc;
-    // lfs_gut_finish_adam's order: means, raw_scales, raw_quats, raw_opacities = FusedAdam groups 0, 3, 4, 5
-    float* const m[4] = {a->exp_avg[0], a->exp_avg[3], a->exp_avg[4], a->exp_avg[5]};
-    float* const v[4] = {a->exp_avg_sq[0], a->exp_avg_sq[3], a->exp_avg_sq[4], a->exp_avg_sq[5]};
-    float sc[24];
+const float* acc_rows_of(const lfs_gut_step_args* a, const StepWs& w) {
+    return reinterpret_cast<const float*>(static_cast<const char*>(w.raster_ws) + lfs_rasterize_workspace_acc_offset(1, a->N));
+}
+
+// finish + activation backward + Adam on means, raw_scales, raw_quats, raw_opacities = FusedAdam groups 0, 3, 4, 5 (lfs_gut_finish_adam's order). loss (nullable):
+// receives the fused MSE of the backward.
+int finish_adam(const lfs_gut_step_args* a, const StepWs& w, float* loss, hipStream_t s) {
     const int grp[4] = {0, 3, 4, 5};
-    for (int k = 0; k < 4; ++k) for (int j = 0; j < 6; ++j) sc[6 * k + j] = a->adam[grp[k]][j];
+    float *m[4], *v[4], sc[24];
+    for (int k = 0; k < 4; ++k) {
+        m[k] = a->exp_avg[grp[k]]; v[k] = a->exp_avg_sq[grp[k]];
+        for (int j = 0; j < 6; ++j) sc[6 * k + j] = a->adam[grp[k]][j];
+    }
     return gut_finish_adam_impl(a->N, a->means, a->raw_scales, a->raw_quats, a->raw_opacities, w.quats, w.scales, w.opacities, w.v_dirs, m, v, sc, a->scale_reg,
                                 a->opacity_reg, loss, w.raster_ws, w.raster_ws_bytes, s, w.abort_flag);
+}
+
+// The tail as three per-Gaussian passes (SH backward + Adam on sh0 / shN, then finish + Adam on the other four tensors): the three-pass form, and what the fused-tail
+// form runs for K > 16 (no colours for the next step).
+int three_pass_tail(const lfs_gut_step_args* a, const StepWs& w, float* loss, hipStream_t s) {
+    const int rc = sh_model_bwd_adam_all_impl(a->N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, w.radii, w.colors, acc_rows_of(a, w), w.v_dirs, a->exp_avg[1],
+                                              a->exp_avg_sq[1], a->adam[1], a->exp_avg[2], a->exp_avg_sq[2], a->adam[2], s, w.abort_flag);
+    return rc ? rc : finish_adam(a, w, loss, s);
+}
+
+// The fused-tail form's tail: the three passes as ONE launch (raster.hip: gut_tail_kernel), with shN frozen and the MCMC noise on request. K > 16 (SH degree 4) has no
+// such kernel: the three passes run (the caller's next call must pass colors_ready = 0 - GutStep checks K); freeze and noise were refused by open_step.
+int enqueue_tail(const lfs_gut_step_args* a, const StepWs& w, const lfs_gut_step_options& o, const float* next_viewmat, float* loss, hipStream_t s) {
+    if (a->K > 16) return three_pass_tail(a, w, loss, s);
+    return gut_tail_impl(a->N, a->K, a->sh_degree, a->means, a->sh0, a->shN, a->raw_scales, a->raw_quats, a->raw_opacities, w.quats, w.scales, w.opacities, a->viewmat,
+                         next_viewmat, w.radii, w.colors, a->exp_avg, a->exp_avg_sq, a->adam, a->scale_reg, a->opacity_reg, loss, w.raster_ws, w.raster_ws_bytes, s,
+                         w.abort_flag, o.freeze_shN != 0, o.noise, o.noise_lr);
+}
+
+// The pipelined form's tail: the SH direction pass and the finish pass stay on the caller's stream, the SH Adam pass goes to the side stream, beside the finish pass.
+int pipelined_tail(const lfs_gut_step_args* a, const StepWs& w, Pipeline& pipe, hipStream_t s) {
+    int rc = sh_pipe_dirs_impl(a->N, a->K, a->sh_degree, a->means, a->viewmat, a->shN, w.radii, w.colors, acc_rows_of(a, w), w.v_dirs, w.handover, w.abort_flag,
+                               w.abort_snapshot, s);
+    if (rc) return rc;
+    hipError_t e = hipEventRecord(pipe.dirs, s);
+    if (e == hipSuccess) e = hipStreamWaitEvent(pipe.side, pipe.dirs, 0);
+    if (e != hipSuccess) return (int)e;
+    rc = sh_pipe_adam_impl(a->N, a->K, a->sh_degree, a->sh0, a->shN, w.handover, a->exp_avg[1], a->exp_avg_sq[1], a->adam[1], a->exp_avg[2], a->exp_avg_sq[2], a->adam[2],
+                           w.abort_snapshot, pipe.side);
+    if (rc) return rc;
+    e = hipEventRecord(pipe.done, pipe.side);
+    if (e != hipSuccess) return (int)e;
+    pipe.pending = true;
+    return finish_adam(a, w, a->loss, s);
+}
+
+// ---- the training step: ONE sequence (open -> forward -> [loss kernels] -> backward -> tail) in three forms ---------------------------------------------------
+//
+// ThreePass (lfs_gut_train_step): the tail is SH backward + Adam(sh0, shN) | finish + Adam(means, scales, quaternions, opacities).
+//
+// FusedTail (lfs_gut_train_step_ex / _opt): those passes as ONE launch, dL/d(dirs) handed over in registers - and, when the caller names the NEXT step's view
+// (next_viewmat, device [4,4]), that view's SH colours for every Gaussian from the coefficient rows as they leave their Adam update: the next call then passes
+// colors_ready = 1 and its SH colour kernel is not launched.
+//   three-pass :  ... backward | SH backward + Adam (0.26 ms) | finish + Adam (0.10) | [next step] SH colours (0.07) | projection ...
+//   fused tail :  ... backward | tail (SH backward + six Adam updates + next colours) | [next step] projection ...
+// colors_ready = 1 is the caller's statement that (a) the previous call on this workspace was this form with next_viewmat pointing at the matrix args->viewmat holds
+// now, (b) with the same N, K and sh_degree, (c) it fitted its buffers (lfs_gut_step_fits), and (d) nothing has written means / sh0 / shN since. gut_step.GutStep keeps that
+// book. Same results as the three-pass form, bit for bit in the deterministic accumulation mode.
+// With options - what the reference actually trains (trainer.cpp:122-126, mcmc.cpp:349-386, fused_adam.cpp:68-70): the photometric loss L1 + D-SSIM instead of the folded
+// MSE, the MCMC strategy's noise in front of the means' Adam update, and shN frozen while iteration <= 1000 - still one enqueue, no host read, no gradient tensor.
+// loss_kind 1:
+//   forward | memset(*loss) | ssim_fwd + ssim_bwd on the workspace's render -> loss_workspace (derivative maps, then v_render [H,W,3]) | accumulator-rows backward with that
+//   v_render | tail (loss == NULL: *loss was written by the loss kernels)
+// An attempt that did not fit rendered empty lists: its loss kernels see the background, its backward accumulates nothing, its tail returns at the abort flag - no parameter,
+// no moment and no noise is applied, and *loss holds the loss of the empty render. NULL or all-zero options: the step without options, bit for bit.
+//
+// Pipelined (lfs_gut_train_step_pipelined): the three-pass form with the step's HBM-bound SH kernels moved UNDER its latency- and VALU-bound front end (round 6). Same
+// arguments, same results (bit for bit in the deterministic accumulation mode); what changes is the ORDER across two streams:
+//
+//   stream (caller's)                                                         side stream (the library's)
+//   projection(k) -> records without colours ----- event `projected` ------>  SH colours(k): visible Gaussians, -> colors [N,3] + the rgb slots of the records
+//   tile count + scan, row / tile binning, sort, culling                      (behind SH Adam(k - 1): the coefficients it reads are the updated ones)
+//   <------------------------------------------------ event `colours` ------
+//   forward, backward (MSE folded in)
+//   SH direction pass(k): dL/d(dirs) + 32-byte hand-over rows --- `dirs` -->  SH Adam(k): sh0 / shN read-modify-write, 1.1 GB at 1 M Gaussians
+//   finish + Adam(means, scales, quaternions, opacities)                      |  runs under finish(k), projection(k + 1), binning(k + 1), sort, culling:
+//   [next call] projection(k + 1) ...                                         v  kernels that leave the HBM idle
+//
+// In the three-pass form everything is one chain, and 0.33 ms of it (SH backward + Adam, SH colours) is pure HBM time during which no other kernel can run, while the
+// front end (0.25 ms) is latency / LDS / VALU bound and moves < 1 TB/s. Contract: between two pipelined calls sh0, shN and their moments belong to the side stream -
+// call lfs_gut_pipeline_join(stream) before anything else reads or writes them on `stream` (another step form, a strategy, evaluation, a checkpoint): this form does NOT
+// join in front of itself. Every other tensor is ordered on `stream` as before. The price: the direction pass re-reads the coefficient rows of the Gaussians that
+// received a gradient (<= 180 MB).
+enum class Form { ThreePass, FusedTail, Pipelined };
+
+int train_step_impl(Form form, const lfs_gut_step_args* a, const lfs_gut_step_options* opts, const float* next_viewmat, int colors_ready, int64_t capacity,
+                    int64_t assumed_longest, void* workspace, size_t workspace_bytes, int64_t* host_counts, int64_t stamp, lfs_stream_t stream) {
+    const lfs_gut_step_options none{};
+    const lfs_gut_step_options& o = opts ? *opts : none;
+    if (o.loss_kind > 1) return LFS_E_INVALID;
+    const bool ssim = o.loss_kind == 1;
+    hipStream_t s = (hipStream_t)stream;
+    StepWs w;
+    int rc = open_step(a, o.freeze_shN ? Need::AdamFrozenShN : Need::Adam, &o, capacity, workspace, workspace_bytes, s, form != Form::Pipelined, w);
+    if (rc) return rc;
+    if (form == Form::Pipelined) {
+        rc = g_pipe.init();
+        if (rc) return rc;
+    }
+    Front f;
+    rc = enqueue_forward(a, w, capacity, assumed_longest, host_counts, stamp, s, f, form == Form::Pipelined ? &g_pipe : nullptr, colors_ready != 0);
+    if (rc) return rc;
+    float* v_render = nullptr;
+    if (ssim) {
+        const size_t maps_bytes = lfs_photometric_loss_workspace_bytes(a->image_height, a->image_width);
+        v_render = reinterpret_cast<float*>(static_cast<char*>(o.loss_workspace) + a256(maps_bytes));
+        const hipError_t e = hipMemsetAsync(a->loss, 0, sizeof(float), s);
+        if (e != hipSuccess) return (int)e;
+        rc = lfs_photometric_loss_fwd_bwd(a->image_height, a->image_width, w.render, a->target_chw, o.lambda_dssim, a->loss_weight, v_render, a->loss, o.loss_workspace,
+                                          maps_bytes, stream);
+        if (rc) return rc;
+    }
+    rc = enqueue_backward(a, w, f, capacity, v_render, s);
+    if (rc) return rc;
+    float* const tail_loss = ssim ? nullptr : a->loss;
+    if (form == Form::Pipelined) return pipelined_tail(a, w, g_pipe, s);
+    if (form == Form::FusedTail) return enqueue_tail(a, w, o, next_viewmat, tail_loss, s);
+    return three_pass_tail(a, w, tail_loss, s);
 }
 
 } // namespace
@@ -237,190 +358,30 @@ extern "C" int lfs_gut_step_fits(int64_t n_isects, int64_t longest, int64_t capa
     return (n_isects <= capacity && uint64_t(longest) <= uint64_t(sort_class_limit(assumed_longest))) ? 1 : 0;
 }
 
-extern "C" int lfs_gut_train_step(const lfs_gut_step_args* a, int64_t capacity, int64_t assumed_longest, void* workspace, size_t workspace_bytes,
-                                  int64_t* host_counts, int64_t stamp, lfs_stream_t stream) {
-    int rc = check_args(a, true);
-    if (rc) return rc;
-    if (!workspace) return LFS_E_INVALID;
-    StepWs w;
-    if (!step_ws(workspace, a->N, a->image_width, a->image_height, a->tile_size, capacity, w, nullptr)) return LFS_E_INVALID;
-    if (workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    rc = auto_join(s);
-    if (rc) return rc;
-    Front f;
-    rc = enqueue_forward(a, w, capacity, assumed_longest, host_counts, stamp, s, f);
-    if (rc) return rc;
-    rc = raster_bwd_mse_acc_guarded(a->N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &f.cams, a->tile_size, f.offsets, w.flatten_ids, capacity,
-                                    w.render, w.alpha, w.last_ids, a->target_chw, a->loss_weight, w.raster_ws, w.raster_ws_bytes, s);
-    if (rc) return rc;
-    return three_pass_tail(a, w, a->loss, s);
-}
-
-// lfs_gut_train_step with its three per-Gaussian tail passes as ONE (round 6; raster.hip: gut_tail_kernel): SH backward + Adam(sh0, shN) + finish + Adam(means, scales,
-// quaternions, opacities) in one launch, dL/d(dirs) handed over in registers - and, when the caller names the NEXT step's view (next_viewmat, device [4,4]), that view's SH
-// colours for every Gaussian from the coefficient rows as they leave their Adam update: the next call then passes colors_ready = 1 and its SH colour kernel is not launched.
-//   one-call step :  ... backward | SH backward + Adam (0.26 ms) | finish + Adam (0.10) | [next step] SH colours (0.07) | projection ...
-//   this form     :  ... backward | tail (SH backward + six Adam updates + next colours) | [next step] projection ...
-// colors_ready = 1 is the caller's statement that (a) the previous call on this workspace was this entry point with next_viewmat pointing at the matrix args->viewmat holds
-// now, (b) with the same N, K and sh_degree, (c) it fitted its buffers (lfs_gut_step_fits), and (d) nothing has written means / sh0 / shN since. gut_step.GutStep keeps that
-// book. Same results as lfs_gut_train_step, bit for bit in the deterministic accumulation mode. K > 16 (SH degree 4): the three separate passes run, as there.
-extern "C" int lfs_gut_train_step_ex(const lfs_gut_step_args* a, const float* next_viewmat, int colors_ready, int64_t capacity, int64_t assumed_longest, void* workspace,
-                                     size_t workspace_bytes, int64_t* host_counts, int64_t stamp, lfs_stream_t stream) {
-    int rc = check_args(a, true);
-    if (rc) return rc;
-    if (!workspace) return LFS_E_INVALID;
-    StepWs w;
-    if (!step_ws(workspace, a->N, a->image_width, a->image_height, a->tile_size, capacity, w, nullptr)) return LFS_E_INVALID;
-    if (workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    rc = auto_join(s);
-    if (rc) return rc;
-    Front f;
-    rc = enqueue_forward(a, w, capacity, assumed_longest, host_counts, stamp, s, f, nullptr, colors_ready != 0);
-    if (rc) return rc;
-    rc = raster_bwd_mse_acc_guarded(a->N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &f.cams, a->tile_size, f.offsets, w.flatten_ids, capacity,
-                                    w.render, w.alpha, w.last_ids, a->target_chw, a->loss_weight, w.raster_ws, w.raster_ws_bytes, s);
-    if (rc) return rc;
-    rc = gut_tail_impl(a->N, a->K, a->sh_degree, a->means, a->sh0, a->shN, a->raw_scales, a->raw_quats, a->raw_opacities, w.quats, w.scales, w.opacities, a->viewmat,
-                       next_viewmat, w.radii, w.colors, a->exp_avg, a->exp_avg_sq, a->adam, a->scale_reg, a->opacity_reg, a->loss, w.raster_ws, w.raster_ws_bytes, s, w.abort_flag);
-    if (rc != LFS_E_UNSUPPORTED) return rc;
-    // K > 16: the separate passes of lfs_gut_train_step (no colours for the next step: the caller's next call must pass colors_ready = 0 - GutStep checks K)
-    return three_pass_tail(a, w, a->loss, s);
-}
-
-// lfs_gut_train_step_ex for what the reference actually trains (trainer.cpp:122-126, mcmc.cpp:349-386, fused_adam.cpp:68-70): the photometric loss L1 + D-SSIM instead of
-// the folded MSE, the MCMC strategy's noise in front of the means' Adam update, and shN frozen while iteration <= 1000 - still one enqueue, no host read, no gradient
-// tensor. loss_kind 1:
-//   forward | memset(*loss) | ssim_fwd + ssim_bwd on the workspace's render -> loss_workspace (derivative maps, then v_render [H,W,3]) | accumulator-rows backward with that
-//   v_render | tail (loss == NULL: *loss was written by the loss kernels)
-// An attempt that did not fit rendered empty lists: its loss kernels see the background, its backward accumulates nothing, its tail returns at the abort flag - no parameter,
-// no moment and no noise is applied, and *loss holds the loss of the empty render.
-// The loss kernels live in ssim.hip. This file is also linked WITHOUT it (tests/test_emulated_step_pack.py builds the step driver from a fixed list of sources), so the
-// two entry points are weak references here: absent -> loss_kind 1 is LFS_E_UNSUPPORTED, everything else works. In liblfs_gsplat.so they are always present.
-extern "C" __attribute__((weak)) size_t lfs_photometric_loss_workspace_bytes(uint32_t H, uint32_t W);
-extern "C" __attribute__((weak)) int lfs_photometric_loss_fwd_bwd(uint32_t H, uint32_t W, const float* render_hwc, const float* target_chw, float lambda_dssim, float weight,
-                                                                  float* v_render_hwc, float* loss, void* workspace, size_t workspace_bytes, lfs_stream_t stream);
-static bool have_loss_kernels() { return &lfs_photometric_loss_workspace_bytes != nullptr && &lfs_photometric_loss_fwd_bwd != nullptr; }
-
 extern "C" size_t lfs_gut_step_loss_workspace_bytes(uint32_t image_width, uint32_t image_height) {
     if (!have_loss_kernels()) return 0;
     return a256(lfs_photometric_loss_workspace_bytes(image_height, image_width)) + a256(size_t(12) * image_width * image_height);
 }
 
-extern "C" int lfs_gut_train_step_opt(const lfs_gut_step_args* a, const lfs_gut_step_options* opts, const float* next_viewmat, int colors_ready, int64_t capacity,
-                                      int64_t assumed_longest, void* workspace, size_t workspace_bytes, int64_t* host_counts, int64_t stamp, lfs_stream_t stream) {
-    const lfs_gut_step_options none{};
-    const lfs_gut_step_options& o = opts ? *opts : none;
-    const bool freeze = o.freeze_shN != 0, ssim = o.loss_kind == 1;
-    if (!ssim && !freeze && !o.noise) {
-        if (o.loss_kind != 0) return LFS_E_INVALID;
-        return lfs_gut_train_step_ex(a, next_viewmat, colors_ready, capacity, assumed_longest, workspace, workspace_bytes, host_counts, stamp, stream);
-    }
-    if (o.loss_kind > 1) return LFS_E_INVALID;
-    // (check_args(.., true) with shN's moments optional while the group is frozen)
-    int rc = check_args(a, false);
-    if (rc) return rc;
-    if (a->K < 2 || !a->target_chw || !a->loss) return LFS_E_INVALID;
-    for (int k = 0; k < 6; ++k) if ((!a->exp_avg[k] || !a->exp_avg_sq[k]) && !(freeze && k == 2)) return LFS_E_INVALID;
-    if (a->K > 16 && (freeze || o.noise)) return LFS_E_UNSUPPORTED;   // the three-pass tail of degree 4 has neither
-    if (!workspace) return LFS_E_INVALID;
-    StepWs w;
-    if (!step_ws(workspace, a->N, a->image_width, a->image_height, a->tile_size, capacity, w, nullptr)) return LFS_E_INVALID;
-    if (workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
-    if (ssim) {
-        if (!have_loss_kernels()) return LFS_E_UNSUPPORTED;
-        if (!o.loss_workspace) return LFS_E_INVALID;
-        if (o.loss_workspace_bytes < lfs_gut_step_loss_workspace_bytes(a->image_width, a->image_height)) return LFS_E_WORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    rc = auto_join(s);
-    if (rc) return rc;
-    Front f;
-    rc = enqueue_forward(a, w, capacity, assumed_longest, host_counts, stamp, s, f, nullptr, colors_ready != 0);
-    if (rc) return rc;
-    if (ssim) {
-        const size_t maps_bytes = lfs_photometric_loss_workspace_bytes(a->image_height, a->image_width);
-        float* v_render = reinterpret_cast<float*>(static_cast<char*>(o.loss_workspace) + a256(maps_bytes));
-        const hipError_t e = hipMemsetAsync(a->loss, 0, sizeof(float), s);
-        if (e != hipSuccess) return (int)e;
-        rc = lfs_photometric_loss_fwd_bwd(a->image_height, a->image_width, w.render, a->target_chw, o.lambda_dssim, a->loss_weight, v_render, a->loss, o.loss_workspace,
-                                          maps_bytes, stream);
-        if (rc) return rc;
-        rc = raster_bwd_acc_guarded(a->N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &f.cams, a->tile_size, f.offsets, w.flatten_ids, capacity, w.alpha,
-                                    w.last_ids, v_render, w.raster_ws, w.raster_ws_bytes, s);
-    } else {
-        rc = raster_bwd_mse_acc_guarded(a->N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &f.cams, a->tile_size, f.offsets, w.flatten_ids, capacity,
-                                        w.render, w.alpha, w.last_ids, a->target_chw, a->loss_weight, w.raster_ws, w.raster_ws_bytes, s);
-    }
-    if (rc) return rc;
-    float* const tail_loss = ssim ? nullptr : a->loss;
-    if (a->K <= 16)
-        return gut_tail_impl(a->N, a->K, a->sh_degree, a->means, a->sh0, a->shN, a->raw_scales, a->raw_quats, a->raw_opacities, w.quats, w.scales, w.opacities, a->viewmat,
-                             next_viewmat, w.radii, w.colors, a->exp_avg, a->exp_avg_sq, a->adam, a->scale_reg, a->opacity_reg, tail_loss, w.raster_ws, w.raster_ws_bytes, s,
-                             w.abort_flag, freeze, o.noise, o.noise_lr);
-    // K > 16 with loss_kind 1 alone: the separate passes of lfs_gut_train_step (no colours for the next step)
-    return three_pass_tail(a, w, tail_loss, s);
+// the four entry points of the training step: argument adapters of train_step_impl
+extern "C" int lfs_gut_train_step(const lfs_gut_step_args* a, int64_t capacity, int64_t assumed_longest, void* workspace, size_t workspace_bytes,
+                                  int64_t* host_counts, int64_t stamp, lfs_stream_t stream) {
+    return train_step_impl(Form::ThreePass, a, nullptr, nullptr, 0, capacity, assumed_longest, workspace, workspace_bytes, host_counts, stamp, stream);
 }
 
-// lfs_gut_train_step with the step's HBM-bound SH kernels moved UNDER its latency- and VALU-bound front end (round 6). Same arguments, same results (bit for bit in
-// the deterministic accumulation mode); what changes is the ORDER across two streams:
-//
-//   stream (caller's)                                                         side stream (the library's)
-//   projection(k) -> records without colours ----- event `projected` ------>  SH colours(k): visible Gaussians, -> colors [N,3] + the rgb slots of the records
-//   tile count + scan, row / tile binning, sort, culling                      (behind SH Adam(k - 1): the coefficients it reads are the updated ones)
-//   <------------------------------------------------ event `colours` ------
-//   forward, backward (MSE folded in)
-//   SH direction pass(k): dL/d(dirs) + 32-byte hand-over rows --- `dirs` -->  SH Adam(k): sh0 / shN read-modify-write, 1.1 GB at 1 M Gaussians
-//   finish + Adam(means, scales, quaternions, opacities)                      |  runs under finish(k), projection(k + 1), binning(k + 1), sort, culling:
-//   [next call] projection(k + 1) ...                                         v  kernels that leave the HBM idle
-//
-// In lfs_gut_train_step everything is one chain, and 0.33 ms of it (SH backward + Adam, SH colours) is pure HBM time during which no other kernel can run, while the
-// front end (0.25 ms) is latency / LDS / VALU bound and moves < 1 TB/s. Contract: between two pipelined calls sh0, shN and their moments belong to the side stream -
-// call lfs_gut_pipeline_join(stream) before anything else reads or writes them on `stream` (another step form, a strategy, evaluation, a checkpoint). Every other
-// tensor is ordered on `stream` as before. The price: the direction pass re-reads the coefficient rows of the Gaussians that received a gradient (<= 180 MB).
+extern "C" int lfs_gut_train_step_ex(const lfs_gut_step_args* a, const float* next_viewmat, int colors_ready, int64_t capacity, int64_t assumed_longest, void* workspace,
+                                     size_t workspace_bytes, int64_t* host_counts, int64_t stamp, lfs_stream_t stream) {
+    return train_step_impl(Form::FusedTail, a, nullptr, next_viewmat, colors_ready, capacity, assumed_longest, workspace, workspace_bytes, host_counts, stamp, stream);
+}
+
+extern "C" int lfs_gut_train_step_opt(const lfs_gut_step_args* a, const lfs_gut_step_options* opts, const float* next_viewmat, int colors_ready, int64_t capacity,
+                                      int64_t assumed_longest, void* workspace, size_t workspace_bytes, int64_t* host_counts, int64_t stamp, lfs_stream_t stream) {
+    return train_step_impl(Form::FusedTail, a, opts, next_viewmat, colors_ready, capacity, assumed_longest, workspace, workspace_bytes, host_counts, stamp, stream);
+}
+
 extern "C" int lfs_gut_train_step_pipelined(const lfs_gut_step_args* a, int64_t capacity, int64_t assumed_longest, void* workspace, size_t workspace_bytes,
                                             int64_t* host_counts, int64_t stamp, lfs_stream_t stream) {
-    int rc = check_args(a, true);
-    if (rc) return rc;
-    if (!workspace) return LFS_E_INVALID;
-    StepWs w;
-    if (!step_ws(workspace, a->N, a->image_width, a->image_height, a->tile_size, capacity, w, nullptr)) return LFS_E_INVALID;
-    if (workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
-    rc = g_pipe.init();
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    Front f;
-    rc = enqueue_forward(a, w, capacity, assumed_longest, host_counts, stamp, s, f, &g_pipe);
-    if (rc) return rc;
-    rc = raster_bwd_mse_acc_guarded(a->N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &f.cams, a->tile_size, f.offsets, w.flatten_ids, capacity,
-                                    w.render, w.alpha, w.last_ids, a->target_chw, a->loss_weight, w.raster_ws, w.raster_ws_bytes, s);
-    if (rc) return rc;
-    const float* acc_rows = reinterpret_cast<const float*>(static_cast<const char*>(w.raster_ws) + lfs_rasterize_workspace_acc_offset(1, a->N));
-    rc = sh_pipe_dirs_impl(a->N, a->K, a->sh_degree, a->means, a->viewmat, a->shN, w.radii, w.colors, acc_rows, w.v_dirs, w.handover, w.abort_flag, w.abort_snapshot, s);
-    if (rc) return rc;
-    float* const m[4] = {a->exp_avg[0], a->exp_avg[3], a->exp_avg[4], a->exp_avg[5]};
-    float* const v[4] = {a->exp_avg_sq[0], a->exp_avg_sq[3], a->exp_avg_sq[4], a->exp_avg_sq[5]};
-    float sc[24];
-    const int grp[4] = {0, 3, 4, 5};
-    for (int k = 0; k < 4; ++k) for (int j = 0; j < 6; ++j) sc[6 * k + j] = a->adam[grp[k]][j];
-    if (g_pipe.start_after_finish) {
-        rc = gut_finish_adam_impl(a->N, a->means, a->raw_scales, a->raw_quats, a->raw_opacities, w.quats, w.scales, w.opacities, w.v_dirs, m, v, sc, a->scale_reg,
-                                  a->opacity_reg, a->loss, w.raster_ws, w.raster_ws_bytes, s, w.abort_flag);
-        if (rc) return rc;
-    }
-    hipError_t e = hipEventRecord(g_pipe.dirs, s);
-    if (e == hipSuccess) e = hipStreamWaitEvent(g_pipe.side, g_pipe.dirs, 0);
-    if (e != hipSuccess) return (int)e;
-    rc = sh_pipe_adam_impl(a->N, a->K, a->sh_degree, a->sh0, a->shN, w.handover, a->exp_avg[1], a->exp_avg_sq[1], a->adam[1], a->exp_avg[2], a->exp_avg_sq[2], a->adam[2],
-                           w.abort_snapshot, g_pipe.side);
-    if (rc) return rc;
-    e = hipEventRecord(g_pipe.done, g_pipe.side);
-    if (e != hipSuccess) return (int)e;
-    g_pipe.pending = true;
-    if (g_pipe.start_after_finish) return LFS_OK;
-    return gut_finish_adam_impl(a->N, a->means, a->raw_scales, a->raw_quats, a->raw_opacities, w.quats, w.scales, w.opacities, w.v_dirs, m, v, sc, a->scale_reg,
-                                a->opacity_reg, a->loss, w.raster_ws, w.raster_ws_bytes, s, w.abort_flag);
+    return train_step_impl(Form::Pipelined, a, nullptr, nullptr, 0, capacity, assumed_longest, workspace, workspace_bytes, host_counts, stamp, stream);
 }
 
 // `stream` waits for the side stream's last SH update (no host wait). Cheap and idempotent: call it whenever sh0 / shN / their moments are about to be used outside
@@ -440,49 +401,29 @@ extern "C" int lfs_gut_pipeline_join(lfs_stream_t stream) {
 //                                  caller's dL/d(render)), then the SH backward straight from the accumulator rows -> grads[1], grads[2] final for this view
 //   lfs_gut_view_backward_finish : rows + dL/d(dirs) -> grads[0], grads[3..5] (raster_finish + activation backward + regularisers); *loss += the fused MSE
 // An attempt that did not fit its buffers (lfs_gut_step_fits) rendered EMPTY lists: the caller checks the counts of the forward before it calls these.
-static int view_setup(const lfs_gut_step_args* a, int64_t capacity, void* workspace, size_t workspace_bytes, StepWs& w, lfs_cameras& cams, const int32_t*& offsets) {
-    int rc = check_args(a, false);
-    if (rc) return rc;
-    if (!workspace) return LFS_E_INVALID;
-    if (!step_ws(workspace, a->N, a->image_width, a->image_height, a->tile_size, capacity, w, nullptr)) return LFS_E_INVALID;
-    if (workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
-    const uint32_t tile = a->tile_size, tw = (a->image_width + tile - 1) / tile, th = (a->image_height + tile - 1) / tile;
-    cams = lfs_cameras{};
-    cams.C = 1; cams.image_width = a->image_width; cams.image_height = a->image_height; cams.camera_model = LFS_CAMERA_PINHOLE; cams.rs_type = LFS_SHUTTER_GLOBAL;
-    cams.viewmats0 = a->viewmat; cams.Ks = a->Kmat;
-    offsets = isect_workspace_offsets(w.isect_ws, 1, a->N, tw, th);
-    return LFS_OK;
-}
-
 extern "C" int lfs_gut_view_backward_sh(const lfs_gut_step_args* a, int64_t capacity, const float* v_render, float* const* grads /* [6] host */, int accumulate,
                                         void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
-    StepWs w; lfs_cameras cams; const int32_t* offsets;
-    int rc = view_setup(a, capacity, workspace, workspace_bytes, w, cams, offsets);
+    hipStream_t s = (hipStream_t)stream;
+    StepWs w;
+    int rc = open_step(a, Need::Forward, nullptr, capacity, workspace, workspace_bytes, s, true, w);
     if (rc) return rc;
     // args->exp_avg[2] given: shN's Adam step runs inside the SH backward (one view per step, one rank - the reference's MCMC / L1+D-SSIM / bilateral-grid
     // steps, whose other five tensors go through gradient tensors and FusedAdam); grads[2] is then neither read nor written
     const bool inline_shN = a->K > 1 && a->exp_avg[2] != nullptr;
     if (inline_shN && (accumulate || !a->exp_avg_sq[2])) return LFS_E_INVALID;
     if (!grads || !grads[1] || (a->K > 1 && !grads[2] && !inline_shN) || (!a->target_chw && !v_render)) return LFS_E_INVALID;
-    hipStream_t s = (hipStream_t)stream;
-    rc = auto_join(s);
+    Front f;
+    front_of(a, w, f);
+    rc = enqueue_backward(a, w, f, capacity, a->target_chw ? nullptr : v_render, s);
     if (rc) return rc;
-    if (a->target_chw)
-        rc = raster_bwd_mse_acc_guarded(a->N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &cams, a->tile_size, offsets, w.flatten_ids, capacity,
-                                        w.render, w.alpha, w.last_ids, a->target_chw, a->loss_weight, w.raster_ws, w.raster_ws_bytes, s);
-    else
-        rc = raster_bwd_acc_guarded(a->N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &cams, a->tile_size, offsets, w.flatten_ids, capacity, w.alpha,
-                                    w.last_ids, v_render, w.raster_ws, w.raster_ws_bytes, s);
-    if (rc) return rc;
-    const float* acc_rows = reinterpret_cast<const float*>(static_cast<const char*>(w.raster_ws) + lfs_rasterize_workspace_acc_offset(1, a->N));
-    return sh_model_bwd_rows_impl(a->N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, w.radii, w.colors, acc_rows, accumulate, grads[1], grads[2], w.v_dirs, s,
-                                  inline_shN ? a->exp_avg[2] : nullptr, inline_shN ? a->exp_avg_sq[2] : nullptr, inline_shN ? a->adam[2] : nullptr);
+    return sh_model_bwd_rows_impl(a->N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, w.radii, w.colors, acc_rows_of(a, w), accumulate, grads[1], grads[2], w.v_dirs,
+                                  s, inline_shN ? a->exp_avg[2] : nullptr, inline_shN ? a->exp_avg_sq[2] : nullptr, inline_shN ? a->adam[2] : nullptr);
 }
 
 extern "C" int lfs_gut_view_backward_finish(const lfs_gut_step_args* a, int64_t capacity, float* const* grads /* [6] host */, int accumulate,
                                             void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
-    StepWs w; lfs_cameras cams; const int32_t* offsets;
-    int rc = view_setup(a, capacity, workspace, workspace_bytes, w, cams, offsets);
+    StepWs w;
+    const int rc = open_step(a, Need::Forward, nullptr, capacity, workspace, workspace_bytes, (hipStream_t)stream, /*join=*/false, w);   // (the first half has joined)
     if (rc) return rc;
     if (!grads || !grads[0] || !grads[3] || !grads[4] || !grads[5] || (a->target_chw && !a->loss)) return LFS_E_INVALID;
     return gut_finish_grads_impl(a->N, a->means, a->raw_quats, w.quats, w.scales, w.opacities, a->scale_reg, a->opacity_reg, accumulate, grads[0], grads[3], grads[4],
@@ -495,17 +436,14 @@ extern "C" int lfs_gut_view_backward_finish(const lfs_gut_step_args* a, int64_t 
 // exchange the 3-float rows and each evaluates the multi-view SH backward (lfs_sh_model_bwd_views) over ALL views itself.
 extern "C" int lfs_gut_view_backward_rows(const lfs_gut_step_args* a, int64_t capacity, const float* v_render, float* const* grads /* [6] host */, int accumulate,
                                           float* v_colors_out, void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
-    StepWs w; lfs_cameras cams; const int32_t* offsets;
-    int rc = view_setup(a, capacity, workspace, workspace_bytes, w, cams, offsets);
+    hipStream_t s = (hipStream_t)stream;
+    StepWs w;
+    int rc = open_step(a, Need::Forward, nullptr, capacity, workspace, workspace_bytes, s, true, w);   // (the join is a no-op here: the view's forward has joined)
     if (rc) return rc;
     if (!grads || !grads[0] || !grads[3] || !grads[4] || !grads[5] || !v_colors_out || (!a->target_chw && !v_render) || (a->target_chw && !a->loss)) return LFS_E_INVALID;
-    hipStream_t s = (hipStream_t)stream;
-    if (a->target_chw)
-        rc = raster_bwd_mse_acc_guarded(a->N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &cams, a->tile_size, offsets, w.flatten_ids, capacity,
-                                        w.render, w.alpha, w.last_ids, a->target_chw, a->loss_weight, w.raster_ws, w.raster_ws_bytes, s);
-    else
-        rc = raster_bwd_acc_guarded(a->N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &cams, a->tile_size, offsets, w.flatten_ids, capacity, w.alpha,
-                                    w.last_ids, v_render, w.raster_ws, w.raster_ws_bytes, s);
+    Front f;
+    front_of(a, w, f);
+    rc = enqueue_backward(a, w, f, capacity, a->target_chw ? nullptr : v_render, s);
     if (rc) return rc;
     return gut_finish_grads_impl(a->N, a->means, a->raw_quats, w.quats, w.scales, w.opacities, a->scale_reg, a->opacity_reg, accumulate, grads[0], grads[3], grads[4],
                                  grads[5], v_colors_out, nullptr, a->target_chw ? a->loss : nullptr, w.raster_ws, w.raster_ws_bytes, s);
@@ -519,16 +457,12 @@ extern "C" int lfs_gut_view_backward(const lfs_gut_step_args* a, int64_t capacit
 
 extern "C" int lfs_gut_view_forward(const lfs_gut_step_args* a, int64_t capacity, int64_t assumed_longest, void* workspace, size_t workspace_bytes,
                                     int64_t* host_counts, int64_t stamp, lfs_stream_t stream) {
-    int rc = check_args(a, false);
-    if (rc) return rc;
-    if (!workspace) return LFS_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
     StepWs w;
-    if (!step_ws(workspace, a->N, a->image_width, a->image_height, a->tile_size, capacity, w, nullptr)) return LFS_E_INVALID;
-    if (workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
-    rc = auto_join((hipStream_t)stream);
+    const int rc = open_step(a, Need::Forward, nullptr, capacity, workspace, workspace_bytes, s, true, w);
     if (rc) return rc;
     Front f;
-    return enqueue_forward(a, w, capacity, assumed_longest, host_counts, stamp, (hipStream_t)stream, f);
+    return enqueue_forward(a, w, capacity, assumed_longest, host_counts, stamp, s, f);
 }
 
 // Wait until the counts of the call stamped `stamp` have arrived in pinned host memory (they were written early in the step; by the time the host has

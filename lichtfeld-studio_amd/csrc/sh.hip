@@ -447,18 +447,8 @@ __global__ void __launch_bounds__(64) sh_pipe_adam_kernel(const uint32_t n, cons
     }
 }
 
-// wavefronts the side-stream kernels of the pipelined step run with: LFS_PIPE_WAVES per CU (default 8 = two of a SIMD's eight slots) x 256 CUs
-static inline uint32_t sh_pipe_side_grid() {
-    static uint32_t g = 0;
-    if (g == 0) {
-        uint32_t per_cu = 8;
-#ifndef LFS_EMULATE
-        if (const char* e = getenv("LFS_PIPE_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= 32) per_cu = uint32_t(v); }
-#endif
-        g = 256u * per_cu;
-    }
-    return g;
-}
+// wavefronts the side-stream kernels of the pipelined step run with: 8 per CU (two of a SIMD's eight slots) x 256 CUs - the best of 4 .. 24 measured (profiles/r06/pipeline/README.md)
+static inline uint32_t sh_pipe_side_grid() { return 256u * 8u; }
 static inline int lanes_for(uint32_t k) { return k <= 1 ? 1 : k <= 4 ? 4 : k <= 16 ? 16 : 32; }
 
 template <bool MODEL>

@@ -442,7 +442,7 @@ int64_t GutTrainStep::run(torch::Tensor& means, torch::Tensor& sh0, torch::Tenso
     a.viewmat = viewmat.data_ptr<float>(); a.Kmat = K.data_ptr<float>();
     a.background = opt_ptr<float>(background); a.target_chw = target_chw.data_ptr<float>();
     a.loss_weight = loss_weight; a.scale_reg = scale_reg; a.opacity_reg = opacity_reg; a.loss = loss.data_ptr<float>();
-    // Round 6: the fused tail (lfs_gut_train_step_ex). The colours in the workspace are "ready" for this call when the previous call's tail evaluated them for exactly
+    // Round 6: the fused tail (lfs_gut_train_step_opt; without options it is lfs_gut_train_step_ex). The colours in the workspace are "ready" for this call when the previous call's tail evaluated them for exactly
     // this view tensor from exactly these parameter tensors and nothing has written to either since (storage address + autograd version: every in-place torch op and the
     // raw-pointer wrappers of this file bump the version; this step's own writes are recorded AFTER the call, below).
     const float* next_vm = nullptr;
@@ -482,10 +482,8 @@ int64_t GutTrainStep::run(torch::Tensor& means, torch::Tensor& sh0, torch::Tenso
         int64_t* counts = counts_.data_ptr<int64_t>();
         const bool ready = describes(colours_for_, viewmat);
         colours_for_.valid = false;   // whatever happens below, the colours of THIS view are consumed / overwritten
-        if (options != nullptr)
-            check_rc(lfs_gut_train_step_opt(&a, &o, next_vm, ready ? 1 : 0, capacity_, assumed_longest_, ws_.data_ptr(), (size_t)ws_.numel(), counts, stamp_, cur_stream()), "gut_train_step_opt");
-        else
-            check_rc(lfs_gut_train_step_ex(&a, next_vm, ready ? 1 : 0, capacity_, assumed_longest_, ws_.data_ptr(), (size_t)ws_.numel(), counts, stamp_, cur_stream()), "gut_train_step_ex");
+        check_rc(lfs_gut_train_step_opt(&a, options ? &o : nullptr, next_vm, ready ? 1 : 0, capacity_, assumed_longest_, ws_.data_ptr(), (size_t)ws_.numel(), counts, stamp_, cur_stream()),
+                 "gut_train_step_opt");
         // the counts were written by the scan kernel early in the step: by now they have long arrived (no GPU idle time behind this wait)
         check_rc(lfs_gut_step_wait(counts, stamp_, 30.0, &n_isects_, &longest_), "gut_step_wait");
         if (lfs_gut_step_fits(n_isects_, longest_, capacity_, assumed_longest_)) {

@@ -1,5 +1,7 @@
-"""Host side of csrc/gut_step.hip: the --gut training step as ONE C call (lfs_gut_train_step) and its split form for gradient tensors
-(lfs_gut_view_forward / lfs_gut_view_backward). Mirrors what Trainer::train_step does around rasterize() on the --gut path
+"""Host side of csrc/gut_step.hip: the --gut training step as ONE C call - lfs_gut_train_step (three tail passes), lfs_gut_train_step_opt (the fused tail, with the
+photometric loss, the MCMC noise and the shN freeze as options; lfs_gut_train_step_ex is the same call without options) and lfs_gut_train_step_pipelined (SH kernels on
+the library's side stream, lfs_gut_pipeline_join) - and its split form for gradient tensors: lfs_gut_view_forward, then lfs_gut_view_backward, its two halves
+lfs_gut_view_backward_sh / _finish, or lfs_gut_view_backward_rows for the factored exchange. Mirrors what Trainer::train_step does around rasterize() on the --gut path
 (/root/reference/src/training/trainer.cpp:579-770, rasterization/rasterizer.cpp:200-344) - minus the host synchronisation of
 gsplat/Intersect.cpp:75-76: the intersection lists live in a workspace sized for a CAPACITY, the count stays on the device, and this class
 looks at the (pinned) counts only after the whole step has been enqueued. An attempt that did not fit (count above capacity, or a tile list longer
@@ -58,7 +60,7 @@ class GutStep:
         self.longest = 0
         self.wait_poll_s = 5.0    # how long _wait spins on the pinned counts before it falls back to a stream synchronisation
         self.retries = 0          # attempts that did not fit (each one is re-run): a few right after start-up or a densification, none in steady state
-        self.colors_for = None    # fused tail (lfs_gut_train_step_ex): what the workspace's SH colours were evaluated for by the previous step - (viewmat pointer and version, N, K,
+        self.colors_for = None    # fused tail (lfs_gut_train_step_opt): what the workspace's SH colours were evaluated for by the previous step - (viewmat pointer and version, N, K,
                                   # degree, workspace pointer, pointers and versions of means / sh0 / shN) - or None; a step for exactly that skips its SH colour kernel
         self.colour_launches_saved = 0
         self.loss_ws: Optional[torch.Tensor] = None   # lfs_gut_train_step_opt, loss "l1_ssim": the SSIM derivative maps + dL/d(render) (lfs_gut_step_loss_workspace_bytes)
@@ -146,18 +148,43 @@ class GutStep:
         return 1024 if a <= 1024 else 4096 if a <= 4096 else 16384 if a <= 16384 else 1 << 62
 
     # ---- the step -------------------------------------------------------------------------------------------------------------------------------
+    def _ws_args(self):
+        """the trailing arguments of every speculative entry point: capacity, assumed_longest, workspace, workspace_bytes, host_counts, stamp, stream"""
+        return (C.c_int64(self.capacity), C.c_int64(self.assumed_longest), C.c_void_p(self.ws.data_ptr()), C.c_size_t(self.ws.numel()),
+                C.c_void_p(self.counts.data_ptr()), C.c_int64(self._stamp), stream())
+
+    def _attempt(self, N: int, W: int, H: int, args, enqueue, what: str, after_fit: bool = True) -> int:
+        """The one attempt loop of train_step (all forms) and view_forward: workspace -> argument block (args()) -> stamp -> enqueue(a) -> counts. An attempt that fitted
+        returns n_isects; one that did not applied nothing and is run again with a larger workspace. enqueue may return a callable(fitted) for book-keeping of its own
+        between the look at the counts and the growth of the workspace."""
+        for attempt in range(4):
+            self._ensure(N, W, H)
+            a = args()
+            self._stamp += 1
+            settle = enqueue(a)
+            fitted = self._wait()
+            if settle is not None:
+                settle(fitted)
+            if fitted:
+                if after_fit:
+                    self._after_fit()
+                return self.n_isects
+            self.retries += 1
+            self._grow(self.n_isects, self.longest)
+        raise LfsError(f"gut_step: the {what} did not fit its workspace after 4 attempts")
+
     def train_step(self, params: Sequence[torch.Tensor], adam: Dict[str, dict], sh_degree: int, W: int, H: int, viewmat: torch.Tensor, Kmat: torch.Tensor,
                    bg: Optional[torch.Tensor], target_chw: torch.Tensor, weight: float, loss_acc: torch.Tensor, scale_reg: float = 0.0,
                    opacity_reg: float = 0.0, pipelined: bool = False, fused_tail: bool = False, next_viewmat: Optional[torch.Tensor] = None,
                    loss: str = "mse", lambda_dssim: float = 0.2, freeze_shN: bool = False, noise: Optional[torch.Tensor] = None, noise_lr: float = 0.0) -> int:
         """Forward + backward + Adam on all six parameter tensors, in place; *loss_acc = weight * mse. `adam[name]` = FusedAdam.prepare_inline(param) for
-        the six names of GROUPS. Returns n_isects.
+        the six names of GROUPS. Returns n_isects. Default: lfs_gut_train_step (three tail passes).
         pipelined: lfs_gut_train_step_pipelined - the SH Adam pass of this step and the SH colours of the next run on the library's side stream, under the next step's
         front end. Same results; sh0 / shN and their moments then belong to that stream until join() (every other method of this class joins by itself).
-        fused_tail: lfs_gut_train_step_ex - SH backward, the six Adam updates and (next_viewmat: the view the NEXT step renders, a tensor that stays untouched until then)
+        fused_tail: lfs_gut_train_step_opt - SH backward, the six Adam updates and (next_viewmat: the view the NEXT step renders, a tensor that stays untouched until then)
         the next step's SH colours in one launch; a following step for exactly that view (same tensor, same N / K / degree / workspace) skips its SH colour kernel.
         loss "l1_ssim" (with lambda_dssim), freeze_shN (iteration <= 1000: FusedAdam skips shN - `adam` then needs no "shN" entry) and noise [N,3] + noise_lr (the MCMC
-        strategy's draw and lr * noise_lr, added to the means in front of their Adam update as lfs_add_noise would) select lfs_gut_train_step_opt: the fused-tail form for
+        strategy's draw and lr * noise_lr, added to the means in front of their Adam update as lfs_add_noise would) are that call's options: the fused-tail form for
         what the reference trains. An attempt that did not fit applied nothing, the noise included: the re-run takes the same noise tensor."""
         lib = load_library()
         N = params[0].shape[0]
@@ -180,49 +207,36 @@ class GutStep:
                     self.loss_ws = None
                     self.loss_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
                 opts.loss_workspace, opts.loss_workspace_bytes = self.loss_ws.data_ptr(), self.loss_ws.numel()
-        fn, what = (lib.lfs_gut_train_step_pipelined, "gut_train_step_pipelined") if pipelined else (lib.lfs_gut_train_step, "gut_train_step")
-        for attempt in range(4):
-            self._ensure(N, W, H)
-            a = self._args(params, sh_degree, W, H, viewmat, Kmat, bg, target_chw, weight, scale_reg, opacity_reg, loss_acc, adam)
-            self._stamp += 1
-            if fused_tail and not pipelined:
-                # (replaced parameter tensors void the colours too - and so does an in-place write to the view matrix, means, sh0 or shN between the two steps: their
-                #  autograd version counters, which a detach() or an index view shares with its base, as the C++ GutTrainStep compares them. The step's own updates go
-                #  through raw pointers and leave the counters alone: the fast path stays.)
-                key = lambda vm: (vm.data_ptr(), vm._version, N, K, sh_degree, self.ws.data_ptr(), params[0].data_ptr(), params[1].data_ptr(), params[2].data_ptr(),
-                                  params[0]._version, params[1]._version, params[2]._version)
+        if fused_tail and not pipelined:
+            # (replaced parameter tensors void the colours too - and so does an in-place write to the view matrix, means, sh0 or shN between the two steps: their
+            #  autograd version counters, which a detach() or an index view shares with its base, as the C++ GutTrainStep compares them. The step's own updates go
+            #  through raw pointers and leave the counters alone: the fast path stays.)
+            key = lambda vm: (vm.data_ptr(), vm._version, N, K, sh_degree, self.ws.data_ptr(), params[0].data_ptr(), params[1].data_ptr(), params[2].data_ptr(),
+                              params[0]._version, params[1]._version, params[2]._version)
+            nxt = next_viewmat if (next_viewmat is not None and K <= 16) else None
+
+            def enqueue(a):
                 ready = self.colors_for is not None and self.colors_for == key(viewmat)
-                nxt = next_viewmat if (next_viewmat is not None and K <= 16) else None
                 self.colors_for = None   # (whatever happens below, the colours of THIS view are consumed / overwritten)
-                if opts is not None:
-                    check(lib.lfs_gut_train_step_opt(C.byref(a), C.byref(opts), C.c_void_p(nxt.data_ptr()) if nxt is not None else None, C.c_int(int(ready)),
-                                                     C.c_int64(self.capacity), C.c_int64(self.assumed_longest), C.c_void_p(self.ws.data_ptr()), C.c_size_t(self.ws.numel()),
-                                                     C.c_void_p(self.counts.data_ptr()), C.c_int64(self._stamp), stream()), "gut_train_step_opt")
-                else:
-                    check(lib.lfs_gut_train_step_ex(C.byref(a), C.c_void_p(nxt.data_ptr()) if nxt is not None else None, C.c_int(int(ready)), C.c_int64(self.capacity),
-                                                    C.c_int64(self.assumed_longest), C.c_void_p(self.ws.data_ptr()), C.c_size_t(self.ws.numel()),
-                                                    C.c_void_p(self.counts.data_ptr()), C.c_int64(self._stamp), stream()), "gut_train_step_ex")
-                if self._wait():
-                    if nxt is not None:
-                        self.colors_for = key(nxt)
-                    self.colour_launches_saved += int(ready)
-                    self._after_fit()
-                    return self.n_isects
-                # the attempt did not fit: its tail returned without writing anything, so colours that were ready still are - unless _grow replaces the workspace below
-                if ready:
-                    self.colors_for = key(viewmat)
-                self.retries += 1
-                self._grow(self.n_isects, self.longest)
-                continue
-            self.colors_for = None
-            check(fn(C.byref(a), C.c_int64(self.capacity), C.c_int64(self.assumed_longest), C.c_void_p(self.ws.data_ptr()),
-                     C.c_size_t(self.ws.numel()), C.c_void_p(self.counts.data_ptr()), C.c_int64(self._stamp), stream()), what)
-            if self._wait():
-                self._after_fit()
-                return self.n_isects
-            self.retries += 1
-            self._grow(self.n_isects, self.longest)
-        raise LfsError("gut_step: the step did not fit its workspace after 4 attempts")
+                check(lib.lfs_gut_train_step_opt(C.byref(a), C.byref(opts) if opts is not None else None, C.c_void_p(nxt.data_ptr()) if nxt is not None else None,
+                                                 C.c_int(int(ready)), *self._ws_args()), "gut_train_step_opt")
+
+                def settle(fitted):
+                    if fitted:
+                        if nxt is not None:
+                            self.colors_for = key(nxt)
+                        self.colour_launches_saved += int(ready)
+                    elif ready:   # the tail returned without writing anything, so colours that were ready still are - unless _grow replaces the workspace
+                        self.colors_for = key(viewmat)
+                return settle
+        else:
+            fn, what = (lib.lfs_gut_train_step_pipelined, "gut_train_step_pipelined") if pipelined else (lib.lfs_gut_train_step, "gut_train_step")
+
+            def enqueue(a):
+                self.colors_for = None
+                check(fn(C.byref(a), *self._ws_args()), what)
+        return self._attempt(N, W, H, lambda: self._args(params, sh_degree, W, H, viewmat, Kmat, bg, target_chw, weight, scale_reg, opacity_reg, loss_acc, adam),
+                             enqueue, "step")
 
     @staticmethod
     def join() -> bool:
@@ -235,22 +249,12 @@ class GutStep:
     def view_forward(self, params: Sequence[torch.Tensor], sh_degree: int, W: int, H: int, viewmat, Kmat, bg) -> int:
         """Forward of one view into the workspace (render / alpha / radii via .view()); re-run on overflow. Returns n_isects."""
         lib = load_library()
-        N = params[0].shape[0]
         self.colors_for = None   # (this forward evaluates its own colours into the workspace)
-        for attempt in range(4):
-            self._ensure(N, W, H)
-            a = self._args(params, sh_degree, W, H, viewmat, Kmat, bg, None, 0.0, 0.0, 0.0, None, None)
-            self._stamp += 1
-            check(lib.lfs_gut_view_forward(C.byref(a), C.c_int64(self.capacity), C.c_int64(self.assumed_longest), C.c_void_p(self.ws.data_ptr()),
-                                           C.c_size_t(self.ws.numel()), C.c_void_p(self.counts.data_ptr()), C.c_int64(self._stamp), stream()), "gut_view_forward")
-            if self._wait():
-                return self.n_isects
-            self.retries += 1
-            self._grow(self.n_isects, self.longest)
-        raise LfsError("gut_step: the view did not fit its workspace after 4 attempts")
+        return self._attempt(params[0].shape[0], W, H, lambda: self._args(params, sh_degree, W, H, viewmat, Kmat, bg, None, 0.0, 0.0, 0.0, None, None),
+                             lambda a: check(lib.lfs_gut_view_forward(C.byref(a), *self._ws_args()), "gut_view_forward"), "view", after_fit=False)
 
     def _backward_call(self, fn_name: str, params, sh_degree, W, H, viewmat, Kmat, bg, grads, accumulate, target_chw, weight, loss_acc, v_render, scale_reg, opacity_reg,
-                       adam=None):
+                       adam=None, rows_out=None):
         lib = load_library()
         a = self._args(params, sh_degree, W, H, viewmat, Kmat, bg, target_chw, weight, scale_reg, opacity_reg, loss_acc, adam)
         for g in grads:
@@ -263,8 +267,9 @@ class GutStep:
             return
         if v_render is not None:
             v_render = v_render.contiguous()
+        rows = () if rows_out is None else (C.c_void_p(rows_out.data_ptr()),)   # (lfs_gut_view_backward_rows: dL/dcolour [N,3], in front of the workspace)
         check(getattr(lib, fn_name)(C.byref(a), C.c_int64(self.capacity), C.c_void_p(v_render.data_ptr()) if v_render is not None else None, gp,
-                                    C.c_int(int(accumulate)), ws, nb, stream()), fn_name)
+                                    C.c_int(int(accumulate)), *rows, ws, nb, stream()), fn_name)
 
     def view_backward(self, params: Sequence[torch.Tensor], sh_degree: int, W: int, H: int, viewmat, Kmat, bg, grads: List[torch.Tensor], accumulate: bool, *,
                       target_chw: Optional[torch.Tensor] = None, weight: float = 0.0, loss_acc: Optional[torch.Tensor] = None,
@@ -285,16 +290,10 @@ class GutStep:
                            v_render=None, scale_reg: float = 0.0, opacity_reg: float = 0.0) -> None:
         """The view's backward for the factored gradient exchange (dist.ColorGradExchange): grads[0] (means, without the SH direction term), grads[3..5] written / added
         to, dL/dcolour -> rows_out [N,3], masked with the clamp of the SH colours (colour > 0) - what the multi-view SH backward of every rank takes as it is."""
-        lib = load_library()
-        a = self._args(params, sh_degree, W, H, viewmat, Kmat, bg, target_chw, weight, scale_reg, opacity_reg, loss_acc, None)
         if not rows_out.is_cuda or not rows_out.is_contiguous() or rows_out.numel() != 3 * params[0].shape[0]:
             raise LfsError("gut_step: rows_out must be a contiguous CUDA (HIP) tensor [N,3]")
-        gp = (C.c_void_p * 6)(*[g.data_ptr() if g.numel() else None for g in grads])
-        if v_render is not None:
-            v_render = v_render.contiguous()
-        check(lib.lfs_gut_view_backward_rows(C.byref(a), C.c_int64(self.capacity), C.c_void_p(v_render.data_ptr()) if v_render is not None else None, gp,
-                                             C.c_int(int(accumulate)), C.c_void_p(rows_out.data_ptr()), C.c_void_p(self.ws.data_ptr()), C.c_size_t(self.ws.numel()),
-                                             stream()), "gut_view_backward_rows")
+        self._backward_call("lfs_gut_view_backward_rows", params, sh_degree, W, H, viewmat, Kmat, bg, grads, accumulate, target_chw, weight, loss_acc, v_render,
+                            scale_reg, opacity_reg, rows_out=rows_out)
         N = params[0].shape[0]
         rows_out.view(N, 3).mul_(self.view("colors", torch.float32, (N, 3)) > 0)   # clamp_min backward of rasterizer.cpp:262 (colours of invisible Gaussians: rows are 0 anyway)
 

@@ -438,6 +438,21 @@ class GutTrainer:
         if self._gut_step is not None:
             self._gut_step.join()
 
+    def _view_loss(self, gs, view: int, target, weight: float):
+        """The loss of the view gs.view_forward() left in the step workspace -> (v_render, fold): dL/d(render) [H,W,3] from the loss kernels (bilateral grid, L1 + D-SSIM)
+        with fold None, or v_render None and fold = the target the rasterizer backward derives the clamped MSE from itself. The loss is added to loss_acc."""
+        sc = self.scene
+        if self.bilateral is not None:   # clamp -> slice -> loss on the un-clamped result -> slice backward (fused.render_and_backward does the same)
+            from .losses import loss_fwd_bwd
+            render = gs.view("render", torch.float32, (sc.height, sc.width, 3))
+            shown = self.bilateral.apply_fused(render, view, chw=False)
+            v_shown = loss_fwd_bwd(self.loss_kind, shown, target, weight, self.loss_acc, chw=False, clamp=False, lambda_dssim=self.lambda_dssim)
+            return self.bilateral.apply_fused_backward(render, view, v_shown, chw=False), None
+        if self.loss_kind == "l1_ssim":
+            from .losses import photometric_loss_fwd_bwd
+            return photometric_loss_fwd_bwd(gs.view("render", torch.float32, (1, sc.height, sc.width, 3)), target, self.lambda_dssim, weight, self.loss_acc), None
+        return None, target
+
     def _step_cxx_views(self, plan, targets, views, total_views) -> None:
         """Gradient-tensor form of the C++ step (data-parallel ranks with the north-star layout - replicated Gaussians, one all-reduce of the flat bucket -,
         single-rank steps while iteration <= 1000, and every step whose loss is not the folded MSE: L1 + D-SSIM, bilateral grid, MCMC): per view one speculative
@@ -453,18 +468,7 @@ class GutTrainer:
         for k, v in enumerate(views):
             vm, Km, tgt = sc.viewmats[v], sc.Ks[v], targets[k % len(targets)]
             self.last_n_isects = gs.view_forward(ps, deg, sc.width, sc.height, vm, Km, self.bg)
-            v_render, fold = None, None
-            if self.bilateral is not None:   # clamp -> slice -> loss on the un-clamped result -> slice backward (fused.render_and_backward does the same)
-                from .losses import loss_fwd_bwd
-                render = gs.view("render", torch.float32, (sc.height, sc.width, 3))
-                shown = self.bilateral.apply_fused(render, v, chw=False)
-                v_shown = loss_fwd_bwd(self.loss_kind, shown, tgt, weight, self.loss_acc, chw=False, clamp=False, lambda_dssim=self.lambda_dssim)
-                v_render = self.bilateral.apply_fused_backward(render, v, v_shown, chw=False)
-            elif self.loss_kind == "l1_ssim":
-                from .losses import photometric_loss_fwd_bwd
-                v_render = photometric_loss_fwd_bwd(gs.view("render", torch.float32, (1, sc.height, sc.width, 3)), tgt, self.lambda_dssim, weight, self.loss_acc)
-            else:
-                fold = tgt                   # the clamped MSE is derived inside the rasterizer backward
+            v_render, fold = self._view_loss(gs, v, tgt, weight)
             gs.view_backward_sh(ps, deg, sc.width, sc.height, vm, Km, self.bg, self.bucket.views, k > 0, target_chw=fold, weight=weight,
                                 loss_acc=self.loss_acc, v_render=v_render, adam_shN=inline)
             if plan.multi and k == len(views) - 1 and self.iteration > 1000 and ps[2].numel():
@@ -491,18 +495,7 @@ class GutTrainer:
         for k, v in enumerate(views):
             vm, Km, tgt = sc.viewmats[v], sc.Ks[v], targets[k % len(targets)]
             self.last_n_isects = gs.view_forward(ps, deg, sc.width, sc.height, vm, Km, self.bg)
-            v_render, fold = None, None
-            if self.bilateral is not None:
-                from .losses import loss_fwd_bwd
-                render = gs.view("render", torch.float32, (sc.height, sc.width, 3))
-                shown = self.bilateral.apply_fused(render, v, chw=False)
-                v_shown = loss_fwd_bwd(self.loss_kind, shown, tgt, weight, self.loss_acc, chw=False, clamp=False, lambda_dssim=self.lambda_dssim)
-                v_render = self.bilateral.apply_fused_backward(render, v, v_shown, chw=False)
-            elif self.loss_kind == "l1_ssim":
-                from .losses import photometric_loss_fwd_bwd
-                v_render = photometric_loss_fwd_bwd(gs.view("render", torch.float32, (1, sc.height, sc.width, 3)), tgt, self.lambda_dssim, weight, self.loss_acc)
-            else:
-                fold = tgt
+            v_render, fold = self._view_loss(gs, v, tgt, weight)
             gs.view_backward_rows(ps, deg, sc.width, sc.height, vm, Km, self.bg, self.bucket.views, k > 0, ex.send[k], target_chw=fold, weight=weight,
                                   loss_acc=self.loss_acc, v_render=v_render, scale_reg=self.scale_reg / self.world if k == 0 else 0.0,
                                   opacity_reg=self.opacity_reg / self.world if k == 0 else 0.0)
