@@ -289,6 +289,20 @@ LFS_API int lfs_fastgs_backward(
     void* instance_workspace, size_t instance_workspace_bytes, const float* grad_image, const float* grad_alpha, const float* alpha,
     float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
     float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest, lfs_stream_t stream);
+/* lfs_fastgs_backward + grad_w2c, the camera gradient of the reference's pose optimisation (rasterization_api.cu:133-136: requested when w2c requires grad).
+ * grad_w2c [4,4] row-major, device, FULLY written: rows 0-2 = sum over the primitives with n_touched > 0 of dL/d(mean in camera space) (x) (mean, 1)
+ * (kernels_backward.cuh:165-183: no term through cam_position, none for the direct dependence of the EWA Jacobian on w2c, none from the SH colours), row 3 = 0.
+ * Summed without float atomics, in a fixed order: the same bits on every run for the same dL/d(mean in camera space). w2c_workspace (16-byte aligned,
+ * lfs_fastgs_w2c_workspace_bytes(N) bytes) holds one row of partial sums per 256 primitives. LFS_E_INVALID: grad_w2c NULL or a workspace that is not 16-byte aligned; LFS_E_WORKSPACE: workspace NULL / short. */
+LFS_API size_t lfs_fastgs_w2c_workspace_bytes(uint32_t N);
+LFS_API int lfs_fastgs_backward_w2c(
+    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* sh_coefficients_0, const float* sh_coefficients_rest,
+    uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position, uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy,
+    float cx, float cy, float near_plane, float far_plane, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
+    void* instance_workspace, size_t instance_workspace_bytes, const float* grad_image, const float* grad_alpha, const float* alpha,
+    float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
+    float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest, float* grad_w2c /* [4,4], fully written */, void* w2c_workspace, size_t w2c_workspace_bytes,
+    lfs_stream_t stream);
 /* lfs_fastgs_backward for a step with ONE view, fused with the optimizer (extension): sh_coefficients_rest and its Adam moments are updated in
  * place by the SH backward (fast_gs::optimizer::adam_step arithmetic); the [N,total_rest,3] gradient is never stored. */
 LFS_API int lfs_fastgs_backward_adam(
@@ -299,7 +313,12 @@ LFS_API int lfs_fastgs_backward_adam(
     float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
     float* grad_sh_coefficients_0, float* sh_rest_exp_avg, float* sh_rest_exp_avg_sq, float lr, float beta1, float beta2, float eps,
     float bias_correction1_rcp, float bias_correction2_sqrt_rcp, lfs_stream_t stream);
-LFS_API void lfs_fastgs_set_debug_flags(uint32_t flags); /* bit 0: no per-cell culling (bit-identity test) */
+LFS_API void lfs_fastgs_set_debug_flags(uint32_t flags); /* bit 0: no per-cell culling (bit-identity test); bit 1: the backward entry points skip the blending
+                                                           * backward and reuse the accumulator rows the previous backward left in the primitive workspace (its float
+                                                           * atomics round differently from run to run: bit-identity tests of the per-primitive stage hold them fixed).
+                                                           * Bit 1 is for tests ONLY and must never be set elsewhere: while it is set, every gradient of
+                                                           * lfs_fastgs_backward / lfs_fastgs_backward_w2c comes from stale accumulator rows. lfs_fastgs_backward_adam,
+                                                           * which updates parameters in place, ignores it. */
 
 /* ---- "next" row 2 of SURVEY.md §8f: fused SSIM (fusedssim / fusedssim_backward, include/kernels/ssim.cuh:11-30,
  *      src/training/kernels/ssim.cu:64-510) and the trainer's photometric loss (trainer.cpp:122-125).

@@ -17,7 +17,9 @@ namespace fgs {
 int launch_scatter(uint32_t N, const Frame& f, const PrimWs& w, int64_t* keys, hipStream_t s);
 int launch_preprocess_bwd(uint32_t N, const float* means, const float* scales_raw, const float* rot_raw, const float* sh0, const float* sh_rest, const Frame& f, const PrimWs& w,
                           float* g_means, float* g_scales_raw, float* g_rot_raw, float* g_opac_raw, float* g_sh0, float* g_sh_rest, float* densification_info, hipStream_t s,
-                          const ShAdamArgs* adam);
+                          const ShAdamArgs* adam, float* grad_w2c, float* w2c_partials);
+size_t w2c_workspace_bytes(uint32_t N);
+int launch_w2c_reduce(uint32_t N, const float* w2c_partials, float* grad_w2c, hipStream_t s);
 
 // cell-level version of kernel_utils.cuh:108-148 on the record's conic in bits (A, B, C) = log2(e) (a/2, b, c/2): the ratios that
 // locate the maximum are scale free; thr already carries the safety margin
@@ -267,28 +269,36 @@ static int fastgs_backward_impl(
     float cx, float cy, float near_plane, float far_plane, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
     void* instance_workspace, size_t instance_workspace_bytes, const float* grad_image, const float* grad_alpha, const float* alpha,
     float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
-    float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest, lfs_stream_t stream, const lfs::ShAdamArgs* adam) {
+    float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest, lfs_stream_t stream, const lfs::ShAdamArgs* adam, float* grad_w2c = nullptr,
+    void* w2c_workspace = nullptr) {
     if (!primitive_workspace || !w2c || !cam_position || !grad_image || !grad_alpha || !alpha || width == 0 || height == 0 || n_instances < 0) return LFS_E_INVALID;
     fgs::PrimWs w = fgs::prim_ws(primitive_workspace, N, width, height);
     if (primitive_workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
     fgs::InstWs iw = fgs::inst_ws(instance_workspace, width, height, uint64_t(n_instances));
     if (!instance_workspace || instance_workspace_bytes < iw.bytes) return LFS_E_WORKSPACE;
-    if (N == 0) return LFS_OK;
+    if (N == 0) return grad_w2c ? fgs::launch_w2c_reduce(0, static_cast<const float*>(w2c_workspace), grad_w2c, (hipStream_t)stream) : LFS_OK;   // (grad_w2c is fully written: zeros)
     if (!means || !scales_raw || !rotations_raw || !grad_means || !grad_scales_raw || !grad_rotations_raw || !grad_opacities_raw || !grad_sh_coefficients_0 ||
         (total_bases_sh_rest > 0 && (!sh_coefficients_rest || (!grad_sh_coefficients_rest && !adam)))) return LFS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const fgs::Frame f = make_frame(w2c, cam_position, active_sh_bases, total_bases_sh_rest, width, height, fx, fy, cx, cy, near_plane, far_plane);
-    hipError_t e = hipMemsetAsync(w.acc, 0, sizeof(float) * ACC_STRIDE * size_t(N), s);
-    if (e != hipSuccess) return (int)e;
+    // debug bit 1: the accumulator rows of the previous backward on this workspace are kept (no blending backward). Its float atomics arrive in a different order on
+    // every run; with the rows held fixed, the per-primitive stage of two calls can be compared bit for bit (tests/test_gpu_fastgs_w2c.py)
+    // TEST-ONLY: with the bit left set every gradient is computed from stale rows. The optimizer-fused entry point (adam != nullptr) ignores it.
+    const bool keep_acc = (fgs::g_fastgs_debug & 2u) != 0 && adam == nullptr;
+    if (!keep_acc) {
+        hipError_t e = hipMemsetAsync(w.acc, 0, sizeof(float) * ACC_STRIDE * size_t(N), s);
+        if (e != hipSuccess) return (int)e;
+    }
     const uint32_t T = f.gw * f.gh;
-    if (n_instances > 0) {
+    if (n_instances > 0 && !keep_acc) {
         lfs::ProfScope prof("fastgs_blend_bwd", s);
         const uint32_t wgrid = cell_grid_blocks(uint64_t(T) * fgs::WPT, fgs::WPT);
         hipLaunchKernelGGL(fgs::fg_blend_bwd_kernel, dim3(wgrid), dim3(64), 0, s, f.gw, f.gh, width, height, w.rec, w.offsets, iw.cell_count, iw.cell_list,
                            alpha, w.n_contrib, grad_image, grad_alpha, w.acc);
     }
     return fgs::launch_preprocess_bwd(N, means, scales_raw, rotations_raw, sh_coefficients_0, sh_coefficients_rest, f, w, grad_means, grad_scales_raw, grad_rotations_raw,
-                                      grad_opacities_raw, grad_sh_coefficients_0, grad_sh_coefficients_rest, densification_info, s, adam);
+                                      grad_opacities_raw, grad_sh_coefficients_0, grad_sh_coefficients_rest, densification_info, s, adam, grad_w2c,
+                                      static_cast<float*>(w2c_workspace));
 }
 
 extern "C" int lfs_fastgs_backward(
@@ -302,6 +312,26 @@ extern "C" int lfs_fastgs_backward(
                                 width, height, fx, fy, cx, cy, near_plane, far_plane, n_instances, primitive_workspace, primitive_workspace_bytes, instance_workspace,
                                 instance_workspace_bytes, grad_image, grad_alpha, alpha, densification_info, grad_means, grad_scales_raw, grad_rotations_raw,
                                 grad_opacities_raw, grad_sh_coefficients_0, grad_sh_coefficients_rest, stream, nullptr);
+}
+
+extern "C" size_t lfs_fastgs_w2c_workspace_bytes(uint32_t N) { return fgs::w2c_workspace_bytes(N); }
+
+// lfs_fastgs_backward + the camera gradient of pose optimisation (rasterization_api.cu:133-136, 163, 180): grad_w2c [4,4] = sum over the primitives with
+// n_touched > 0 of dL/d(mean in camera space) (x) (mean, 1) in rows 0-2, row 3 = 0; all 16 floats are written, whatever N and n_instances are.
+extern "C" int lfs_fastgs_backward_w2c(
+    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* sh_coefficients_0, const float* sh_coefficients_rest,
+    uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position, uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy,
+    float cx, float cy, float near_plane, float far_plane, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
+    void* instance_workspace, size_t instance_workspace_bytes, const float* grad_image, const float* grad_alpha, const float* alpha,
+    float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
+    float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest, float* grad_w2c, void* w2c_workspace, size_t w2c_workspace_bytes, lfs_stream_t stream) {
+    if (!grad_w2c) return LFS_E_INVALID;
+    if (!w2c_workspace || w2c_workspace_bytes < fgs::w2c_workspace_bytes(N)) return LFS_E_WORKSPACE;
+    if (reinterpret_cast<uintptr_t>(w2c_workspace) % 16 != 0) return LFS_E_INVALID;   // fg_w2c_reduce_kernel reads the partial rows as float4
+    return fastgs_backward_impl(N, means, scales_raw, rotations_raw, sh_coefficients_0, sh_coefficients_rest, total_bases_sh_rest, w2c, cam_position, active_sh_bases,
+                                width, height, fx, fy, cx, cy, near_plane, far_plane, n_instances, primitive_workspace, primitive_workspace_bytes, instance_workspace,
+                                instance_workspace_bytes, grad_image, grad_alpha, alpha, densification_info, grad_means, grad_scales_raw, grad_rotations_raw,
+                                grad_opacities_raw, grad_sh_coefficients_0, grad_sh_coefficients_rest, stream, nullptr, grad_w2c, w2c_workspace);
 }
 
 // lfs_fastgs_backward for a step with ONE view, fused with the optimizer: sh_coefficients_rest and its Adam moments are updated in place by the SH

@@ -187,20 +187,21 @@ __global__ void __launch_bounds__(1024) fg_scatter_kernel(
 // ---------------------------------------------------------------------------
 // backward preprocess: blend-backward accumulator -> gradients of the raw parameters (+ densification_info)
 // ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) fg_preprocess_bwd_kernel(
-    const uint32_t N, const float* __restrict__ means, const float* __restrict__ scales_raw, const float* __restrict__ rot_raw,
-    const Frame f, const GaussRec* __restrict__ rec, const float4* __restrict__ conic_opacity,
-    const uint32_t* __restrict__ n_touched, const float* __restrict__ acc, float* __restrict__ g_means, float* __restrict__ g_scales_raw, float* __restrict__ g_rot_raw,
-    float* __restrict__ g_opac_raw, float* __restrict__ densification_info) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    if (n_touched[i] == 0) { // the reference leaves these rows at the zeros they were allocated with
+// an invisible primitive (n_touched == 0): the reference leaves these rows at the zeros they were allocated with
+LFS_DI void preprocess_bwd_zero_rows(const uint32_t i, float* __restrict__ g_means, float* __restrict__ g_scales_raw, float* __restrict__ g_rot_raw,
+                                     float* __restrict__ g_opac_raw) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) { g_means[3 * size_t(i) + c] = 0.f; g_scales_raw[3 * size_t(i) + c] = 0.f; }
-        reinterpret_cast<float4*>(g_rot_raw)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        g_opac_raw[i] = 0.f;
-        return;
-    }
+    for (int c = 0; c < 3; ++c) { g_means[3 * size_t(i) + c] = 0.f; g_scales_raw[3 * size_t(i) + c] = 0.f; }
+    reinterpret_cast<float4*>(g_rot_raw)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    g_opac_raw[i] = 0.f;
+}
+
+// one visible primitive; dcam = dL/d(mean in camera space) (kernels_backward.cuh:165-168), which the camera gradient below is made of
+LFS_DI void preprocess_bwd_one(
+    const uint32_t i, const uint32_t N, const float* __restrict__ means, const float* __restrict__ scales_raw, const float* __restrict__ rot_raw,
+    const Frame& f, const GaussRec* __restrict__ rec, const float4* __restrict__ conic_opacity, const float* __restrict__ acc,
+    float* __restrict__ g_means, float* __restrict__ g_scales_raw, float* __restrict__ g_rot_raw, float* __restrict__ g_opac_raw,
+    float* __restrict__ densification_info, float (&dcam)[3]) {
     const float4* a4 = reinterpret_cast<const float4*>(acc + size_t(i) * ACC_STRIDE);
     const float4 a0 = a4[0], a1 = a4[1], a2 = a4[2];
     const GaussRec r = rec[i];
@@ -235,8 +236,8 @@ __global__ void __launch_bounds__(256) fg_preprocess_bwd_kernel(
     const float dj11 = r1[0] * djw1[0] + r1[1] * djw1[1] + r1[2] * djw1[2], dj22 = r2[0] * djw2[0] + r2[1] * djw2[1] + r2[2] * djw2[2];
     const float dj13 = r3[0] * djw1[0] + r3[1] * djw1[1] + r3[2] * djw1[2], dj23 = r3[0] * djw2[0] + r3[1] * djw2[1] + r3[2] * djw2[2];
     const float h1 = dj11 - 2.0f * cv.tx * dj13, h2 = dj22 - 2.0f * cv.ty * dj23;
-    const float dcam[3] = {cv.j11 * (dm2[0] - dj13 / cv.depth), cv.j22 * (dm2[1] - dj23 / cv.depth),
-                           -cv.j11 * (cv.x * dm2[0] + h1 / cv.depth) - cv.j22 * (cv.y * dm2[1] + h2 / cv.depth)};
+    dcam[0] = cv.j11 * (dm2[0] - dj13 / cv.depth); dcam[1] = cv.j22 * (dm2[1] - dj23 / cv.depth);
+    dcam[2] = -cv.j11 * (cv.x * dm2[0] + h1 / cv.depth) - cv.j22 * (cv.y * dm2[1] + h2 / cv.depth);
 #pragma unroll
     for (int c = 0; c < 3; ++c) g_means[3 * size_t(i) + c] = r1[c] * dcam[0] + r2[c] * dcam[1] + r3[c] * dcam[2] + dpos[c];
 #pragma unroll
@@ -266,6 +267,72 @@ __global__ void __launch_bounds__(256) fg_preprocess_bwd_kernel(
     }
 }
 
+// Sum of W2C_VALS per-lane values over a 256-thread workgroup in a FIXED order (no float atomics: the result is the same bits on every run): wave64 butterfly,
+// lane 0 of each wavefront -> LDS, then thread j < W2C_VALS adds the four wavefronts' values front to back. Every lane of the workgroup must call it.
+constexpr uint32_t W2C_VALS = 12; // rows 0-2 of the [4,4] gradient, row-major
+LFS_DI float block_sum12(float (&v)[W2C_VALS], float (*s_part)[W2C_VALS]) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1)
+#pragma unroll
+        for (uint32_t j = 0; j < W2C_VALS; ++j) v[j] += __shfl_xor(v[j], m, 64);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (uint32_t j = 0; j < W2C_VALS; ++j) s_part[threadIdx.x >> 6][j] = v[j];
+    }
+    __syncthreads();
+    const uint32_t j = threadIdx.x < W2C_VALS ? threadIdx.x : 0u;
+    return ((s_part[0][j] + s_part[1][j]) + s_part[2][j]) + s_part[3][j];
+}
+
+// W2C = false: the kernel as it always was (w2c_partials is not read or written). W2C = true (pose optimisation, rasterization_api.cu:133-136 /
+// kernels_backward.cuh:165-183) additionally sums, over the primitives with n_touched > 0, grad_w2c[r][c] += dcam[r] * mean[c], grad_w2c[r][3] += dcam[r]:
+// no lane leaves before the workgroup sum (rows past N and invisible primitives take part with dcam = 0), and the workgroup's 12 sums go to
+// w2c_partials[blockIdx.x * 12 ..] with plain stores; fg_w2c_reduce_kernel adds the rows up.
+template <bool W2C>
+__global__ void __launch_bounds__(256) fg_preprocess_bwd_kernel(
+    const uint32_t N, const float* __restrict__ means, const float* __restrict__ scales_raw, const float* __restrict__ rot_raw,
+    const Frame f, const GaussRec* __restrict__ rec, const float4* __restrict__ conic_opacity,
+    const uint32_t* __restrict__ n_touched, const float* __restrict__ acc, float* __restrict__ g_means, float* __restrict__ g_scales_raw, float* __restrict__ g_rot_raw,
+    float* __restrict__ g_opac_raw, float* __restrict__ densification_info, float* __restrict__ w2c_partials) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if constexpr (!W2C) {   // the kernel as it was: the same early returns, no operand of the sum below exists
+        if (i >= N) return;
+        if (n_touched[i] == 0) { preprocess_bwd_zero_rows(i, g_means, g_scales_raw, g_rot_raw, g_opac_raw); return; }
+        float dcam[3];
+        preprocess_bwd_one(i, N, means, scales_raw, rot_raw, f, rec, conic_opacity, acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, dcam);
+    } else {
+        __shared__ float s_part[4][W2C_VALS];
+        float dcam[3] = {0.f, 0.f, 0.f}, m[3] = {0.f, 0.f, 0.f};
+        bool visible = i < N;
+        if (visible && n_touched[i] == 0) { preprocess_bwd_zero_rows(i, g_means, g_scales_raw, g_rot_raw, g_opac_raw); visible = false; }
+        if (visible) {
+            preprocess_bwd_one(i, N, means, scales_raw, rot_raw, f, rec, conic_opacity, acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, dcam);
+            m[0] = means[3 * size_t(i)]; m[1] = means[3 * size_t(i) + 1]; m[2] = means[3 * size_t(i) + 2];
+        }
+        float v[W2C_VALS];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) { v[4 * r] = dcam[r] * m[0]; v[4 * r + 1] = dcam[r] * m[1]; v[4 * r + 2] = dcam[r] * m[2]; v[4 * r + 3] = dcam[r]; }
+        const float sum = block_sum12(v, s_part);   // every lane of the workgroup arrives here
+        if (threadIdx.x < W2C_VALS) w2c_partials[size_t(blockIdx.x) * W2C_VALS + threadIdx.x] = sum;
+    }
+}
+
+// one workgroup: the n_rows partial rows of fg_preprocess_bwd_kernel<true> -> grad_w2c [4,4], all 16 floats written (row 3 = 0; n_rows == 0 -> all zeros).
+// Thread t adds rows t, t + 256, ... in that order, then the same workgroup sum as above.
+__global__ void __launch_bounds__(256) fg_w2c_reduce_kernel(const uint32_t n_rows, const float* __restrict__ w2c_partials, float* __restrict__ grad_w2c) {
+    __shared__ float s_part[4][W2C_VALS];
+    float v[W2C_VALS];
+#pragma unroll
+    for (uint32_t j = 0; j < W2C_VALS; ++j) v[j] = 0.f;
+    for (uint32_t row = threadIdx.x; row < n_rows; row += 256) {
+        const float4* p = reinterpret_cast<const float4*>(w2c_partials + size_t(row) * W2C_VALS);
+        const float4 a = p[0], b = p[1], c = p[2];
+        v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w; v[4] += b.x; v[5] += b.y; v[6] += b.z; v[7] += b.w; v[8] += c.x; v[9] += c.y; v[10] += c.z; v[11] += c.w;
+    }
+    const float sum = block_sum12(v, s_part);
+    if (threadIdx.x < 16) grad_w2c[threadIdx.x] = threadIdx.x < W2C_VALS ? sum : 0.f;
+}
+
 static inline uint32_t per_block_for(uint32_t N) {
     size_t pb = (size_t(N) + 511) / 512;
     if (pb < 1024) pb = 1024;
@@ -273,6 +340,15 @@ static inline uint32_t per_block_for(uint32_t N) {
 }
 
 // host-side launchers used by fastgs_blend.hip as well
+size_t w2c_workspace_bytes(uint32_t N) { // one row of 12 floats per workgroup of fg_preprocess_bwd_kernel<true> (never 0: N == 0 still gets a valid pointer)
+    const size_t rows = (size_t(N) + 255) / 256;
+    return align256(sizeof(float) * W2C_VALS * (rows ? rows : 1));
+}
+int launch_w2c_reduce(uint32_t N, const float* w2c_partials, float* grad_w2c, hipStream_t s) {   // N == 0: no partial rows, grad_w2c = 0
+    lfs::ProfScope prof("fastgs_w2c_reduce", s);
+    hipLaunchKernelGGL(fg_w2c_reduce_kernel, dim3(1), dim3(256), 0, s, (N + 255) / 256, w2c_partials, grad_w2c);
+    return (int)hipGetLastError();
+}
 int launch_scatter(uint32_t N, const Frame& f, const PrimWs& w, int64_t* keys, hipStream_t s) {
     const uint32_t T = f.gw * f.gh, pb = per_block_for(N), blocks = (N + pb - 1) / pb;
     lfs::ProfScope prof("fastgs_scatter", s);
@@ -284,11 +360,19 @@ int launch_scatter(uint32_t N, const Frame& f, const PrimWs& w, int64_t* keys, h
 }
 int launch_preprocess_bwd(uint32_t N, const float* means, const float* scales_raw, const float* rot_raw, const float* sh0, const float* sh_rest, const Frame& f, const PrimWs& w,
                           float* g_means, float* g_scales_raw, float* g_rot_raw, float* g_opac_raw, float* g_sh0, float* g_sh_rest, float* densification_info, hipStream_t s,
-                          const ShAdamArgs* adam) {
+                          const ShAdamArgs* adam, float* grad_w2c, float* w2c_partials) {
     {
         lfs::ProfScope prof("fastgs_preprocess_bwd", s);
-        hipLaunchKernelGGL(fg_preprocess_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, means, scales_raw, rot_raw, f, w.rec, w.conic_opacity, w.n_touched, w.acc,
-                           g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info);
+        if (grad_w2c != nullptr)
+            hipLaunchKernelGGL(fg_preprocess_bwd_kernel<true>, dim3((N + 255) / 256), dim3(256), 0, s, N, means, scales_raw, rot_raw, f, w.rec, w.conic_opacity, w.n_touched, w.acc,
+                               g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, w2c_partials);
+        else
+            hipLaunchKernelGGL(fg_preprocess_bwd_kernel<false>, dim3((N + 255) / 256), dim3(256), 0, s, N, means, scales_raw, rot_raw, f, w.rec, w.conic_opacity, w.n_touched, w.acc,
+                               g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, static_cast<float*>(nullptr));
+    }
+    if (grad_w2c != nullptr) {
+        const int rc = launch_w2c_reduce(N, w2c_partials, grad_w2c, s);
+        if (rc) return rc;
     }
     // SH backward (convert_sh_to_color_backward, kernel_utils.cuh:38-106) with the coalesced three-phase kernel of sh.hip: reads dL/d(clamped colour) from the
     // accumulator rows (floats 6..8 of 16), the clamp mask from the record's colour (floats 8..10 of 16), writes g_sh0 / g_sh_rest fully, adds dL/dposition to g_means

@@ -567,13 +567,25 @@ fast_gs::rasterization::backward_wrapper(
     (void)image; (void)per_tile_buffers; (void)per_bucket_buffers; (void)n_visible_primitives; (void)n_buckets;
     (void)primitive_primitive_indices_selector; (void)instance_primitive_indices_selector;
     LFS_DEVICE_GUARD(means);
-    TORCH_CHECK(!w2c.requires_grad(), "pose optimisation (grad_w2c) is not implemented by this backend");
     const uint32_t N = (uint32_t)means.size(0), total_rest = (uint32_t)sh_coefficients_rest.size(1);
     const auto fopt = means.options().dtype(at::kFloat);
     at::Tensor g_means = at::empty({N, 3}, fopt), g_scales = at::empty({N, 3}, fopt), g_rot = at::empty({N, 4}, fopt), g_opac = at::empty({N, 1}, fopt);
     at::Tensor g_sh0 = at::empty({N, 1, 3}, fopt), g_shr = at::empty({N, (int64_t)total_rest, 3}, fopt);
     const at::Tensor gi = grad_image.contiguous(), ga = grad_alpha.contiguous(), al = alpha.contiguous(), w2c_c = w2c.contiguous(), cam_c = cam_position.contiguous();
     const bool dens = densification_info.defined() && densification_info.dim() > 0 && densification_info.size(0) > 0;
+    if (w2c.requires_grad()) {   // pose optimisation (rasterization_api.cu:133-136): the camera gradient as the 7th element, shaped like w2c
+        TORCH_CHECK(w2c.numel() == 16, "w2c must hold one [4,4] transform");
+        at::Tensor g_w2c = at::empty_like(w2c_c), ws = at::empty({(int64_t)lfs_fastgs_w2c_workspace_bytes(N)}, means.options().dtype(at::kByte));
+        check_rc(lfs_fastgs_backward_w2c(N, means.data_ptr<float>(), scales_raw.data_ptr<float>(), rotations_raw.data_ptr<float>(), nullptr,
+                                         total_rest ? sh_coefficients_rest.data_ptr<float>() : nullptr, total_rest, w2c_c.data_ptr<float>(), cam_c.data_ptr<float>(),
+                                         (uint32_t)active_sh_bases, (uint32_t)width, (uint32_t)height, focal_x, focal_y, center_x, center_y, near_plane, far_plane,
+                                         (int64_t)n_instances, per_primitive_buffers.data_ptr(), (size_t)per_primitive_buffers.numel(), per_instance_buffers.data_ptr(),
+                                         (size_t)per_instance_buffers.numel(), gi.data_ptr<float>(), ga.data_ptr<float>(), al.data_ptr<float>(),
+                                         dens ? densification_info.data_ptr<float>() : nullptr, g_means.data_ptr<float>(), g_scales.data_ptr<float>(),
+                                         g_rot.data_ptr<float>(), g_opac.data_ptr<float>(), g_sh0.data_ptr<float>(), total_rest ? g_shr.data_ptr<float>() : nullptr,
+                                         g_w2c.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(), cur_stream()), "fast_gs::rasterization::backward (grad_w2c)");
+        return {g_means, g_scales, g_rot, g_opac, g_sh0, g_shr, g_w2c};
+    }
     check_rc(lfs_fastgs_backward(N, means.data_ptr<float>(), scales_raw.data_ptr<float>(), rotations_raw.data_ptr<float>(), nullptr,
                                  total_rest ? sh_coefficients_rest.data_ptr<float>() : nullptr, total_rest, w2c_c.data_ptr<float>(), cam_c.data_ptr<float>(),
                                  (uint32_t)active_sh_bases, (uint32_t)width, (uint32_t)height, focal_x, focal_y, center_x, center_y, near_plane, far_plane,

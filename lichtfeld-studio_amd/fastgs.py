@@ -14,7 +14,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from .capi import LfsError, check, load_library, ptr, require_gpu, stream
+from .capi import LfsError, check, load_library, ptr, require_gpu, stream, workspace
 from .rasterizer import Camera, RenderOutput, SplatModel
 
 
@@ -76,11 +76,14 @@ def forward_wrapper(means, scales_raw, rotations_raw, opacities_raw, sh_coeffici
 
 def backward_wrapper(densification_info: Optional[torch.Tensor], grad_image, grad_alpha, image, alpha, means, scales_raw, rotations_raw,
                      sh_coefficients_0, sh_coefficients_rest, primitive_workspace, instance_workspace, w2c, s: FastGSSettings, n_instances: int, out=None,
-                     adam_sh_rest: Optional[dict] = None):
+                     adam_sh_rest: Optional[dict] = None, grad_w2c: Optional[torch.Tensor] = None):
     """-> (grad_means, grad_scales_raw, grad_rotations_raw, grad_opacities_raw [N,1], grad_sh_coefficients_0, grad_sh_coefficients_rest);
     densification_info [2,N] (when given and non-empty) is accumulated into in place (kernels_backward.cuh:229-232).
     Extension `adam_sh_rest` (FusedAdam.prepare_inline of sh_coefficients_rest; single-view steps): the rest-coefficient gradient is not
-    written, the coefficients and their moments are updated in place by the SH backward (lfs_fastgs_backward_adam)."""
+    written, the coefficients and their moments are updated in place by the SH backward (lfs_fastgs_backward_adam).
+    `grad_w2c` (pose optimisation; a contiguous float32 out buffer of 16 elements, e.g. zeros_like(w2c)): the camera gradient the reference's backward returns
+    when w2c requires grad (rasterization_api.cu:133-136) is WRITTEN into it - rows 0-2 = sum over the visible primitives of dL/d(mean in camera space) (x) (mean, 1),
+    row 3 = 0 (lfs_fastgs_backward_w2c). None: today's entry points. Not combined with adam_sh_rest."""
     w2c = w2c.reshape(-1, 4, 4)[0].contiguous()
     cam_position = s.cam_position.reshape(-1)[:3].contiguous()
     grad_image, grad_alpha, alpha = grad_image.contiguous(), grad_alpha.contiguous(), alpha.contiguous()
@@ -100,6 +103,20 @@ def backward_wrapper(densification_info: Optional[torch.Tensor], grad_image, gra
         g_opac = torch.empty((N, 1), dtype=means.dtype, device=means.device)
         g_sh0 = torch.empty((N, 1, 3), dtype=means.dtype, device=means.device)
         g_shr = torch.empty_like(shr)
+    if grad_w2c is not None:
+        if adam_sh_rest is not None:
+            raise LfsError("grad_w2c is not available together with adam_sh_rest: pose optimisation takes the separate optimizer")
+        if grad_w2c.numel() != 16 or grad_w2c.dtype != torch.float32 or not grad_w2c.is_contiguous():
+            raise LfsError("grad_w2c must be a contiguous float32 buffer of 16 elements ([4,4] or [1,4,4])")
+        require_gpu(grad_w2c)
+        lib = load_library()
+        ws = workspace(lib.lfs_fastgs_w2c_workspace_bytes(C.c_uint32(N)), means.device, "fastgs_w2c")
+        check(lib.lfs_fastgs_backward_w2c(
+            C.c_uint32(N), ptr(means), ptr(scales_raw), ptr(rotations_raw), ptr(sh0), ptr(shr), C.c_uint32(total_rest), ptr(w2c), ptr(cam_position), *_frame_args(s),
+            C.c_int64(n_instances), ptr(primitive_workspace), C.c_size_t(primitive_workspace.numel()), ptr(instance_workspace), C.c_size_t(instance_workspace.numel()),
+            ptr(grad_image), ptr(grad_alpha), ptr(alpha), ptr(dens), ptr(g_means), ptr(g_scales), ptr(g_rot), ptr(g_opac), ptr(g_sh0), ptr(g_shr),
+            ptr(grad_w2c), ptr(ws), C.c_size_t(ws.numel()), stream()), "fastgs_backward_w2c")
+        return g_means, g_scales, g_rot, g_opac, g_sh0, g_shr
     if adam_sh_rest is not None and total_rest > 0:
         a = adam_sh_rest
         if not sh_coefficients_rest.is_contiguous():
@@ -132,8 +149,10 @@ class FastGSRasterize(torch.autograd.Function):
     def backward(ctx, grad_image, grad_alpha):
         image, alpha, means, scales_raw, rotations_raw, sh0, sh_rest, w2c = ctx.saved_tensors
         pws, iws, n_instances, settings, dens, opac_shape = ctx.state
-        g = backward_wrapper(dens, grad_image, grad_alpha, image, alpha, means, scales_raw, rotations_raw, sh0, sh_rest, pws, iws, w2c, settings, n_instances)
-        return g[0], g[1], g[2], g[3].reshape(opac_shape), g[4], g[5], None, None, None
+        g_w2c = torch.empty_like(w2c, memory_format=torch.contiguous_format) if ctx.needs_input_grad[6] else None   # pose optimisation: fast_rasterizer_autograd.cpp hands grad_w2c on
+        g = backward_wrapper(dens, grad_image, grad_alpha, image, alpha, means, scales_raw, rotations_raw, sh0, sh_rest, pws, iws, w2c, settings, n_instances,
+                             grad_w2c=g_w2c)
+        return g[0], g[1], g[2], g[3].reshape(opac_shape), g[4], g[5], g_w2c, None, None
 
 
 def fast_rasterize(camera: Camera, model: SplatModel, bg_color: torch.Tensor, densification_info: Optional[torch.Tensor] = None) -> RenderOutput:
@@ -163,10 +182,11 @@ def mse_loss_chw_fwd_bwd(render_chw: torch.Tensor, target_chw: torch.Tensor, wei
 
 def render_and_backward(settings: FastGSSettings, w2c: torch.Tensor, model: SplatModel, target_chw: torch.Tensor, weight: float, grads, loss_acc: torch.Tensor,
                         densification_info: Optional[torch.Tensor] = None, loss: str = "mse", lambda_dssim: float = 0.2, bilateral=None, image_idx: int = 0,
-                        adam_shN: Optional[dict] = None):
+                        adam_shN: Optional[dict] = None, grad_w2c: Optional[torch.Tensor] = None):
     """One training view without an autograd graph (black background; loss "mse" or the trainer's "l1_ssim", trainer.cpp:122-125):
     forward, [bilateral-grid slice, trainer.cpp:662-664,] loss, backward; the gradients of (means, sh0, shN, raw_scales, raw_quats,
-    raw_opacities) are WRITTEN into `grads` (param-group order); the bilateral grid's gradient is accumulated into its .grad."""
+    raw_opacities) are WRITTEN into `grads` (param-group order); the bilateral grid's gradient is accumulated into its .grad;
+    `grad_w2c` (optional out buffer, pose optimisation): the camera gradient is written into it (backward_wrapper)."""
     means, sh0, shN, raw_scales, raw_quats, raw_opac = [p.detach() for p in model.parameters()]
     g_means, g_sh0, g_shN, g_scales, g_quats, g_opac = grads
     with torch.no_grad():
@@ -184,5 +204,5 @@ def render_and_backward(settings: FastGSSettings, w2c: torch.Tensor, model: Spla
         if not hasattr(render_and_backward, "_zero") or render_and_backward._zero.shape != alpha.shape or render_and_backward._zero.device != alpha.device:
             render_and_backward._zero = torch.zeros_like(alpha)
         backward_wrapper(densification_info, v_image, render_and_backward._zero, image, alpha, means, raw_scales, raw_quats, sh0, shN, pws, iws, w2c, settings, n_inst,
-                         out=(g_means, g_scales, g_quats, g_opac.view(-1, 1), g_sh0, g_shN), adam_sh_rest=adam_shN)
+                         out=(g_means, g_scales, g_quats, g_opac.view(-1, 1), g_sh0, g_shN), adam_sh_rest=adam_shN, grad_w2c=grad_w2c)
     return image, alpha, n_inst

@@ -45,7 +45,8 @@ def plan_step(*, rasterizer: str, fused_l2: bool, world: int, force_collectives:
         off - -> the kernels enqueued from Python view by view (py_views).
       * one_call (opt-in, GutTrainer(one_call=True)): one view on one rank ALSO takes the one-call form (cxx_all, lfs_gut_train_step_opt) for what the reference trains -
         loss "mse" or "l1_ssim", no strategy or MCMC between refinements (its noise is folded into the tail), at ANY iteration (<= 1000: freeze_shN, the tail skips
-        shN as FusedAdam does) - given the fused optimizer, an shN, cxx_step and no bilateral grid. Everything else keeps the form it has with the keyword off."""
+        shN as FusedAdam does) - given the fused optimizer, an shN, cxx_step and no bilateral grid. Everything else keeps the form it has with the keyword off.
+      * pose optimisation is not an input: GutTrainer's constructor admits it on the fastgs rasterizer of one rank only, whose plan has no inline form."""
     multi = world > 1 or force_collectives
     if rasterizer == "fastgs":
         return StepPlan("fastgs", False, False, False, multi, iteration <= 1000)
@@ -82,13 +83,22 @@ class GutTrainer:
                  views_per_rank: int = 1, fused_adam: bool = True, fused_l2: bool = True, loss: str = "mse", lambda_dssim: float = 0.2,
                  strategy: Optional[str] = None, opt_params=None, scene_scale: float = 1.0, seed: int = 0, rasterizer: str = "gut",
                  use_bilateral_grid: bool = False, bilateral_grid_dims=(16, 16, 8), bilateral_grid_lr: float = 2e-3, tv_loss_weight: float = 10.0,
-                 sh_sharded: Optional[bool] = None, factored_sh: bool = False, one_call: bool = False):
+                 sh_sharded: Optional[bool] = None, factored_sh: bool = False, one_call: bool = False, pose_optimization: str = "none", pose_lr: float = 1e-5):
         """strategy: None (fixed set of Gaussians: the benchmark), "mcmc" (strategies.MCMC: relocation + growth + SGLD noise, with
         the scale / opacity regularisers of trainer.cpp:132-158) or "default" (ADC; needs densification_info, see strategies.py).
         `seed` seeds the strategy's generator: the same on every rank, so replicas densify identically.
         one_call: one view per step on one rank takes the one-call C++ step (no host read, no gradient tensors) for loss "l1_ssim", for MCMC between refinements and
         while iteration <= 1000 as well, not only for the MSE benchmark configuration (plan_step). Same trajectory as the default forms; off by default. A model with
-        SH degree 4 (more than 16 coefficients per channel) keeps the default forms: the switch has no effect there."""
+        SH degree 4 (more than 16 coefficients per channel) keeps the default forms: the switch has no effect there.
+        pose_optimization: "none" | "direct" | "mlp" (trainer.cpp:366-389; poseopt.py): a learned correction of every training camera's world-to-camera transform,
+        trained with Adam(pose_lr) on the camera gradient of the fastgs backward. fastgs rasterizer, one rank."""
+        if pose_optimization not in ("none", "direct", "mlp"):
+            raise ValueError(f"Invalid pose optimization type: {pose_optimization}")
+        if pose_optimization != "none":
+            if rasterizer == "gut":   # trainer.cpp:371-374
+                raise ValueError("The 3DGUT rasterizer doesn't have camera gradients yet. Please disable pose optimization or disable gut.")
+            if world > 1:
+                raise ValueError("pose optimisation is implemented for one rank (world == 1)")
         self.one_call = bool(one_call)
         self.device, self.world, self.rank, self.views_per_rank = device, world, rank, views_per_rank
         sc = scene.to(device)
@@ -171,6 +181,13 @@ class GutTrainer:
         self.iteration = 0
         self.last_plan: Optional[StepPlan] = None   # the form the last step took (plan_step): tests and tools read it
         self.last_n_isects = 0
+        # pose optimisation (trainer.cpp:366-389, :648-649, :763-765): None for "none" - nothing below then differs from a trainer without the argument
+        self.pose_module, self.pose_optimizer = None, None
+        self.last_grad_w2c = None     # [1,4,4]: the camera gradient of the last view rendered with pose optimisation on (tests and tools read it)
+        if pose_optimization != "none":
+            from .poseopt import make_pose_module
+            self.pose_module = make_pose_module(pose_optimization, int(sc.viewmats.shape[0])).to(device)
+            self.pose_optimizer = torch.optim.Adam(self.pose_module.parameters(), lr=pose_lr)
         self._last_radii = None
         self._last_visible = None
 
@@ -227,13 +244,21 @@ class GutTrainer:
             self._fg_tmp = [torch.empty_like(v) for v in self.bucket.views]
         inline = None   # one view on one rank, Adam reading shN: the SH backward inside lfs_fastgs_backward_adam updates shN itself
         if (self.inline_shN_adam and self.world == 1 and len(views) == 1 and self.strategy is None and self.iteration > 1000 and self.model.shN.shape[1] > 0
-                and getattr(self.optimizer, "fused", False)):
+                and getattr(self.optimizer, "fused", False) and self.pose_module is None):   # (lfs_fastgs_backward_adam has no camera gradient)
             inline = self.optimizer.prepare_inline(self.model.shN)
         for k, v in enumerate(views):
             dst = self.bucket.views if k == 0 else self._fg_tmp
-            _, _, self.last_n_isects = fg_step(self._fastgs_settings(v), self.scene.viewmats[v:v + 1].contiguous(), self.model, targets[k % len(targets)],
+            w2c, w2c_adj, g_w2c = self.scene.viewmats[v:v + 1].contiguous(), None, None
+            if self.pose_module is not None:
+                # trainer.cpp:648-649: the adjusted transform under autograd; cam_position stays the stored camera's (Camera(const Camera&, transform) copies it)
+                w2c_adj = self.pose_module(w2c, [v])
+                w2c, g_w2c = w2c_adj.detach().contiguous(), torch.empty_like(w2c)
+            _, _, self.last_n_isects = fg_step(self._fastgs_settings(v), w2c, self.model, targets[k % len(targets)],
                                                1.0 / total_views, dst, self.loss_acc, densification_info=dens, loss=self.loss_kind,
-                                               lambda_dssim=self.lambda_dssim, bilateral=self.bilateral, image_idx=v, adam_shN=inline)
+                                               lambda_dssim=self.lambda_dssim, bilateral=self.bilateral, image_idx=v, adam_shN=inline, grad_w2c=g_w2c)
+            if w2c_adj is not None:
+                w2c_adj.backward(g_w2c)   # accumulates into the module's parameters over the views of the step
+                self.last_grad_w2c = g_w2c
             if k > 0:
                 for a, b in zip(self.bucket.views, self._fg_tmp):
                     a.add_(b)
@@ -263,6 +288,9 @@ class GutTrainer:
         else:
             self.optimizer.step(self.iteration)
             self.scheduler.step()
+        if self.pose_optimizer is not None:   # trainer.cpp:763-765: after the model's optimizer step
+            self.pose_optimizer.step()
+            self.pose_optimizer.zero_grad(set_to_none=True)
         return self.loss_acc
 
     def _bilateral_step(self) -> None:

@@ -34,7 +34,11 @@ def main():
     ap.add_argument("-o", "--output-path", default="output")
     ap.add_argument("--text", action="store_true", help="read cameras.txt / images.txt / points3D.txt")
     ap.add_argument("--eval-every", type=int, default=0, help="with --eval: held-out PSNR (the renderer the model trains with) every N iterations -> 'psnr_curve' (the turbulence of an MCMC run)")
+    ap.add_argument("--pose-optimization", default="none", choices=["none", "direct", "mlp"],
+                    help="learn a correction of every training camera's pose (fastgs rasterizer only; not together with --eval, as in the reference)")
     args = ap.parse_args()
+    if args.pose_optimization != "none" and args.eval:   # trainer.cpp:367-370
+        raise SystemExit("Evaluating with pose optimization is not supported yet. Please disable pose optimization or evaluation.")
 
     import lichtfeld_studio_amd  # noqa: F401
     from lichtfeld_studio_amd import evaluate, loader, strategies
@@ -56,7 +60,7 @@ def main():
     if args.bilateral_grid and rast != "fastgs":
         raise SystemExit("--bilateral-grid needs the fastgs rasterizer")
     tr = GutTrainer(scene, dev, iterations=args.iterations, loss="l1_ssim", strategy=None if args.strategy == "none" else args.strategy, opt_params=op,
-                    scene_scale=scene_scale, rasterizer=rast, use_bilateral_grid=args.bilateral_grid)
+                    scene_scale=scene_scale, rasterizer=rast, use_bilateral_grid=args.bilateral_grid, pose_optimization=args.pose_optimization)
     g = torch.Generator().manual_seed(0)
     val_set = None
     if args.eval and args.eval_every > 0:
@@ -102,7 +106,7 @@ def main():
     torch.cuda.synchronize()
     t_train = time.time() - t0 - t_eval
     out = {"data": args.data_path, "images": len(ds), "size": [scene.width, scene.height], "iterations": args.iterations, "rasterizer": rast,
-           "strategy": args.strategy, "gaussians": int(tr.model.means.shape[0]), "load_s": round(t_load, 1), "train_s": round(t_train, 1),
+           "strategy": args.strategy, "pose_optimization": args.pose_optimization, "gaussians": int(tr.model.means.shape[0]), "load_s": round(t_load, 1), "train_s": round(t_train, 1),
            "iters_per_s": round(args.iterations / max(t_train, 1e-9), 1)}
     if args.eval:
         cams_all, _ = (loader.read_colmap_cameras_and_images_text if args.text else loader.read_colmap_cameras_and_images)(args.data_path, args.images)
