@@ -572,6 +572,27 @@ typedef struct lfs_adam_tensor {
 #define LFS_ADAM_MAX_TENSORS 8
 LFS_API int lfs_adam_step_multi(const lfs_adam_tensor* tensors /* host array */, int32_t n_tensors, lfs_stream_t stream);
 
+/* ---- SOG export (csrc/sog.hip): Morton codes (kernels/morton_encoding.cu:21-97) and the three kernels of Lloyd's iteration (kernels/kmeans.cu:18-122).
+ *      All entry points are asynchronous on `stream`, validate on the host before any launch (LFS_E_INVALID: NULL pointer, negative count, k or D of 0, a
+ *      workspace that is not 16-byte aligned; LFS_E_UNSUPPORTED: k > 65536 or D > 64; LFS_E_WORKSPACE: workspace short), use no float atomics (same bits on every
+ *      run) and return LFS_OK without a launch for N == 0.
+ *      lfs_morton_encode: codes[i] = interleave21(x, y, z) + INT64_MIN with q = uint32((double)(p - min) / (double)cube * 2097151.0), the subtraction in f32,
+ *        cube = max(max_axis(max - min), 1e-7f); min / max are part of the call (per-block partials, one folding block, no host read).
+ *      lfs_kmeans_assign: labels[i] = argmax_c (x_i . c - |c|^2 / 2), lowest index among exactly equal scores; each score is an ascending-d f32 fmaf chain on
+ *        -|c|^2 / 2 (v_mfma_f32_16x16x4_f32). 1 <= k <= 65536, 1 <= D <= 64.
+ *      lfs_kmeans_assign_1d: centroids ascending; labels[i] = the first index that minimises fabsf(p - c) under a strict < (kmeans.cu:58-83), duplicates included.
+ *      lfs_kmeans_update: centroids[c] = mean of data[order[seg_start[c] .. seg_start[c+1])] (f64 sums in a fixed order); order = point indices sorted by label,
+ *        seg_start[k + 1] = the segment bounds. An empty segment leaves its centroid untouched (kmeans.cu:119-121). Indices outside [0, N) are skipped. */
+LFS_API size_t lfs_morton_workspace_bytes(int64_t N);
+LFS_API int lfs_morton_encode(int64_t N, const float* means /* [N,3] */, int64_t* codes /* [N] */, void* workspace, size_t workspace_bytes, lfs_stream_t stream);
+LFS_API size_t lfs_kmeans_assign_workspace_bytes(uint32_t k, uint32_t D); /* 0: k / D out of range */
+LFS_API int lfs_kmeans_assign(int64_t N, uint32_t k, uint32_t D, const float* data /* [N,D] */, const float* centroids /* [k,D] */, int32_t* labels /* [N] */,
+                              void* workspace, size_t workspace_bytes, lfs_stream_t stream);
+LFS_API int lfs_kmeans_assign_1d(int64_t n, uint32_t k, const float* data /* [n] */, const float* sorted_centroids /* [k] */, int32_t* labels /* [n] */,
+                                 lfs_stream_t stream);
+LFS_API int lfs_kmeans_update(int64_t N, uint32_t k, uint32_t D, const float* data /* [N,D] */, const int32_t* order /* [N] */, const int32_t* seg_start /* [k+1] */,
+                              float* centroids /* [k,D], in place */, lfs_stream_t stream);
+
 /* ---- instrumentation (not in the reference): per-kernel HIP-event timing on the launch stream.
  *      lfs_profile_enable(1) makes every entry point bracket its principal kernel(s) with events;
  *      lfs_profile_collect waits for them, sums by kernel name (names: max_entries x 64 chars)

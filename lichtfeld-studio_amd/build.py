@@ -38,6 +38,7 @@ SOURCES = {
     "bilateral_grid.hip": ["-ffp-contract=off"],
     "dataprep.hip": ["-ffp-contract=off"],
     "fastgs_prep.hip": ["-ffp-contract=off"],
+    "sog.hip": ["-ffp-contract=off"],   # SOG export: Morton codes, k-means (the MFMA assignment is an fmaf chain by construction; the flag holds the rest)
     "fastgs_blend.hip": ["-fno-slp-vectorize"],
     "prof.hip": [],
     # no SLP packing: v_pk_* operand pairing forces SGPR shuffles right after the scalar record

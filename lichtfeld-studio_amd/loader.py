@@ -6,6 +6,7 @@ liblfs_io.so (include/lfs_io.h; C++17, no GPU) plus the two GPU kernels of csrc/
   load_image                             src/core/image_io.cpp:112-270 + src/core/camera.cpp:101-140 -> f32 [3,h,w] on the GPU
   init_model_from_pointcloud             src/core/splat_data.cpp:508-614          -> (SplatModel, scene_scale)
   save_ply / load_ply                    src/core/splat_data.cpp:113-169, :402-419 / src/loader/formats/ply.cpp
+  save_sog / load_sog                    src/core/sogs.cpp:335-744 / src/loader/formats/sogs.cpp (sog.py)
   CameraDataset                          src/training/dataset.hpp:25-75 (every test_every-th image is a validation view)
   colmap_scene                           the Scene the trainer consumes (viewmats [R|t], K scaled to the loaded image size:
                                          src/core/camera.cpp:15-23, :77-98)
@@ -304,6 +305,19 @@ def save_ply(model, path: str) -> None:
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     _check(io_library().lfs_ply_write_splat(os.fsencode(path), C.c_uint64(N), C.c_uint32(f_dc.shape[1]), C.c_uint32(f_rest.shape[1]), p(arrs[0]), None, p(f_dc),
                                             p(f_rest), p(arrs[3]), p(arrs[4]), p(rot)))
+
+
+def save_sog(model, path: str, iterations: int = 10, palette_size: Optional[int] = None) -> dict:
+    """write_sog (src/core/sogs.cpp:335-744): the compressed bundle web viewers load - a ZIP for a path ending in .sog, loose files beside any other path.
+    See sog.write_sog for the layout and for the differences from the reference writer. -> the meta dictionary."""
+    from .sog import write_sog
+    return write_sog(model, path, iterations=iterations, palette_size=palette_size)
+
+
+def load_sog(path: str, device="cuda:0"):
+    """src/loader/formats/sogs.cpp: a .sog bundle, a meta.json or its directory -> SplatModel (in the file's Morton order)."""
+    from .sog import read_sog
+    return read_sog(path, device)
 
 
 def read_ply(path: str) -> Tuple[List[str], np.ndarray]:

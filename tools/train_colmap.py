@@ -5,7 +5,7 @@
     python tools/train_colmap.py -d /data/garden --images images_4 --iterations 30000 --strategy default --eval -o out/garden
 
 COLMAP reader -> point-cloud initialisation -> fastgs (default) or 3DGUT training with the L1 + SSIM loss and the ADC / MCMC strategy ->
-PSNR / SSIM on the held-out views -> splat PLY. Prints one JSON line. All views must share one image size.
+PSNR / SSIM on the held-out views -> splat PLY (and, with --save-sog, the .sog bundle). Prints one JSON line. All views must share one image size.
 """
 import argparse
 import json
@@ -36,6 +36,9 @@ def main():
     ap.add_argument("--eval-every", type=int, default=0, help="with --eval: held-out PSNR (the renderer the model trains with) every N iterations -> 'psnr_curve' (the turbulence of an MCMC run)")
     ap.add_argument("--pose-optimization", default="none", choices=["none", "direct", "mlp"],
                     help="learn a correction of every training camera's pose (fastgs rasterizer only; not together with --eval, as in the reference)")
+    ap.add_argument("--save-sog", action="store_true", help="also write splat_<iterations>.sog, the compressed bundle web viewers load (the reference's --save-sog)")
+    ap.add_argument("--sog-iterations", type=int, default=10, help="k-means iterations of the SOG export (the reference's sog_iterations)")
+    ap.add_argument("--sog-palette-size", type=int, default=None, help="entries of the SOG shN palette, up to min(65536, N) (default: the reference's value, 64 from 1024 Gaussians on)")
     args = ap.parse_args()
     if args.pose_optimization != "none" and args.eval:   # trainer.cpp:367-370
         raise SystemExit("Evaluating with pose optimization is not supported yet. Please disable pose optimization or evaluation.")
@@ -128,6 +131,10 @@ def main():
     ply = os.path.join(args.output_path, f"splat_{args.iterations}.ply")
     loader.save_ply(tr.model, ply)
     out["ply"] = ply
+    if args.save_sog:
+        sog_path = os.path.join(args.output_path, f"splat_{args.iterations}.sog")
+        loader.save_sog(tr.model, sog_path, iterations=args.sog_iterations, palette_size=args.sog_palette_size)
+        out.update(sog=sog_path, sog_bytes=os.path.getsize(sog_path), ply_bytes=os.path.getsize(ply))
     print(json.dumps(out), flush=True)
 
 
