@@ -457,7 +457,7 @@ LFS_API int lfs_gut_step_wait(const int64_t* host_counts, int64_t stamp, double 
  *      workspace's colours for every Gaussian, from the coefficient rows as they leave their Adam update. colors_ready != 0: the caller's statement that the previous call on
  *      this workspace was this entry point with next_viewmat naming the matrix args->viewmat holds now, same N / K / sh_degree, that it fitted its buffers, and that nothing
  *      has written means / sh0 / shN since - the SH colour kernel is then not launched. Same results as lfs_gut_train_step. (= lfs_gut_train_step_opt with opts == NULL:
- *      the four lfs_gut_train_step* entry points are argument adapters of one enqueue sequence in csrc/gut_step.hip.) */
+ *      the three lfs_gut_train_step* entry points are argument adapters of one enqueue sequence in csrc/gut_step.hip.) */
 LFS_API int lfs_gut_train_step_ex(const lfs_gut_step_args* args, const float* next_viewmat, int colors_ready, int64_t capacity, int64_t assumed_longest, void* workspace,
                                   size_t workspace_bytes, int64_t* host_counts, int64_t stamp, lfs_stream_t stream);
 /*   lfs_gut_train_step_opt: lfs_gut_train_step_ex for the configuration the reference trains - the photometric loss, the MCMC strategy's noise, shN frozen for the first
@@ -485,17 +485,6 @@ LFS_API size_t lfs_gut_step_loss_workspace_bytes(uint32_t image_width, uint32_t 
 LFS_API int lfs_gut_train_step_opt(const lfs_gut_step_args* args, const lfs_gut_step_options* opts /* NULL = all zero */, const float* next_viewmat, int colors_ready,
                                    int64_t capacity, int64_t assumed_longest, void* workspace, size_t workspace_bytes, int64_t* host_counts, int64_t stamp,
                                    lfs_stream_t stream);
-/*   lfs_gut_train_step_pipelined (round 6): lfs_gut_train_step - same arguments, same results - with the step's HBM-bound SH kernels on a side stream of the library,
- *      UNDER the latency- / VALU-bound front end of the NEXT step: projection(k+1) (records without colours) | tile lists | culling run on `stream` while SH Adam(k)
- *      (1.1 GB of read-modify-write at 1 M Gaussians) and the SH colours(k+1) run beside them; `stream` waits for the colours in front of the forward kernel. The SH
- *      backward is split for it: a direction pass on `stream` (dL/d(dirs) + a 32-byte hand-over row per Gaussian) and the Adam pass on the side stream.
- *      CONTRACT: between two pipelined calls sh0, shN and their Adam moments belong to the side stream - lfs_gut_pipeline_join(stream) makes `stream` wait (device-side,
- *      no host wait) for the last update before anything else touches them (every other lfs_gut_* entry point that enqueues SH work joins by itself; this one never joins in
- *      front of its own step). All other tensors stay ordered on `stream`.
- *   lfs_gut_pipeline_join: 1 = there was a pending update and `stream` now waits for it, 0 = nothing pending, < 0 = error. */
-LFS_API int lfs_gut_train_step_pipelined(const lfs_gut_step_args* args, int64_t capacity, int64_t assumed_longest, void* workspace, size_t workspace_bytes,
-                                         int64_t* host_counts, int64_t stamp, lfs_stream_t stream);
-LFS_API int lfs_gut_pipeline_join(lfs_stream_t stream);
 
 /* Extension: the all-inline training step of the fused 3DGUT path (one camera, global shutter, 3 channels, ONE view per step on one rank - the
  * reference's training configuration). No parameter gradient is materialised:

@@ -34,8 +34,7 @@ inline size_t a256(size_t v) { return (v + 255) & ~size_t(255); }
 
 struct StepWs {
     float *quats, *scales, *opacities, *means2d, *depths, *colors, *v_dirs, *render, *alpha;
-    int32_t *radii, *tiles_per_gauss, *flatten_ids, *last_ids, *abort_flag, *abort_snapshot;
-    void* handover;   // pipelined step: 32 bytes per Gaussian from the SH direction kernel (main stream) to the SH Adam kernel (side stream)
+    int32_t *radii, *tiles_per_gauss, *flatten_ids, *last_ids, *abort_flag;
     int64_t *isect_ids, *binned, *dev_counts;
     void *isect_ws, *raster_ws;
     size_t isect_ws_bytes, raster_ws_bytes, bytes;
@@ -57,9 +56,7 @@ bool step_ws(void* base, uint32_t N, uint32_t W, uint32_t H, uint32_t tile, int6
     if (w.raster_ws_bytes == 0) return false;
     const size_t o_rws = take(w.raster_ws_bytes);
     const size_t o_render = take(12 * P), o_alpha = take(4 * P), o_last = take(4 * P), o_flag = take(4), o_counts = take(32);
-    const size_t o_hand = take(32 * n), o_snap = take(4);   // (appended in round 6: every earlier offset is where it was)
     w.bytes = o;
-    w.handover = p + o_hand; w.abort_snapshot = (int32_t*)(p + o_snap);
     w.quats = (float*)(p + o_quats); w.scales = (float*)(p + o_scales); w.opacities = (float*)(p + o_opac); w.radii = (int32_t*)(p + o_radii);
     w.means2d = (float*)(p + o_m2d); w.depths = (float*)(p + o_depths); w.tiles_per_gauss = (int32_t*)(p + o_tpg); w.colors = (float*)(p + o_colors);
     w.v_dirs = (float*)(p + o_vdirs); w.isect_ws = p + o_iws; w.isect_ids = (int64_t*)(p + o_ids); w.flatten_ids = (int32_t*)(p + o_flat);
@@ -85,34 +82,6 @@ void front_of(const lfs_gut_step_args* a, const StepWs& w, Front& f) {
     f.offsets = isect_workspace_offsets(w.isect_ws, 1, a->N, tw, th);
 }
 
-// ---- the pipelined step's side stream -------------------------------------------------------------------------------------------------------------------
-// One per process (one process per GPU). The SH colour kernel of step k + 1 and the SH Adam kernel of step k live on it; three events tie it to the caller's
-// stream (see the pipelined form below). `done` is what lfs_gut_pipeline_join makes a stream wait for.
-struct Pipeline {
-    hipStream_t side = nullptr;
-    hipEvent_t projected = nullptr, colours = nullptr, dirs = nullptr, done = nullptr;
-    bool pending = false;   // a side-stream update has been enqueued since the last join
-    int init() {
-        if (side != nullptr) return LFS_OK;
-        // a plain stream, the SH Adam pass beside the finish pass: stream priority, CU masks and start-behind-finish were measured and rejected (profiles/r06/pipeline/README.md)
-        hipError_t e = hipStreamCreateWithFlags(&side, hipStreamNonBlocking);   // (non-blocking: no implicit ordering against the legacy default stream torch may hand in)
-        if (e != hipSuccess) { side = nullptr; return (int)e; }
-        for (hipEvent_t* ev : {&projected, &colours, &dirs, &done}) {
-            e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
-            if (e != hipSuccess) return (int)e;
-        }
-        return LFS_OK;
-    }
-};
-Pipeline g_pipe;
-// the other step forms read / write sh0 and shN on the caller's stream: they wait for a pending side-stream update first
-int auto_join(hipStream_t s) {
-    if (!g_pipe.pending || g_pipe.side == nullptr) return LFS_OK;
-    if (hipStreamWaitEvent(s, g_pipe.done, 0) != hipSuccess) return LFS_E_INVALID;
-    g_pipe.pending = false;
-    return LFS_OK;
-}
-
 // what a call needs of its argument block: the forward's tensors only; all six Adam states; or all six with shN's optional (FusedAdam skips the frozen group)
 enum class Need { Forward, Adam, AdamFrozenShN };
 
@@ -127,10 +96,8 @@ int check_args(const lfs_gut_step_args* a, Need need) {
     return LFS_OK;
 }
 
-// What every entry point does before it enqueues anything: check the arguments (and, for the training step, its options `o`), lay the workspace out, check its size, and
-// - `join` - make the stream wait for a pending side-stream update: every form but the pipelined one reads / writes sh0 and shN on the caller's stream.
-int open_step(const lfs_gut_step_args* a, Need need, const lfs_gut_step_options* o, int64_t capacity, void* workspace, size_t workspace_bytes, hipStream_t s, bool join,
-              StepWs& w) {
+// What every entry point does before it enqueues anything: check the arguments (and, for the training step, its options `o`), lay the workspace out and check its size.
+int open_step(const lfs_gut_step_args* a, Need need, const lfs_gut_step_options* o, int64_t capacity, void* workspace, size_t workspace_bytes, StepWs& w) {
     const int rc = check_args(a, need);
     if (rc) return rc;
     if (o && a->K > 16 && (o->freeze_shN || o->noise)) return LFS_E_UNSUPPORTED;   // the three-pass tail of degree 4 has neither (enqueue_tail)
@@ -142,12 +109,12 @@ int open_step(const lfs_gut_step_args* a, Need need, const lfs_gut_step_options*
         if (!o->loss_workspace) return LFS_E_INVALID;
         if (o->loss_workspace_bytes < lfs_gut_step_loss_workspace_bytes(a->image_width, a->image_height)) return LFS_E_WORKSPACE;
     }
-    return join ? auto_join(s) : LFS_OK;
+    return LFS_OK;
 }
 
 // everything up to and including the rasterizer forward; shared by the Adam-inline step and the gradient-tensor step
 int enqueue_forward(const lfs_gut_step_args* a, const StepWs& w, int64_t capacity, int64_t assumed_longest, int64_t* host_counts, int64_t stamp, hipStream_t s, Front& f,
-                    Pipeline* pipe = nullptr, bool colors_ready = false) {   // colors_ready: w.colors holds this view's SH colours already (the previous step's fused tail wrote them)
+                    bool colors_ready = false) {   // colors_ready: w.colors holds this view's SH colours already (the previous step's fused tail wrote them)
     const uint32_t N = a->N, W = a->image_width, H = a->image_height, tile = a->tile_size;
     const uint32_t tw = (W + tile - 1) / tile, th = (H + tile - 1) / tile;
     front_of(a, w, f);
@@ -158,30 +125,18 @@ int enqueue_forward(const lfs_gut_step_args* a, const StepWs& w, int64_t capacit
     // Round 4: the SH colours are evaluated FIRST (for every Gaussian - visibility is not known yet, 6 % more coefficient rows on SYN-B) so that the projection
     // kernel, which has the activated quaternion / scale / opacity in registers, can write the rasterizer's 64-byte record and the 32-byte culling record of every
     // visible Gaussian itself: raster_pack_kernel's second pass over the Gaussians (0.040 ms, 152 MB re-read) is gone. Debug bit 6: the round-3 order (A/B, tests).
-    // Pipelined: the projection goes FIRST and packs the records without colours; the SH colours (visible Gaussians only - the radii exist now) follow on the side
-    // stream, behind the previous step's SH Adam kernel, into `colors` and into the rgb slots of the records; the main stream carries on with the tile lists and
-    // waits for them in front of the forward kernel.
-    const bool pack_here = pipe != nullptr || !(lfs_get_debug_flags() & 64u);
+    const bool pack_here = !(lfs_get_debug_flags() & 64u);
     void *recs = nullptr, *cull = nullptr;
     raster_workspace_parts(w.raster_ws, N, nullptr, &recs, &cull);
     int rc = LFS_OK;
-    if (pipe == nullptr && pack_here && !colors_ready) {
+    if (pack_here && !colors_ready) {
         rc = sh_model_fwd_impl(N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, nullptr, w.colors, s);
         if (rc) return rc;
     }
     rc = activations_project_ut_impl(N, a->means, a->raw_quats, a->raw_scales, a->raw_opacities, &f.cams, 0.3f, 0.01f, 10000.f, 0.f, &ut, w.quats, w.scales,
                                      w.opacities, w.radii, w.means2d, w.depths, isect_workspace_totals(w.isect_ws, 1, N, tw, th), tw * th, w.raster_ws, s,
-                                     pack_here ? recs : nullptr, pack_here ? cull : nullptr, pack_here && pipe == nullptr ? w.colors : nullptr);
+                                     pack_here ? recs : nullptr, pack_here ? cull : nullptr, pack_here ? w.colors : nullptr);
     if (rc) return rc;
-    if (pipe != nullptr) {
-        hipError_t e = hipEventRecord(pipe->projected, s);
-        if (e == hipSuccess) e = hipStreamWaitEvent(pipe->side, pipe->projected, 0);
-        if (e != hipSuccess) return (int)e;
-        rc = sh_model_fwd_records_impl(N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, w.radii, w.colors, static_cast<float*>(recs) + 13, 16, pipe->side);
-        if (rc) return rc;
-        e = hipEventRecord(pipe->colours, pipe->side);
-        if (e != hipSuccess) return (int)e;
-    }
     const IsectGuard guard{capacity, assumed_longest, w.abort_flag};
     int64_t* counts = host_counts ? host_counts : w.dev_counts;   // [n_isects, longest tile list, stamp]
     rc = isect_count_impl(1, N, w.means2d, w.radii, tile, tw, th, w.tiles_per_gauss, counts, counts + 1, nullptr, LFS_ISECT_COUNTERS_ZERO, counts + 2, stamp, w.isect_ws,
@@ -195,8 +150,7 @@ int enqueue_forward(const lfs_gut_step_args* a, const StepWs& w, int64_t capacit
                          w.isect_ws_bytes, s, &guard);
     if (rc) return rc;
     return raster_fwd_guarded(N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &f.cams, tile, f.offsets, w.flatten_ids, capacity, w.render, w.alpha,
-                              w.last_ids, w.raster_ws, w.raster_ws_bytes, s, /*cams_ready=*/true, /*records_ready=*/pack_here,
-                              /*wait_before_fwd=*/pipe != nullptr ? pipe->colours : nullptr);
+                              w.last_ids, w.raster_ws, w.raster_ws_bytes, s, /*cams_ready=*/true, /*records_ready=*/pack_here);
 }
 
 // accumulator-rows rasterizer backward of the view in the workspace. v_render NULL: args->target_chw is the loss target, the clamped MSE is folded in; otherwise
@@ -243,24 +197,7 @@ int enqueue_tail(const lfs_gut_step_args* a, const StepWs& w, const lfs_gut_step
                          w.abort_flag, o.freeze_shN != 0, o.noise, o.noise_lr);
 }
 
-// The pipelined form's tail: the SH direction pass and the finish pass stay on the caller's stream, the SH Adam pass goes to the side stream, beside the finish pass.
-int pipelined_tail(const lfs_gut_step_args* a, const StepWs& w, Pipeline& pipe, hipStream_t s) {
-    int rc = sh_pipe_dirs_impl(a->N, a->K, a->sh_degree, a->means, a->viewmat, a->shN, w.radii, w.colors, acc_rows_of(a, w), w.v_dirs, w.handover, w.abort_flag,
-                               w.abort_snapshot, s);
-    if (rc) return rc;
-    hipError_t e = hipEventRecord(pipe.dirs, s);
-    if (e == hipSuccess) e = hipStreamWaitEvent(pipe.side, pipe.dirs, 0);
-    if (e != hipSuccess) return (int)e;
-    rc = sh_pipe_adam_impl(a->N, a->K, a->sh_degree, a->sh0, a->shN, w.handover, a->exp_avg[1], a->exp_avg_sq[1], a->adam[1], a->exp_avg[2], a->exp_avg_sq[2], a->adam[2],
-                           w.abort_snapshot, pipe.side);
-    if (rc) return rc;
-    e = hipEventRecord(pipe.done, pipe.side);
-    if (e != hipSuccess) return (int)e;
-    pipe.pending = true;
-    return finish_adam(a, w, a->loss, s);
-}
-
-// ---- the training step: ONE sequence (open -> forward -> [loss kernels] -> backward -> tail) in three forms ---------------------------------------------------
+// ---- the training step: ONE sequence (open -> forward -> [loss kernels] -> backward -> tail) in two forms ----------------------------------------------------
 //
 // ThreePass (lfs_gut_train_step): the tail is SH backward + Adam(sh0, shN) | finish + Adam(means, scales, quaternions, opacities).
 //
@@ -279,25 +216,7 @@ int pipelined_tail(const lfs_gut_step_args* a, const StepWs& w, Pipeline& pipe, 
 //   v_render | tail (loss == NULL: *loss was written by the loss kernels)
 // An attempt that did not fit rendered empty lists: its loss kernels see the background, its backward accumulates nothing, its tail returns at the abort flag - no parameter,
 // no moment and no noise is applied, and *loss holds the loss of the empty render. NULL or all-zero options: the step without options, bit for bit.
-//
-// Pipelined (lfs_gut_train_step_pipelined): the three-pass form with the step's HBM-bound SH kernels moved UNDER its latency- and VALU-bound front end (round 6). Same
-// arguments, same results (bit for bit in the deterministic accumulation mode); what changes is the ORDER across two streams:
-//
-//   stream (caller's)                                                         side stream (the library's)
-//   projection(k) -> records without colours ----- event `projected` ------>  SH colours(k): visible Gaussians, -> colors [N,3] + the rgb slots of the records
-//   tile count + scan, row / tile binning, sort, culling                      (behind SH Adam(k - 1): the coefficients it reads are the updated ones)
-//   <------------------------------------------------ event `colours` ------
-//   forward, backward (MSE folded in)
-//   SH direction pass(k): dL/d(dirs) + 32-byte hand-over rows --- `dirs` -->  SH Adam(k): sh0 / shN read-modify-write, 1.1 GB at 1 M Gaussians
-//   finish + Adam(means, scales, quaternions, opacities)                      |  runs under finish(k), projection(k + 1), binning(k + 1), sort, culling:
-//   [next call] projection(k + 1) ...                                         v  kernels that leave the HBM idle
-//
-// In the three-pass form everything is one chain, and 0.33 ms of it (SH backward + Adam, SH colours) is pure HBM time during which no other kernel can run, while the
-// front end (0.25 ms) is latency / LDS / VALU bound and moves < 1 TB/s. Contract: between two pipelined calls sh0, shN and their moments belong to the side stream -
-// call lfs_gut_pipeline_join(stream) before anything else reads or writes them on `stream` (another step form, a strategy, evaluation, a checkpoint): this form does NOT
-// join in front of itself. Every other tensor is ordered on `stream` as before. The price: the direction pass re-reads the coefficient rows of the Gaussians that
-// received a gradient (<= 180 MB).
-enum class Form { ThreePass, FusedTail, Pipelined };
+enum class Form { ThreePass, FusedTail };
 
 int train_step_impl(Form form, const lfs_gut_step_args* a, const lfs_gut_step_options* opts, const float* next_viewmat, int colors_ready, int64_t capacity,
                     int64_t assumed_longest, void* workspace, size_t workspace_bytes, int64_t* host_counts, int64_t stamp, lfs_stream_t stream) {
@@ -307,14 +226,10 @@ int train_step_impl(Form form, const lfs_gut_step_args* a, const lfs_gut_step_op
     const bool ssim = o.loss_kind == 1;
     hipStream_t s = (hipStream_t)stream;
     StepWs w;
-    int rc = open_step(a, o.freeze_shN ? Need::AdamFrozenShN : Need::Adam, &o, capacity, workspace, workspace_bytes, s, form != Form::Pipelined, w);
+    int rc = open_step(a, o.freeze_shN ? Need::AdamFrozenShN : Need::Adam, &o, capacity, workspace, workspace_bytes, w);
     if (rc) return rc;
-    if (form == Form::Pipelined) {
-        rc = g_pipe.init();
-        if (rc) return rc;
-    }
     Front f;
-    rc = enqueue_forward(a, w, capacity, assumed_longest, host_counts, stamp, s, f, form == Form::Pipelined ? &g_pipe : nullptr, colors_ready != 0);
+    rc = enqueue_forward(a, w, capacity, assumed_longest, host_counts, stamp, s, f, colors_ready != 0);
     if (rc) return rc;
     float* v_render = nullptr;
     if (ssim) {
@@ -329,7 +244,6 @@ int train_step_impl(Form form, const lfs_gut_step_args* a, const lfs_gut_step_op
     rc = enqueue_backward(a, w, f, capacity, v_render, s);
     if (rc) return rc;
     float* const tail_loss = ssim ? nullptr : a->loss;
-    if (form == Form::Pipelined) return pipelined_tail(a, w, g_pipe, s);
     if (form == Form::FusedTail) return enqueue_tail(a, w, o, next_viewmat, tail_loss, s);
     return three_pass_tail(a, w, tail_loss, s);
 }
@@ -363,7 +277,7 @@ extern "C" size_t lfs_gut_step_loss_workspace_bytes(uint32_t image_width, uint32
     return a256(lfs_photometric_loss_workspace_bytes(image_height, image_width)) + a256(size_t(12) * image_width * image_height);
 }
 
-// the four entry points of the training step: argument adapters of train_step_impl
+// the three entry points of the training step: argument adapters of train_step_impl
 extern "C" int lfs_gut_train_step(const lfs_gut_step_args* a, int64_t capacity, int64_t assumed_longest, void* workspace, size_t workspace_bytes,
                                   int64_t* host_counts, int64_t stamp, lfs_stream_t stream) {
     return train_step_impl(Form::ThreePass, a, nullptr, nullptr, 0, capacity, assumed_longest, workspace, workspace_bytes, host_counts, stamp, stream);
@@ -379,21 +293,6 @@ extern "C" int lfs_gut_train_step_opt(const lfs_gut_step_args* a, const lfs_gut_
     return train_step_impl(Form::FusedTail, a, opts, next_viewmat, colors_ready, capacity, assumed_longest, workspace, workspace_bytes, host_counts, stamp, stream);
 }
 
-extern "C" int lfs_gut_train_step_pipelined(const lfs_gut_step_args* a, int64_t capacity, int64_t assumed_longest, void* workspace, size_t workspace_bytes,
-                                            int64_t* host_counts, int64_t stamp, lfs_stream_t stream) {
-    return train_step_impl(Form::Pipelined, a, nullptr, nullptr, 0, capacity, assumed_longest, workspace, workspace_bytes, host_counts, stamp, stream);
-}
-
-// `stream` waits for the side stream's last SH update (no host wait). Cheap and idempotent: call it whenever sh0 / shN / their moments are about to be used outside
-// lfs_gut_train_step_pipelined. Returns 1 when there was something to wait for, 0 when not, < 0 on error.
-extern "C" int lfs_gut_pipeline_join(lfs_stream_t stream) {
-    if (!g_pipe.pending || g_pipe.side == nullptr) return 0;
-    const hipError_t e = hipStreamWaitEvent((hipStream_t)stream, g_pipe.done, 0);
-    if (e != hipSuccess) return LFS_E_INVALID;
-    g_pipe.pending = false;
-    return 1;
-}
-
 // Backward of the view lfs_gut_view_forward left in the workspace, into GRADIENT TENSORS (data-parallel ranks, several views per step, iterations <= 1000):
 // grads = means, sh0, shN, raw_scales, raw_quats, raw_opacities - written (accumulate == 0) or added to. Two halves, so that a data-parallel caller can put
 // the all-reduce of the SH gradients (45 of 59 floats per Gaussian at degree 3) on the wire between them:
@@ -405,7 +304,7 @@ extern "C" int lfs_gut_view_backward_sh(const lfs_gut_step_args* a, int64_t capa
                                         void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     StepWs w;
-    int rc = open_step(a, Need::Forward, nullptr, capacity, workspace, workspace_bytes, s, true, w);
+    int rc = open_step(a, Need::Forward, nullptr, capacity, workspace, workspace_bytes, w);
     if (rc) return rc;
     // args->exp_avg[2] given: shN's Adam step runs inside the SH backward (one view per step, one rank - the reference's MCMC / L1+D-SSIM / bilateral-grid
     // steps, whose other five tensors go through gradient tensors and FusedAdam); grads[2] is then neither read nor written
@@ -423,7 +322,7 @@ extern "C" int lfs_gut_view_backward_sh(const lfs_gut_step_args* a, int64_t capa
 extern "C" int lfs_gut_view_backward_finish(const lfs_gut_step_args* a, int64_t capacity, float* const* grads /* [6] host */, int accumulate,
                                             void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
     StepWs w;
-    const int rc = open_step(a, Need::Forward, nullptr, capacity, workspace, workspace_bytes, (hipStream_t)stream, /*join=*/false, w);   // (the first half has joined)
+    const int rc = open_step(a, Need::Forward, nullptr, capacity, workspace, workspace_bytes, w);
     if (rc) return rc;
     if (!grads || !grads[0] || !grads[3] || !grads[4] || !grads[5] || (a->target_chw && !a->loss)) return LFS_E_INVALID;
     return gut_finish_grads_impl(a->N, a->means, a->raw_quats, w.quats, w.scales, w.opacities, a->scale_reg, a->opacity_reg, accumulate, grads[0], grads[3], grads[4],
@@ -438,7 +337,7 @@ extern "C" int lfs_gut_view_backward_rows(const lfs_gut_step_args* a, int64_t ca
                                           float* v_colors_out, void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     StepWs w;
-    int rc = open_step(a, Need::Forward, nullptr, capacity, workspace, workspace_bytes, s, true, w);   // (the join is a no-op here: the view's forward has joined)
+    int rc = open_step(a, Need::Forward, nullptr, capacity, workspace, workspace_bytes, w);
     if (rc) return rc;
     if (!grads || !grads[0] || !grads[3] || !grads[4] || !grads[5] || !v_colors_out || (!a->target_chw && !v_render) || (a->target_chw && !a->loss)) return LFS_E_INVALID;
     Front f;
@@ -459,7 +358,7 @@ extern "C" int lfs_gut_view_forward(const lfs_gut_step_args* a, int64_t capacity
                                     int64_t* host_counts, int64_t stamp, lfs_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     StepWs w;
-    const int rc = open_step(a, Need::Forward, nullptr, capacity, workspace, workspace_bytes, s, true, w);
+    const int rc = open_step(a, Need::Forward, nullptr, capacity, workspace, workspace_bytes, w);
     if (rc) return rc;
     Front f;
     return enqueue_forward(a, w, capacity, assumed_longest, host_counts, stamp, s, f);

@@ -1,6 +1,6 @@
 """Host side of csrc/gut_step.hip: the --gut training step as ONE C call - lfs_gut_train_step (three tail passes), lfs_gut_train_step_opt (the fused tail, with the
-photometric loss, the MCMC noise and the shN freeze as options; lfs_gut_train_step_ex is the same call without options) and lfs_gut_train_step_pipelined (SH kernels on
-the library's side stream, lfs_gut_pipeline_join) - and its split form for gradient tensors: lfs_gut_view_forward, then lfs_gut_view_backward, its two halves
+photometric loss, the MCMC noise and the shN freeze as options; lfs_gut_train_step_ex is the same call without options) - and its split form for gradient tensors:
+lfs_gut_view_forward, then lfs_gut_view_backward, its two halves
 lfs_gut_view_backward_sh / _finish, or lfs_gut_view_backward_rows for the factored exchange. Mirrors what Trainer::train_step does around rasterize() on the --gut path
 (/root/reference/src/training/trainer.cpp:579-770, rasterization/rasterizer.cpp:200-344) - minus the host synchronisation of
 gsplat/Intersect.cpp:75-76: the intersection lists live in a workspace sized for a CAPACITY, the count stays on the device, and this class
@@ -175,12 +175,10 @@ class GutStep:
 
     def train_step(self, params: Sequence[torch.Tensor], adam: Dict[str, dict], sh_degree: int, W: int, H: int, viewmat: torch.Tensor, Kmat: torch.Tensor,
                    bg: Optional[torch.Tensor], target_chw: torch.Tensor, weight: float, loss_acc: torch.Tensor, scale_reg: float = 0.0,
-                   opacity_reg: float = 0.0, pipelined: bool = False, fused_tail: bool = False, next_viewmat: Optional[torch.Tensor] = None,
+                   opacity_reg: float = 0.0, fused_tail: bool = False, next_viewmat: Optional[torch.Tensor] = None,
                    loss: str = "mse", lambda_dssim: float = 0.2, freeze_shN: bool = False, noise: Optional[torch.Tensor] = None, noise_lr: float = 0.0) -> int:
         """Forward + backward + Adam on all six parameter tensors, in place; *loss_acc = weight * mse. `adam[name]` = FusedAdam.prepare_inline(param) for
         the six names of GROUPS. Returns n_isects. Default: lfs_gut_train_step (three tail passes).
-        pipelined: lfs_gut_train_step_pipelined - the SH Adam pass of this step and the SH colours of the next run on the library's side stream, under the next step's
-        front end. Same results; sh0 / shN and their moments then belong to that stream until join() (every other method of this class joins by itself).
         fused_tail: lfs_gut_train_step_opt - SH backward, the six Adam updates and (next_viewmat: the view the NEXT step renders, a tensor that stays untouched until then)
         the next step's SH colours in one launch; a following step for exactly that view (same tensor, same N / K / degree / workspace) skips its SH colour kernel.
         loss "l1_ssim" (with lambda_dssim), freeze_shN (iteration <= 1000: FusedAdam skips shN - `adam` then needs no "shN" entry) and noise [N,3] + noise_lr (the MCMC
@@ -191,8 +189,8 @@ class GutStep:
         K = 1 + params[2].shape[1]
         opts = None
         if loss != "mse" or freeze_shN or noise is not None:
-            if pipelined or not fused_tail:
-                raise LfsError("gut_step: loss / freeze_shN / noise need the fused-tail form (fused_tail=True, pipelined=False)")
+            if not fused_tail:
+                raise LfsError("gut_step: loss / freeze_shN / noise need the fused-tail form (fused_tail=True)")
             if loss not in LOSS_KINDS:
                 raise LfsError(f"gut_step: unknown loss {loss!r}")
             opts = StepOptions()
@@ -207,7 +205,7 @@ class GutStep:
                     self.loss_ws = None
                     self.loss_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
                 opts.loss_workspace, opts.loss_workspace_bytes = self.loss_ws.data_ptr(), self.loss_ws.numel()
-        if fused_tail and not pipelined:
+        if fused_tail:
             # (replaced parameter tensors void the colours too - and so does an in-place write to the view matrix, means, sh0 or shN between the two steps: their
             #  autograd version counters, which a detach() or an index view shares with its base, as the C++ GutTrainStep compares them. The step's own updates go
             #  through raw pointers and leave the counters alone: the fast path stays.)
@@ -230,21 +228,11 @@ class GutStep:
                         self.colors_for = key(viewmat)
                 return settle
         else:
-            fn, what = (lib.lfs_gut_train_step_pipelined, "gut_train_step_pipelined") if pipelined else (lib.lfs_gut_train_step, "gut_train_step")
-
             def enqueue(a):
                 self.colors_for = None
-                check(fn(C.byref(a), *self._ws_args()), what)
+                check(lib.lfs_gut_train_step(C.byref(a), *self._ws_args()), "gut_train_step")
         return self._attempt(N, W, H, lambda: self._args(params, sh_degree, W, H, viewmat, Kmat, bg, target_chw, weight, scale_reg, opacity_reg, loss_acc, adam),
                              enqueue, "step")
-
-    @staticmethod
-    def join() -> bool:
-        """The current stream waits (on the device) for the side stream's last SH update of a pipelined step. -> was there one?"""
-        rc = load_library().lfs_gut_pipeline_join(stream())
-        if rc < 0:
-            raise LfsError("gut_pipeline_join failed")
-        return rc == 1
 
     def view_forward(self, params: Sequence[torch.Tensor], sh_degree: int, W: int, H: int, viewmat, Kmat, bg) -> int:
         """Forward of one view into the workspace (render / alpha / radii via .view()); re-run on overflow. Returns n_isects."""

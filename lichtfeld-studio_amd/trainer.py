@@ -174,7 +174,6 @@ class GutTrainer:
         self.inline_all_adam = True   # one view / one rank / MSE: all six parameters are updated inside the backward kernels (fused.backward_adam_all)
         self.fused_tail = True        # ... whose three per-Gaussian tail passes (SH backward + Adam, finish + Adam, next step's SH colours) are ONE launch (lfs_gut_train_step_ex)
         self._next_view = None        #     the view the NEXT step renders, when the trainer knows it (round-robin schedule, or train_step(next_views=...))
-        self.pipelined = False        # True: with its SH Adam pass / SH colours on the library's side stream, under the next step's front end (lfs_gut_train_step_pipelined)
         self.cxx_step = True          # ... and that step is ONE C++ call without a host read on the critical path (gut_step.GutStep -> csrc/gut_step.hip);
         self._gut_step = None         #     False: the same kernels enqueued call by call from Python (fused.py; tests compare the two)
         self.inline_shN_adam = True   # see train_step; False keeps the SH backward and the optimizer separate (tests compare the two)
@@ -340,12 +339,10 @@ class GutTrainer:
 
     def full_shN(self) -> torch.Tensor:
         """[N,K-1,3] on every rank (all-gathers the owners' rows when SH-sharded): export, evaluation."""
-        self.join_pipeline()
         return self.model.shN.detach() if self.sh_exchange is None else self.sh_exchange.gather_rows(self.model.shN.detach())
 
     def export_model(self) -> SplatModel:
         """The complete model on this rank (SH-sharded: shN all-gathered; every rank must call it): what loader.save_ply / evaluate.evaluate take."""
-        self.join_pipeline()
         m = self.model
         out = SplatModel(m.means.detach(), m.sh0.detach(), self.full_shN(), m.raw_scales.detach(), m.raw_quats.detach(), m.raw_opacities.detach(), m.max_sh_degree,
                          active_sh_degree=m.active_sh_degree)
@@ -392,10 +389,8 @@ class GutTrainer:
         self._views_all = views_all
         total_views = self.world * len(views)
         plan = self.last_plan = self._plan(len(views))   # (kept for tests and tools: which form the step took)
-        if plan.path != "cxx_all":
-            self.join_pipeline()
-            if self._gut_step is not None:
-                self._gut_step.colors_for = None   # (another step form is about to change the parameters: colours a fused tail left for this step are void)
+        if plan.path != "cxx_all" and self._gut_step is not None:
+            self._gut_step.colors_for = None   # (another step form is about to change the parameters: colours a fused tail left for this step are void)
         if plan.path == "fastgs":
             return self._train_step_fastgs(targets, views, total_views)
         if plan.path == "autograd":
@@ -456,15 +451,20 @@ class GutTrainer:
         opt_form = bool(extra) and (self.loss_kind != "mse" or plan.freeze_shN or "noise" in extra)   # lfs_gut_train_step_opt: always the fused-tail form
         self.last_n_isects = gs.train_step([p.detach() for p in self.model.parameters()], inline_all, self.model.get_active_sh_degree(), sc.width, sc.height,
                                            sc.viewmats[v], sc.Ks[v], self.bg, targets[0], 1.0 / total_views, self.loss_acc, self.scale_reg, self.opacity_reg,
-                                           pipelined=self.pipelined and not opt_form, fused_tail=self.fused_tail or opt_form,
+                                           fused_tail=self.fused_tail or opt_form,
                                            next_viewmat=None if self._next_view is None else sc.viewmats[self._next_view], **extra)
         self._last_radii = gs.view("radii", torch.int32, (1, N, 2))
 
-    def join_pipeline(self) -> None:
-        """After pipelined steps sh0 / shN and their moments belong to the library's side stream: the current stream waits for its last update (device-side, no host
-        wait). Called before everything that touches them outside the pipelined step - other step forms, strategies, export, evaluation."""
-        if self._gut_step is not None:
-            self._gut_step.join()
+    @property
+    def pipelined(self) -> bool:
+        """Always False: the two-stream form of the one-call step was measured, rejected and removed (benchmark drivers still assign and read the attribute)."""
+        return False
+
+    @pipelined.setter
+    def pipelined(self, value) -> None:
+        if value:
+            raise ValueError("the two-stream (pipelined) training step was removed: measured -4.5 % at best and slower on most variants "
+                             "(profiles/r06/pipeline/README.md); the last commit that contains it is 13aac0e")
 
     def _view_loss(self, gs, view: int, target, weight: float):
         """The loss of the view gs.view_forward() left in the step workspace -> (v_render, fold): dL/d(render) [H,W,3] from the loss kernels (bilateral grid, L1 + D-SSIM)

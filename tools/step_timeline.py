@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Start / end / queue of every kernel of ONE training step out of a `rocprofv3 --kernel-trace --output-format csv` directory (the last-but-one complete step of the run):
-what ran beside what on the two streams of the pipelined step.   python tools/step_timeline.py <trace dir> [<trace dir> ...]"""
+what ran when, on which queue, and the idle gaps between the launches.   python tools/step_timeline.py <trace dir> [<trace dir> ...]"""
 import csv
 import glob
 import re
