@@ -163,7 +163,8 @@ LFS_API size_t lfs_rasterize_workspace_bytes(uint32_t C, uint32_t N, uint32_t ch
                                              uint32_t image_height, uint32_t tile_size, int64_t n_isects);
 /*      developer switch, not part of the reference API: bit 0 = build the per-cell lists without culling (fwd output must be bit-identical either way;
  *      tests/test_gpu_raster.py); bits 1 - 3: unused (the experimental kernels they selected were measured and removed);
- *      bit 4 = deterministic backward accumulation (two passes, 64-bit fixed point: run-to-run bit-identical gradients; lfs_rasterize_workspace_bytes grows while it is set);
+ *      bit 4 = deterministic backward accumulation (two passes, 64-bit fixed point: run-to-run bit-identical gradients; lfs_rasterize_workspace_bytes and
+ *      lfs_fastgs_primitive_workspace_bytes grow while it is set, and both backwards refuse a workspace sized without it);
  *      bit 5 = the one-pass intersection scatter even when a scratch array is given; bit 6 = the training step packs the rasterizer's records with the separate
  *      raster_pack pass of rounds 1 - 3 instead of inside the projection kernel (A/B, tests/test_emulated_step_pack.py); bit 7: unused (round 6: the projection kernel clearing the
  *      backward's accumulator rows instead of the memset - measured slower, removed). */
@@ -581,6 +582,32 @@ LFS_API int lfs_kmeans_assign_1d(int64_t n, uint32_t k, const float* data /* [n]
                                  lfs_stream_t stream);
 LFS_API int lfs_kmeans_update(int64_t N, uint32_t k, uint32_t D, const float* data /* [N,D] */, const int32_t* order /* [N] */, const int32_t* seg_start /* [k+1] */,
                               float* centroids /* [k,D], in place */, lfs_stream_t stream);
+
+/* ---- ADMM sparsity optimisation (csrc/sparsity.hip; the reference's training/components/sparsity_optimizer.cpp as device passes without a sort or a host read).
+ *      All entry points are asynchronous on `stream`, validate on the host before any launch (LFS_E_INVALID: NULL pointer, a count outside 0 .. 2^31 - 1, a rank
+ *      outside its range, a workspace that is not 16-byte aligned; LFS_E_WORKSPACE: workspace short), use no float atomics (same bits on every run) and return
+ *      LFS_OK without a launch for N == 0. The workspace is scratch: nothing in it has to survive between calls.
+ *      lfs_select_kth_f32: out_value[0] = sort(x)[k - 1] (1 <= k <= N) in torch.sort's order: -0 == +0 (a zero result is +0), any NaN above +inf. A 4-pass radix
+ *        select over an order-preserving key: per-workgroup LDS histograms flushed with integer atomics, a one-wave kernel between the passes.
+ *      lfs_admm_update: opa = sigmoid(raw); v = opa + u; thr = the k-th smallest v; z = v > thr ? v : 0; u = u + (opa - z) - single-precision operations in this
+ *        order; sigmoid is 1 / (1 + expf(-x)), the expression of lfs_activations_fwd. 0 <= k <= N; k == 0: z = 0. `initialize` is this call on a zero-filled u.
+ *      lfs_admm_loss_grad: d = (opa - z) + u; g_raw_opacities (+)= scale rho d opa (1 - opa); loss[0] += scale rho / 2 sum d^2 (fixed-order two-stage tree; loss may
+ *        be NULL, the workspace is then not used).
+ *      lfs_admm_prune_mask: mask_u8[i] = 1 for exactly n_prune (0 .. N) elements, every one of them <= every other raw opacity; among the values equal to the
+ *        boundary value the lowest indices are taken. */
+LFS_API size_t lfs_select_kth_workspace_bytes(int64_t N);
+LFS_API int lfs_select_kth_f32(const float* x /* [N] */, int64_t N, int64_t k, float* out_value /* [1], device */, void* workspace, size_t workspace_bytes,
+                               lfs_stream_t stream);
+LFS_API size_t lfs_admm_update_workspace_bytes(int64_t N);
+LFS_API int lfs_admm_update(const float* raw_opacities /* [N] */, float* u /* [N], in place */, float* z /* [N], out */, int64_t N, int64_t k, void* workspace,
+                            size_t workspace_bytes, lfs_stream_t stream);
+LFS_API size_t lfs_admm_loss_grad_workspace_bytes(int64_t N);
+LFS_API int lfs_admm_loss_grad(const float* raw_opacities /* [N] */, const float* z /* [N] */, const float* u /* [N] */, int64_t N, float rho, float scale,
+                               float* g_raw_opacities /* [N] */, int accumulate, float* loss /* [1] or NULL */, void* workspace, size_t workspace_bytes,
+                               lfs_stream_t stream);
+LFS_API size_t lfs_admm_prune_mask_workspace_bytes(int64_t N);
+LFS_API int lfs_admm_prune_mask(const float* raw_opacities /* [N] */, int64_t N, int64_t n_prune, uint8_t* mask_u8 /* [N] */, void* workspace, size_t workspace_bytes,
+                                lfs_stream_t stream);
 
 /* ---- instrumentation (not in the reference): per-kernel HIP-event timing on the launch stream.
  *      lfs_profile_enable(1) makes every entry point bracket its principal kernel(s) with events;

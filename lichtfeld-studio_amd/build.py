@@ -39,6 +39,7 @@ SOURCES = {
     "dataprep.hip": ["-ffp-contract=off"],
     "fastgs_prep.hip": ["-ffp-contract=off"],
     "sog.hip": ["-ffp-contract=off"],   # SOG export: Morton codes, k-means (the MFMA assignment is an fmaf chain by construction; the flag holds the rest)
+    "sparsity.hip": ["-ffp-contract=off"],   # ADMM sparsity: radix select, state update, loss + gradient (the sigmoid of l2_fused.hip, same flags: same bits)
     "fastgs_blend.hip": ["-fno-slp-vectorize"],
     "prof.hip": [],
     # no SLP packing: v_pk_* operand pairing forces SGPR shuffles right after the scalar record

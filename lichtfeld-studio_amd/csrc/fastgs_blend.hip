@@ -148,11 +148,14 @@ __global__ void __launch_bounds__(64) fg_blend_fwd_kernel(
     }
 }
 
+// ACC 0: the rows are summed with float atomics, whose arrival order - and so the last bits of every gradient - differs from run to run. ACC 1 / 2: the two passes of
+// the deterministic mode (lfs_set_debug_flags bit 4, as the 3DGUT backward's: wave_sum16_atomic in lfs_raster_common.cuh), fg_det_resolve_kernel turns the sums back into floats.
+template <int ACC>
 __global__ void __launch_bounds__(64) fg_blend_bwd_kernel(
     const uint32_t gw, const uint32_t gh, const uint32_t width, const uint32_t height,
     const GaussRec* __restrict__ recs, const int32_t* __restrict__ offsets, const int32_t* __restrict__ cell_count, const int2* __restrict__ cell_list,
     const float* __restrict__ alpha_map, const int32_t* __restrict__ n_contrib, const float* __restrict__ g_image, const float* __restrict__ g_alpha,
-    float* __restrict__ acc) {
+    float* __restrict__ acc, unsigned long long* __restrict__ det64) {
     const uint32_t total_tiles = gw * gh;
     __shared__ __attribute__((aligned(16))) float s_red[RED9_SCRATCH_FLOATS]; // this wavefront's transpose block (wave_sum9_atomic_lds)
     float* const red_scratch = s_red;
@@ -201,9 +204,22 @@ __global__ void __launch_bounds__(64) fg_blend_bwd_kernel(
         //   dL/dmean2d = conic . (sum hx, sum hy), dL/dconic = 0.5 (sum hx dx, sum hx dy, sum hy dy)   (fastgs_prep.hip)
         float* row = acc + size_t(e.x) * ACC_STRIDE;
         const float v[9] = {hx, hy, hx * f.dx, hx * f.dy, hy * f.dy, w * gc0, w * gc1, w * gc2, aD};
-        wave_sum9_atomic_lds(v, row, lane, red_scratch);
+        wave_sum9_atomic_lds<ACC>(v, row, lane, red_scratch, ACC == 2 ? det64 + size_t(e.x) * ACC_STRIDE : nullptr);
     };
     walk_cell_list<-1>(cl, recs, lo - 1, lo, eval, []() { return true; });
+}
+
+// deterministic mode, after pass 2: acc[i] = fixed-point sum * 2^(e - 40), e from the pass-1 maximum that acc[i] still holds as bits (slots 9 .. 15 hold 0 and stay 0)
+__global__ void __launch_bounds__(256) fg_det_resolve_kernel(const size_t n, float* __restrict__ acc, const unsigned long long* __restrict__ det64) {
+    const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t mbits = reinterpret_cast<const uint32_t*>(acc)[i];
+    float out = 0.f;
+    if (mbits != 0u) {
+        const int e = max(int((mbits >> 23) & 0xffu), 1) - 127;
+        out = float(ldexp(double((long long)det64[i]), e - 40)); // exact scaling; one rounding to float
+    }
+    acc[i] = out;
 }
 
 static uint32_t g_fastgs_debug = 0;
@@ -272,7 +288,12 @@ static int fastgs_backward_impl(
     float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest, lfs_stream_t stream, const lfs::ShAdamArgs* adam, float* grad_w2c = nullptr,
     void* w2c_workspace = nullptr) {
     if (!primitive_workspace || !w2c || !cam_position || !grad_image || !grad_alpha || !alpha || width == 0 || height == 0 || n_instances < 0) return LFS_E_INVALID;
-    fgs::PrimWs w = fgs::prim_ws(primitive_workspace, N, width, height);
+#ifdef LFS_EMULATE
+    const bool det = false;   // (the emulated library has no integer-atomic passes)
+#else
+    const bool det = (lfs_get_debug_flags() & 16u) != 0;   // the workspace then carries the int64 rows: it was sized with the bit set, or it is refused here
+#endif
+    fgs::PrimWs w = fgs::prim_ws(primitive_workspace, N, width, height, det);
     if (primitive_workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
     fgs::InstWs iw = fgs::inst_ws(instance_workspace, width, height, uint64_t(n_instances));
     if (!instance_workspace || instance_workspace_bytes < iw.bytes) return LFS_E_WORKSPACE;
@@ -293,8 +314,16 @@ static int fastgs_backward_impl(
     if (n_instances > 0 && !keep_acc) {
         lfs::ProfScope prof("fastgs_blend_bwd", s);
         const uint32_t wgrid = cell_grid_blocks(uint64_t(T) * fgs::WPT, fgs::WPT);
-        hipLaunchKernelGGL(fgs::fg_blend_bwd_kernel, dim3(wgrid), dim3(64), 0, s, f.gw, f.gh, width, height, w.rec, w.offsets, iw.cell_count, iw.cell_list,
-                           alpha, w.n_contrib, grad_image, grad_alpha, w.acc);
+#define LFS_FG_BWD(ACC) hipLaunchKernelGGL(fgs::fg_blend_bwd_kernel<ACC>, dim3(wgrid), dim3(64), 0, s, f.gw, f.gh, width, height, w.rec, w.offsets, iw.cell_count, \
+                                          iw.cell_list, alpha, w.n_contrib, grad_image, grad_alpha, w.acc, w.det64)
+        if (det) { // pass 1: per-slot maxima of |total| (integer atomicMax), pass 2: 64-bit fixed-point sums, then back to float
+            const size_t n_acc = ACC_STRIDE * size_t(N);
+            hipError_t e = hipMemsetAsync(w.det64, 0, sizeof(unsigned long long) * n_acc, s);
+            if (e != hipSuccess) return (int)e;
+            LFS_FG_BWD(1); LFS_FG_BWD(2);
+            hipLaunchKernelGGL(fgs::fg_det_resolve_kernel, dim3(uint32_t((n_acc + 255) / 256)), dim3(256), 0, s, n_acc, w.acc, w.det64);
+        } else LFS_FG_BWD(0);
+#undef LFS_FG_BWD
     }
     return fgs::launch_preprocess_bwd(N, means, scales_raw, rotations_raw, sh_coefficients_0, sh_coefficients_rest, f, w, grad_means, grad_scales_raw, grad_rotations_raw,
                                       grad_opacities_raw, grad_sh_coefficients_0, grad_sh_coefficients_rest, densification_info, s, adam, grad_w2c,

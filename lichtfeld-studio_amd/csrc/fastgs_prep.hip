@@ -412,7 +412,9 @@ extern "C" int lfs_fastgs_wait_n_instances(int64_t* n_instances) {
     return LFS_OK;
 }
 
-extern "C" size_t lfs_fastgs_primitive_workspace_bytes(uint32_t N, uint32_t width, uint32_t height) { return fgs::prim_ws(nullptr, N, width, height).bytes; }
+extern "C" size_t lfs_fastgs_primitive_workspace_bytes(uint32_t N, uint32_t width, uint32_t height) {
+    return fgs::prim_ws(nullptr, N, width, height, (lfs_get_debug_flags() & 16u) != 0).bytes;   // (the deterministic backward's int64 rows: lfs_fastgs.cuh)
+}
 extern "C" size_t lfs_fastgs_instance_workspace_bytes(uint32_t width, uint32_t height, int64_t n_instances) {
     return n_instances < 0 ? 0 : fgs::inst_ws(nullptr, width, height, uint64_t(n_instances)).bytes;
 }

@@ -22,7 +22,7 @@ __global__ void __launch_bounds__(256) activations_fwd_kernel(
     reinterpret_cast<float4*>(quats)[g] = make_float4(q.x / den, q.y / den, q.z / den, q.w / den); // true divisions, as ATen
 #pragma unroll
     for (int k = 0; k < 3; ++k) scales[3 * g + k] = expf(raw_scales[3 * g + k]);
-    opacities[g] = 1.f / (1.f + expf(-raw_opacities[g]));
+    opacities[g] = sigmoid(raw_opacities[g]);
 }
 
 // grads w.r.t. the raw parameters from grads w.r.t. the activated ones. ACCUM adds to the outputs.

@@ -37,9 +37,11 @@ inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 //            log(255 * opacity): sigma' = A dx^2 + B dx dy + C dy^2 is the Gaussian exponent in bits (one v_exp_f32).
 struct PrimWs {
     GaussRec* rec; float2* mean2d; float4* conic_opacity; ushort4* bounds; uint32_t* n_touched; uint32_t* depth_bits;
-    uint32_t* totals; uint32_t* cursor; int32_t* offsets; int64_t* n_instances; int32_t* n_contrib; float* acc; size_t bytes;
+    uint32_t* totals; uint32_t* cursor; int32_t* offsets; int64_t* n_instances; int32_t* n_contrib; float* acc; unsigned long long* det64; size_t bytes;
 };
-inline PrimWs prim_ws(void* base, uint32_t N, uint32_t width, uint32_t height) {
+// det (lfs_set_debug_flags bit 4, the deterministic backward): one int64 accumulator row per primitive behind everything else, so the other pointers do not move.
+// The size query and the backward ask for it; preprocess and render neither need nor check it.
+inline PrimWs prim_ws(void* base, uint32_t N, uint32_t width, uint32_t height, bool det = false) {
     const size_t T = size_t((width + TILE - 1) / TILE) * ((height + TILE - 1) / TILE), P = size_t(width) * height;
     PrimWs w; char* p = (char*)base; size_t o = 0;
     w.rec = (GaussRec*)(p + o); o += align256(sizeof(GaussRec) * N);
@@ -54,6 +56,8 @@ inline PrimWs prim_ws(void* base, uint32_t N, uint32_t width, uint32_t height) {
     w.n_instances = (int64_t*)(p + o); o += 256;
     w.n_contrib = (int32_t*)(p + o); o += align256(4 * P);
     w.acc = (float*)(p + o); o += align256(sizeof(float) * ACC_STRIDE * N);
+    w.det64 = nullptr;
+    if (det) { w.det64 = (unsigned long long*)(p + o); o += align256(sizeof(unsigned long long) * ACC_STRIDE * size_t(N)); }
     w.bytes = o;
     return w;
 }

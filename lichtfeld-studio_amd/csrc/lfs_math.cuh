@@ -32,6 +32,18 @@ struct m3 { float m[3][3]; };
 #define LFS_WAVE_LOCKSTEP() ((void)0)
 #endif
 
+// the opacity activation (gs::SplatData::get_opacity): ONE expression for activations_fwd_kernel (l2_fused.hip) and the ADMM sparsity kernels (sparsity.hip), both
+// built with -ffp-contract=off, so the two agree bit for bit
+LFS_DI float sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+// ... and 1 - sigmoid(x) next to it without the cancellation of the subtraction near 1: e / (1 + e) = e * sigmoid(x) for x >= 0 (e <= 1: no overflow); the
+// return value is the expression above, bit for bit
+LFS_DI float sigmoid(float x, float& one_minus) {
+    const float e = expf(-x);
+    const float s = 1.f / (1.f + e);
+    one_minus = x >= 0.f ? e * s : 1.f - s;
+    return s;
+}
+
 LFS_DI f3 ld3(const float* __restrict__ base, size_t i) { const V3f t = reinterpret_cast<const V3f*>(base)[i]; return {t.a[0], t.a[1], t.a[2]}; }
 LFS_DI void st3(float* __restrict__ base, size_t i, f3 v) { V3f t; t.a[0] = v.x; t.a[1] = v.y; t.a[2] = v.z; reinterpret_cast<V3f*>(base)[i] = t; }
 LFS_DI f3 operator+(f3 a, f3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }

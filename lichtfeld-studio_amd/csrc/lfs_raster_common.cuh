@@ -453,7 +453,10 @@ LFS_DI void wave_sum16_atomic_quad(const v2f (&V)[8], float* __restrict__ dst /*
 // fastgs_blend_bwd 0.452 - 0.457 -> 0.391 - 0.395 ms (profiles/r03/fastgs_blend_bwd_lds_reduce_ab.txt).
 constexpr int RED9_STRIDE = 9;
 constexpr int RED9_SCRATCH_FLOATS = (LFS_RED_ADDTID ? 16 * RED_ROW : 64 * RED9_STRIDE); // per wavefront (value-major form: rows 9..15 are read by the dropped lanes, never written)
-LFS_DI void wave_sum9_atomic_lds(const float (&v)[9], float* __restrict__ dst, const uint32_t lane, float* __restrict__ scratch /* this wavefront's [RED9_SCRATCH_FLOATS] */) {
+// ACC as for wave_sum16_atomic: 0 float atomics, 1 / 2 the two passes of the deterministic mode (det64 = the int64 accumulator row, 16 per Gaussian).
+template <int ACC = 0>
+LFS_DI void wave_sum9_atomic_lds(const float (&v)[9], float* __restrict__ dst, const uint32_t lane, float* __restrict__ scratch /* this wavefront's [RED9_SCRATCH_FLOATS] */,
+                                 unsigned long long* __restrict__ det64 = nullptr) {
     float c[16];
 #if LFS_RED_ADDTID && !defined(LFS_EMULATE)
     {   // value-major block through ds_write_addtid_b32 / ds_read_b128 (LFS_RED_ADDTID above)
@@ -500,7 +503,19 @@ LFS_DI void wave_sum9_atomic_lds(const float (&v)[9], float* __restrict__ dst, c
     t = __uint_as_float(q[0]) + __uint_as_float(q[1]);
     auto rr = __builtin_amdgcn_permlane32_swap(__float_as_uint(t), __float_as_uint(t), false, false);
     t = __uint_as_float(rr[0]) + __uint_as_float(rr[1]);
-    if (lane < 9) unsafeAtomicAdd(dst + lane, t);
+    if (lane < 9) {
+        if (ACC == 0) unsafeAtomicAdd(dst + lane, t);
+#ifndef LFS_EMULATE
+        else if (ACC == 1) atomicMax(reinterpret_cast<uint32_t*>(dst) + lane, __float_as_uint(t) & 0x7fffffffu);
+        else {
+            const uint32_t mbits = reinterpret_cast<const uint32_t*>(dst)[lane];
+            if (mbits != 0u && t != 0.f) {
+                const int e = max(int((mbits >> 23) & 0xffu), 1) - 127;
+                atomicAdd(det64 + lane, (unsigned long long)__float2ll_rn(ldexpf(t, 40 - e)));
+            }
+        }
+#endif
+    }
 }
 
 } // namespace lfs

@@ -94,6 +94,9 @@ class _StrategyBase:
         self.optimizer = FusedAdam(default_param_groups(model, scene_scale, params.means_lr, params.shs_lr, params.scaling_lr,
                                                         params.rotation_lr, params.opacity_lr))
         self.scheduler = ExponentialLR(self.optimizer, gamma=0.01 ** (1.0 / params.iterations), param_group_index=0)
+        # the optimizer steps while it < step_limit. The reference guards with the strategy's own copy of `iterations` (mcmc.cpp:447, default_strategy.cpp:20), which a
+        # run extended by the sparsification phase does not raise - its optimizer is off for the whole phase; the trainer raises this limit instead
+        self.step_limit = params.iterations
 
     # -- strategy_utils.cpp:57-129 ------------------------------------------------------------------------------------
     def _update_params(self, param_fn, state_fn, idxs=range(6)) -> None:
@@ -121,7 +124,7 @@ class _StrategyBase:
         self._remove(mask)
 
     def step(self, it: int) -> None:  # mcmc.cpp:386-393 / default_strategy.cpp:327-334
-        if it < self.params.iterations:
+        if it < self.step_limit:
             self.optimizer.step(it)
             self.optimizer.zero_grad(set_to_none=True)
             self.scheduler.step()

@@ -83,7 +83,8 @@ class GutTrainer:
                  views_per_rank: int = 1, fused_adam: bool = True, fused_l2: bool = True, loss: str = "mse", lambda_dssim: float = 0.2,
                  strategy: Optional[str] = None, opt_params=None, scene_scale: float = 1.0, seed: int = 0, rasterizer: str = "gut",
                  use_bilateral_grid: bool = False, bilateral_grid_dims=(16, 16, 8), bilateral_grid_lr: float = 2e-3, tv_loss_weight: float = 10.0,
-                 sh_sharded: Optional[bool] = None, factored_sh: bool = False, one_call: bool = False, pose_optimization: str = "none", pose_lr: float = 1e-5):
+                 sh_sharded: Optional[bool] = None, factored_sh: bool = False, one_call: bool = False, pose_optimization: str = "none", pose_lr: float = 1e-5,
+                 enable_sparsity: bool = False, sparsify_steps: int = 15000, init_rho: float = 0.0005, prune_ratio: float = 0.6, sparsity_update_every: int = 50):
         """strategy: None (fixed set of Gaussians: the benchmark), "mcmc" (strategies.MCMC: relocation + growth + SGLD noise, with
         the scale / opacity regularisers of trainer.cpp:132-158) or "default" (ADC; needs densification_info, see strategies.py).
         `seed` seeds the strategy's generator: the same on every rank, so replicas densify identically.
@@ -91,7 +92,11 @@ class GutTrainer:
         while iteration <= 1000 as well, not only for the MSE benchmark configuration (plan_step). Same trajectory as the default forms; off by default. A model with
         SH degree 4 (more than 16 coefficients per channel) keeps the default forms: the switch has no effect there.
         pose_optimization: "none" | "direct" | "mlp" (trainer.cpp:366-389; poseopt.py): a learned correction of every training camera's world-to-camera transform,
-        trained with Adam(pose_lr) on the camera gradient of the fastgs backward. fastgs rasterizer, one rank."""
+        trained with Adam(pose_lr) on the camera gradient of the fastgs backward. fastgs rasterizer, one rank.
+        enable_sparsity (trainer.cpp:331-360; sparsity.py): the run is extended by `sparsify_steps` iterations after the `iterations` of the base run. During them the
+        ADMM penalty (init_rho) pulls the opacities towards a state with prune_ratio of them at zero, refreshed every sparsity_update_every iterations, and no
+        strategy refinement, noise or SH-degree change happens; at the last iteration int(prune_ratio * N) Gaussians of lowest opacity are removed. `total_iterations`
+        is the length of the whole run. The learning-rate schedule stays the base run's."""
         if pose_optimization not in ("none", "direct", "mlp"):
             raise ValueError(f"Invalid pose optimization type: {pose_optimization}")
         if pose_optimization != "none":
@@ -189,6 +194,72 @@ class GutTrainer:
             self.pose_optimizer = torch.optim.Adam(self.pose_module.parameters(), lr=pose_lr)
         self._last_radii = None
         self._last_visible = None
+        # ADMM sparsity (trainer.cpp:331-360): None when off - nothing below then differs from a trainer without the arguments
+        self.base_iterations = self.total_iterations = int(iterations)
+        self.sparsity = None
+        if enable_sparsity:
+            from .sparsity import ADMMSparsityOptimizer, Config as SparsityConfig
+            self.sparsity = ADMMSparsityOptimizer(SparsityConfig(sparsify_steps=int(sparsify_steps), init_rho=float(init_rho), prune_ratio=float(prune_ratio),
+                                                                 update_every=int(sparsity_update_every), start_iteration=int(iterations)))
+            self.total_iterations = int(iterations) + int(sparsify_steps)
+            if self.strategy is not None:
+                # the strategy's own iteration count stays the base run's (refinement windows, the scheduler's gamma), but its optimizer steps through the phase:
+                # the reference's strategies keep the base count for that guard too and train nothing towards z
+                self.strategy.step_limit = self.total_iterations
+        self._sparsity_added_at = -1
+
+    def _sparsity_applies(self) -> bool:
+        """this iteration carries the ADMM term (should_apply_loss)"""
+        return self.sparsity is not None and self.sparsity.should_apply_loss(self.iteration)
+
+    def _past_base(self) -> bool:
+        """sparsification phase proper: no strategy.post_backward, no SH-degree change (trainer.cpp:745-750: post_backward only while iter <= base)"""
+        return self.total_iterations != self.base_iterations and self.iteration > self.base_iterations
+
+    def _add_sparsity_term(self, grad_view=None, loss_acc=None) -> None:
+        """The ADMM penalty's gradient into the raw-opacity gradient (default: the flat bucket's segment) and its value into the loss accumulator, 1 / world of both
+        per rank: after the backward of the step's last view, before that segment is all-reduced. Once per step - the forms that send the segment early call it
+        themselves, the common tail then finds it done."""
+        if not self._sparsity_applies() or self._sparsity_added_at == self.iteration:
+            return
+        self._sparsity_added_at = self.iteration
+        with torch.no_grad():
+            self.sparsity.add_loss_and_grad(self.model.raw_opacities.detach(), self.bucket.views[5] if grad_view is None else grad_view,
+                                            self.loss_acc if loss_acc is None else loss_acc, 1.0 / self.world)
+
+    def _sparsity_after_step(self) -> None:
+        """trainer.cpp:776-784, after the optimizer step: the state update on the iterations should_update names, the prune at the last iteration."""
+        sp = self.sparsity
+        if sp is None:
+            return
+        if sp.should_update(self.iteration):
+            sp.update_state(self.model.raw_opacities.detach())
+        if sp.should_prune(self.iteration):
+            mask = sp.get_prune_mask(self.model.raw_opacities.detach())
+            self._remove_gaussians(mask)
+            self.sparsity = None   # (trainer.cpp:240: the optimiser object is dropped after the prune)
+
+    @torch.no_grad()
+    def _remove_gaussians(self, mask: torch.Tensor) -> None:
+        """strategy.remove_gaussians(mask), or the same surgery (strategy_utils.cpp:57-129: index_select on every parameter and both Adam moments) on the trainer's
+        own optimizer when there is no strategy. SH-sharded: on the gathered shN, re-sharded for the new count."""
+        if self.strategy is not None:
+            fn = lambda: self.strategy.remove_gaussians(mask)
+        else:
+            def fn():
+                keep = mask.logical_not().nonzero().squeeze(-1)
+                if keep.numel() == mask.numel():
+                    return
+                for i, name in enumerate(("means", "sh0", "shN", "raw_scales", "raw_quats", "raw_opacities")):
+                    old = getattr(self.model, name)
+                    new = old.detach().index_select(0, keep).contiguous().requires_grad_(old.requires_grad)
+                    self.optimizer.replace_param(i, old, new, lambda t: t.index_select(0, keep))
+                    setattr(self.model, name, new)
+                self._on_resize()
+        if self.sh_exchange is not None:
+            self._refine_with_full_shN(fn)
+        else:
+            fn()
 
     def _deferred(self):
         """bucket segments that stay out of the flat all-reduce: shN (2) while Adam does not read it; with the factored exchange sh0 (1) and shN always"""
@@ -272,12 +343,15 @@ class GutTrainer:
                     self.bucket.views[5].add_((sg * (1 - sg)).view_as(self.bucket.views[5]), alpha=self.opacity_reg / self.world / raw_opac.numel())
                     self.loss_acc += self.opacity_reg / self.world * sg.mean()
         self._last_radii = None
+        self._add_sparsity_term()
         self.bucket.all_reduce(skip_deferred=self.iteration <= 1000)
         for p, gv in zip(params, self.bucket.views):
             p.grad = gv
         self._bilateral_step()
         if self.strategy is not None:
-            if self.strategy_kind == "default":
+            if self._past_base():
+                pass
+            elif self.strategy_kind == "default":
                 if dens is not None and self.world > 1 and self.strategy.is_refining(self.iteration):
                     lfs_dist.all_reduce_sum(dens)   # replicas must take the same densification decisions
                 self.densification_info = self.strategy.post_backward(self.iteration, dens)
@@ -365,8 +439,10 @@ class GutTrainer:
         out = self._train_step(targets, views, views_all)
         # the SH schedule, AFTER the backward / optimizer step of the iteration, where the strategies keep it (post_backward: mcmc.cpp:366-368,
         # default_strategy.cpp) - iteration 1000, 2000, ... still renders with the old degree, as the reference does; without a strategy the trainer does it
-        if self.strategy is None and self.iteration % self.sh_degree_interval == 0 and self.model.active_sh_degree < self.model.max_sh_degree:
+        if (self.strategy is None and self.iteration % self.sh_degree_interval == 0 and self.model.active_sh_degree < self.model.max_sh_degree
+                and not self._past_base()):
             self.model.active_sh_degree += 1
+        self._sparsity_after_step()
         return out
 
     def _train_step(self, targets: List[torch.Tensor], views: Optional[List[int]] = None, views_all: Optional[List[List[int]]] = None) -> float:
@@ -422,12 +498,14 @@ class GutTrainer:
                          sh_sharded=self.sh_exchange is not None, shard_rows=(self.sh_exchange.n if self.sh_exchange is not None else 0), n_views=n_views,
                          loss=self.loss_kind, strategy=(None if st is None else self.strategy_kind), refining=bool(st is not None and st.is_refining(self.iteration)),
                          iteration=self.iteration, has_shN=self.model.shN.shape[1] > 0, optimizer_fused=bool(getattr(self.optimizer, "fused", False)),
-                         bilateral=self.bilateral is not None, inline_shN_adam=self.inline_shN_adam, inline_all_adam=self.inline_all_adam,
+                         # (the ADMM term needs the opacity gradient as a tensor: no all-inline and no one-call form while it applies)
+                         bilateral=self.bilateral is not None, inline_shN_adam=self.inline_shN_adam, inline_all_adam=self.inline_all_adam and not self._sparsity_applies(),
                          cxx_step=self.cxx_step and self.rasterizer != "fastgs" and self.fused_l2 and self._cxx_supported(), batch_views=self.batch_views,
                          factored_sh=self.factored_sh,
                          # (a strategy stops updating at its last iteration, strategies._StrategyBase.step: those steps keep the split form; so does a model with
                          #  SH degree 4 - K = 25 > 16: the fused tail, which carries the freeze and the noise, has no instantiation for it)
-                         one_call=self.one_call and (st is None or self.iteration < st.params.iterations) and 1 + self.model.shN.shape[1] <= 16)
+                         one_call=(self.one_call and (st is None or self.iteration < st.params.iterations) and 1 + self.model.shN.shape[1] <= 16
+                                   and not self._sparsity_applies()))
 
     def _gut(self):
         from .gut_step import GutStep
@@ -532,6 +610,7 @@ class GutTrainer:
         # gathered rows and for nothing else, the 11-float all-reduce is only needed by the optimizer afterwards - issued second it travels UNDER the SH backward
         # (rounds 4 - 5 issued it first: the rows, and with them the SH backward, started one all-reduce later).
         rows = ex.gather()                                            # [world * views, N, 3], rank-major
+        self._add_sparsity_term()                                     # (the opacity segment leaves with the early all-reduce)
         self.bucket.all_reduce_early([0, 3, 4, 5], chunks=1)          # 11 floats per Gaussian, on RCCL's stream while the SH backward runs
         every = self._views_all or [lfs_dist.views_for_step(self.iteration - 1, j, self.world, sc.viewmats.shape[0], len(views)) for j in range(self.world)]
         if rows.shape[0] != len(every) * len(views):                  # (one GPU forced through the collectives: the gathered rows are this rank's own)
@@ -577,12 +656,14 @@ class GutTrainer:
                                       sh_exchange=self.sh_exchange, viewmats_all=vm_all, adam_shN=inline, adam_shard=inline_shard, adam_all=inline_all,
                                       bilateral=self.bilateral, image_idx=v,
                                       # last view: scales / quats / opacities gradients are final before the SH backward starts - their all-reduce overlaps with it
-                                      on_geometry_grads=(lambda: self.bucket.all_reduce_early([3, 4, 5])) if (self.world > 1 and k == len(views) - 1) else None)
+                                      # (the ADMM term goes into the opacity gradient before it leaves)
+                                      on_geometry_grads=(lambda: (self._add_sparsity_term(), self.bucket.all_reduce_early([3, 4, 5]))) if (self.world > 1 and k == len(views) - 1) else None)
             self.last_n_isects, self._last_radii = out.n_isects, out.radii
 
     def _finish_fused_step(self, plan):
         """What follows the backward of every fused step form: all-reduce of the flat bucket, the bilateral grid's own optimizer, strategy / optimizer step."""
         params = self.model.parameters()
+        self._add_sparsity_term()
         # the deferred segment (shN) stays out of the all-reduce while Adam does not read it (iteration <= 1000) and, SH-sharded, always
         self.bucket.all_reduce(skip_deferred=plan.skip_deferred)
         if plan.path == "cxx_factored":   # the SH direction term of dL/dmeans, summed over every rank's views by the multi-view SH backward: identical on all ranks
@@ -591,7 +672,9 @@ class GutTrainer:
         for p, gv in zip(params, self.bucket.views):
             p.grad = gv
         if self.strategy is not None:  # trainer.cpp:741-760: post_backward (may replace the parameter tensors) then step
-            if plan.path == "cxx_all":   # (one_call: the noise went into the tail - what is left of post_backward is the SH schedule)
+            if self._past_base():      # (trainer.cpp:745-750: none of it during the sparsification phase)
+                pass
+            elif plan.path == "cxx_all":   # (one_call: the noise went into the tail - what is left of post_backward is the SH schedule)
                 self.strategy.post_backward_schedule(self.iteration)
             elif self.sh_exchange is not None and self.strategy.is_refining(self.iteration):
                 self._refine_with_full_shN(lambda: self.strategy.post_backward(self.iteration))
@@ -620,6 +703,8 @@ class GutTrainer:
             loss.backward()
             loss_value = loss.detach()
             self.last_n_isects, self._last_visible = out.n_isects, out.visibility
+        if self._sparsity_applies():   # where the reference's sparsity loss.backward() accumulates: p.grad, before the all-reduce
+            self._add_sparsity_term(self.model.raw_opacities.grad, loss_value)
         if self.bucket is not None:
             params = self.model.parameters()
             self.bucket.gather([p.grad for p in params])
@@ -627,7 +712,8 @@ class GutTrainer:
             for p, gv in zip(params, self.bucket.views):
                 p.grad = gv
         if self.strategy is not None:
-            self.strategy.post_backward(self.iteration)
+            if not self._past_base():
+                self.strategy.post_backward(self.iteration)
             self.strategy.step(self.iteration)
             return loss_value
         self.optimizer.step(self.iteration)

@@ -5,7 +5,7 @@
     python tools/train_colmap.py -d /data/garden --images images_4 --iterations 30000 --strategy default --eval -o out/garden
 
 COLMAP reader -> point-cloud initialisation -> fastgs (default) or 3DGUT training with the L1 + SSIM loss and the ADC / MCMC strategy ->
-PSNR / SSIM on the held-out views -> splat PLY (and, with --save-sog, the .sog bundle). Prints one JSON line. All views must share one image size.
+[--enable-sparsity: ADMM sparsification phase + prune] -> PSNR / SSIM on the held-out views -> splat PLY (and, with --save-sog, the .sog bundle). Prints one JSON line. All views must share one image size.
 """
 import argparse
 import json
@@ -39,6 +39,10 @@ def main():
     ap.add_argument("--save-sog", action="store_true", help="also write splat_<iterations>.sog, the compressed bundle web viewers load (the reference's --save-sog)")
     ap.add_argument("--sog-iterations", type=int, default=10, help="k-means iterations of the SOG export (the reference's sog_iterations)")
     ap.add_argument("--sog-palette-size", type=int, default=None, help="entries of the SOG shN palette, up to min(65536, N) (default: the reference's value, 64 from 1024 Gaussians on)")
+    ap.add_argument("--enable-sparsity", action="store_true", help="after --iterations, ADMM sparsification for --sparsify-steps more iterations, then prune to (1 - --prune-ratio) of the Gaussians")
+    ap.add_argument("--sparsify-steps", type=int, default=15000)
+    ap.add_argument("--init-rho", type=float, default=0.0005, help="ADMM penalty parameter")
+    ap.add_argument("--prune-ratio", type=float, default=0.6, help="share of the Gaussians the final prune removes")
     args = ap.parse_args()
     if args.pose_optimization != "none" and args.eval:   # trainer.cpp:367-370
         raise SystemExit("Evaluating with pose optimization is not supported yet. Please disable pose optimization or evaluation.")
@@ -63,7 +67,10 @@ def main():
     if args.bilateral_grid and rast != "fastgs":
         raise SystemExit("--bilateral-grid needs the fastgs rasterizer")
     tr = GutTrainer(scene, dev, iterations=args.iterations, loss="l1_ssim", strategy=None if args.strategy == "none" else args.strategy, opt_params=op,
-                    scene_scale=scene_scale, rasterizer=rast, use_bilateral_grid=args.bilateral_grid, pose_optimization=args.pose_optimization)
+                    scene_scale=scene_scale, rasterizer=rast, use_bilateral_grid=args.bilateral_grid, pose_optimization=args.pose_optimization,
+                    enable_sparsity=args.enable_sparsity, sparsify_steps=args.sparsify_steps, init_rho=args.init_rho, prune_ratio=args.prune_ratio)
+    total = tr.total_iterations                                             # --iterations, plus the sparsification phase
+    os.makedirs(args.output_path, exist_ok=True)
     g = torch.Generator().manual_seed(0)
     val_set = None
     if args.eval and args.eval_every > 0:
@@ -80,11 +87,13 @@ def main():
     t0 = time.time()
     t_eval = 0.0
     order = []
-    for it in range(args.iterations):
+    for it in range(total):
         if not order:
             order = torch.randperm(len(ds), generator=g).tolist()          # infinite random sampler, one view per step
         v = order.pop()
         tr.train_step([targets[v]], views=[v])
+        if args.enable_sparsity and it + 1 == args.iterations:              # the model of the base run, before sparsification touches it
+            loader.save_ply(tr.model, os.path.join(args.output_path, f"splat_{args.iterations}.ply"))
         if val_set is not None and (it + 1) % args.eval_every == 0:
             torch.cuda.synchronize(); te = time.time()
             m = evaluate.evaluate(tr.model, val_set[0], val_set[1], it + 1, rasterizer=rast if args.gut else "fastgs")
@@ -108,9 +117,11 @@ def main():
             t_eval += time.time() - te
     torch.cuda.synchronize()
     t_train = time.time() - t0 - t_eval
-    out = {"data": args.data_path, "images": len(ds), "size": [scene.width, scene.height], "iterations": args.iterations, "rasterizer": rast,
+    out = {"data": args.data_path, "images": len(ds), "size": [scene.width, scene.height], "iterations": total, "rasterizer": rast,
            "strategy": args.strategy, "pose_optimization": args.pose_optimization, "gaussians": int(tr.model.means.shape[0]), "load_s": round(t_load, 1), "train_s": round(t_train, 1),
-           "iters_per_s": round(args.iterations / max(t_train, 1e-9), 1)}
+           "iters_per_s": round(total / max(t_train, 1e-9), 1)}
+    if args.enable_sparsity:
+        out.update(base_iterations=args.iterations, sparsify_steps=args.sparsify_steps, prune_ratio=args.prune_ratio, init_rho=args.init_rho)
     if args.eval:
         cams_all, _ = (loader.read_colmap_cameras_and_images_text if args.text else loader.read_colmap_cameras_and_images)(args.data_path, args.images)
         val = loader.CameraDataset(cams_all, "val", args.test_every, args.resize_factor, args.max_width)
@@ -120,19 +131,18 @@ def main():
             h, w = img.shape[1:]
             cameras.append(Camera(torch.from_numpy(loader.world_to_view(cam))[None].to(dev), torch.from_numpy(loader.intrinsics(cam, w, h))[None].to(dev), w, h))
             images.append(img)
-        m = evaluate.evaluate(tr.model, cameras, images, args.iterations)
+        m = evaluate.evaluate(tr.model, cameras, images, total)
         out.update(psnr=round(m.psnr, 4), ssim=round(m.ssim, 5), val_images=m.n_images)
         if args.gut:   # the reference's protocol above renders with the EWA rasterizer; this is the renderer the model was trained with
-            mg = evaluate.evaluate(tr.model, cameras, images, args.iterations, rasterizer="gut")
+            mg = evaluate.evaluate(tr.model, cameras, images, total, rasterizer="gut")
             out.update(psnr_gut=round(mg.psnr, 4), ssim_gut=round(mg.ssim, 5))
     if curve:
         out["psnr_curve"] = curve
-    os.makedirs(args.output_path, exist_ok=True)
-    ply = os.path.join(args.output_path, f"splat_{args.iterations}.ply")
+    ply = os.path.join(args.output_path, f"splat_{total}.ply")
     loader.save_ply(tr.model, ply)
     out["ply"] = ply
     if args.save_sog:
-        sog_path = os.path.join(args.output_path, f"splat_{args.iterations}.sog")
+        sog_path = os.path.join(args.output_path, f"splat_{total}.sog")
         loader.save_sog(tr.model, sog_path, iterations=args.sog_iterations, palette_size=args.sog_palette_size)
         out.update(sog=sog_path, sog_bytes=os.path.getsize(sog_path), ply_bytes=os.path.getsize(ply))
     print(json.dumps(out), flush=True)
