@@ -349,6 +349,22 @@ LFS_API int lfs_photometric_loss_ex_fwd_bwd(uint32_t H, uint32_t W, const float*
 LFS_API int lfs_mse_loss_ex_fwd_bwd(uint32_t H, uint32_t W, const float* render, uint32_t render_is_chw, uint32_t clamp_render, const float* target_chw, float weight,
                                     float* v_render, float* loss, lfs_stream_t stream);
 
+/* masked forms (extension; DESIGN.md §8 "Masked training"). mask_u8 [H,W]: 255 = the pixel counts fully, 0 = ignored; mask_sums int64[2] on the device =
+ * {S_img = sum of the mask, S_crop = sum over the SSIM crop (5 pixels per side when H, W > 10, else the image)}, as lfs_mask_prepare writes them. The kernels read
+ * the sums on the device (no host read):
+ *   L1m   = sum_c sum_p M_p |r - t| / (3 S_img)                     (0 when S_img == 0)
+ *   SSIMm = sum_c sum_{p in crop} M_p ssim_{c,p} / (3 S_crop)        (the SSIM map is that of the UNMASKED images)
+ *   *loss += weight * ((1 - lambda) L1m + lambda (1 - SSIMm))       (the SSIM term is 0 when S_crop == 0)
+ * and, when alpha [H,W] is given (with v_alpha [H,W]; both or neither), the opacity penalty outside the mask:
+ *   *loss += weight * alpha_weight * sum_p (255 - M_p) alpha_p / (255 H W),   v_alpha_p = weight * alpha_weight * (255 - M_p) / (255 H W).
+ * Workspace: lfs_photometric_loss_workspace_bytes. The MSE form: *loss += weight * sum_c sum_p M_p (r - t)^2 / (3 S_img). */
+LFS_API int lfs_photometric_loss_masked_fwd_bwd(uint32_t H, uint32_t W, const float* render, uint32_t render_is_chw, uint32_t clamp_render, const float* target_chw,
+                                                const uint8_t* mask_u8, const int64_t* mask_sums, float lambda_dssim, float weight, const float* alpha,
+                                                float alpha_weight, float* v_alpha, float* v_render, float* loss, void* workspace, size_t workspace_bytes,
+                                                lfs_stream_t stream);
+LFS_API int lfs_mse_loss_masked_fwd_bwd(uint32_t H, uint32_t W, const float* render, uint32_t render_is_chw, uint32_t clamp_render, const float* target_chw,
+                                        const uint8_t* mask_u8, const int64_t* mask_sums, float weight, float* v_render, float* loss, lfs_stream_t stream);
+
 /* ---- bilateral-grid appearance model (row 2 of §8f, BASELINE config 5): gs::bilateral_grid::slice_forward_cuda /
  *      slice_backward_cuda / tv_loss_forward_cuda / tv_loss_backward_cuda (include/kernels/bilateral_grid.cuh:12-33,
  *      src/training/kernels/bilateral_grid_{forward,backward,tv}.cu). grid [12,L,H,W]; image h x w (both >= 2), uniform
@@ -378,6 +394,11 @@ LFS_API int lfs_bilateral_tv_loss_bwd(uint32_t N, uint32_t L, uint32_t H, uint32
  *      lfs_mean_neighbor_distances_exact (extension): the same quantity from an exact all-pairs search; asynchronous. */
 LFS_API int lfs_image_u8_to_chw_f32(const uint8_t* src_hwc, uint32_t src_width, uint32_t src_height, float* dst_chw, uint32_t dst_width,
                                     uint32_t dst_height, lfs_stream_t stream);
+/* lfs_mask_prepare (extension): one u8 plane [sh,sw] -> the training-size mask [dh,dw] through the sample positions and the 8-bit re-quantisation of
+ * lfs_image_u8_to_chw_f32 (mask and image stay registered), then threshold (threshold >= 0: value >= threshold ? 255 : 0; < 0 keeps soft values), then invert
+ * (255 - value). WRITES sums int64[2] = {sum of dst, sum of dst over the loss's crop}: exact integers, identical on every run. Asynchronous. */
+LFS_API int lfs_mask_prepare(const uint8_t* src_u8, uint32_t src_width, uint32_t src_height, uint8_t* dst_u8, uint32_t dst_width, uint32_t dst_height,
+                             uint32_t invert, int32_t threshold, int64_t* sums, lfs_stream_t stream);
 LFS_API int lfs_mean_neighbor_distances(uint32_t N, const float* points, float* out, lfs_stream_t stream);
 LFS_API int lfs_mean_neighbor_distances_exact(uint32_t N, const float* points, float* out, lfs_stream_t stream);
 

@@ -92,6 +92,9 @@ LFS_IO_API int lfs_image_target_size(int32_t width, int32_t height, int32_t res_
  * libjpeg-turbo); anything else returns LFS_IO_E_UNSUPPORTED (the Python host layer then tries Pillow). The buffer is owned by the
  * library: release with lfs_io_free. */
 LFS_IO_API int lfs_image_load_rgb8(const char* path, uint8_t** data, int32_t* width, int32_t* height);
+/* The alpha channel alone, 8-bit [h,w], of a PNG of colour type 4 (grey + alpha) or 6 (RGBA); 16-bit samples are reduced as the RGB path reduces them
+ * (the high byte). Anything else returns LFS_IO_E_UNSUPPORTED (the Python host layer then tries Pillow). Release with lfs_io_free. */
+LFS_IO_API int lfs_image_load_alpha8(const char* path, uint8_t** data, int32_t* width, int32_t* height);
 LFS_IO_API int lfs_image_write_png_rgb8(const char* path, const uint8_t* data, int32_t width, int32_t height);
 LFS_IO_API void lfs_io_free(void* p);
 

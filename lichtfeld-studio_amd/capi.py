@@ -92,6 +92,7 @@ EXPORTS = [
     "lfs_morton_workspace_bytes", "lfs_morton_encode", "lfs_kmeans_assign_workspace_bytes", "lfs_kmeans_assign", "lfs_kmeans_assign_1d", "lfs_kmeans_update",
     "lfs_select_kth_workspace_bytes", "lfs_select_kth_f32", "lfs_admm_update_workspace_bytes", "lfs_admm_update", "lfs_admm_loss_grad_workspace_bytes", "lfs_admm_loss_grad",
     "lfs_admm_prune_mask_workspace_bytes", "lfs_admm_prune_mask",
+    "lfs_mask_prepare", "lfs_photometric_loss_masked_fwd_bwd", "lfs_mse_loss_masked_fwd_bwd",
 ]
 
 

@@ -65,6 +65,49 @@ __global__ void __launch_bounds__(256) image_to_chw_kernel(const uint8_t* __rest
     }
 }
 
+// lfs_mask_prepare: one plane through the sample positions, the arithmetic and the 8-bit re-quantisation of image_to_chw_kernel (a mask stays registered with
+// its image), then threshold (>= threshold ? 255 : 0; threshold < 0 keeps the soft value), then invert. sums[0] += sum over the image, sums[1] += sum over the
+// loss's crop (5 pixels per side when dh, dw > 10, else the whole image): integer wave sums and one 64-bit integer atomic per block - exact, the same on every run.
+__global__ void __launch_bounds__(256) mask_prepare_kernel(const uint8_t* __restrict__ src, int sw, int sh, uint8_t* __restrict__ dst, int dw, int dh, int resample,
+                                                           int invert, int threshold, unsigned long long* __restrict__ sums) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    unsigned int m = 0, m_crop = 0;
+    if (x < dw && y < dh) {
+        const size_t o = (size_t)y * dw + x;
+        int q;
+        if (!resample) {
+            q = src[o];
+        } else {
+            const float s = ((float)x + 0.5f) * (1.0f / (float)dw), t = ((float)y + 0.5f) * (1.0f / (float)dh);
+            const float fx = s * (float)sw - 0.5f, fy = t * (float)sh - 0.5f;
+            const float flx = floorf(fx), fly = floorf(fy);
+            const float ax = fx - flx, ay = fy - fly;
+            const int x0 = min(max((int)flx, 0), sw - 1), x1 = min(max((int)flx + 1, 0), sw - 1);
+            const int y0 = min(max((int)fly, 0), sh - 1), y1 = min(max((int)fly + 1, 0), sh - 1);
+            const float v00 = (float)src[(size_t)y0 * sw + x0] * (1.0f / 255.0f), v01 = (float)src[(size_t)y0 * sw + x1] * (1.0f / 255.0f);
+            const float v10 = (float)src[(size_t)y1 * sw + x0] * (1.0f / 255.0f), v11 = (float)src[(size_t)y1 * sw + x1] * (1.0f / 255.0f);
+            const float top = (1.0f - ax) * v00 + ax * v01, bot = (1.0f - ax) * v10 + ax * v11;
+            const float v = (1.0f - ay) * top + ay * bot;
+            q = (int)fminf(fmaxf(v * 255.0f + 0.5f, 0.0f), 255.0f);
+        }
+        if (threshold >= 0) q = q >= threshold ? 255 : 0;
+        if (invert) q = 255 - q;
+        dst[o] = (uint8_t)q;
+        m = (unsigned int)q;
+        const bool crop = dh > 10 && dw > 10;
+        m_crop = (!crop || (x >= 5 && x < dw - 5 && y >= 5 && y < dh - 5)) ? m : 0u;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { m += __shfl_xor(m, d, 64); m_crop += __shfl_xor(m_crop, d, 64); }
+    __shared__ unsigned int part[2][4];
+    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = m; part[1][threadIdx.x >> 6] = m_crop; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const unsigned int v = part[threadIdx.x][0] + part[threadIdx.x][1] + part[threadIdx.x][2] + part[threadIdx.x][3];
+        if (v) atomicAdd(&sums[threadIdx.x], (unsigned long long)v);
+    }
+}
+
 constexpr int KNN_THREADS = 256;
 
 // sorted insert into the 4 smallest (ascending); ties keep the earlier entry first, as a stable selection does
@@ -340,6 +383,20 @@ extern "C" int lfs_image_u8_to_chw_f32(const uint8_t* src_hwc, uint32_t src_widt
     const int resample = (dst_width != src_width || dst_height != src_height) ? 1 : 0;
     hipLaunchKernelGGL(image_to_chw_kernel, dim3((dst_width + 63) / 64, (dst_height + 3) / 4), dim3(256), 0, s, src_hwc, (int)src_width, (int)src_height, dst_chw,
                        (int)dst_width, (int)dst_height, resample);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lfs_mask_prepare(const uint8_t* src_u8, uint32_t src_width, uint32_t src_height, uint8_t* dst_u8, uint32_t dst_width, uint32_t dst_height,
+                                uint32_t invert, int32_t threshold, int64_t* sums, lfs_stream_t stream) {
+    if (!src_u8 || !dst_u8 || !sums || !src_width || !src_height || src_width >= (1u << 30) || src_height >= (1u << 30)) return LFS_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    lfs::ProfScope prof("mask_prepare", s);
+    hipError_t e = hipMemsetAsync(sums, 0, 2 * sizeof(int64_t), s); // the sums are written, not accumulated
+    if (e != hipSuccess) return (int)e;
+    if (!dst_width || !dst_height) return LFS_OK;
+    const int resample = (dst_width != src_width || dst_height != src_height) ? 1 : 0;
+    hipLaunchKernelGGL(mask_prepare_kernel, dim3((dst_width + 63) / 64, (dst_height + 3) / 4), dim3(256), 0, s, src_u8, (int)src_width, (int)src_height, dst_u8,
+                       (int)dst_width, (int)dst_height, resample, invert ? 1 : 0, (int)threshold, (unsigned long long*)sums);
     return (int)hipGetLastError();
 }
 

@@ -62,20 +62,30 @@ __global__ void __launch_bounds__(256) activations_bwd_kernel(
 // loss += sum((clamp(x,0,1) - t)^2) * inv_numel * weight; v_render = 2 (clamp(x) - t) * inv_numel * weight where 0 <= x <= 1
 // (torch::clamp passes the gradient on the closed interval). render HWC, target CHW.
 // CHW = true: render / v_render are [3,H,W] and NOT clamped (the fastgs path: fast_rasterizer.cpp hands the image on as is)
-template <bool CHW>
-__global__ void __launch_bounds__(256) mse_loss_kernel(
-    const uint32_t H, const uint32_t W, const float* __restrict__ render, const float* __restrict__ target,
-    const float scale, float* __restrict__ v_render, float* __restrict__ loss, const bool clamp = !CHW) {
+// MASKED (lfs_mse_loss_masked_fwd_bwd): every pixel weighted by its mask byte M_p, normalised by 3 * sum(M) read from the device (`scale` is unused:
+// the factor is wscale / S_img, a double division rounded to float once, 0 under an empty mask). A compile-time switch of one shared body.
+template <bool CHW, bool MASKED>
+__device__ __forceinline__ void mse_loss_body(
+    const uint32_t H, const uint32_t W, const float* render, const float* target, float scale, float* v_render, float* loss, const bool clamp,
+    const uint8_t* mask, const long long* sums, const double wscale, const uint32_t p0, const uint32_t stride) {
     const uint32_t P = H * W;
     float acc = 0.f;
-    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) {
+    if constexpr (MASKED) scale = sums[0] > 0 ? float(wscale / double(sums[0])) : 0.f;
+    for (uint32_t p = p0; p < P; p += stride) {
+        float m = 1.f;
+        if constexpr (MASKED) m = float(mask[p]);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const size_t ri = CHW ? size_t(c) * P + p : 3 * size_t(p) + c;
             const float x = render[ri];
             const float d = (clamp ? fminf(fmaxf(x, 0.f), 1.f) : x) - target[size_t(c) * P + p];
-            acc += d * d;
-            v_render[ri] = (!clamp || (x >= 0.f && x <= 1.f)) ? 2.f * d * scale : 0.f;
+            if constexpr (MASKED) {
+                acc += m * (d * d);
+                v_render[ri] = (m != 0.f && (!clamp || (x >= 0.f && x <= 1.f))) ? 2.f * d * (m * scale) : 0.f;
+            } else {
+                acc += d * d;
+                v_render[ri] = (!clamp || (x >= 0.f && x <= 1.f)) ? 2.f * d * scale : 0.f;
+            }
         }
     }
 #pragma unroll
@@ -84,6 +94,20 @@ __global__ void __launch_bounds__(256) mse_loss_kernel(
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(loss, (part[0] + part[1] + part[2] + part[3]) * scale);
+}
+
+template <bool CHW>
+__global__ void __launch_bounds__(256) mse_loss_kernel(
+    const uint32_t H, const uint32_t W, const float* __restrict__ render, const float* __restrict__ target,
+    const float scale, float* __restrict__ v_render, float* __restrict__ loss, const bool clamp = !CHW) {
+    mse_loss_body<CHW, false>(H, W, render, target, scale, v_render, loss, clamp, nullptr, nullptr, 0.0, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
+
+template <bool CHW>
+__global__ void __launch_bounds__(256) mse_loss_masked_kernel(
+    const uint32_t H, const uint32_t W, const float* __restrict__ render, const float* __restrict__ target, const uint8_t* __restrict__ mask,
+    const long long* __restrict__ sums, const double wscale, float* __restrict__ v_render, float* __restrict__ loss, const bool clamp) {
+    mse_loss_body<CHW, true>(H, W, render, target, 0.f, v_render, loss, clamp, mask, sums, wscale, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
 } // namespace lfs
@@ -148,5 +172,20 @@ extern "C" int lfs_mse_loss_ex_fwd_bwd(uint32_t H, uint32_t W, const float* rend
     const uint32_t blocks = (P + 255) / 256 < 2048 ? (P + 255) / 256 : 2048;
     if (render_is_chw) hipLaunchKernelGGL(lfs::mse_loss_kernel<true>, dim3(blocks), dim3(256), 0, s, H, W, render, target_chw, weight / float(3u * P), v_render, loss, clamp_render != 0);
     else hipLaunchKernelGGL(lfs::mse_loss_kernel<false>, dim3(blocks), dim3(256), 0, s, H, W, render, target_chw, weight / float(3u * P), v_render, loss, clamp_render != 0);
+    return (int)hipGetLastError();
+}
+
+// masked form: *loss += weight * sum_c sum_p M_p (r - t)^2 / (3 sum_p M_p); the normaliser comes from mask_sums[0] on the device
+extern "C" int lfs_mse_loss_masked_fwd_bwd(uint32_t H, uint32_t W, const float* render, uint32_t render_is_chw, uint32_t clamp_render, const float* target_chw,
+                                           const uint8_t* mask_u8, const int64_t* mask_sums, float weight, float* v_render, float* loss, lfs_stream_t stream) {
+    if (H == 0 || W == 0) return LFS_OK;
+    if (!render || !target_chw || !v_render || !loss || !mask_u8 || !mask_sums) return LFS_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    lfs::ProfScope prof("mse_loss_masked", s);
+    const uint32_t P = H * W;
+    const uint32_t blocks = (P + 255) / 256 < 2048 ? (P + 255) / 256 : 2048;
+    const double wscale = double(weight) / 3.0;
+    if (render_is_chw) hipLaunchKernelGGL(lfs::mse_loss_masked_kernel<true>, dim3(blocks), dim3(256), 0, s, H, W, render, target_chw, mask_u8, (const long long*)mask_sums, wscale, v_render, loss, clamp_render != 0);
+    else hipLaunchKernelGGL(lfs::mse_loss_masked_kernel<false>, dim3(blocks), dim3(256), 0, s, H, W, render, target_chw, mask_u8, (const long long*)mask_sums, wscale, v_render, loss, clamp_render != 0);
     return (int)hipGetLastError();
 }

@@ -48,7 +48,20 @@ struct SsimFwdArgs {
     int fused; float chain; int crop; float* loss; float w_ssim, w_l1, loss_const;
 };
 
-__global__ void __launch_bounds__(256) ssim_fwd_kernel(const SsimFwdArgs a) {
+// The mask of the masked photometric loss (lfs_photometric_loss_masked_fwd_bwd): one byte per pixel (255 counts fully, 0 is ignored) and its two exact
+// integer sums {sum over the image, sum over the crop}, from which every thread derives the same two normalisers (a double division of host-prepared
+// numerators, rounded to float once). The SSIM statistics stay those of the unmasked images: only the per-pixel weights change.
+struct SsimMaskArgs {
+    const uint8_t* mask; const long long* sums;
+    double num_ssim, num_l1;                    // -weight * lambda / 3 and weight * (1 - lambda) / 3: divided by S_crop / S_img in the kernel
+    const float* alpha; float* v_alpha; float w_alpha; // optional opacity penalty outside the mask: w_alpha = weight * w_a / (255 H W)
+};
+// (wave-uniform: handed on through an SGPR, so the weights cost no vector register over the stencil)
+LFS_DI float mask_norm(double num, long long s) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(s > 0 ? float(num / double(s)) : 0.f))); }
+
+// MASKED is a compile-time switch of one shared body: the unmasked instantiation is the kernel as it was, statement for statement.
+template <bool MASKED>
+LFS_DI void ssim_fwd_body(const SsimFwdArgs a, const SsimMaskArgs k) {
     __shared__ float s_tile[SS_T][SS_T][2];
     __shared__ float s_conv[SS_T][SS_B][5]; // after the horizontal pass: E[x], E[x^2], E[y], E[y^2], E[xy]
     __shared__ float s_red[2][4];
@@ -59,6 +72,11 @@ __global__ void __launch_bounds__(256) ssim_fwd_kernel(const SsimFwdArgs a) {
     const bool in_img = px < a.W && py < a.H;
     const bool in_crop = !a.crop || (px >= SS_HALO && px < a.W - SS_HALO && py >= SS_HALO && py < a.H - SS_HALO);
     float acc_ssim = 0.f, acc_l1 = 0.f;
+    float m_px = 0.f, w_ssim_m = 0.f, w_l1_m = 0.f; // MASKED only
+    if constexpr (MASKED) {
+        w_ssim_m = mask_norm(k.num_ssim, k.sums[1]); w_l1_m = mask_norm(k.num_l1, k.sums[0]);
+        if (in_img) m_px = float(k.mask[size_t(py) * a.W + px]);
+    }
     for (int c = 0; c < a.CH; ++c) {
         for (int i = threadIdx.x; i < SS_T * SS_T; i += 256) {
             const int ly = i / SS_T, lx = i % SS_T;
@@ -104,13 +122,23 @@ __global__ void __launch_bounds__(256) ssim_fwd_kernel(const SsimFwdArgs a) {
                 const float val = (Cn * Dn) / (A * B);
                 const size_t gi = ((size_t(b) * a.CH + c) * a.H + py) * a.W + px;
                 if (a.ssim_map) a.ssim_map[gi] = val;
+                float m_chain = 0.f; // MASKED only; kept quirk: no SSIM gradient when the image cannot be cropped
+                if constexpr (MASKED) m_chain = (a.crop && in_crop) ? w_ssim_m * m_px : 0.f;
+                if (MASKED && m_chain == 0.f) { // an exact 0 wherever the pixel carries no weight, whatever the derivatives are (and they are not computed)
+                    a.dm_dmu1[gi] = 0.f; a.dm_dsigma1_sq[gi] = 0.f; a.dm_dsigma12[gi] = 0.f;
+                } else
                 if (a.dm_dmu1) {
                     float d_mu1 = ((mu2 * 2.f * Dn) / (A * B) - (mu2 * 2.f * Cn) / (A * B) - (mu1 * 2.f * Cn * Dn) / (A * A * B) + (mu1 * 2.f * Cn * Dn) / (A * B * B));
                     float d_s1 = (-Cn * Dn) / (A * B * B);
                     float d_s12 = (2.f * Cn) / (A * B);
+                    if constexpr (MASKED) { d_mu1 *= m_chain; d_s1 *= m_chain; d_s12 *= m_chain; } else
                     if (a.fused) { const float ch = in_crop ? a.chain : 0.f; d_mu1 *= ch; d_s1 *= ch; d_s12 *= ch; }
                     a.dm_dmu1[gi] = d_mu1; a.dm_dsigma1_sq[gi] = d_s1; a.dm_dsigma12[gi] = d_s12;
                 }
+                if constexpr (MASKED) {
+                    if (in_crop) acc_ssim += m_px * val;
+                    acc_l1 += m_px * fabsf(s_tile[ty + SS_HALO][tx + SS_HALO][0] - s_tile[ty + SS_HALO][tx + SS_HALO][1]);
+                } else
                 if (a.loss) {
                     if (in_crop) acc_ssim += val;
                     acc_l1 += fabsf(s_tile[ty + SS_HALO][tx + SS_HALO][0] - s_tile[ty + SS_HALO][tx + SS_HALO][1]);
@@ -119,6 +147,26 @@ __global__ void __launch_bounds__(256) ssim_fwd_kernel(const SsimFwdArgs a) {
         }
         __syncthreads();
     }
+    if constexpr (MASKED) {
+        __shared__ float s_red_m[3][4];
+        float acc_alpha = 0.f;
+        if (k.alpha && in_img) { // once per pixel, not per channel: w_alpha * (255 - M) * alpha
+            const size_t pi = size_t(py) * a.W + px;
+            const float g = k.w_alpha * (255.f - m_px);
+            k.v_alpha[pi] = g;
+            acc_alpha = g * k.alpha[pi];
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) { acc_ssim += __shfl_xor(acc_ssim, m, 64); acc_l1 += __shfl_xor(acc_l1, m, 64); acc_alpha += __shfl_xor(acc_alpha, m, 64); }
+        if ((threadIdx.x & 63) == 0) { s_red_m[0][threadIdx.x >> 6] = acc_ssim; s_red_m[1][threadIdx.x >> 6] = acc_l1; s_red_m[2][threadIdx.x >> 6] = acc_alpha; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float v = w_ssim_m * (s_red_m[0][0] + s_red_m[0][1] + s_red_m[0][2] + s_red_m[0][3]) + w_l1_m * (s_red_m[1][0] + s_red_m[1][1] + s_red_m[1][2] + s_red_m[1][3]) +
+                      (s_red_m[2][0] + s_red_m[2][1] + s_red_m[2][2] + s_red_m[2][3]);
+            if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && k.sums[1] > 0) v += a.loss_const; // the SSIM term is 0, not lambda, under an empty crop
+            atomicAdd(a.loss, v);
+        }
+    } else
     if (a.loss) {
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) { acc_ssim += __shfl_xor(acc_ssim, m, 64); acc_l1 += __shfl_xor(acc_l1, m, 64); }
@@ -132,6 +180,16 @@ __global__ void __launch_bounds__(256) ssim_fwd_kernel(const SsimFwdArgs a) {
     }
 }
 
+__global__ void __launch_bounds__(256) ssim_fwd_kernel(const SsimFwdArgs a) { ssim_fwd_body<false>(a, SsimMaskArgs{}); }
+#ifdef LFS_EMULATE
+#define SS_WAVES_PER_EU(n)
+#else
+#define SS_WAVES_PER_EU(n) __attribute__((amdgpu_waves_per_eu(n)))
+#endif
+// (the occupancy hint: left alone, the register allocator takes 103 VGPRs for the masked instantiation - 4 waves per SIMD against the unmasked kernel's 6 at 79 -
+//  with the hint 81 and no scratch)
+__global__ void __launch_bounds__(256) SS_WAVES_PER_EU(5) ssim_fwd_masked_kernel(const SsimFwdArgs a, const SsimMaskArgs k) { ssim_fwd_body<true>(a, k); }
+
 struct SsimBwdArgs {
     int H, W, CH;
     SsimImg img1; const float* img2;
@@ -141,7 +199,8 @@ struct SsimBwdArgs {
     float g_l1;                                 // fused-loss mode: + g_l1 * sign(img1 - img2), and the clamp's gradient mask
 };
 
-__global__ void __launch_bounds__(256) ssim_bwd_kernel(const SsimBwdArgs a) {
+template <bool MASKED>
+LFS_DI void ssim_bwd_body(const SsimBwdArgs a, const SsimMaskArgs k) {
     __shared__ float s_data[3][SS_T][SS_T];
     __shared__ float s_conv[SS_T][SS_B][3];
     const int b = blockIdx.z;
@@ -149,6 +208,11 @@ __global__ void __launch_bounds__(256) ssim_bwd_kernel(const SsimBwdArgs a) {
     const int x0 = blockIdx.x * SS_B, y0 = blockIdx.y * SS_B;
     const int px = x0 + tx, py = y0 + ty;
     const bool in_img = px < a.W && py < a.H;
+    float g_l1_m = 0.f; // MASKED only: weight (1 - lambda) M_p / (3 S_img)
+    if constexpr (MASKED) {
+        const float w = mask_norm(k.num_l1, k.sums[0]);
+        if (in_img) g_l1_m = w * float(k.mask[size_t(py) * a.W + px]);
+    }
     for (int c = 0; c < a.CH; ++c) {
         for (int i = threadIdx.x; i < SS_T * SS_T; i += 256) {
             const int ly = i / SS_T, lx = i % SS_T;
@@ -197,6 +261,8 @@ __global__ void __launch_bounds__(256) ssim_bwd_kernel(const SsimBwdArgs a) {
                 const float p1 = clamped ? fminf(fmaxf(raw, 0.f), 1.f) : raw;
                 float g = s0 + (2.f * p1) * s1 + p2 * s2;
                 const float diff = p1 - p2;
+                if constexpr (MASKED) g += g_l1_m * (diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f));
+                else
                 g += a.g_l1 * (diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f)); // torch::l1_loss: sign(), 0 at 0
                 a.dL_dimg1[gi] = (!clamped || (raw >= 0.f && raw <= 1.f)) ? g : 0.f; // torch::clamp passes the gradient on [0, 1]
             } else {
@@ -208,6 +274,9 @@ __global__ void __launch_bounds__(256) ssim_bwd_kernel(const SsimBwdArgs a) {
         __syncthreads();
     }
 }
+
+__global__ void __launch_bounds__(256) ssim_bwd_kernel(const SsimBwdArgs a) { ssim_bwd_body<false>(a, SsimMaskArgs{}); }
+__global__ void __launch_bounds__(256) ssim_bwd_masked_kernel(const SsimBwdArgs a, const SsimMaskArgs k) { ssim_bwd_body<true>(a, k); }
 
 static dim3 ssim_grid(int B, int H, int W) { return dim3((W + SS_B - 1) / SS_B, (H + SS_B - 1) / SS_B, B); }
 
@@ -250,8 +319,10 @@ extern "C" size_t lfs_photometric_loss_workspace_bytes(uint32_t H, uint32_t W) {
 
 // *loss += weight * ((1 - lambda) * mean|clamp(render) - target| + lambda * (1 - mean_valid SSIM(clamp(render), target)));
 // v_render = d(that)/d(render). render / v_render HWC [H,W,3] (un-clamped rasterizer output), target CHW [3,H,W].
+// mask != nullptr: the masked form (SsimMaskArgs; the normalisers n_map / n_img are replaced by the mask's sums inside the kernels)
 static int photometric_loss(uint32_t H, uint32_t W, const float* render_hwc, int render_is_chw, int clamp, const float* target_chw, float lambda_dssim,
-                            float weight, float* v_render_hwc, float* loss, void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
+                            float weight, float* v_render_hwc, float* loss, void* workspace, size_t workspace_bytes, lfs_stream_t stream,
+                            const SsimMaskArgs* mask = nullptr) {
     if (H == 0 || W == 0) return LFS_OK;
     if (!render_hwc || !target_chw || !v_render_hwc || !loss || !workspace) return LFS_E_INVALID;
     if (workspace_bytes < lfs_photometric_loss_workspace_bytes(H, W)) return LFS_E_WORKSPACE;
@@ -272,14 +343,16 @@ static int photometric_loss(uint32_t H, uint32_t W, const float* render_hwc, int
     f.crop = crop ? 1 : 0; f.loss = loss; f.loss_const = weight * lambda_dssim;
     f.w_ssim = float(-double(weight) * lambda_dssim / n_map); f.w_l1 = float(double(weight) * (1.0 - lambda_dssim) / n_img);
     hipStream_t s = (hipStream_t)stream;
-    lfs::ProfScope prof("photometric_loss", s);
-    hipLaunchKernelGGL(ssim_fwd_kernel, ssim_grid(1, int(H), int(W)), dim3(256), 0, s, f);
+    lfs::ProfScope prof(mask ? "photometric_loss_masked" : "photometric_loss", s);
+    if (mask) hipLaunchKernelGGL(ssim_fwd_masked_kernel, ssim_grid(1, int(H), int(W)), dim3(256), 0, s, f, *mask);
+    else hipLaunchKernelGGL(ssim_fwd_kernel, ssim_grid(1, int(H), int(W)), dim3(256), 0, s, f);
     SsimBwdArgs b{};
     b.H = int(H); b.W = int(W); b.CH = CH;
     b.img1 = SsimImg{render_hwc, 1, render_is_chw, clamp}; b.img2 = target_chw; b.dL_dmap = nullptr;
     b.dm_dmu1 = f.dm_dmu1; b.dm_dsigma1_sq = f.dm_dsigma1_sq; b.dm_dsigma12 = f.dm_dsigma12; b.dL_dimg1 = v_render_hwc;
     b.g_l1 = f.w_l1;
-    hipLaunchKernelGGL(ssim_bwd_kernel, ssim_grid(1, int(H), int(W)), dim3(256), 0, s, b);
+    if (mask) hipLaunchKernelGGL(ssim_bwd_masked_kernel, ssim_grid(1, int(H), int(W)), dim3(256), 0, s, b, *mask);
+    else hipLaunchKernelGGL(ssim_bwd_kernel, ssim_grid(1, int(H), int(W)), dim3(256), 0, s, b);
     return (int)hipGetLastError();
 }
 
@@ -302,4 +375,18 @@ extern "C" int lfs_photometric_loss_ex_fwd_bwd(uint32_t H, uint32_t W, const flo
                                                float lambda_dssim, float weight, float* v_render, float* loss, void* workspace, size_t workspace_bytes,
                                                lfs_stream_t stream) {
     return photometric_loss(H, W, render, render_is_chw ? 1 : 0, clamp_render ? 1 : 0, target_chw, lambda_dssim, weight, v_render, loss, workspace, workspace_bytes, stream);
+}
+
+// masked form of the general entry (include/lfs_gsplat.h): per-pixel weights M_p, normalisers from the device-side sums (no host read), SSIM statistics unmasked
+extern "C" int lfs_photometric_loss_masked_fwd_bwd(uint32_t H, uint32_t W, const float* render, uint32_t render_is_chw, uint32_t clamp_render, const float* target_chw,
+                                                   const uint8_t* mask_u8, const int64_t* mask_sums, float lambda_dssim, float weight, const float* alpha,
+                                                   float alpha_weight, float* v_alpha, float* v_render, float* loss, void* workspace, size_t workspace_bytes,
+                                                   lfs_stream_t stream) {
+    if (H == 0 || W == 0) return LFS_OK;
+    if (!mask_u8 || !mask_sums || (alpha != nullptr) != (v_alpha != nullptr)) return LFS_E_INVALID;
+    SsimMaskArgs k{};
+    k.mask = mask_u8; k.sums = (const long long*)mask_sums;
+    k.num_ssim = -double(weight) * lambda_dssim / 3.0; k.num_l1 = double(weight) * (1.0 - lambda_dssim) / 3.0;
+    k.alpha = alpha; k.v_alpha = v_alpha; k.w_alpha = alpha ? float(double(weight) * alpha_weight / (255.0 * double(H) * double(W))) : 0.f;
+    return photometric_loss(H, W, render, render_is_chw ? 1 : 0, clamp_render ? 1 : 0, target_chw, lambda_dssim, weight, v_render, loss, workspace, workspace_bytes, stream, &k);
 }

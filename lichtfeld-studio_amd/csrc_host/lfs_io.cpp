@@ -593,11 +593,13 @@ void to_rgb(const uint8_t* src, int ch, size_t n, uint8_t* dst) {
     }
 }
 
-uint8_t* decode_png(const std::vector<char>& f, int32_t& w, int32_t& h) {
+// alpha_only: the alpha channel alone, [h,w] (colour types 4 and 6; anything else is LFS_IO_E_UNSUPPORTED), samples reduced as the colour path reduces them
+uint8_t* decode_png(const std::vector<char>& f, int32_t& w, int32_t& h, bool alpha_only = false) {
     const unsigned char* u = (const unsigned char*)f.data();
     w = (int32_t)be32(u + 16); h = (int32_t)be32(u + 20);
     const int depth = u[24], ct = u[25], interlace = u[28];
     if (interlace) fail(LFS_IO_E_UNSUPPORTED, "PNG: interlaced files are not supported");
+    if (alpha_only && ct != 4 && ct != 6) fail(LFS_IO_E_UNSUPPORTED, "PNG: colour type %d has no alpha channel", ct);
     if (ct != 0 && ct != 2 && ct != 3 && ct != 4 && ct != 6) fail(LFS_IO_E_FORMAT, "PNG: bad colour type %d", ct);
     if (depth != 1 && depth != 2 && depth != 4 && depth != 8 && depth != 16) fail(LFS_IO_E_FORMAT, "PNG: bad bit depth %d", depth);
     if ((depth < 8 && ct != 0 && ct != 3) || (depth == 16 && ct == 3)) // PNG spec table 11.1: packed samples only for grey / palette, no 16-bit palette
@@ -649,6 +651,12 @@ uint8_t* decode_png(const std::vector<char>& f, int32_t& w, int32_t& h) {
             const int v = (cur[(size_t)x * depth / 8] >> (8 - depth - (x * depth) % 8)) & ((1 << depth) - 1);
             dst[x] = ct == 3 ? (uint8_t)v : (uint8_t)(v * 255 / ((1 << depth) - 1));
         }
+    }
+    if (alpha_only) {
+        uint8_t* a = (uint8_t*)std::malloc((size_t)w * h);
+        if (!a) throw std::bad_alloc();
+        for (size_t i = 0; i < (size_t)w * h; ++i) a[i] = pix[i * samples + samples - 1];
+        return a;
     }
     uint8_t* out = (uint8_t*)std::malloc((size_t)w * h * 3);
     if (!out) throw std::bad_alloc();
@@ -1107,6 +1115,16 @@ int lfs_image_load_rgb8(const char* path, uint8_t** data, int32_t* width, int32_
             return;
         }
         fail(LFS_IO_E_UNSUPPORTED, "Unrecognised image format: %s", path);
+    });
+}
+
+int lfs_image_load_alpha8(const char* path, uint8_t** data, int32_t* width, int32_t* height) {
+    return guarded([&] {
+        if (!path || !data || !width || !height) fail(LFS_IO_E_INVALID, "lfs_image_load_alpha8: bad arguments");
+        *data = nullptr;
+        const auto f = slurp(path);
+        if (f.size() >= 33 && std::memcmp(f.data(), kPngSig, 8) == 0) { *data = decode_png(f, *width, *height, true); return; }
+        fail(LFS_IO_E_UNSUPPORTED, "No alpha channel can be read from %s", path);
     });
 }
 

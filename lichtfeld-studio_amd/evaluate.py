@@ -12,12 +12,21 @@ from typing import List, Optional
 import torch
 
 
-def psnr(pred: torch.Tensor, target: torch.Tensor, data_range: float = 1.0) -> float:
-    """[B,C,H,W] (or [C,H,W]) -> mean over the batch of 20 log10(data_range / sqrt(mse))."""
+def psnr(pred: torch.Tensor, target: torch.Tensor, data_range: float = 1.0, mask=None) -> float:
+    """[B,C,H,W] (or [C,H,W]) -> mean over the batch of 20 log10(data_range / sqrt(mse)).
+    mask (a losses.PreparedMask or a [H,W] tensor of byte values, 255 = counts fully): the masked MSE sum M (p - t)^2 / (C sum M) instead; an all-zero mask
+    gives the clamped MSE's PSNR (100 dB), as an exact match does."""
     if pred.shape != target.shape:
         raise ValueError("Prediction and target must have the same shape")
     if pred.dim() == 3:
         pred, target = pred[None], target[None]
+    if mask is not None:
+        m = getattr(mask, "mask_u8", mask).to(device=pred.device, dtype=pred.dtype)
+        if tuple(m.shape) != tuple(pred.shape[-2:]):
+            raise ValueError("the mask must have the images' height and width")
+        num = (m * (pred - target).pow(2)).reshape(pred.shape[0], -1).sum(1, keepdim=True)
+        mse = (num / (pred.shape[1] * m.sum()).clamp_min(1.0)).clamp_min(1e-10)
+        return float((20.0 * torch.log10(data_range / mse.sqrt())).mean())
     mse = (pred.contiguous() - target.contiguous()).pow(2).reshape(pred.shape[0], -1).mean(1, keepdim=True).clamp_min(1e-10)
     return float((20.0 * torch.log10(data_range / mse.sqrt())).mean())
 
@@ -40,11 +49,13 @@ class EvalMetrics:
 
 @torch.no_grad()
 def evaluate(model, cameras: List, images: List[torch.Tensor], iteration: int = 0, background: Optional[torch.Tensor] = None,
-             rasterizer: str = "fastgs") -> EvalMetrics:
+             rasterizer: str = "fastgs", masks: Optional[List] = None) -> EvalMetrics:
     """cameras: rasterizer.Camera per validation view; images: the ground truth [3,H,W] in [0,1]. rasterizer="fastgs" is the reference's protocol
     (metrics.cpp:430 renders with fast_rasterize whatever was trained with); "gut" renders with the 3DGUT rasterizer instead - what a model trained with
     --gut was optimised for: 3DGUT has no screen-space dilation, the EWA renderer adds its 0.3-pixel low-pass to Gaussians the training shrank below a
-    pixel (profiles/r04/scale_train_*: up to 13 dB between the two numbers on an MCMC model with noise injection)."""
+    pixel (profiles/r04/scale_train_*: up to 13 dB between the two numbers on an MCMC model with noise injection).
+    masks (parallel to images; None entries = unmasked views): the PSNR is the masked one (psnr(mask=...)). SSIM stays UNMASKED: its 11x11 window has no
+    per-pixel form that a mask could weight without printing the mask's edge into the statistics."""
     from .fastgs import fast_rasterize
     from .rasterizer import rasterize
     if rasterizer not in ("fastgs", "gut"):
@@ -53,9 +64,11 @@ def evaluate(model, cameras: List, images: List[torch.Tensor], iteration: int = 
     dev = model.means.device
     bg = background if background is not None else torch.zeros(3, device=dev)
     ps, ss = [], []
-    for cam, gt in zip(cameras, images):
+    if masks is not None and len(masks) != len(images):
+        raise ValueError("masks must be parallel to images")
+    for i, (cam, gt) in enumerate(zip(cameras, images)):
         img = torch.clamp(render(cam, model, bg).image, 0.0, 1.0)
-        ps.append(psnr(img, gt.to(dev)))
+        ps.append(psnr(img, gt.to(dev), mask=masks[i] if masks is not None else None))
         ss.append(ssim(img, gt.to(dev)))
     n = max(len(ps), 1)
     return EvalMetrics(sum(ps) / n, sum(ss) / n, int(model.means.shape[0]), iteration, len(ps))

@@ -33,7 +33,7 @@ IO_EXPORTS = [
     "lfs_colmap_image_name", "lfs_colmap_image_path", "lfs_colmap_scene_center", "lfs_colmap_points_open", "lfs_point_cloud_size",
     "lfs_point_cloud_copy", "lfs_point_cloud_close", "lfs_ply_write_splat", "lfs_ply_open", "lfs_ply_num_vertices", "lfs_ply_num_properties",
     "lfs_ply_property_name", "lfs_ply_read", "lfs_ply_close", "lfs_image_info", "lfs_image_target_size", "lfs_image_load_rgb8",
-    "lfs_image_write_png_rgb8",
+    "lfs_image_write_png_rgb8", "lfs_image_load_alpha8",
 ]
 IO_E_UNSUPPORTED = -4
 
@@ -225,6 +225,67 @@ def decode_rgb8(path: str) -> np.ndarray:
     return np.stack([r, g, (r + g) // 2], -1).astype(np.uint8)
 
 
+def decode_mask8(path: str, alpha: bool = False) -> np.ndarray:
+    """-> uint8 [h,w]. alpha=False: a mask file, its first channel (decode_rgb8's red). alpha=True: the image's own alpha channel - the native PNG decoder
+    (colour types 4 and 6) first, Pillow for what liblfs_io does not decode."""
+    if not alpha:
+        return np.ascontiguousarray(decode_rgb8(path)[..., 0])
+    lib = io_library()
+    data, w, h = C.POINTER(C.c_uint8)(), C.c_int32(), C.c_int32()
+    rc = lib.lfs_image_load_alpha8(os.fsencode(path), C.byref(data), C.byref(w), C.byref(h))
+    if rc == 0:
+        try:
+            return np.ctypeslib.as_array(data, shape=(h.value, w.value)).copy()
+        finally:
+            lib.lfs_io_free(data)
+    if rc != IO_E_UNSUPPORTED:
+        _check(rc)
+    return _pillow_alpha8(path)
+
+
+def _pillow_alpha8(path: str) -> np.ndarray:
+    from PIL import Image, UnidentifiedImageError
+    try:
+        im = Image.open(path)
+    except (UnidentifiedImageError, OSError) as e:
+        raise LoaderError(f"Load failed: {path} : {e}") from None
+    with im:
+        if "A" not in im.getbands() and "transparency" in im.info:
+            im = im.convert("RGBA")
+        if "A" not in im.getbands():
+            raise LoaderError(f"{path} has no alpha channel")
+        a = np.asarray(im.getchannel("A"))
+    if a.dtype != np.uint8:   # 16-bit samples: the high byte, as the native decoder
+        a = (a.astype(np.uint32) >> 8).astype(np.uint8)
+    return np.ascontiguousarray(a)
+
+
+def find_mask(image_path: str, data_path: Optional[str], masks_folder: Optional[str] = "masks") -> Optional[Tuple[str, bool]]:
+    """Where an image's mask comes from: (path, is_alpha) or None (the view trains unmasked). In <data>/<masks folder>/ the names tried are, in order,
+    <image file name>.png (COLMAP's convention), <stem>.png, <stem><image ext>; otherwise the image's own alpha when its header reports 2 or 4 channels."""
+    name = os.path.basename(image_path)
+    stem, ext = os.path.splitext(name)
+    if data_path and masks_folder:
+        folder = os.path.join(data_path, masks_folder)
+        for cand in (name + ".png", stem + ".png", stem + ext):
+            p = os.path.join(folder, cand)
+            if os.path.isfile(p):
+                return p, False
+    if os.path.isfile(image_path) and get_image_info(image_path)[2] in (2, 4):
+        return image_path, True
+    return None
+
+
+def load_mask8(image_path: str, source: Tuple[str, bool]) -> np.ndarray:
+    """The mask of find_mask as uint8 [h,w] at the image's SOURCE size; any other size is an error (mask and image share one resample)."""
+    path, is_alpha = source
+    m = decode_mask8(path, alpha=is_alpha)
+    w, h, _ = get_image_info(image_path)
+    if m.shape != (h, w):
+        raise LoaderError(f"mask {path} is {m.shape[1]}x{m.shape[0]} but its image {image_path} is {w}x{h}")
+    return m
+
+
 def u8_to_chw_f32(image_u8: torch.Tensor, out_width: Optional[int] = None, out_height: Optional[int] = None) -> torch.Tensor:
     """GPU: u8 [h,w,3] -> f32 [3,oh,ow] in [0,1] (bilinear resample + 8-bit requantisation when the size changes)."""
     from .capi import check, load_library, ptr, require_gpu, stream
@@ -381,6 +442,12 @@ class CameraDataset:
     resize_factor: int = -1
     max_width: int = 0
     indices: List[int] = field(default_factory=list)
+    data_path: Optional[str] = None     # the scene's directory: where the masks folder is looked for
+    masks_folder: Optional[str] = "masks"
+
+    def mask_source(self, index: int) -> Optional[Tuple[str, bool]]:
+        """(path, is_alpha) of the view's mask (find_mask), or None: that view trains unmasked"""
+        return find_mask(self.cameras[self.indices[index]].image_path, self.data_path, self.masks_folder)
 
     def __post_init__(self):
         self.indices = [i for i in range(len(self.cameras))
@@ -420,6 +487,25 @@ def preload(ds: "CameraDataset", device="cuda:0", workers: int = 8) -> List[torc
     return out
 
 
+def preload_masks(ds: "CameraDataset", device="cuda:0", invert: bool = False, threshold: int = -1) -> list:
+    """The masks of the split, parallel to preload(): a losses.PreparedMask at image_target_size per view that has a mask source, None for the others."""
+    from .losses import prepare_mask
+    out = []
+    for i in range(len(ds)):
+        src = ds.mask_source(i)
+        if src is None:
+            out.append(None)
+            continue
+        cam = ds.cameras[ds.indices[i]]
+        m = load_mask8(cam.image_path, src)
+        ow, oh = image_target_size(m.shape[1], m.shape[0], ds.resize_factor, ds.max_width)
+        host = torch.from_numpy(m)
+        if torch.cuda.is_available():
+            host = host.pin_memory()
+        out.append(prepare_mask(host.to(device, non_blocking=True), ow, oh, invert, threshold))
+    return out
+
+
 def world_to_view(cam: CameraData) -> np.ndarray:
     """camera.cpp:15-23: [R | t] with the COLMAP translation as is."""
     m = np.eye(4, dtype=np.float32)
@@ -437,13 +523,13 @@ def intrinsics(cam: CameraData, image_width: int, image_height: int) -> np.ndarr
 
 
 def colmap_scene(base: str, images_folder: str = "images", split: str = "train", test_every: int = 8, resize_factor: int = -1, max_width: int = 0,
-                 sh_degree: int = 3, init_scaling: float = 1.0, init_opacity: float = 0.1, text: bool = False, device="cuda:0"):
+                 sh_degree: int = 3, init_scaling: float = 1.0, init_opacity: float = 0.1, text: bool = False, device="cuda:0", masks_folder: Optional[str] = "masks"):
     """COLMAP directory -> (Scene for GutTrainer, CameraDataset, scene_scale). All views must share one image size (the trainer's
     view batches are rectangular)."""
     from .scenes import Scene
     cams, center = (read_colmap_cameras_and_images_text if text else read_colmap_cameras_and_images)(base, images_folder)
     pcd = (read_colmap_point_cloud_text if text else read_colmap_point_cloud)(base)
-    ds = CameraDataset(cams, split, test_every, resize_factor, max_width)
+    ds = CameraDataset(cams, split, test_every, resize_factor, max_width, data_path=base, masks_folder=masks_folder)
     if not len(ds):
         raise LoaderError("the requested split has no images")
     w, h = ds.image_size(0)

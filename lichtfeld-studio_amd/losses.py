@@ -7,7 +7,7 @@ H, W > 10; returns the MEAN of the map) and the photometric loss of Trainer::com
 from __future__ import annotations
 
 import ctypes as C
-from typing import Tuple
+from typing import NamedTuple, Tuple
 
 import torch
 
@@ -131,10 +131,35 @@ def photometric_loss_chw_fwd_bwd(render_chw: torch.Tensor, target_chw: torch.Ten
     return v
 
 
+class PreparedMask(NamedTuple):
+    """A training-size mask on the device: mask_u8 uint8 [H,W] (255 = the pixel counts fully, 0 = ignored) and sums int64[2] = {sum over the image, sum over
+    the SSIM crop}, the two exact integers the masked loss kernels normalise with (read on the device)."""
+    mask_u8: torch.Tensor
+    sums: torch.Tensor
+
+
+def prepare_mask(mask_u8_device: torch.Tensor, out_width: int, out_height: int, invert: bool = False, threshold: int = -1) -> PreparedMask:
+    """lfs_mask_prepare: a uint8 [h,w] plane -> the mask at the training resolution (the sample positions and 8-bit re-quantisation of u8_to_chw_f32), then
+    threshold (>= threshold -> 255, else 0; negative keeps soft values), then invert; and its two integer sums. Asynchronous."""
+    src = mask_u8_device.contiguous()
+    require_gpu(src)
+    if src.dim() != 2 or src.dtype != torch.uint8:
+        raise LfsError("prepare_mask expects a uint8 [h,w] tensor")
+    sh, sw = src.shape
+    dst = torch.empty(int(out_height), int(out_width), dtype=torch.uint8, device=src.device)
+    sums = torch.empty(2, dtype=torch.int64, device=src.device)
+    check(load_library().lfs_mask_prepare(ptr(src), C.c_uint32(sw), C.c_uint32(sh), ptr(dst), C.c_uint32(int(out_width)), C.c_uint32(int(out_height)),
+                                          C.c_uint32(int(bool(invert))), C.c_int32(int(threshold)), ptr(sums), stream()), "mask_prepare")
+    return PreparedMask(dst, sums)
+
+
 def loss_fwd_bwd(kind: str, render: torch.Tensor, target_chw: torch.Tensor, weight: float, loss_acc: torch.Tensor, chw: bool, clamp: bool,
-                 lambda_dssim: float = 0.2) -> torch.Tensor:
+                 lambda_dssim: float = 0.2, mask: PreparedMask | None = None, alpha: torch.Tensor | None = None, alpha_weight: float = 0.0):
     """General fused loss: kind "mse" | "l1_ssim"; render [H,W,3] (chw False) or [3,H,W]; clamp = clamp(render, 0, 1) first (gradient masked).
-    loss_acc += weight * loss; returns dL/d(render) in the render's layout."""
+    loss_acc += weight * loss; returns dL/d(render) in the render's layout.
+    mask (a PreparedMask of the render's size): the masked forms - every pixel weighted by its mask byte, normalised by the mask's sums; the SSIM map itself is
+    that of the unmasked images. alpha [H,W] (with mask, "l1_ssim" only) adds weight * alpha_weight * sum (255 - M) alpha / (255 H W) and makes the return value
+    (v_render, v_alpha). mask=None is the unmasked call, unchanged."""
     target_chw = target_chw.contiguous()
     render = render.contiguous()
     require_gpu(render, target_chw, loss_acc)
@@ -142,7 +167,28 @@ def loss_fwd_bwd(kind: str, render: torch.Tensor, target_chw: torch.Tensor, weig
     assert tuple(target_chw.shape) == (3, H, W) and render.shape[0 if chw else -1] == 3, (render.shape, target_chw.shape)
     lib = load_library()
     v = torch.empty_like(render)
-    if kind == "mse":
+    if mask is None:
+        if alpha is not None:
+            raise ValueError("loss_fwd_bwd: alpha needs a mask")
+    else:
+        require_gpu(mask.mask_u8, mask.sums, alpha)
+        if tuple(mask.mask_u8.shape) != (H, W) or mask.mask_u8.dtype != torch.uint8 or mask.sums.dtype != torch.int64 or mask.sums.numel() != 2:
+            raise LfsError(f"loss_fwd_bwd: the mask must be uint8 [{H},{W}] with int64[2] sums (got {tuple(mask.mask_u8.shape)})")
+        if alpha is not None and (kind != "l1_ssim" or alpha.numel() != H * W or alpha.dtype != torch.float32):
+            raise LfsError("loss_fwd_bwd: alpha is a float32 [H,W] tensor of the l1_ssim loss")
+    if kind == "mse" and mask is not None:
+        check(lib.lfs_mse_loss_masked_fwd_bwd(C.c_uint32(H), C.c_uint32(W), ptr(render), C.c_uint32(int(chw)), C.c_uint32(int(clamp)), ptr(target_chw),
+                                              ptr(mask.mask_u8), ptr(mask.sums), C.c_float(weight), ptr(v), ptr(loss_acc), stream()), "mse_loss_masked_fwd_bwd")
+    elif kind == "l1_ssim" and mask is not None:
+        ws = workspace(lib.lfs_photometric_loss_workspace_bytes(C.c_uint32(H), C.c_uint32(W)), render.device, "photometric")
+        v_alpha = torch.empty_like(alpha) if alpha is not None else None
+        check(lib.lfs_photometric_loss_masked_fwd_bwd(C.c_uint32(H), C.c_uint32(W), ptr(render), C.c_uint32(int(chw)), C.c_uint32(int(clamp)), ptr(target_chw),
+                                                      ptr(mask.mask_u8), ptr(mask.sums), C.c_float(lambda_dssim), C.c_float(weight), ptr(alpha),
+                                                      C.c_float(alpha_weight), ptr(v_alpha), ptr(v), ptr(loss_acc), ptr(ws), C.c_size_t(ws.numel()), stream()),
+              "photometric_loss_masked_fwd_bwd")
+        if alpha is not None:
+            return v, v_alpha
+    elif kind == "mse":
         check(lib.lfs_mse_loss_ex_fwd_bwd(C.c_uint32(H), C.c_uint32(W), ptr(render), C.c_uint32(int(chw)), C.c_uint32(int(clamp)), ptr(target_chw), C.c_float(weight),
                                           ptr(v), ptr(loss_acc), stream()), "mse_loss_ex_fwd_bwd")
     elif kind == "l1_ssim":
@@ -153,3 +199,20 @@ def loss_fwd_bwd(kind: str, render: torch.Tensor, target_chw: torch.Tensor, weig
     else:
         raise ValueError(f"unknown loss {kind!r}")
     return v
+
+
+def masked_photometric_loss(rendered: torch.Tensor, gt: torch.Tensor, mask: PreparedMask, lambda_dssim: float = 0.2) -> torch.Tensor:
+    """The masked L1 + D-SSIM of lfs_photometric_loss_masked_fwd_bwd through autograd, on [3,H,W] images: built on _FusedSSIM's map of the UNMASKED images
+    (padding "valid": the crop, and the kept quirk that an image too small to crop gets no SSIM gradient), weighted per pixel by the mask and normalised by
+    its device-side sums. For the autograd step form and as a cross-check of the fused kernel."""
+    if rendered.dim() != 3 or gt.dim() != 3:
+        raise ValueError("masked_photometric_loss expects [3,H,W] images")
+    H, W = rendered.shape[-2], rendered.shape[-1]
+    m = mask.mask_u8.to(rendered.dtype)
+    s_img, s_crop = mask.sums[0].to(rendered.dtype), mask.sums[1].to(rendered.dtype)
+    zero = rendered.new_zeros(())
+    l1 = torch.where(s_img > 0, (m * (rendered - gt).abs()).sum() / (3.0 * s_img.clamp_min(1.0)), zero)
+    smap = _FusedSSIM.apply(rendered.contiguous(), gt, "valid", True)[0]
+    mc = m[5:H - 5, 5:W - 5] if (H > 10 and W > 10) else m
+    ssim_term = torch.where(s_crop > 0, 1.0 - (mc * smap).sum() / (3.0 * s_crop.clamp_min(1.0)), zero)
+    return (1.0 - lambda_dssim) * l1 + lambda_dssim * ssim_term

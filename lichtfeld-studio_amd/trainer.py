@@ -30,7 +30,8 @@ class StepPlan:
 
 def plan_step(*, rasterizer: str, fused_l2: bool, world: int, force_collectives: bool, sh_sharded: bool, shard_rows: int, n_views: int, loss: str,
               strategy: Optional[str], refining: bool, iteration: int, has_shN: bool, optimizer_fused: bool, bilateral: bool, inline_shN_adam: bool = True,
-              inline_all_adam: bool = True, cxx_step: bool = True, batch_views: bool = True, factored_sh: bool = False, one_call: bool = False) -> StepPlan:
+              inline_all_adam: bool = True, cxx_step: bool = True, batch_views: bool = True, factored_sh: bool = False, one_call: bool = False,
+              masked: bool = False) -> StepPlan:
     """Pure function of the configuration -> the step form. The rules, in the order they are applied:
       * fastgs rasterizer -> its own step; fused_l2 off -> torch autograd over the op-by-op mirror.
       * shN's Adam update moves into the SH backward (inline_shN) when Adam reads shN anyway (iteration > 1000, fused_adam.cpp:68-70), there IS an shN, the
@@ -46,6 +47,8 @@ def plan_step(*, rasterizer: str, fused_l2: bool, world: int, force_collectives:
       * one_call (opt-in, GutTrainer(one_call=True)): one view on one rank ALSO takes the one-call form (cxx_all, lfs_gut_train_step_opt) for what the reference trains -
         loss "mse" or "l1_ssim", no strategy or MCMC between refinements (its noise is folded into the tail), at ANY iteration (<= 1000: freeze_shN, the tail skips
         shN as FusedAdam does) - given the fused optimizer, an shN, cxx_step and no bilateral grid. Everything else keeps the form it has with the keyword off.
+      * masked (the step carries an image mask): never the one-call form (cxx_all), neither through inline_all nor through one_call - the one-call C++ step
+        computes its loss inside, without a mask; the step takes the form it has without those two rules (GutTrainer raises for batch_views / py_views).
       * pose optimisation is not an input: GutTrainer's constructor admits it on the fastgs rasterizer of one rank only, whose plan has no inline form."""
     multi = world > 1 or force_collectives
     if rasterizer == "fastgs":
@@ -55,10 +58,10 @@ def plan_step(*, rasterizer: str, fused_l2: bool, world: int, force_collectives:
     strat_ok = strategy is None or (strategy == "mcmc" and not refining)
     adam_reads_shN = iteration > 1000 and has_shN and optimizer_fused
     inline_one = inline_shN_adam and not multi and not sh_sharded and n_views == 1 and strat_ok and adam_reads_shN
-    inline_all = inline_one and inline_all_adam and strategy is None and loss == "mse" and not bilateral
+    inline_all = inline_one and inline_all_adam and strategy is None and loss == "mse" and not bilateral and not masked
     inline_shard = inline_shN_adam and sh_sharded and n_views == 1 and adam_reads_shN and shard_rows > 0 and not refining
     skip_deferred = iteration <= 1000 or sh_sharded
-    if (one_call and cxx_step and not multi and not sh_sharded and n_views == 1 and strat_ok and has_shN and optimizer_fused and not bilateral
+    if (one_call and not masked and cxx_step and not multi and not sh_sharded and n_views == 1 and strat_ok and has_shN and optimizer_fused and not bilateral
             and loss in ("mse", "l1_ssim")):
         return StepPlan("cxx_all", adam_reads_shN, True, False, multi, skip_deferred, freeze_shN=not adam_reads_shN)
     if factored_sh and multi and not sh_sharded:
@@ -84,7 +87,8 @@ class GutTrainer:
                  strategy: Optional[str] = None, opt_params=None, scene_scale: float = 1.0, seed: int = 0, rasterizer: str = "gut",
                  use_bilateral_grid: bool = False, bilateral_grid_dims=(16, 16, 8), bilateral_grid_lr: float = 2e-3, tv_loss_weight: float = 10.0,
                  sh_sharded: Optional[bool] = None, factored_sh: bool = False, one_call: bool = False, pose_optimization: str = "none", pose_lr: float = 1e-5,
-                 enable_sparsity: bool = False, sparsify_steps: int = 15000, init_rho: float = 0.0005, prune_ratio: float = 0.6, sparsity_update_every: int = 50):
+                 enable_sparsity: bool = False, sparsify_steps: int = 15000, init_rho: float = 0.0005, prune_ratio: float = 0.6, sparsity_update_every: int = 50,
+                 mask_mode: str = "none", mask_alpha_weight: float = 1.0):
         """strategy: None (fixed set of Gaussians: the benchmark), "mcmc" (strategies.MCMC: relocation + growth + SGLD noise, with
         the scale / opacity regularisers of trainer.cpp:132-158) or "default" (ADC; needs densification_info, see strategies.py).
         `seed` seeds the strategy's generator: the same on every rank, so replicas densify identically.
@@ -96,7 +100,20 @@ class GutTrainer:
         enable_sparsity (trainer.cpp:331-360; sparsity.py): the run is extended by `sparsify_steps` iterations after the `iterations` of the base run. During them the
         ADMM penalty (init_rho) pulls the opacities towards a state with prune_ratio of them at zero, refreshed every sparsity_update_every iterations, and no
         strategy refinement, noise or SH-degree change happens; at the last iteration int(prune_ratio * N) Gaussians of lowest opacity are removed. `total_iterations`
-        is the length of the whole run. The learning-rate schedule stays the base run's."""
+        is the length of the whole run. The learning-rate schedule stays the base run's.
+        mask_mode: "none" | "ignore" | "segment" (DESIGN.md 8 "Masked training"): what train_step(masks=...) does with a view's mask. "ignore": the loss weights every
+        pixel by its mask byte (the masked loss kernels). "segment": additionally the rendered opacity outside the mask is penalised with mask_alpha_weight (L1 + D-SSIM
+        on the fastgs rasterizer, whose backward takes an alpha gradient; the autograd form of the 3DGUT rasterizer as well)."""
+        if mask_mode not in ("none", "ignore", "segment"):
+            raise ValueError(f"Invalid mask mode: {mask_mode}")
+        if mask_mode == "segment":
+            if rasterizer == "gut" and fused_l2:
+                raise ValueError("mask_mode='segment' is not wired into the fused forms of the 3DGUT rasterizer (rasterizer='gut', fused_l2=True): their backward calls "
+                                 "carry no alpha gradient. Use rasterizer='fastgs', or mask_mode='ignore'.")
+            if loss != "l1_ssim" and rasterizer == "fastgs":
+                raise ValueError("mask_mode='segment' on the fastgs rasterizer needs loss='l1_ssim': the opacity penalty is part of the masked L1 + D-SSIM kernel")
+        self.mask_mode, self.mask_alpha_weight = mask_mode, float(mask_alpha_weight)
+        self._masks = None
         if pose_optimization not in ("none", "direct", "mlp"):
             raise ValueError(f"Invalid pose optimization type: {pose_optimization}")
         if pose_optimization != "none":
@@ -325,7 +342,8 @@ class GutTrainer:
                 w2c, g_w2c = w2c_adj.detach().contiguous(), torch.empty_like(w2c)
             _, _, self.last_n_isects = fg_step(self._fastgs_settings(v), w2c, self.model, targets[k % len(targets)],
                                                1.0 / total_views, dst, self.loss_acc, densification_info=dens, loss=self.loss_kind,
-                                               lambda_dssim=self.lambda_dssim, bilateral=self.bilateral, image_idx=v, adam_shN=inline, grad_w2c=g_w2c)
+                                               lambda_dssim=self.lambda_dssim, bilateral=self.bilateral, image_idx=v, adam_shN=inline, grad_w2c=g_w2c,
+                                               **self._fastgs_mask_args(k))
             if w2c_adj is not None:
                 w2c_adj.backward(g_w2c)   # accumulates into the module's parameters over the views of the step
                 self.last_grad_w2c = g_w2c
@@ -365,6 +383,16 @@ class GutTrainer:
             self.pose_optimizer.step()
             self.pose_optimizer.zero_grad(set_to_none=True)
         return self.loss_acc
+
+    def _mask_of(self, k: int):
+        """the PreparedMask of the step's k-th view, or None (no masks this step, or that view has none)"""
+        return None if self._masks is None else self._masks[k % len(self._masks)]
+
+    def _fastgs_mask_args(self, k: int) -> dict:
+        m = self._mask_of(k)
+        if m is None:
+            return {}
+        return {"mask": m, "mask_alpha_weight": self.mask_alpha_weight if self.mask_mode == "segment" else 0.0}
 
     def _bilateral_step(self) -> None:
         """trainer.cpp:699-705, :758-761: TV regulariser (1/world of it per rank), sum of the ranks' grid gradients, Adam + warm-up schedule."""
@@ -427,8 +455,10 @@ class GutTrainer:
         return Camera(sc.viewmats[view:view + 1].contiguous(), sc.Ks[view:view + 1].contiguous(), sc.width, sc.height)
 
     def train_step(self, targets: List[torch.Tensor], views: Optional[List[int]] = None, views_all: Optional[List[List[int]]] = None,
-                   next_views: Optional[List[int]] = None) -> float:
-        """next_views: with an explicit `views`, the views the NEXT call will pass (a data loader knows them: src/training/dataloader.cpp prefetches) - the one-call step's
+                   next_views: Optional[List[int]] = None, masks: Optional[List] = None) -> float:
+        """masks: a list parallel to `targets` of losses.PreparedMask (at the training resolution) or None (that view is unmasked); needs mask_mode "ignore" or
+        "segment". A step whose masks are all None is the unmasked step.
+        next_views: with an explicit `views`, the views the NEXT call will pass (a data loader knows them: src/training/dataloader.cpp prefetches) - the one-call step's
         fused tail then evaluates their SH colours on the side. Without `views` the round-robin schedule names them."""
         self._next_view = None
         if self.world == 1 and self.views_per_rank == 1:
@@ -436,7 +466,17 @@ class GutTrainer:
                 self._next_view = lfs_dist.views_for_step(self.iteration + 1, self.rank, self.world, self.scene.viewmats.shape[0], self.views_per_rank)[0]
             elif next_views:
                 self._next_view = int(next_views[0])
-        out = self._train_step(targets, views, views_all)
+        self._masks = None
+        if masks is not None and any(m is not None for m in masks):
+            if self.mask_mode == "none":
+                raise ValueError("train_step(masks=...) needs GutTrainer(mask_mode='ignore' | 'segment') (mask_mode='none')")
+            if len(masks) != len(targets):
+                raise ValueError("masks must be parallel to targets")
+            self._masks = list(masks)
+        try:
+            out = self._train_step(targets, views, views_all)
+        finally:
+            self._masks = None
         # the SH schedule, AFTER the backward / optimizer step of the iteration, where the strategies keep it (post_backward: mcmc.cpp:366-368,
         # default_strategy.cpp) - iteration 1000, 2000, ... still renders with the old degree, as the reference does; without a strategy the trainer does it
         if (self.strategy is None and self.iteration % self.sh_degree_interval == 0 and self.model.active_sh_degree < self.model.max_sh_degree
@@ -465,6 +505,10 @@ class GutTrainer:
         self._views_all = views_all
         total_views = self.world * len(views)
         plan = self.last_plan = self._plan(len(views))   # (kept for tests and tools: which form the step took)
+        if self._masks is not None and plan.path in ("batch_views", "py_views"):
+            raise ValueError(f"masked training is not wired into the {plan.path} step form (rasterizer={self.rasterizer!r}, world={self.world}, views per step="
+                             f"{len(views)}, sh_sharded={self.sh_exchange is not None}, cxx_step={self.cxx_step}): masks run in the fastgs, autograd, cxx_views and "
+                             "cxx_factored forms")
         if plan.path != "cxx_all" and self._gut_step is not None:
             self._gut_step.colors_for = None   # (another step form is about to change the parameters: colours a fused tail left for this step are void)
         if plan.path == "fastgs":
@@ -501,7 +545,7 @@ class GutTrainer:
                          # (the ADMM term needs the opacity gradient as a tensor: no all-inline and no one-call form while it applies)
                          bilateral=self.bilateral is not None, inline_shN_adam=self.inline_shN_adam, inline_all_adam=self.inline_all_adam and not self._sparsity_applies(),
                          cxx_step=self.cxx_step and self.rasterizer != "fastgs" and self.fused_l2 and self._cxx_supported(), batch_views=self.batch_views,
-                         factored_sh=self.factored_sh,
+                         factored_sh=self.factored_sh, masked=self._masks is not None,
                          # (a strategy stops updating at its last iteration, strategies._StrategyBase.step: those steps keep the split form; so does a model with
                          #  SH degree 4 - K = 25 > 16: the fused tail, which carries the freeze and the noise, has no instantiation for it)
                          one_call=(self.one_call and (st is None or self.iteration < st.params.iterations) and 1 + self.model.shN.shape[1] <= 16
@@ -544,10 +588,19 @@ class GutTrainer:
             raise ValueError("the two-stream (pipelined) training step was removed: measured -4.5 % at best and slower on most variants "
                              "(profiles/r06/pipeline/README.md); the last commit that contains it is 13aac0e")
 
-    def _view_loss(self, gs, view: int, target, weight: float):
+    def _view_loss(self, gs, view: int, target, weight: float, mask=None):
         """The loss of the view gs.view_forward() left in the step workspace -> (v_render, fold): dL/d(render) [H,W,3] from the loss kernels (bilateral grid, L1 + D-SSIM)
-        with fold None, or v_render None and fold = the target the rasterizer backward derives the clamped MSE from itself. The loss is added to loss_acc."""
+        with fold None, or v_render None and fold = the target the rasterizer backward derives the clamped MSE from itself. The loss is added to loss_acc.
+        With a mask it is always the loss-kernel route (the masked kernels), never the folded MSE."""
         sc = self.scene
+        if mask is not None:
+            from .losses import loss_fwd_bwd
+            render = gs.view("render", torch.float32, (sc.height, sc.width, 3))
+            if self.bilateral is not None:
+                shown = self.bilateral.apply_fused(render, view, chw=False)
+                v_shown = loss_fwd_bwd(self.loss_kind, shown, target, weight, self.loss_acc, chw=False, clamp=False, lambda_dssim=self.lambda_dssim, mask=mask)
+                return self.bilateral.apply_fused_backward(render, view, v_shown, chw=False), None
+            return loss_fwd_bwd(self.loss_kind, render, target, weight, self.loss_acc, chw=False, clamp=True, lambda_dssim=self.lambda_dssim, mask=mask), None
         if self.bilateral is not None:   # clamp -> slice -> loss on the un-clamped result -> slice backward (fused.render_and_backward does the same)
             from .losses import loss_fwd_bwd
             render = gs.view("render", torch.float32, (sc.height, sc.width, 3))
@@ -574,7 +627,7 @@ class GutTrainer:
         for k, v in enumerate(views):
             vm, Km, tgt = sc.viewmats[v], sc.Ks[v], targets[k % len(targets)]
             self.last_n_isects = gs.view_forward(ps, deg, sc.width, sc.height, vm, Km, self.bg)
-            v_render, fold = self._view_loss(gs, v, tgt, weight)
+            v_render, fold = self._view_loss(gs, v, tgt, weight, self._mask_of(k))
             gs.view_backward_sh(ps, deg, sc.width, sc.height, vm, Km, self.bg, self.bucket.views, k > 0, target_chw=fold, weight=weight,
                                 loss_acc=self.loss_acc, v_render=v_render, adam_shN=inline)
             if plan.multi and k == len(views) - 1 and self.iteration > 1000 and ps[2].numel():
@@ -601,7 +654,7 @@ class GutTrainer:
         for k, v in enumerate(views):
             vm, Km, tgt = sc.viewmats[v], sc.Ks[v], targets[k % len(targets)]
             self.last_n_isects = gs.view_forward(ps, deg, sc.width, sc.height, vm, Km, self.bg)
-            v_render, fold = self._view_loss(gs, v, tgt, weight)
+            v_render, fold = self._view_loss(gs, v, tgt, weight, self._mask_of(k))
             gs.view_backward_rows(ps, deg, sc.width, sc.height, vm, Km, self.bg, self.bucket.views, k > 0, ex.send[k], target_chw=fold, weight=weight,
                                   loss_acc=self.loss_acc, v_render=v_render, scale_reg=self.scale_reg / self.world if k == 0 else 0.0,
                                   opacity_reg=self.opacity_reg / self.world if k == 0 else 0.0)
@@ -691,7 +744,19 @@ class GutTrainer:
         loss_value = None
         for k, v in enumerate(views):
             out = rasterize(self.camera(v), self.model, self.bg, 1.0, False, False, RenderMode.RGB)
-            if self.loss_kind == "l1_ssim":
+            mask = self._mask_of(k)
+            if mask is not None:
+                tgt = targets[k % len(targets)]
+                if self.loss_kind == "l1_ssim":
+                    from .losses import masked_photometric_loss
+                    loss = masked_photometric_loss(out.image, tgt, mask, self.lambda_dssim) / total_views
+                else:
+                    m, s_img = mask.mask_u8.to(out.image.dtype), mask.sums[0].to(out.image.dtype)
+                    loss = torch.where(s_img > 0, (m * (out.image - tgt) ** 2).sum() / (3.0 * s_img.clamp_min(1.0)), out.image.new_zeros(())) / total_views
+                if self.mask_mode == "segment":
+                    loss = loss + self.mask_alpha_weight / total_views * ((255.0 - mask.mask_u8.to(out.alpha.dtype)) * out.alpha.reshape(mask.mask_u8.shape)).sum() / (
+                        255.0 * mask.mask_u8.numel())
+            elif self.loss_kind == "l1_ssim":
                 from .losses import photometric_loss
                 loss = photometric_loss(out.image, targets[k % len(targets)], self.lambda_dssim) / total_views
             else:

@@ -43,6 +43,12 @@ def main():
     ap.add_argument("--sparsify-steps", type=int, default=15000)
     ap.add_argument("--init-rho", type=float, default=0.0005, help="ADMM penalty parameter")
     ap.add_argument("--prune-ratio", type=float, default=0.6, help="share of the Gaussians the final prune removes")
+    ap.add_argument("--mask-mode", default="none", choices=["none", "ignore", "segment"],
+                    help="image masks (<data>/<masks folder>/<image name>.png, or the image's own alpha): ignore = masked pixels leave the loss; segment = and the opacity outside the mask is penalised (fastgs rasterizer)")
+    ap.add_argument("--masks-folder", default="masks")
+    ap.add_argument("--invert-masks", action="store_true", help="the mask files mark what to IGNORE (white = ignored)")
+    ap.add_argument("--mask-threshold", type=int, default=-1, help="binarise: mask byte >= N counts fully, below it not at all (default: keep soft values)")
+    ap.add_argument("--mask-alpha-weight", type=float, default=1.0, help="weight of the opacity penalty of --mask-mode segment")
     args = ap.parse_args()
     if args.pose_optimization != "none" and args.eval:   # trainer.cpp:367-370
         raise SystemExit("Evaluating with pose optimization is not supported yet. Please disable pose optimization or evaluation.")
@@ -60,7 +66,8 @@ def main():
     split = "train" if args.eval else "all"
     scene, ds, scene_scale = loader.colmap_scene(args.data_path, args.images, split=split, test_every=args.test_every, resize_factor=args.resize_factor,
                                                  max_width=args.max_width, sh_degree=args.sh_degree, init_scaling=init_scaling, init_opacity=init_opacity,
-                                                 text=args.text, device=dev)
+                                                 text=args.text, device=dev, masks_folder=args.masks_folder)
+    masks = loader.preload_masks(ds, dev, args.invert_masks, args.mask_threshold) if args.mask_mode != "none" else None
     targets = loader.preload(ds, dev, workers=os.cpu_count() or 8)          # resident in HBM: 288 GB hold a Mip-NeRF360 scene at full resolution
     t_load = time.time() - t0
     rast = "gut" if args.gut else "fastgs"
@@ -68,7 +75,8 @@ def main():
         raise SystemExit("--bilateral-grid needs the fastgs rasterizer")
     tr = GutTrainer(scene, dev, iterations=args.iterations, loss="l1_ssim", strategy=None if args.strategy == "none" else args.strategy, opt_params=op,
                     scene_scale=scene_scale, rasterizer=rast, use_bilateral_grid=args.bilateral_grid, pose_optimization=args.pose_optimization,
-                    enable_sparsity=args.enable_sparsity, sparsify_steps=args.sparsify_steps, init_rho=args.init_rho, prune_ratio=args.prune_ratio)
+                    enable_sparsity=args.enable_sparsity, sparsify_steps=args.sparsify_steps, init_rho=args.init_rho, prune_ratio=args.prune_ratio,
+                    mask_mode=args.mask_mode, mask_alpha_weight=args.mask_alpha_weight)
     total = tr.total_iterations                                             # --iterations, plus the sparsification phase
     os.makedirs(args.output_path, exist_ok=True)
     g = torch.Generator().manual_seed(0)
@@ -91,7 +99,7 @@ def main():
         if not order:
             order = torch.randperm(len(ds), generator=g).tolist()          # infinite random sampler, one view per step
         v = order.pop()
-        tr.train_step([targets[v]], views=[v])
+        tr.train_step([targets[v]], views=[v], masks=None if masks is None else [masks[v]])
         if args.enable_sparsity and it + 1 == args.iterations:              # the model of the base run, before sparsification touches it
             loader.save_ply(tr.model, os.path.join(args.output_path, f"splat_{args.iterations}.ply"))
         if val_set is not None and (it + 1) % args.eval_every == 0:
@@ -120,21 +128,24 @@ def main():
     out = {"data": args.data_path, "images": len(ds), "size": [scene.width, scene.height], "iterations": total, "rasterizer": rast,
            "strategy": args.strategy, "pose_optimization": args.pose_optimization, "gaussians": int(tr.model.means.shape[0]), "load_s": round(t_load, 1), "train_s": round(t_train, 1),
            "iters_per_s": round(total / max(t_train, 1e-9), 1)}
+    if masks is not None:
+        out.update(mask_mode=args.mask_mode, masked_views=sum(m is not None for m in masks))
     if args.enable_sparsity:
         out.update(base_iterations=args.iterations, sparsify_steps=args.sparsify_steps, prune_ratio=args.prune_ratio, init_rho=args.init_rho)
     if args.eval:
         cams_all, _ = (loader.read_colmap_cameras_and_images_text if args.text else loader.read_colmap_cameras_and_images)(args.data_path, args.images)
-        val = loader.CameraDataset(cams_all, "val", args.test_every, args.resize_factor, args.max_width)
+        val = loader.CameraDataset(cams_all, "val", args.test_every, args.resize_factor, args.max_width, data_path=args.data_path, masks_folder=args.masks_folder)
+        val_masks = loader.preload_masks(val, dev, args.invert_masks, args.mask_threshold) if args.mask_mode != "none" else None   # PSNR over the masked pixels; SSIM unmasked
         cameras, images = [], []
         for k, img in enumerate(loader.preload(val, dev)):
             cam = val.cameras[val.indices[k]]
             h, w = img.shape[1:]
             cameras.append(Camera(torch.from_numpy(loader.world_to_view(cam))[None].to(dev), torch.from_numpy(loader.intrinsics(cam, w, h))[None].to(dev), w, h))
             images.append(img)
-        m = evaluate.evaluate(tr.model, cameras, images, total)
+        m = evaluate.evaluate(tr.model, cameras, images, total, masks=val_masks)
         out.update(psnr=round(m.psnr, 4), ssim=round(m.ssim, 5), val_images=m.n_images)
         if args.gut:   # the reference's protocol above renders with the EWA rasterizer; this is the renderer the model was trained with
-            mg = evaluate.evaluate(tr.model, cameras, images, total, rasterizer="gut")
+            mg = evaluate.evaluate(tr.model, cameras, images, total, rasterizer="gut", masks=val_masks)
             out.update(psnr_gut=round(mg.psnr, 4), ssim_gut=round(mg.ssim, 5))
     if curve:
         out["psnr_curve"] = curve
