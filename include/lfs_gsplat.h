@@ -552,7 +552,9 @@ LFS_API int lfs_gut_finish_adam(
  * them, copies every parameter row source -> dead and zeroes the sources' Adam moments. Here, all on `stream`:
  *   dead_i   = sigmoid(raw_opacities_i) <= min_opacity  ||  |raw_quats_i|^2 < 1e-8
  *   source_i = inverse-CDF sample over the alive opacities with the caller's uniform number uniforms[i] in [0,1) (dead i only; fp64 prefix sums in a
- *              fixed order: the same uniforms give the same sources on every rank), count_j = how often j was drawn
+ *              fixed order: the same uniforms give the same sources on every rank), count_j = how often j was drawn. source_i = the first j with
+ *              cdf_j > uniforms[i] * total; a source is never a dead row, for any uniforms[i] in [0, 1] (whether the row found is alive is read from its
+ *              weight: a dead one - a target at the total, an ulp step of the rounded sums - gives way to the last alive row before it)
  *   for every drawn j: (opacity, scale)_j <- relocation(opacity_j, scale_j, min(count_j + 1, n_max)), opacity clamped to [min_opacity, 1 - 1e-7]
  *                      (mcmc.cpp:149-164), raw values written back; Adam moments of ALL rows[] of j zeroed (mcmc.cpp:87-111)
  *   for every dead i : every parameter row of rows[] <- the (updated) row of source_i

@@ -144,7 +144,11 @@ __global__ void __launch_bounds__(256) relocate_cdf_kernel(const uint32_t N, con
 #pragma unroll
     for (uint32_t k = 0; k < 4; ++k) { run += w[k]; if (base + k < N) cdf[base + k] = run; }
 }
-// dead i: source = first j with cdf[j] > u_i * total (never a dead j: their weight is 0, so cdf does not move across them)
+// dead i: source = first j with cdf[j] > u_i * total. In exact arithmetic that j is alive (a dead row's weight is 0, so the cdf does not move across it), and
+// the fp64 sums ARE exact while the total stays below 2^22 (fp32 weights above 2^-8: 53 bits hold every partial sum). Above that the prefix of a thread or a
+// workgroup (a Hillis-Steele tree) and the running sum of its left neighbour round differently, so cdf may step by an ulp across a dead row; and a target at or
+// above the total lands on the last row, dead or not. Whether the row found is alive is therefore decided from its weight, never from a comparison of cdf
+// values: a dead one is replaced by the last alive row before it (the first after it when there is none before). A source is never a dead row.
 __global__ void __launch_bounds__(256) relocate_sample_kernel(const uint32_t N, const float* __restrict__ raw_o, const float* __restrict__ raw_q, const float min_opacity,
                                                               const double* __restrict__ cdf, const double* __restrict__ total_p, const double* __restrict__ uniforms,
                                                               int32_t* __restrict__ source, int32_t* __restrict__ counts) {
@@ -161,8 +165,11 @@ __global__ void __launch_bounds__(256) relocate_sample_kernel(const uint32_t N, 
             const uint32_t mid = (lo + hi) >> 1;
             if (cdf[mid] > target) hi = mid; else lo = mid + 1;
         }
-        // rounding at the very end of the CDF could land on a trailing dead element: step back to the last alive one
-        while (lo > 0 && !(cdf[lo] > (lo ? cdf[lo - 1] : 0.0))) --lo;
+        const float4* q = reinterpret_cast<const float4*>(raw_q);
+        bool src_dead;
+        relocate_weight(raw_o[lo], q[lo], min_opacity, src_dead);
+        while (src_dead && lo > 0) { --lo; relocate_weight(raw_o[lo], q[lo], min_opacity, src_dead); }
+        while (src_dead && lo + 1 < N) { ++lo; relocate_weight(raw_o[lo], q[lo], min_opacity, src_dead); }   // total > 0: there is an alive row
         src = int32_t(lo);
         atomicAdd(counts + lo, 1);
     }

@@ -173,7 +173,8 @@ class MCMC(_StrategyBase):
         """Dead Gaussians (opacity <= min_opacity or a degenerate quaternion) become copies of alive ones drawn in proportion to opacity; the
         drawn sources get the relocated opacity / scale (gsplat::relocation) and zeroed Adam moments. ONE enqueue, no host round trip
         (lfs_mcmc_relocate: the reference's nonzero() / multinomial() pipeline as fixed-size device passes). The random
-        numbers come from this strategy's generator, so identically seeded replicas relocate identically. -> n_dead as a DEVICE tensor."""
+        numbers come from this strategy's generator, so identically seeded replicas relocate identically. -> n_dead as a DEVICE tensor.
+        lfs_mcmc_relocate refuses more than 2^24 rows (LfsError), whereas multinomial_sample above falls back to inverse-CDF sampling there."""
         import ctypes as C
 
         from .capi import ParamRows, check, load_library, ptr, stream, workspace
