@@ -277,6 +277,18 @@ LFS_API int lfs_fastgs_preprocess(
     const float* sh_coefficients_0, const float* sh_coefficients_rest, uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position,
     uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy, float cx, float cy, float near_plane, float far_plane,
     int64_t* n_instances, void* primitive_workspace, size_t primitive_workspace_bytes, lfs_stream_t stream);
+/* lfs_fastgs_preprocess with flags; lfs_fastgs_preprocess is flags = 0. A bit that is not defined here: LFS_E_INVALID before any launch.
+ * LFS_FASTGS_ANTIALIASED (the reference's OptimizationParameters::antialiasing, which it connects to nothing): with (a0, b, c0) the projected covariance before the
+ * 0.3 px^2 dilation and (a, b, c) after it, rho = sqrt(max(0, (a0 c0 - b^2) / (a c - b^2))) (add_blur, gsplat/Utils.cuh:171-179) and the opacity of the primitive is
+ * sigmoid(raw) * rho wherever the default mode uses sigmoid(raw): the 1/255 cut (after the cuts on sigmoid(raw), the quaternion and a c - b^2), the power threshold,
+ * the extents, the tile tests, the blend. The mode is recorded in the primitive workspace: lfs_fastgs_render and the three backward entry points take the same
+ * arguments in both modes, and the backward is the full derivative (through rho into means, scales, rotations and grad_w2c). */
+#define LFS_FASTGS_ANTIALIASED 1u
+LFS_API int lfs_fastgs_preprocess_ex(
+    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* opacities_raw,
+    const float* sh_coefficients_0, const float* sh_coefficients_rest, uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position,
+    uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy, float cx, float cy, float near_plane, float far_plane,
+    int64_t* n_instances, void* primitive_workspace, size_t primitive_workspace_bytes, uint32_t flags, lfs_stream_t stream);
 /* n_instances of this process's last lfs_fastgs_preprocess call, read back asynchronously: blocks until the 8-byte copy (queued before the SH kernel)
  * has landed, not until the stream is idle. Alternative to reading the device value with a stream synchronisation. */
 LFS_API int lfs_fastgs_wait_n_instances(int64_t* n_instances);

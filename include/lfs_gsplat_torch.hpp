@@ -108,6 +108,15 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Te
     const float center_y, const float near_plane, const float far_plane, const int n_visible_primitives, const int n_instances,
     const int n_buckets, const int primitive_primitive_indices_selector, const int instance_primitive_indices_selector);
 } // namespace fast_gs::rasterization
+namespace lfs {
+// Extension: fast_gs::rasterization::forward_wrapper with the antialiased mode (lfs_fastgs_preprocess_ex, LFS_FASTGS_ANTIALIASED) - what a trainer that honours
+// OptimizationParameters::antialiasing calls in its place. The mode is kept in per_primitive_buffers: fast_gs::rasterization::backward_wrapper serves both modes.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int> fastgs_forward_wrapper_ex(
+    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
+    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
+    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
+    const float center_y, const float near_plane, const float far_plane, const bool antialiased);
+} // namespace lfs
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> fusedssim(float C1, float C2, torch::Tensor& img1, torch::Tensor& img2, bool train);
 torch::Tensor fusedssim_backward(float C1, float C2, torch::Tensor& img1, torch::Tensor& img2, torch::Tensor& dL_dmap, torch::Tensor& dm_dmu1,

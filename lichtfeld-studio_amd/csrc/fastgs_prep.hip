@@ -34,6 +34,7 @@ struct Cov { // what forward and backward both need of a primitive's geometry
     float depth, x, y, var[3], R[3][3], RS[3][3], cov[3][3], qr, qx, qy, qz, qn;
     float qxx, qyy, qzz, qxy, qxz, qyz, qrx, qry, qrz;
     float tx, ty, j11, j13, j22, j23, jw1[3], jw2[3], jc1[3], jc2[3], a, b, c;
+    float a0, c0; // (a, c) before the dilation: the antialiased mode's compensation needs both determinants
 };
 LFS_DI void ewa(const Frame& f, const float* __restrict__ m, const float* __restrict__ rs, const float4 q, Cov& o) {
     const float* r1 = f.w2c; const float* r2 = f.w2c + 4; const float* r3 = f.w2c + 8;
@@ -68,22 +69,28 @@ LFS_DI void ewa(const Frame& f, const float* __restrict__ m, const float* __rest
         o.jc1[v] = o.jw1[0] * o.cov[0][v] + o.jw1[1] * o.cov[1][v] + o.jw1[2] * o.cov[2][v];
         o.jc2[v] = o.jw2[0] * o.cov[0][v] + o.jw2[1] * o.cov[1][v] + o.jw2[2] * o.cov[2][v];
     }
-    o.a = o.jc1[0] * o.jw1[0] + o.jc1[1] * o.jw1[1] + o.jc1[2] * o.jw1[2] + DILATION;
+    o.a0 = o.jc1[0] * o.jw1[0] + o.jc1[1] * o.jw1[1] + o.jc1[2] * o.jw1[2];
+    o.a = o.a0 + DILATION;
     o.b = o.jc1[0] * o.jw2[0] + o.jc1[1] * o.jw2[1] + o.jc1[2] * o.jw2[2];
-    o.c = o.jc2[0] * o.jw2[0] + o.jc2[1] * o.jw2[1] + o.jc2[2] * o.jw2[2] + DILATION;
+    o.c0 = o.jc2[0] * o.jw2[0] + o.jc2[1] * o.jw2[1] + o.jc2[2] * o.jw2[2];
+    o.c = o.c0 + DILATION;
 }
 
 // ---------------------------------------------------------------------------
 // forward preprocess: one thread per primitive. Per-tile counts go through an LDS histogram (one coalesced global atomic
 // per touched (workgroup, tile), see intersect.hip) when the tile grid fits.
+// AA (LFS_FASTGS_ANTIALIASED): the opacity is multiplied by rho = sqrt(max(0, det(Sigma2d) / det(Sigma2d + DILATION I))) (add_blur, gsplat/Utils.cuh:171-179) before
+// anything looks at it - the 1/255 cut, the power threshold, the extents, the tile tests and the records all see o_eff = sigmoid(raw) * rho. sigmoid(raw) is kept in
+// the record's free r1.w for the backward. Thread 0 writes the mode word of the workspace: the backward reads it there.
 // ---------------------------------------------------------------------------
-template <bool LDS_HIST>
+template <bool LDS_HIST, bool AA>
 __global__ void __launch_bounds__(1024) fg_preprocess_kernel(
     const uint32_t N, const uint32_t per_block, const float* __restrict__ means, const float* __restrict__ scales_raw, const float* __restrict__ rot_raw,
     const float* __restrict__ opac_raw, const Frame f,
     GaussRec* __restrict__ rec, float2* __restrict__ mean2d_o, float4* __restrict__ conic_opacity_o, ushort4* __restrict__ bounds_o,
-    uint32_t* __restrict__ n_touched_o, uint32_t* __restrict__ depth_bits_o, uint32_t* __restrict__ totals) {
+    uint32_t* __restrict__ n_touched_o, uint32_t* __restrict__ depth_bits_o, uint32_t* __restrict__ totals, uint32_t* __restrict__ mode_o) {
     extern __shared__ __attribute__((aligned(16))) uint32_t hist[];
+    if (blockIdx.x == 0 && threadIdx.x == 0) *mode_o = AA ? MODE_ANTIALIASED : 0u;
     const uint32_t T = f.gw * f.gh;
     if (LDS_HIST) {
         for (uint32_t t = threadIdx.x; t < T; t += blockDim.x) hist[t] = 0u;
@@ -97,14 +104,19 @@ __global__ void __launch_bounds__(1024) fg_preprocess_kernel(
             const float* r3 = f.w2c + 8;
             const float depth = r3[0] * m[0] + r3[1] * m[1] + r3[2] * m[2] + r3[3];
             if (depth < f.near_ || depth > f.far_) break;
-            const float opacity = 1.0f / (1.0f + expf(-opac_raw[i]));
-            if (opacity < MIN_ALPHA) break;
+            const float sig = 1.0f / (1.0f + expf(-opac_raw[i]));
+            if (sig < MIN_ALPHA) break;
             const float4 q = reinterpret_cast<const float4*>(rot_raw)[i];
             if (q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w < 1e-8f) break;
             Cov cv;
             ewa(f, m, scales_raw + 3 * size_t(i), q, cv);
             const float det = cv.a * cv.c - cv.b * cv.b;
             if (det < 1e-8f) break;
+            float opacity = sig;
+            if constexpr (AA) {
+                opacity = sig * sqrtf(fmaxf(0.f, (cv.a0 * cv.c0 - cv.b * cv.b) / det));
+                if (opacity < MIN_ALPHA) break;
+            }
             const float ca = cv.c / det, cb = -cv.b / det, cc = cv.a / det;
             const float mx = cv.x * f.fx + f.cx, my = cv.y * f.fy + f.cy;
             const float power_threshold = logf(opacity * MIN_ALPHA_RCP);
@@ -125,7 +137,7 @@ __global__ void __launch_bounds__(1024) fg_preprocess_kernel(
             // (r2 = max(SH colour + 0.5, 0) is filled in by the SH kernel of sh.hip right after this one)
             float4* r = reinterpret_cast<float4*>(rec + i);
             r[0] = make_float4(mx, my, 0.5f * LOG2E * ca, LOG2E * cb);
-            r[1] = make_float4(0.5f * LOG2E * cc, LOG2E * power_threshold, opacity, 0.f);
+            r[1] = make_float4(0.5f * LOG2E * cc, LOG2E * power_threshold, opacity, AA ? sig : 0.f);
             mean2d_o[i] = make_float2(mx, my);
             conic_opacity_o[i] = make_float4(ca, cb, cc, opacity);
             bounds_o[i] = make_ushort4(uint16_t(x0), uint16_t(x1), uint16_t(y0), uint16_t(y1));
@@ -197,6 +209,10 @@ LFS_DI void preprocess_bwd_zero_rows(const uint32_t i, float* __restrict__ g_mea
 }
 
 // one visible primitive; dcam = dL/d(mean in camera space) (kernels_backward.cuh:165-168), which the camera gradient below is made of
+// AA: the record's opacity is o_eff = sigmoid(raw) * rho, so the accumulator's S = sum alpha dL/dalpha is o_eff dL/do_eff: dL/draw = S (1 - sigmoid(raw)) with the
+// sigmoid from r1.w, and dL/drho = S / rho reaches the 2-D covariance through rho^2 = det0 / det1: dL/d(a0, b, c0) += S/2 (c0/det0 - c/det1, 2b (1/det1 - 1/det0),
+// a0/det0 - a/det1) - no division by rho (a visible primitive has rho >= 1/255, hence det0 > 0). Everything below dcv is the code both modes share.
+template <bool AA>
 LFS_DI void preprocess_bwd_one(
     const uint32_t i, const uint32_t N, const float* __restrict__ means, const float* __restrict__ scales_raw, const float* __restrict__ rot_raw,
     const Frame& f, const GaussRec* __restrict__ rec, const float4* __restrict__ conic_opacity, const float* __restrict__ acc,
@@ -210,7 +226,7 @@ LFS_DI void preprocess_bwd_one(
     const float4 co = conic_opacity[i];
     const float dm2[2] = {co.x * a0.x + co.y * a0.y, co.y * a0.x + co.z * a0.y};
     const float dcon[3] = {0.5f * a0.z, 0.5f * a0.w, 0.5f * a1.x};
-    const float opacity = r.r1.z;
+    const float opacity = AA ? r.r1.w : r.r1.z;   // sigmoid(raw)
     g_opac_raw[i] = a2.x * (1.0f - opacity);
     const float* m = means + 3 * size_t(i);
     const float dpos[3] = {0.f, 0.f, 0.f}; // (the colour -> position term is added by the SH backward kernel of sh.hip, which runs after this one)
@@ -221,9 +237,15 @@ LFS_DI void preprocess_bwd_one(
     const float* r1 = f.w2c; const float* r2 = f.w2c + 4; const float* r3 = f.w2c + 8;
     const float A = cv.a, B = cv.b, C = cv.c;
     const float det = A * C - B * B, dr = 1.0f / det, dr2 = dr * dr;
-    const float dcv[3] = {dr2 * (2.0f * B * C * dcon[1] - C * C * dcon[0] - B * B * dcon[2]),
-                          dr2 * (B * C * dcon[0] - (A * C + B * B) * dcon[1] + A * B * dcon[2]),
-                          dr2 * (2.0f * A * B * dcon[1] - B * B * dcon[0] - A * A * dcon[2])};
+    float dcv[3] = {dr2 * (2.0f * B * C * dcon[1] - C * C * dcon[0] - B * B * dcon[2]),
+                    dr2 * (B * C * dcon[0] - (A * C + B * B) * dcon[1] + A * B * dcon[2]),
+                    dr2 * (2.0f * A * B * dcon[1] - B * B * dcon[0] - A * A * dcon[2])};
+    if constexpr (AA) {   // (dcv[1] is half of dL/db: b enters G twice)
+        const float hs = 0.5f * a2.x, dr0 = 1.0f / (cv.a0 * cv.c0 - B * B);
+        dcv[0] += hs * (cv.c0 * dr0 - C * dr);
+        dcv[1] += hs * B * (dr - dr0);
+        dcv[2] += hs * (cv.a0 * dr0 - A * dr);
+    }
     float G[3][3];
 #pragma unroll
     for (int u = 0; u < 3; ++u)
@@ -288,25 +310,27 @@ LFS_DI float block_sum12(float (&v)[W2C_VALS], float (*s_part)[W2C_VALS]) {
 // kernels_backward.cuh:165-183) additionally sums, over the primitives with n_touched > 0, grad_w2c[r][c] += dcam[r] * mean[c], grad_w2c[r][3] += dcam[r]:
 // no lane leaves before the workgroup sum (rows past N and invisible primitives take part with dcam = 0), and the workgroup's 12 sums go to
 // w2c_partials[blockIdx.x * 12 ..] with plain stores; fg_w2c_reduce_kernel adds the rows up.
-template <bool W2C>
+// AA: the instantiation for the antialiased mode. The launcher queues both; the one that does not match the mode word the forward left in the workspace returns at once.
+template <bool W2C, bool AA>
 __global__ void __launch_bounds__(256) fg_preprocess_bwd_kernel(
     const uint32_t N, const float* __restrict__ means, const float* __restrict__ scales_raw, const float* __restrict__ rot_raw,
     const Frame f, const GaussRec* __restrict__ rec, const float4* __restrict__ conic_opacity,
     const uint32_t* __restrict__ n_touched, const float* __restrict__ acc, float* __restrict__ g_means, float* __restrict__ g_scales_raw, float* __restrict__ g_rot_raw,
-    float* __restrict__ g_opac_raw, float* __restrict__ densification_info, float* __restrict__ w2c_partials) {
+    float* __restrict__ g_opac_raw, float* __restrict__ densification_info, float* __restrict__ w2c_partials, const uint32_t* __restrict__ mode) {
+    if (((*mode & MODE_ANTIALIASED) != 0u) != AA) return;   // (uniform: before any barrier)
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if constexpr (!W2C) {   // the kernel as it was: the same early returns, no operand of the sum below exists
         if (i >= N) return;
         if (n_touched[i] == 0) { preprocess_bwd_zero_rows(i, g_means, g_scales_raw, g_rot_raw, g_opac_raw); return; }
         float dcam[3];
-        preprocess_bwd_one(i, N, means, scales_raw, rot_raw, f, rec, conic_opacity, acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, dcam);
+        preprocess_bwd_one<AA>(i, N, means, scales_raw, rot_raw, f, rec, conic_opacity, acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, dcam);
     } else {
         __shared__ float s_part[4][W2C_VALS];
         float dcam[3] = {0.f, 0.f, 0.f}, m[3] = {0.f, 0.f, 0.f};
         bool visible = i < N;
         if (visible && n_touched[i] == 0) { preprocess_bwd_zero_rows(i, g_means, g_scales_raw, g_rot_raw, g_opac_raw); visible = false; }
         if (visible) {
-            preprocess_bwd_one(i, N, means, scales_raw, rot_raw, f, rec, conic_opacity, acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, dcam);
+            preprocess_bwd_one<AA>(i, N, means, scales_raw, rot_raw, f, rec, conic_opacity, acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, dcam);
             m[0] = means[3 * size_t(i)]; m[1] = means[3 * size_t(i) + 1]; m[2] = means[3 * size_t(i) + 2];
         }
         float v[W2C_VALS];
@@ -362,13 +386,13 @@ int launch_preprocess_bwd(uint32_t N, const float* means, const float* scales_ra
                           float* g_means, float* g_scales_raw, float* g_rot_raw, float* g_opac_raw, float* g_sh0, float* g_sh_rest, float* densification_info, hipStream_t s,
                           const ShAdamArgs* adam, float* grad_w2c, float* w2c_partials) {
     {
+        // the mode of the forward that filled this workspace is a word IN the workspace, which the host does not read: both instantiations are queued, one returns at once
         lfs::ProfScope prof("fastgs_preprocess_bwd", s);
-        if (grad_w2c != nullptr)
-            hipLaunchKernelGGL(fg_preprocess_bwd_kernel<true>, dim3((N + 255) / 256), dim3(256), 0, s, N, means, scales_raw, rot_raw, f, w.rec, w.conic_opacity, w.n_touched, w.acc,
-                               g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, w2c_partials);
-        else
-            hipLaunchKernelGGL(fg_preprocess_bwd_kernel<false>, dim3((N + 255) / 256), dim3(256), 0, s, N, means, scales_raw, rot_raw, f, w.rec, w.conic_opacity, w.n_touched, w.acc,
-                               g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, static_cast<float*>(nullptr));
+#define LFS_FG_PREP_BWD(W2C, AA, PARTIALS) hipLaunchKernelGGL((fg_preprocess_bwd_kernel<W2C, AA>), dim3((N + 255) / 256), dim3(256), 0, s, N, means, scales_raw, rot_raw, f, w.rec, \
+                                                              w.conic_opacity, w.n_touched, w.acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, PARTIALS, w.mode)
+        if (grad_w2c != nullptr) { LFS_FG_PREP_BWD(true, false, w2c_partials); LFS_FG_PREP_BWD(true, true, w2c_partials); }
+        else { LFS_FG_PREP_BWD(false, false, static_cast<float*>(nullptr)); LFS_FG_PREP_BWD(false, true, static_cast<float*>(nullptr)); }
+#undef LFS_FG_PREP_BWD
     }
     if (grad_w2c != nullptr) {
         const int rc = launch_w2c_reduce(N, w2c_partials, grad_w2c, s);
@@ -419,11 +443,15 @@ extern "C" size_t lfs_fastgs_instance_workspace_bytes(uint32_t width, uint32_t h
     return n_instances < 0 ? 0 : fgs::inst_ws(nullptr, width, height, uint64_t(n_instances)).bytes;
 }
 
-extern "C" int lfs_fastgs_preprocess(
+// flags bit 0 (LFS_FASTGS_ANTIALIASED): the antialiased mode of fg_preprocess_kernel. The mode is recorded in the primitive workspace (PrimWs::mode), rewritten by
+// every call with N > 0; render and the backward entry points need no flag.
+extern "C" int lfs_fastgs_preprocess_ex(
     uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* opacities_raw,
     const float* sh_coefficients_0, const float* sh_coefficients_rest, uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position,
     uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy, float cx, float cy, float near_plane, float far_plane,
-    int64_t* n_instances, void* primitive_workspace, size_t primitive_workspace_bytes, lfs_stream_t stream) {
+    int64_t* n_instances, void* primitive_workspace, size_t primitive_workspace_bytes, uint32_t flags, lfs_stream_t stream) {
+    if (flags & ~uint32_t(LFS_FASTGS_ANTIALIASED)) return LFS_E_INVALID;
+    const bool aa = (flags & LFS_FASTGS_ANTIALIASED) != 0;
     if (!n_instances || !primitive_workspace || !w2c || !cam_position || width == 0 || height == 0) return LFS_E_INVALID;
     if (active_sh_bases == 0 || active_sh_bases > 16 || (active_sh_bases > 1 && total_bases_sh_rest + 1 < active_sh_bases)) return LFS_E_INVALID;
     fgs::PrimWs w = fgs::prim_ws(primitive_workspace, N, width, height);
@@ -440,12 +468,12 @@ extern "C" int lfs_fastgs_preprocess(
         lfs::ProfScope prof("fastgs_preprocess", s);
         if (N > 0) {
             const uint32_t pb = fgs::per_block_for(N), blocks = (N + pb - 1) / pb;
-            if (size_t(T) * 8 <= 64 * 1024)
-                hipLaunchKernelGGL(fgs::fg_preprocess_kernel<true>, dim3(blocks), dim3(1024), size_t(T) * 4, s, N, pb, means, scales_raw, rotations_raw, opacities_raw,
-                                   f, w.rec, w.mean2d, w.conic_opacity, w.bounds, w.n_touched, w.depth_bits, w.totals);
-            else
-                hipLaunchKernelGGL(fgs::fg_preprocess_kernel<false>, dim3(blocks), dim3(1024), 0, s, N, pb, means, scales_raw, rotations_raw, opacities_raw,
-                                   f, w.rec, w.mean2d, w.conic_opacity, w.bounds, w.n_touched, w.depth_bits, w.totals);
+            const bool lds = size_t(T) * 8 <= 64 * 1024;
+#define LFS_FG_PREP(LDS, AA) hipLaunchKernelGGL((fgs::fg_preprocess_kernel<LDS, AA>), dim3(blocks), dim3(1024), LDS ? size_t(T) * 4 : size_t(0), s, N, pb, means, scales_raw, \
+                                                rotations_raw, opacities_raw, f, w.rec, w.mean2d, w.conic_opacity, w.bounds, w.n_touched, w.depth_bits, w.totals, w.mode)
+            if (lds) { if (aa) LFS_FG_PREP(true, true); else LFS_FG_PREP(true, false); }
+            else { if (aa) LFS_FG_PREP(false, true); else LFS_FG_PREP(false, false); }
+#undef LFS_FG_PREP
         }
         hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, s, T, w.totals, w.offsets, n_instances);
     }
@@ -465,4 +493,13 @@ extern "C" int lfs_fastgs_preprocess(
         if (rc) return rc;
     }
     return (int)hipGetLastError();
+}
+
+extern "C" int lfs_fastgs_preprocess(
+    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* opacities_raw,
+    const float* sh_coefficients_0, const float* sh_coefficients_rest, uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position,
+    uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy, float cx, float cy, float near_plane, float far_plane,
+    int64_t* n_instances, void* primitive_workspace, size_t primitive_workspace_bytes, lfs_stream_t stream) {
+    return lfs_fastgs_preprocess_ex(N, means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, total_bases_sh_rest, w2c, cam_position,
+                                    active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane, n_instances, primitive_workspace, primitive_workspace_bytes, 0u, stream);
 }

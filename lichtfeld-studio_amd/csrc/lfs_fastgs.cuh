@@ -22,6 +22,7 @@ constexpr float MAX_ALPHA = 0.999f;
 constexpr float T_THRESHOLD = 1e-4f;
 constexpr uint32_t TILE = 16;
 constexpr float LOG2E = 1.4426950408889634f;
+constexpr uint32_t MODE_ANTIALIASED = 1u; // PrimWs::mode bit 0 (= LFS_FASTGS_ANTIALIASED of lfs_fastgs_preprocess_ex)
 
 struct Frame { // one camera; w2c / cam_position stay device pointers (torch tensors of the caller)
     const float* w2c; const float* cam_pos;
@@ -35,9 +36,12 @@ inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 //   rec[N]   64-B blend record: r0 = {mean2d.x, mean2d.y, A, B}, r1 = {C, thr', opacity, -}, r2 = {max(colour, 0), -},
 //            r3 unused; with (A, B, C) = log2(e) * (conic.x / 2, conic.y, conic.z / 2) and thr' = log2(e) *
 //            log(255 * opacity): sigma' = A dx^2 + B dx dy + C dy^2 is the Gaussian exponent in bits (one v_exp_f32).
+//            Antialiased mode: opacity = sigmoid(raw) * rho everywhere, and r1.w = sigmoid(raw) for the backward.
+//   mode     one word of the (otherwise spare) 256-byte n_instances slot: the flags of the preprocess that filled the workspace. The backward picks its
+//            instantiation by it on the device, so the backward entry points carry no flag and nothing outside the workspace remembers the mode.
 struct PrimWs {
     GaussRec* rec; float2* mean2d; float4* conic_opacity; ushort4* bounds; uint32_t* n_touched; uint32_t* depth_bits;
-    uint32_t* totals; uint32_t* cursor; int32_t* offsets; int64_t* n_instances; int32_t* n_contrib; float* acc; unsigned long long* det64; size_t bytes;
+    uint32_t* totals; uint32_t* cursor; int32_t* offsets; int64_t* n_instances; uint32_t* mode; int32_t* n_contrib; float* acc; unsigned long long* det64; size_t bytes;
 };
 // det (lfs_set_debug_flags bit 4, the deterministic backward): one int64 accumulator row per primitive behind everything else, so the other pointers do not move.
 // The size query and the backward ask for it; preprocess and render neither need nor check it.
@@ -53,7 +57,7 @@ inline PrimWs prim_ws(void* base, uint32_t N, uint32_t width, uint32_t height, b
     w.totals = (uint32_t*)(p + o); o += align256(4 * T);
     w.cursor = (uint32_t*)(p + o); o += align256(4 * T);
     w.offsets = (int32_t*)(p + o); o += align256(4 * (T + 1));
-    w.n_instances = (int64_t*)(p + o); o += 256;
+    w.n_instances = (int64_t*)(p + o); w.mode = (uint32_t*)(p + o) + 2; o += 256;
     w.n_contrib = (int32_t*)(p + o); o += align256(4 * P);
     w.acc = (float*)(p + o); o += align256(sizeof(float) * ACC_STRIDE * N);
     w.det64 = nullptr;

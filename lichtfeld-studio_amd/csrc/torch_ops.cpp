@@ -527,12 +527,13 @@ torch::Tensor GutTrainStep::radii() const {
 // ---------------------------------------------------------------------------------------------------------
 // fast_gs::rasterization (rasterization_api.h:27-75, src/rasterization_api.cu) and fusedssim (ssim.cuh:11-30)
 // ---------------------------------------------------------------------------------------------------------
+// the forward of both modes; the mode lives in per_primitive_buffers from here on, so backward_wrapper below serves either
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int>
-fast_gs::rasterization::forward_wrapper(
+lfs::fastgs_forward_wrapper_ex(
     const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
     const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
     const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane) {
+    const float center_y, const float near_plane, const float far_plane, const bool antialiased) {
     LFS_DEVICE_GUARD(means);
     LFS_CHECK_INPUT(means); LFS_CHECK_INPUT(scales_raw); LFS_CHECK_INPUT(rotations_raw); LFS_CHECK_INPUT(opacities_raw);
     LFS_CHECK_INPUT(sh_coefficients_0); LFS_CHECK_INPUT(sh_coefficients_rest);
@@ -542,17 +543,27 @@ fast_gs::rasterization::forward_wrapper(
     at::Tensor image = at::empty({3, height, width}, fopt), alpha = at::empty({1, height, width}, fopt);
     at::Tensor prim = at::empty({(int64_t)lfs_fastgs_primitive_workspace_bytes(N, (uint32_t)width, (uint32_t)height)}, bopt);
     at::Tensor n_inst_dev = at::zeros({1}, means.options().dtype(at::kLong));
-    check_rc(lfs_fastgs_preprocess(N, means.data_ptr<float>(), scales_raw.data_ptr<float>(), rotations_raw.data_ptr<float>(), opacities_raw.data_ptr<float>(),
-                                   sh_coefficients_0.data_ptr<float>(), total_rest ? sh_coefficients_rest.data_ptr<float>() : nullptr, total_rest,
-                                   w2c_c.data_ptr<float>(), cam_c.data_ptr<float>(), (uint32_t)active_sh_bases, (uint32_t)width, (uint32_t)height,
-                                   focal_x, focal_y, center_x, center_y, near_plane, far_plane, n_inst_dev.data_ptr<int64_t>(), prim.data_ptr(),
-                                   (size_t)prim.numel(), cur_stream()), "fast_gs::rasterization::forward (preprocess)");
+    check_rc(lfs_fastgs_preprocess_ex(N, means.data_ptr<float>(), scales_raw.data_ptr<float>(), rotations_raw.data_ptr<float>(), opacities_raw.data_ptr<float>(),
+                                      sh_coefficients_0.data_ptr<float>(), total_rest ? sh_coefficients_rest.data_ptr<float>() : nullptr, total_rest,
+                                      w2c_c.data_ptr<float>(), cam_c.data_ptr<float>(), (uint32_t)active_sh_bases, (uint32_t)width, (uint32_t)height,
+                                      focal_x, focal_y, center_x, center_y, near_plane, far_plane, n_inst_dev.data_ptr<int64_t>(), prim.data_ptr(),
+                                      (size_t)prim.numel(), antialiased ? LFS_FASTGS_ANTIALIASED : 0u, cur_stream()), "fast_gs::rasterization::forward (preprocess)");
     const int64_t n_instances = n_inst_dev.item<int64_t>(); // the host sync of forward.cu:114-117
     at::Tensor inst = at::empty({(int64_t)std::max<size_t>(256, lfs_fastgs_instance_workspace_bytes((uint32_t)width, (uint32_t)height, n_instances))}, bopt);
     check_rc(lfs_fastgs_render(N, (uint32_t)width, (uint32_t)height, n_instances, prim.data_ptr(), (size_t)prim.numel(), inst.data_ptr(), (size_t)inst.numel(),
                                image.data_ptr<float>(), alpha.data_ptr<float>(), cur_stream()), "fast_gs::rasterization::forward (render)");
     at::Tensor none = at::empty({0}, bopt);
     return {image, alpha, prim, none, inst, none.clone(), 0, (int)n_instances, 0, 0, 0};
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int>
+fast_gs::rasterization::forward_wrapper(
+    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
+    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
+    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
+    const float center_y, const float near_plane, const float far_plane) {
+    return lfs::fastgs_forward_wrapper_ex(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c, cam_position, active_sh_bases,
+                                          width, height, focal_x, focal_y, center_x, center_y, near_plane, far_plane, false);
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>

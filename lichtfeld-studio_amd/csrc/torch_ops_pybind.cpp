@@ -57,6 +57,13 @@ PYBIND11_MODULE(_lfs_torch_ops, m) {
               return fast_gs::rasterization::forward_wrapper(means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest, w2c, cam_position,
                                                              active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane);
           });
+    m.def("fastgs_forward_wrapper_ex",
+          [](at::Tensor means, at::Tensor scales_raw, at::Tensor rotations_raw, at::Tensor opacities_raw, at::Tensor sh0, at::Tensor sh_rest, at::Tensor w2c,
+             at::Tensor cam_position, int active_sh_bases, int width, int height, float fx, float fy, float cx, float cy, float near_plane, float far_plane,
+             bool antialiased) {
+              return lfs::fastgs_forward_wrapper_ex(means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest, w2c, cam_position,
+                                                    active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane, antialiased);
+          });
     m.def("fastgs_backward_wrapper",
           [](at::Tensor densification_info, at::Tensor grad_image, at::Tensor grad_alpha, at::Tensor image, at::Tensor alpha, at::Tensor means,
              at::Tensor scales_raw, at::Tensor rotations_raw, at::Tensor sh_rest, at::Tensor prim, at::Tensor tile, at::Tensor inst, at::Tensor bucket,

@@ -30,8 +30,10 @@ class FastGSSettings:  # rasterization_api.h:12-24
     center_y: float
     near_plane: float
     far_plane: float
+    antialiased: bool = False   # opacity * sqrt(det(Sigma2d) / det(Sigma2d + 0.3 I)) (LFS_FASTGS_ANTIALIASED; the reference's OptimizationParameters::antialiasing)
 
 
+ANTIALIASED = 1         # LFS_FASTGS_ANTIALIASED
 ASYNC_READBACK = True   # False: n_instances via a stream synchronisation (A/B timing)
 
 
@@ -41,7 +43,8 @@ def _frame_args(s: FastGSSettings):
 
 
 def forward_wrapper(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c, s: FastGSSettings):
-    """-> (image [3,H,W], alpha [1,H,W], primitive_workspace, instance_workspace, n_instances)."""
+    """-> (image [3,H,W], alpha [1,H,W], primitive_workspace, instance_workspace, n_instances). s.antialiased: the antialiased mode; the primitive workspace
+    remembers it, so backward_wrapper takes the same arguments in both modes."""
     w2c = w2c.reshape(-1, 4, 4)[0].contiguous()
     cam_position = s.cam_position.reshape(-1)[:3].contiguous()
     opac = opacities_raw.reshape(-1)
@@ -56,8 +59,13 @@ def forward_wrapper(means, scales_raw, rotations_raw, opacities_raw, sh_coeffici
     lib, dev = load_library(), means.device
     pws = torch.empty(lib.lfs_fastgs_primitive_workspace_bytes(C.c_uint32(N), C.c_uint32(s.width), C.c_uint32(s.height)), dtype=torch.uint8, device=dev)
     n_inst_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-    check(lib.lfs_fastgs_preprocess(C.c_uint32(N), ptr(means), ptr(scales_raw), ptr(rotations_raw), ptr(opac), ptr(sh0), ptr(shr), C.c_uint32(total_rest),
-                                    ptr(w2c), ptr(cam_position), *_frame_args(s), ptr(n_inst_dev), ptr(pws), C.c_size_t(pws.numel()), stream()), "fastgs_preprocess")
+    if s.antialiased:
+        check(lib.lfs_fastgs_preprocess_ex(C.c_uint32(N), ptr(means), ptr(scales_raw), ptr(rotations_raw), ptr(opac), ptr(sh0), ptr(shr), C.c_uint32(total_rest),
+                                           ptr(w2c), ptr(cam_position), *_frame_args(s), ptr(n_inst_dev), ptr(pws), C.c_size_t(pws.numel()), C.c_uint32(ANTIALIASED),
+                                           stream()), "fastgs_preprocess_ex")
+    else:
+        check(lib.lfs_fastgs_preprocess(C.c_uint32(N), ptr(means), ptr(scales_raw), ptr(rotations_raw), ptr(opac), ptr(sh0), ptr(shr), C.c_uint32(total_rest),
+                                        ptr(w2c), ptr(cam_position), *_frame_args(s), ptr(n_inst_dev), ptr(pws), C.c_size_t(pws.numel()), stream()), "fastgs_preprocess")
     # the one host sync (forward.cu:114-117 reads n_visible_primitives and n_instances): waits for the read-back event the library queued before
     # its SH kernel, so the GPU keeps working through the host round trip
     if ASYNC_READBACK:
@@ -155,15 +163,15 @@ class FastGSRasterize(torch.autograd.Function):
         return g[0], g[1], g[2], g[3].reshape(opac_shape), g[4], g[5], g_w2c, None, None
 
 
-def fast_rasterize(camera: Camera, model: SplatModel, bg_color: torch.Tensor, densification_info: Optional[torch.Tensor] = None) -> RenderOutput:
-    """fast_rasterizer.cpp:12-68"""
+def fast_rasterize(camera: Camera, model: SplatModel, bg_color: torch.Tensor, densification_info: Optional[torch.Tensor] = None, antialiased: bool = False) -> RenderOutput:
+    """fast_rasterizer.cpp:12-68; antialiased: FastGSSettings.antialiased (an extension: the reference's fast_rasterize has no such argument)"""
     W, H = int(camera.image_width), int(camera.image_height)
     K = camera.K.reshape(-1, 3, 3)[0]
     w2c = camera.world_view_transform
     R, t = w2c.reshape(-1, 4, 4)[0][:3, :3], w2c.reshape(-1, 4, 4)[0][:3, 3]
     deg = model.get_active_sh_degree()
     settings = FastGSSettings(cam_position=(-(R.T @ t)).contiguous(), active_sh_bases=(deg + 1) ** 2, width=W, height=H,
-                              focal_x=float(K[0, 0]), focal_y=float(K[1, 1]), center_x=float(K[0, 2]), center_y=float(K[1, 2]), near_plane=0.01, far_plane=1e10)
+                              focal_x=float(K[0, 0]), focal_y=float(K[1, 1]), center_x=float(K[0, 2]), center_y=float(K[1, 2]), near_plane=0.01, far_plane=1e10, antialiased=bool(antialiased))
     image, alpha = FastGSRasterize.apply(model.means, model.raw_scales, model.raw_quats, model.raw_opacities, model.sh0, model.shN, w2c, densification_info, settings)
     image = image + (1.0 - alpha) * bg_color.view(3, 1, 1)
     return RenderOutput(image=image, alpha=alpha, depth=None, means2d=None, depths=None, radii=None, visibility=None, width=W, height=H, n_isects=0)

@@ -88,7 +88,7 @@ class GutTrainer:
                  use_bilateral_grid: bool = False, bilateral_grid_dims=(16, 16, 8), bilateral_grid_lr: float = 2e-3, tv_loss_weight: float = 10.0,
                  sh_sharded: Optional[bool] = None, factored_sh: bool = False, one_call: bool = False, pose_optimization: str = "none", pose_lr: float = 1e-5,
                  enable_sparsity: bool = False, sparsify_steps: int = 15000, init_rho: float = 0.0005, prune_ratio: float = 0.6, sparsity_update_every: int = 50,
-                 mask_mode: str = "none", mask_alpha_weight: float = 1.0):
+                 mask_mode: str = "none", mask_alpha_weight: float = 1.0, antialiasing: bool = False):
         """strategy: None (fixed set of Gaussians: the benchmark), "mcmc" (strategies.MCMC: relocation + growth + SGLD noise, with
         the scale / opacity regularisers of trainer.cpp:132-158) or "default" (ADC; needs densification_info, see strategies.py).
         `seed` seeds the strategy's generator: the same on every rank, so replicas densify identically.
@@ -103,7 +103,13 @@ class GutTrainer:
         is the length of the whole run. The learning-rate schedule stays the base run's.
         mask_mode: "none" | "ignore" | "segment" (DESIGN.md 8 "Masked training"): what train_step(masks=...) does with a view's mask. "ignore": the loss weights every
         pixel by its mask byte (the masked loss kernels). "segment": additionally the rendered opacity outside the mask is penalised with mask_alpha_weight (L1 + D-SSIM
-        on the fastgs rasterizer, whose backward takes an alpha gradient; the autograd form of the 3DGUT rasterizer as well)."""
+        on the fastgs rasterizer, whose backward takes an alpha gradient; the autograd form of the 3DGUT rasterizer as well).
+        antialiasing (OptimizationParameters::antialiasing; DESIGN.md 8f): every fastgs render of the trainer runs in the antialiased mode (FastGSSettings.antialiased).
+        fastgs rasterizer only."""
+        if antialiasing and rasterizer == "gut":
+            raise ValueError("antialiasing is not wired into the 3DGUT route (rasterizer='gut'): its fused and autograd steps render without the opacity compensation. "
+                             "Use rasterizer='fastgs'.")
+        self.antialiasing = bool(antialiasing)
         if mask_mode not in ("none", "ignore", "segment"):
             raise ValueError(f"Invalid mask mode: {mask_mode}")
         if mask_mode == "segment":
@@ -306,7 +312,7 @@ class GutTrainer:
             w2c = sc.viewmats[view]
             cam_pos = (-(w2c[:3, :3].T @ w2c[:3, 3])).contiguous()
             deg = self.model.get_active_sh_degree()
-            st = FastGSSettings(cam_pos, (deg + 1) ** 2, sc.width, sc.height, float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), 0.01, 1e10)
+            st = FastGSSettings(cam_pos, (deg + 1) ** 2, sc.width, sc.height, float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), 0.01, 1e10, self.antialiasing)
             self._fg_settings[view] = st
         st.active_sh_bases = (self.model.get_active_sh_degree() + 1) ** 2
         return st

@@ -49,7 +49,10 @@ def main():
     ap.add_argument("--invert-masks", action="store_true", help="the mask files mark what to IGNORE (white = ignored)")
     ap.add_argument("--mask-threshold", type=int, default=-1, help="binarise: mask byte >= N counts fully, below it not at all (default: keep soft values)")
     ap.add_argument("--mask-alpha-weight", type=float, default=1.0, help="weight of the opacity penalty of --mask-mode segment")
+    ap.add_argument("--antialiasing", action="store_true", help="antialiased mode of the EWA rasterizer for training and --eval renders (the reference's antialiasing parameter)")
     args = ap.parse_args()
+    if args.antialiasing and args.gut:
+        raise SystemExit("--antialiasing is not wired into the 3DGUT route. Please disable antialiasing or disable gut.")
     if args.pose_optimization != "none" and args.eval:   # trainer.cpp:367-370
         raise SystemExit("Evaluating with pose optimization is not supported yet. Please disable pose optimization or evaluation.")
 
@@ -76,7 +79,7 @@ def main():
     tr = GutTrainer(scene, dev, iterations=args.iterations, loss="l1_ssim", strategy=None if args.strategy == "none" else args.strategy, opt_params=op,
                     scene_scale=scene_scale, rasterizer=rast, use_bilateral_grid=args.bilateral_grid, pose_optimization=args.pose_optimization,
                     enable_sparsity=args.enable_sparsity, sparsify_steps=args.sparsify_steps, init_rho=args.init_rho, prune_ratio=args.prune_ratio,
-                    mask_mode=args.mask_mode, mask_alpha_weight=args.mask_alpha_weight)
+                    mask_mode=args.mask_mode, mask_alpha_weight=args.mask_alpha_weight, antialiasing=args.antialiasing)
     total = tr.total_iterations                                             # --iterations, plus the sparsification phase
     os.makedirs(args.output_path, exist_ok=True)
     g = torch.Generator().manual_seed(0)
@@ -104,12 +107,12 @@ def main():
             loader.save_ply(tr.model, os.path.join(args.output_path, f"splat_{args.iterations}.ply"))
         if val_set is not None and (it + 1) % args.eval_every == 0:
             torch.cuda.synchronize(); te = time.time()
-            m = evaluate.evaluate(tr.model, val_set[0], val_set[1], it + 1, rasterizer=rast if args.gut else "fastgs")
+            m = evaluate.evaluate(tr.model, val_set[0], val_set[1], it + 1, rasterizer=rast if args.gut else "fastgs", antialiased=args.antialiasing)
             # the same metric on 12 TRAINING views: a held-out PSNR that falls while this one holds is a generalisation gap (Gaussians fitted to the rays the training views
             # sample), both falling is an unstable optimisation
             tsel = list(range(0, len(ds), max(1, len(ds) // 12)))[:12]
             tcams = [tr.camera(v) for v in tsel]
-            mt = evaluate.evaluate(tr.model, tcams, [targets[v] for v in tsel], it + 1, rasterizer=rast if args.gut else "fastgs")
+            mt = evaluate.evaluate(tr.model, tcams, [targets[v] for v in tsel], it + 1, rasterizer=rast if args.gut else "fastgs", antialiased=args.antialiasing)
             s3 = tr.model.raw_scales.detach()
             asp = (s3.max(-1).values - s3.min(-1).values).exp()
             # projected size of the SMALLEST axis of every Gaussian in pixels at the first training camera (focal length x scale / depth): the share below half a pixel
@@ -126,7 +129,7 @@ def main():
     torch.cuda.synchronize()
     t_train = time.time() - t0 - t_eval
     out = {"data": args.data_path, "images": len(ds), "size": [scene.width, scene.height], "iterations": total, "rasterizer": rast,
-           "strategy": args.strategy, "pose_optimization": args.pose_optimization, "gaussians": int(tr.model.means.shape[0]), "load_s": round(t_load, 1), "train_s": round(t_train, 1),
+           "strategy": args.strategy, "antialiasing": bool(args.antialiasing), "pose_optimization": args.pose_optimization, "gaussians": int(tr.model.means.shape[0]), "load_s": round(t_load, 1), "train_s": round(t_train, 1),
            "iters_per_s": round(total / max(t_train, 1e-9), 1)}
     if masks is not None:
         out.update(mask_mode=args.mask_mode, masked_views=sum(m is not None for m in masks))
@@ -142,7 +145,7 @@ def main():
             h, w = img.shape[1:]
             cameras.append(Camera(torch.from_numpy(loader.world_to_view(cam))[None].to(dev), torch.from_numpy(loader.intrinsics(cam, w, h))[None].to(dev), w, h))
             images.append(img)
-        m = evaluate.evaluate(tr.model, cameras, images, total, masks=val_masks)
+        m = evaluate.evaluate(tr.model, cameras, images, total, masks=val_masks, antialiased=args.antialiasing)
         out.update(psnr=round(m.psnr, 4), ssim=round(m.ssim, 5), val_images=m.n_images)
         if args.gut:   # the reference's protocol above renders with the EWA rasterizer; this is the renderer the model was trained with
             mg = evaluate.evaluate(tr.model, cameras, images, total, rasterizer="gut", masks=val_masks)
