@@ -390,6 +390,12 @@ LFS_API int lfs_bilateral_slice_fwd(uint32_t L, uint32_t H, uint32_t W, uint32_t
 LFS_API int lfs_bilateral_slice_bwd(uint32_t L, uint32_t H, uint32_t W, uint32_t h, uint32_t w, const float* grid, const float* rgb,
                                     const float* grad_output, uint32_t chw, uint32_t clamp_input, float* grad_grid, float* grad_rgb,
                                     lfs_stream_t stream);
+/* Pure host, no launch: which kernels lfs_bilateral_slice_fwd / _bwd run for this shape (both take their decision from this function).
+ *   out[0] forward path: 0 generic (grid read from global memory), 1 LDS value window;   out[1] worst-case forward window, in floats
+ *   out[2] backward path: 0 generic (global float atomics per pixel), 1 windowed (MFMA); out[3] dynamic LDS the windowed kernel would need, in bytes
+ *   out[4] bound on the windowed backward's 16-column tiles: ceil(x-extent of a 64-pixel strip's window * L / 16)
+ * LFS_E_INVALID for exactly the shapes the two launchers refuse. */
+LFS_API int lfs_bilateral_slice_plan(uint32_t L, uint32_t H, uint32_t W, uint32_t h, uint32_t w, uint32_t out[5]);
 LFS_API int lfs_bilateral_tv_loss_fwd(uint32_t N, uint32_t L, uint32_t H, uint32_t W, const float* grids, float weight, float* loss,
                                       lfs_stream_t stream);
 LFS_API int lfs_bilateral_tv_loss_bwd(uint32_t N, uint32_t L, uint32_t H, uint32_t W, const float* grids, float grad_output, uint32_t accumulate,

@@ -7,7 +7,7 @@ Extension: `apply_fwd_bwd`-style entry points for the no-autograd trainer take a
 from __future__ import annotations
 
 import ctypes as C
-from typing import Tuple
+from typing import NamedTuple, Tuple
 
 import torch
 
@@ -58,6 +58,22 @@ def slice_backward(grid: torch.Tensor, rgb: torch.Tensor, grad_output: torch.Ten
     check(load_library().lfs_bilateral_slice_bwd(_u(L), _u(H), _u(W), _u(h), _u(w), ptr(grid), ptr(rgb), ptr(grad_output), _u(chw), _u(clamp_input),
                                                  ptr(grad_grid), ptr(grad_rgb), stream()), "bilateral_grid::slice_backward")
     return grad_grid, grad_rgb
+
+
+class SlicePlan(NamedTuple):
+    """What lfs_bilateral_slice_plan reports for (L, H, W, h, w): the kernels slice_forward / slice_backward run at that shape."""
+    fwd_lds: bool          # forward: LDS value window (else the generic kernel)
+    fwd_floats: int        # worst-case forward window, floats
+    bwd_window: bool       # backward: windowed MFMA kernel (else the generic kernel with global atomics)
+    bwd_lds_bytes: int     # dynamic LDS of the windowed backward
+    col_tiles: int         # bound on its 16-column tiles
+
+
+def slice_plan(L: int, H: int, W: int, h: int, w: int) -> SlicePlan:
+    """Pure host query (no launch, no device): which kernel paths a grid [12,L,H,W] against an h x w image takes."""
+    out = (C.c_uint32 * 5)()
+    check(load_library().lfs_bilateral_slice_plan(_u(L), _u(H), _u(W), _u(h), _u(w), out), "bilateral_grid::slice_plan")
+    return SlicePlan(bool(out[0]), int(out[1]), bool(out[2]), int(out[3]), int(out[4]))
 
 
 def tv_loss_forward(grids: torch.Tensor, weight: float = 1.0, loss_acc: torch.Tensor | None = None) -> torch.Tensor:

@@ -372,14 +372,32 @@ static int check_dims(uint32_t L, uint32_t H, uint32_t W, uint32_t h, uint32_t w
     return LFS_OK;
 }
 
-// worst-case window of any tile: decides LDS vs generic path on the host (same arithmetic bound as tile_window)
-static size_t window_floats(uint32_t L, uint32_t H, uint32_t W, uint32_t h, uint32_t w, uint32_t rows = TILE_H) {
-    auto span = [](uint32_t tile, uint32_t n, uint32_t G) {
-        const double per_px = (double)(G - 1) / (double)(n - 1);
-        uint32_t s = (uint32_t)(per_px * (tile - 1) + 1e-3) + 3; // floor of the span + both partial cells + x1 (+ fp32 slack)
-        return s < G ? s : G;
-    };
+// worst-case extent (in grid cells) of the window of any tile of `tile` pixels: same arithmetic bound as tile_window
+static uint32_t span(uint32_t tile, uint32_t n, uint32_t G) {
+    const double per_px = (double)(G - 1) / (double)(n - 1);
+    const uint32_t s = (uint32_t)(per_px * (tile - 1) + 1e-3) + 3; // floor of the span + both partial cells + x1 (+ fp32 slack)
+    return s < G ? s : G;
+}
+
+static size_t window_floats(uint32_t L, uint32_t H, uint32_t W, uint32_t h, uint32_t w, uint32_t rows) {
     return (size_t)12 * L * span(TILE_W, w, W) * span(rows, h, H);
+}
+
+// Which kernel a shape gets: the one place that decides it, for both launchers and for lfs_bilateral_slice_plan.
+//   forward : the LDS value window when the worst-case window of a 64 x 4 tile fits LDS_FLOATS, else the generic kernel.
+//   backward: the windowed (MFMA) kernel when the window of a 64 x 32 tile (values + gradient) and the staging buffers fit the
+//             default 64 KB of LDS, the x-extent of the window times L fits NT_MAX column tiles, and the packed stencil record
+//             holds its indices in 8 bits; else the generic kernel.
+struct SlicePlan { bool fwd_lds; size_t fwd_floats; bool bwd_window; size_t bwd_lds_bytes; uint32_t col_tiles; };
+static SlicePlan slice_plan(uint32_t L, uint32_t H, uint32_t W, uint32_t h, uint32_t w) {
+    SlicePlan p;
+    p.fwd_floats = window_floats(L, H, W, h, w, TILE_H);
+    p.fwd_lds = p.fwd_floats <= LDS_FLOATS;
+    p.bwd_lds_bytes = (2 * window_floats(L, H, W, h, w, BWD_TILE_H) + 4 * 64 * STAGE_STRIDE) * sizeof(float);
+    const uint64_t cols = (uint64_t)span(TILE_W, w, W) * L;
+    p.col_tiles = (uint32_t)((cols + 15) / 16);
+    p.bwd_window = p.bwd_lds_bytes <= 64 * 1024 && cols <= 16 * NT_MAX && L <= 255;
+    return p;
 }
 
 } // namespace bg
@@ -395,9 +413,9 @@ extern "C" int lfs_bilateral_slice_fwd(uint32_t L, uint32_t H, uint32_t W, uint3
     hipStream_t s = (hipStream_t)stream;
     const Dims d{(int)L, (int)H, (int)W, (int)h, (int)w, chw ? 1u : 3u, chw ? h * w : 1u, (int)(clamp_input != 0)};
     const dim3 g((w + TILE_W - 1) / TILE_W, (h + TILE_H - 1) / TILE_H);
-    const size_t wf = window_floats(L, H, W, h, w);
+    const SlicePlan plan = slice_plan(L, H, W, h, w);
     lfs::ProfScope prof("bilateral_slice_fwd", s);
-    if (wf <= LDS_FLOATS) hipLaunchKernelGGL(slice_fwd_kernel<true>, g, dim3(THREADS), wf * sizeof(float), s, d, grid, rgb, output);
+    if (plan.fwd_lds) hipLaunchKernelGGL(slice_fwd_kernel<true>, g, dim3(THREADS), plan.fwd_floats * sizeof(float), s, d, grid, rgb, output);
     else hipLaunchKernelGGL(slice_fwd_kernel<false>, g, dim3(THREADS), 0, s, d, grid, rgb, output);
     return (int)hipGetLastError();
 }
@@ -409,23 +427,26 @@ extern "C" int lfs_bilateral_slice_bwd(uint32_t L, uint32_t H, uint32_t W, uint3
     if (!grid || !rgb || !grad_output || !grad_grid || !grad_rgb) return LFS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const Dims d{(int)L, (int)H, (int)W, (int)h, (int)w, chw ? 1u : 3u, chw ? h * w : 1u, (int)(clamp_input != 0)};
-    // windowed path: the window (values + gradient) and the staging buffers fit the default 64 KB of LDS, the x-extent of the
-    // window times L fits NT_MAX column tiles, and the packed stencil record holds its indices in 8 bits
-    auto span = [](uint32_t tile, uint32_t n, uint32_t G) {
-        uint32_t sp = (uint32_t)((double)(G - 1) / (double)(n - 1) * (tile - 1) + 1e-3) + 3;
-        return sp < G ? sp : G;
-    };
-    const size_t wf = window_floats(L, H, W, h, w, BWD_TILE_H);
-    const size_t lds = (2 * wf + 4 * 64 * STAGE_STRIDE) * sizeof(float);
+    const SlicePlan plan = slice_plan(L, H, W, h, w);
     lfs::ProfScope prof("bilateral_slice_bwd", s);
-    if (lds <= 64 * 1024 && span(TILE_W, w, W) * L <= 16 * NT_MAX && L <= 255) {
+    if (plan.bwd_window) {
         const dim3 g((w + TILE_W - 1) / TILE_W, (h + BWD_TILE_H - 1) / BWD_TILE_H);
-        hipLaunchKernelGGL(slice_bwd_window_kernel, g, dim3(THREADS), lds, s, d, grid, rgb, grad_output, grad_grid, grad_rgb);
+        hipLaunchKernelGGL(slice_bwd_window_kernel, g, dim3(THREADS), plan.bwd_lds_bytes, s, d, grid, rgb, grad_output, grad_grid, grad_rgb);
     } else {
         const dim3 g((w + TILE_W - 1) / TILE_W, (h + TILE_H - 1) / TILE_H);
         hipLaunchKernelGGL(slice_bwd_generic_kernel, g, dim3(THREADS), 0, s, d, grid, rgb, grad_output, grad_grid, grad_rgb);
     }
     return (int)hipGetLastError();
+}
+
+extern "C" int lfs_bilateral_slice_plan(uint32_t L, uint32_t H, uint32_t W, uint32_t h, uint32_t w, uint32_t out[5]) {
+    if (int rc = check_dims(L, H, W, h, w)) return rc;
+    if (!out) return LFS_E_INVALID;
+    const SlicePlan plan = slice_plan(L, H, W, h, w);
+    out[0] = plan.fwd_lds; out[1] = (uint32_t)plan.fwd_floats;
+    out[2] = plan.bwd_window; out[3] = plan.bwd_lds_bytes < 0xffffffffu ? (uint32_t)plan.bwd_lds_bytes : 0xffffffffu; // (saturates: a window far beyond LDS)
+    out[4] = plan.col_tiles;
+    return LFS_OK;
 }
 
 static bool tv_scales(uint32_t N, uint32_t L, uint32_t H, uint32_t W, float k, float& sx, float& sy, float& sz) {

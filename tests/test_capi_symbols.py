@@ -39,6 +39,37 @@ def test_workspace_size_queries_are_pure_host_functions(lfs):
     assert b >= 1000000 * 128 and b % 256 == 0
 
 
+def test_bilateral_slice_plan_is_a_pure_host_function(lfs):
+    """lfs_bilateral_slice_plan (no launch, no device): the kernel paths csrc/bilateral_grid.hip takes at every shape the GPU parity file relies on, held to
+    literals (tests/bilateral_cases.py), so that a changed threshold cannot move a parity case to another kernel unnoticed. The plan's sizes are worst-case
+    bounds of what the kernels stage: checked against the float32 tile_window of every tile. Refused exactly where the launchers' check_dims refuses."""
+    import pytest
+    import bilateral_cases as bc
+    from lichtfeld_studio_amd import bilateral_grid as bg
+    from lichtfeld_studio_amd.capi import LfsError
+    shapes = [(c.dims, c.plan) for c in bc.LIMIT_CASES] + bc.CASES_PLANS
+    assert len(shapes) == 17 and all(d in dict(shapes) for d in bc.UNCLAMPED)
+    for dims, plan in shapes:
+        got = bg.slice_plan(*dims)
+        assert tuple(int(v) for v in got) == tuple(plan), (dims, got, plan)
+        L, H, W, h, w = dims
+        assert 12 * bc.max_window_cells(L, H, W, h, w, bc.TILE_H) <= got.fwd_floats, dims
+        assert (24 * bc.max_window_cells(L, H, W, h, w, bc.BWD_TILE_H) + 4 * 64 * 20) * 4 <= got.bwd_lds_bytes, dims
+        assert max(bc.column_tiles(L, W, w)) <= got.col_tiles, dims
+        if got.bwd_window:
+            assert got.bwd_lds_bytes <= 64 * 1024 and got.col_tiles <= 4 and L <= 255
+    for c in bc.LIMIT_CASES:
+        if c.plan.bwd_window:
+            L, H, W, h, w = c.dims
+            assert set(bc.column_tiles(L, W, w)) == c.nt and set(bc.strip_columns(L, W, w)) == c.cols, c.dims
+    assert bg.slice_plan(64, 1, 1, 8, 8).bwd_window is True and bg.slice_plan(65, 1, 1, 8, 8).bwd_window is False      # 64 columns at most (so L <= 64 < 256: the 8-bit record)
+    assert bg.slice_plan(1, 1, 1, 46340, 46340).fwd_lds is True                                                         # h * w < 2^31
+    assert tuple(bg.slice_plan(10, 4096, 4096, 8, 8))[::2] == (0, 0, 2560) and bg.slice_plan(10, 4096, 4096, 8, 8).bwd_lds_bytes == 0xffffffff   # 12 L H W < 2^31; bytes saturate
+    for bad in [(0, 16, 16, 8, 8), (8, 0, 16, 8, 8), (8, 16, 0, 8, 8), (8, 16, 16, 1, 8), (8, 16, 16, 8, 1), (11, 4096, 4096, 8, 8), (1, 1, 1, 46341, 46341)]:
+        with pytest.raises(LfsError):
+            bg.slice_plan(*bad)
+
+
 def test_ops_refuse_cpu_tensors_loudly(lfs):
     """No CPU fallback: CHECK_INPUT semantics (gsplat/Common.h:12-17)."""
     import pytest
