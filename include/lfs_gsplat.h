@@ -284,6 +284,12 @@ LFS_API int lfs_fastgs_preprocess(
  * the extents, the tile tests, the blend. The mode is recorded in the primitive workspace: lfs_fastgs_render and the three backward entry points take the same
  * arguments in both modes, and the backward is the full derivative (through rho into means, scales, rotations and grad_w2c). */
 #define LFS_FASTGS_ANTIALIASED 1u
+/* Depth modes (the reference's render_mode D / ED / RGB_D / RGB_ED on the EWA path). With z_i the camera-space z of primitive i (>= near_plane when visible):
+ * LFS_FASTGS_DEPTH blends d_i = z_i, LFS_FASTGS_INVDEPTH d_i = 1 / z_i. The two exclude each other (both: LFS_E_INVALID), each combines with LFS_FASTGS_ANTIALIASED.
+ * The preprocess writes d_i into a free word of the blend record and the flag into the workspace's mode word; the workspace size does not change, and colour, alpha
+ * and the three backward entry points above treat such a workspace as an ordinary one. (Bit 1, value 2, stays undefined.) */
+#define LFS_FASTGS_DEPTH 4u
+#define LFS_FASTGS_INVDEPTH 8u
 LFS_API int lfs_fastgs_preprocess_ex(
     uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* opacities_raw,
     const float* sh_coefficients_0, const float* sh_coefficients_rest, uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position,
@@ -295,6 +301,14 @@ LFS_API int lfs_fastgs_wait_n_instances(int64_t* n_instances);
 LFS_API int lfs_fastgs_render(
     uint32_t N, uint32_t width, uint32_t height, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
     void* instance_workspace, size_t instance_workspace_bytes, float* image, float* alpha, lfs_stream_t stream);
+/* lfs_fastgs_render + depth [1,H,W] = sum_i w_i d_i over exactly the instances that contribute to the colour (w_i = T_i alpha_i): the ACCUMULATED value, the
+ * reference's D / RGB_D; the expected value (ED) is depth / alpha, the caller's business. image and alpha are bit-identical to lfs_fastgs_render's.
+ * LFS_E_INVALID: depth NULL, or the primitive workspace was not last filled by a preprocess with a depth flag in this process. The library remembers, by
+ * address and without a device read, the workspaces filled in a depth mode: up to 256 whose backward is still to come (a preprocess without a depth flag takes no
+ * entry and only clears its own address); with more outstanding, the least recently filled one is forgotten and refused here like a default-mode workspace. */
+LFS_API int lfs_fastgs_render_depth(
+    uint32_t N, uint32_t width, uint32_t height, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
+    void* instance_workspace, size_t instance_workspace_bytes, float* image, float* alpha, float* depth, lfs_stream_t stream);
 LFS_API int lfs_fastgs_backward(
     uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* sh_coefficients_0, const float* sh_coefficients_rest,
     uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position, uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy,
@@ -316,6 +330,19 @@ LFS_API int lfs_fastgs_backward_w2c(
     float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
     float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest, float* grad_w2c /* [4,4], fully written */, void* w2c_workspace, size_t w2c_workspace_bytes,
     lfs_stream_t stream);
+/* lfs_fastgs_backward with a gradient for the depth map of lfs_fastgs_render_depth: grad_depth [1,H,W]. Depth is a fourth blended channel of the blending
+ * backward (dL/dalpha and the colour-behind recurrence see d_i g_depth next to c_i . g_image), dL/dd_i = sum w g_depth is one more slot of the accumulator row, and
+ * dL/dz_i = dL/dd_i (1 | -1 / z_i^2) is added to the camera-space mean gradient: it reaches grad_means and, when grad_w2c is given, row 2 of the camera gradient.
+ * grad_w2c NULL: as lfs_fastgs_backward (w2c_workspace is not used); otherwise as lfs_fastgs_backward_w2c. densification_info keeps its definition.
+ * LFS_E_INVALID: grad_depth NULL, or a workspace without a depth flag (as lfs_fastgs_render_depth). */
+LFS_API int lfs_fastgs_backward_depth(
+    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* sh_coefficients_0, const float* sh_coefficients_rest,
+    uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position, uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy,
+    float cx, float cy, float near_plane, float far_plane, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
+    void* instance_workspace, size_t instance_workspace_bytes, const float* grad_image, const float* grad_alpha, const float* alpha,
+    float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
+    float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest, const float* grad_depth, float* grad_w2c /* NULL or [4,4], fully written */, void* w2c_workspace,
+    size_t w2c_workspace_bytes, lfs_stream_t stream);
 /* lfs_fastgs_backward for a step with ONE view, fused with the optimizer (extension): sh_coefficients_rest and its Adam moments are updated in
  * place by the SH backward (fast_gs::optimizer::adam_step arithmetic); the [N,total_rest,3] gradient is never stored. */
 LFS_API int lfs_fastgs_backward_adam(
@@ -376,6 +403,15 @@ LFS_API int lfs_photometric_loss_masked_fwd_bwd(uint32_t H, uint32_t W, const fl
                                                 lfs_stream_t stream);
 LFS_API int lfs_mse_loss_masked_fwd_bwd(uint32_t H, uint32_t W, const float* render, uint32_t render_is_chw, uint32_t clamp_render, const float* target_chw,
                                         const uint8_t* mask_u8, const int64_t* mask_sums, float weight, float* v_render, float* loss, lfs_stream_t stream);
+
+/* depth supervision (extension). lfs_depth_prepare: target_in [H,W] (any float; valid = finite and > 0) -> target_out [H,W] = the value where valid,
+ * NaN where not (target_out may be target_in: the plane is prepared in place), and sums int64[1] on the device = sum_p valid_p M_p with M_p the mask byte (255 without a mask): 255 x the sum of the weights
+ * m_p = valid_p M_p / 255, exact. lfs_depth_l1_loss_fwd_bwd on a prepared target (weights_u8 the same mask or NULL):
+ *   *loss_acc += weight * sum_p m_p |D_p - t_p| / max(sum m, 1),   grad_depth_p = weight * m_p * sign(D_p - t_p) / max(sum m, 1)   (0 where m_p = 0; sign(0) = 0)
+ * with the normaliser read from sums on the device (no host read). */
+LFS_API int lfs_depth_prepare(uint32_t H, uint32_t W, const float* target_in, const uint8_t* weights_u8, float* target_out, int64_t* sums, lfs_stream_t stream);
+LFS_API int lfs_depth_l1_loss_fwd_bwd(uint32_t H, uint32_t W, const float* depth, const float* target, const uint8_t* weights_u8, const int64_t* sums, float weight,
+                                      float* grad_depth, float* loss_acc, lfs_stream_t stream);
 
 /* ---- bilateral-grid appearance model (row 2 of §8f, BASELINE config 5): gs::bilateral_grid::slice_forward_cuda /
  *      slice_backward_cuda / tv_loss_forward_cuda / tv_loss_backward_cuda (include/kernels/bilateral_grid.cuh:12-33,

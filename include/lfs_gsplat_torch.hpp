@@ -116,6 +116,20 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Te
     const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
     const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
     const float center_y, const float near_plane, const float far_plane, const bool antialiased);
+// Extension: the depth modes (lfs_fastgs_render_depth / lfs_fastgs_backward_depth; LFS_FASTGS_DEPTH, LFS_FASTGS_INVDEPTH). Forward: inverse_depth false blends the
+// camera-space z of every Gaussian, true its reciprocal; -> (image [3,H,W], alpha [1,H,W], depth [1,H,W] = the ACCUMULATED sum w_i d_i, per_primitive_buffers,
+// per_instance_buffers, n_instances). Backward: fast_gs::rasterization::backward_wrapper with grad_depth [1,H,W]; the 7th element is grad_w2c when w2c requires grad.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int> fastgs_forward_wrapper_depth(
+    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
+    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
+    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
+    const float center_y, const float near_plane, const float far_plane, const bool antialiased, const bool inverse_depth);
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> fastgs_backward_wrapper_depth(
+    torch::Tensor& densification_info, const torch::Tensor& grad_image, const torch::Tensor& grad_alpha, const torch::Tensor& grad_depth, const torch::Tensor& alpha,
+    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& sh_coefficients_rest,
+    const torch::Tensor& per_primitive_buffers, const torch::Tensor& per_instance_buffers, const torch::Tensor& w2c, const torch::Tensor& cam_position,
+    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
+    const float center_y, const float near_plane, const float far_plane, const int n_instances);
 } // namespace lfs
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> fusedssim(float C1, float C2, torch::Tensor& img1, torch::Tensor& img2, bool train);

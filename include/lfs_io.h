@@ -95,6 +95,9 @@ LFS_IO_API int lfs_image_load_rgb8(const char* path, uint8_t** data, int32_t* wi
 /* The alpha channel alone, 8-bit [h,w], of a PNG of colour type 4 (grey + alpha) or 6 (RGBA); 16-bit samples are reduced as the RGB path reduces them
  * (the high byte). Anything else returns LFS_IO_E_UNSUPPORTED (the Python host layer then tries Pillow). Release with lfs_io_free. */
 LFS_IO_API int lfs_image_load_alpha8(const char* path, uint8_t** data, int32_t* width, int32_t* height);
+/* A 16-bit greyscale PNG (colour type 0, non-interlaced) with BOTH bytes of every sample, [h,w] in host byte order - depth maps (the 8-bit paths above keep the
+ * high byte only). Anything else returns LFS_IO_E_UNSUPPORTED. Release with lfs_io_free. */
+LFS_IO_API int lfs_image_load_gray16(const char* path, uint16_t** data, int32_t* width, int32_t* height);
 LFS_IO_API int lfs_image_write_png_rgb8(const char* path, const uint8_t* data, int32_t width, int32_t height);
 LFS_IO_API void lfs_io_free(void* p);
 

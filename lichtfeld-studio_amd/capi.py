@@ -93,6 +93,7 @@ EXPORTS = [
     "lfs_select_kth_workspace_bytes", "lfs_select_kth_f32", "lfs_admm_update_workspace_bytes", "lfs_admm_update", "lfs_admm_loss_grad_workspace_bytes", "lfs_admm_loss_grad",
     "lfs_admm_prune_mask_workspace_bytes", "lfs_admm_prune_mask",
     "lfs_mask_prepare", "lfs_photometric_loss_masked_fwd_bwd", "lfs_mse_loss_masked_fwd_bwd",
+    "lfs_fastgs_render_depth", "lfs_fastgs_backward_depth", "lfs_depth_prepare", "lfs_depth_l1_loss_fwd_bwd",
 ]
 
 

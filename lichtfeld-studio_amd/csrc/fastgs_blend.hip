@@ -17,7 +17,8 @@ namespace fgs {
 int launch_scatter(uint32_t N, const Frame& f, const PrimWs& w, int64_t* keys, hipStream_t s);
 int launch_preprocess_bwd(uint32_t N, const float* means, const float* scales_raw, const float* rot_raw, const float* sh0, const float* sh_rest, const Frame& f, const PrimWs& w,
                           float* g_means, float* g_scales_raw, float* g_rot_raw, float* g_opac_raw, float* g_sh0, float* g_sh_rest, float* densification_info, hipStream_t s,
-                          const ShAdamArgs* adam, float* grad_w2c, float* w2c_partials);
+                          const ShAdamArgs* adam, float* grad_w2c, float* w2c_partials, int depth);
+uint32_t remembered_flags(const void* primitive_workspace);
 size_t w2c_workspace_bytes(uint32_t N);
 int launch_w2c_reduce(uint32_t N, const float* w2c_partials, float* grad_w2c, hipStream_t s);
 
@@ -109,10 +110,13 @@ LFS_DI Frag frag_eval(const GaussRec& rec, const float px, const float py) {
 }
 
 // fwd / bwd: ONE wavefront per workgroup (the cells of a tile never cooperate here; a finished cell frees its slot at once - as raster.hip's wave_geom)
+// DEPTH (lfs_fastgs_render_depth): one more accumulator D += r2.w T alpha over exactly the instances the colour takes, stored to depth_map [1,H,W]; r2.w arrives with
+// the record. The default form does not read r2.w or depth_map.
+template <bool DEPTH>
 __global__ void __launch_bounds__(64) fg_blend_fwd_kernel(
     const uint32_t gw, const uint32_t gh, const uint32_t width, const uint32_t height,
     const GaussRec* __restrict__ recs, const int32_t* __restrict__ offsets, const int32_t* __restrict__ cell_count, const int2* __restrict__ cell_list,
-    float* __restrict__ image, float* __restrict__ alpha_map, int32_t* __restrict__ n_contrib) {
+    float* __restrict__ image, float* __restrict__ alpha_map, int32_t* __restrict__ n_contrib, float* __restrict__ depth_map) {
     const uint32_t total_tiles = gw * gh;
     const CellCtx cc = cell_ctx(total_tiles, total_tiles, gw, TILE, WPT, 1);
     if (!cc.in_grid) return;
@@ -123,7 +127,7 @@ __global__ void __launch_bounds__(64) fg_blend_fwd_kernel(
     const int32_t cnt = cell_count[size_t(cc.tile_global) * WPT + cc.wl];
     const float INF = __builtin_inff();
     float thr = inside ? MIN_ALPHA : INF; // "done" is carried as the alpha threshold (see raster.hip)
-    float T = 1.f, c0 = 0.f, c1 = 0.f, c2 = 0.f;
+    float T = 1.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, dsum = 0.f;
     int32_t last = 0; // 1 + global list index of the last blended instance (0: none)
     auto eval = [&](const GaussRec& rec, const int2 e) {
         const Frag f = frag_eval(rec, px, py);
@@ -135,6 +139,7 @@ __global__ void __launch_bounds__(64) fg_blend_fwd_kernel(
         const float w = T * f.alpha;
         if (contrib) {
             c0 = __builtin_fmaf(rec.r2.x, w, c0); c1 = __builtin_fmaf(rec.r2.y, w, c1); c2 = __builtin_fmaf(rec.r2.z, w, c2);
+            if constexpr (DEPTH) dsum = __builtin_fmaf(rec.r2.w, w, dsum);
             T = next_T; last = e.y + 1;
         }
         thr = fin ? INF : thr;
@@ -145,19 +150,23 @@ __global__ void __launch_bounds__(64) fg_blend_fwd_kernel(
         image[p] = c0; image[np + p] = c1; image[2 * np + p] = c2;
         alpha_map[p] = 1.f - T;
         n_contrib[p] = last;
+        if constexpr (DEPTH) depth_map[p] = dsum;
     }
 }
 
 // ACC 0: the rows are summed with float atomics, whose arrival order - and so the last bits of every gradient - differs from run to run. ACC 1 / 2: the two passes of
 // the deterministic mode (lfs_set_debug_flags bit 4, as the 3DGUT backward's: wave_sum16_atomic in lfs_raster_common.cuh), fg_det_resolve_kernel turns the sums back into floats.
-template <int ACC>
+// DEPTH (lfs_fastgs_backward_depth): depth is a fourth blended channel - cv = c . g_image + r2.w g_depth feeds dL/dalpha and the colour-behind recurrence - and slot 9
+// of the row takes sum w g_depth = dL/dd; the reduction carries ten values instead of nine (wave_sum9_atomic_lds<ACC, 10>), through the same block and atomic.
+template <int ACC, bool DEPTH>
 __global__ void __launch_bounds__(64) fg_blend_bwd_kernel(
     const uint32_t gw, const uint32_t gh, const uint32_t width, const uint32_t height,
     const GaussRec* __restrict__ recs, const int32_t* __restrict__ offsets, const int32_t* __restrict__ cell_count, const int2* __restrict__ cell_list,
     const float* __restrict__ alpha_map, const int32_t* __restrict__ n_contrib, const float* __restrict__ g_image, const float* __restrict__ g_alpha,
-    float* __restrict__ acc, unsigned long long* __restrict__ det64) {
+    float* __restrict__ acc, unsigned long long* __restrict__ det64, const float* __restrict__ g_depth) {
     const uint32_t total_tiles = gw * gh;
-    __shared__ __attribute__((aligned(16))) float s_red[RED9_SCRATCH_FLOATS]; // this wavefront's transpose block (wave_sum9_atomic_lds)
+    constexpr int NV = DEPTH ? 10 : 9;
+    __shared__ __attribute__((aligned(16))) float s_red[red_n_scratch_floats(NV)]; // this wavefront's transpose block (wave_sum9_atomic_lds)
     float* const red_scratch = s_red;
     const CellCtx cc = cell_ctx(total_tiles, total_tiles, gw, TILE, WPT, 1);
     if (!cc.in_grid) return;
@@ -167,13 +176,14 @@ __global__ void __launch_bounds__(64) fg_blend_bwd_kernel(
     const int32_t start = offsets[cc.tile_global], end = offsets[cc.tile_global + 1];
     const int2* __restrict__ cl = cell_list + (size_t(WPT) * size_t(start) + size_t(cc.wl) * size_t(end - start));
     const int32_t cnt = cell_count[size_t(cc.tile_global) * WPT + cc.wl];
-    float T = 1.f, gc0 = 0.f, gc1 = 0.f, gc2 = 0.f, tail = 0.f, Bsum = 0.f;
+    float T = 1.f, gc0 = 0.f, gc1 = 0.f, gc2 = 0.f, gd = 0.f, tail = 0.f, Bsum = 0.f;
     int32_t last = -1;
     if (inside) {
         const size_t np = size_t(width) * height, p = size_t(cc.i) * width + cc.j;
         T = 1.f - alpha_map[p];
         last = n_contrib[p] - 1;
         gc0 = g_image[p]; gc1 = g_image[np + p]; gc2 = g_image[2 * np + p];
+        if constexpr (DEPTH) gd = g_depth[p];
         tail = g_alpha[p] * T; // grad_alpha * (1 - alpha_pixel), kernels_backward.cuh:352
     }
     int32_t wmax = last;
@@ -194,22 +204,28 @@ __global__ void __launch_bounds__(64) fg_blend_bwd_kernel(
         const float Tn = T * ra;                                  // transmittance in front of this instance
         T = valid ? Tn : T;
         const float w = valid ? Tn * f.alpha : 0.f;               // blending weight (0 masks every sum below)
-        const float cv = __builtin_fmaf(rec.r2.z, gc2, __builtin_fmaf(rec.r2.y, gc1, rec.r2.x * gc0));
+        float cv = __builtin_fmaf(rec.r2.z, gc2, __builtin_fmaf(rec.r2.y, gc1, rec.r2.x * gc0));
+        if constexpr (DEPTH) cv = __builtin_fmaf(rec.r2.w, gd, cv);
         // dL/dalpha = (T c - colour_behind / (1 - alpha)) . g + grad_alpha (1 - alpha_pixel) / (1 - alpha)   (kernels_backward.cuh:412-417)
         const float dl_dalpha = __builtin_fmaf(ra, tail - Bsum, Tn * cv);
         Bsum = __builtin_fmaf(w, cv, Bsum);
         const float aD = valid ? f.alpha * dl_dalpha : 0.f;      // (no clamp mask on alpha, as in the reference)
         const float hx = -aD * f.dx, hy = -aD * f.dy;
         // accumulator row: {sum hx, sum hy, sum hx dx, sum hx dy | sum hy dy, dc.r, dc.g, dc.b | sum alpha dL/dalpha}
-        //   dL/dmean2d = conic . (sum hx, sum hy), dL/dconic = 0.5 (sum hx dx, sum hx dy, sum hy dy)   (fastgs_prep.hip)
+        //   dL/dmean2d = conic . (sum hx, sum hy), dL/dconic = 0.5 (sum hx dx, sum hx dy, sum hy dy)   (fastgs_prep.hip); depth form: | sum w g_depth}
         float* row = acc + size_t(e.x) * ACC_STRIDE;
-        const float v[9] = {hx, hy, hx * f.dx, hx * f.dy, hy * f.dy, w * gc0, w * gc1, w * gc2, aD};
-        wave_sum9_atomic_lds<ACC>(v, row, lane, red_scratch, ACC == 2 ? det64 + size_t(e.x) * ACC_STRIDE : nullptr);
+        if constexpr (DEPTH) {
+            const float v[10] = {hx, hy, hx * f.dx, hx * f.dy, hy * f.dy, w * gc0, w * gc1, w * gc2, aD, w * gd};
+            wave_sum9_atomic_lds<ACC, 10>(v, row, lane, red_scratch, ACC == 2 ? det64 + size_t(e.x) * ACC_STRIDE : nullptr);
+        } else {
+            const float v[9] = {hx, hy, hx * f.dx, hx * f.dy, hy * f.dy, w * gc0, w * gc1, w * gc2, aD};
+            wave_sum9_atomic_lds<ACC>(v, row, lane, red_scratch, ACC == 2 ? det64 + size_t(e.x) * ACC_STRIDE : nullptr);
+        }
     };
     walk_cell_list<-1>(cl, recs, lo - 1, lo, eval, []() { return true; });
 }
 
-// deterministic mode, after pass 2: acc[i] = fixed-point sum * 2^(e - 40), e from the pass-1 maximum that acc[i] still holds as bits (slots 9 .. 15 hold 0 and stay 0)
+// deterministic mode, after pass 2: acc[i] = fixed-point sum * 2^(e - 40), e from the pass-1 maximum that acc[i] still holds as bits (the slots no form writes hold 0 and stay 0)
 __global__ void __launch_bounds__(256) fg_det_resolve_kernel(const size_t n, float* __restrict__ acc, const unsigned long long* __restrict__ det64) {
     const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -237,9 +253,9 @@ static fgs::Frame make_frame(const float* w2c, const float* cam_position, uint32
                       fx, fy, cx, cy, near_plane, far_plane};
 }
 
-extern "C" int lfs_fastgs_render(
+static int fastgs_render_impl(
     uint32_t N, uint32_t width, uint32_t height, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
-    void* instance_workspace, size_t instance_workspace_bytes, float* image, float* alpha, lfs_stream_t stream) {
+    void* instance_workspace, size_t instance_workspace_bytes, float* image, float* alpha, float* depth, lfs_stream_t stream) {
     if (!primitive_workspace || !image || !alpha || width == 0 || height == 0 || n_instances < 0 || n_instances > 0x7FFFFFFFll) return LFS_E_INVALID;
     if (N >= (1u << 26) || uint64_t(n_instances) >= (1ull << 29)) return LFS_E_UNSUPPORTED; // 32-bit byte offsets of the record walker
     fgs::PrimWs w = fgs::prim_ws(primitive_workspace, N, width, height);
@@ -274,9 +290,32 @@ extern "C" int lfs_fastgs_render(
     }
     lfs::ProfScope prof("fastgs_blend_fwd", s);
     const uint32_t wgrid = cell_grid_blocks(uint64_t(T) * fgs::WPT, fgs::WPT);
-    hipLaunchKernelGGL(fgs::fg_blend_fwd_kernel, dim3(wgrid), dim3(64), 0, s, f.gw, f.gh, width, height, w.rec, w.offsets, iw.cell_count, iw.cell_list,
-                       image, alpha, w.n_contrib);
+    if (depth) hipLaunchKernelGGL(fgs::fg_blend_fwd_kernel<true>, dim3(wgrid), dim3(64), 0, s, f.gw, f.gh, width, height, w.rec, w.offsets, iw.cell_count, iw.cell_list,
+                                  image, alpha, w.n_contrib, depth);
+    else hipLaunchKernelGGL(fgs::fg_blend_fwd_kernel<false>, dim3(wgrid), dim3(64), 0, s, f.gw, f.gh, width, height, w.rec, w.offsets, iw.cell_count, iw.cell_list,
+                            image, alpha, w.n_contrib, static_cast<float*>(nullptr));
     return (int)hipGetLastError();
+}
+
+extern "C" int lfs_fastgs_render(
+    uint32_t N, uint32_t width, uint32_t height, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
+    void* instance_workspace, size_t instance_workspace_bytes, float* image, float* alpha, lfs_stream_t stream) {
+    return fastgs_render_impl(N, width, height, n_instances, primitive_workspace, primitive_workspace_bytes, instance_workspace, instance_workspace_bytes, image, alpha,
+                              nullptr, stream);
+}
+
+// the depth kind (1: z, 2: 1 / z) of the preprocess that last filled this workspace, 0 when it carried no depth flag (fastgs_prep.hip: remember_flags)
+static int workspace_depth_kind(const void* primitive_workspace) {
+    const uint32_t flags = fgs::remembered_flags(primitive_workspace);
+    return (flags & LFS_FASTGS_DEPTH) ? 1 : (flags & LFS_FASTGS_INVDEPTH) ? 2 : 0;
+}
+
+extern "C" int lfs_fastgs_render_depth(
+    uint32_t N, uint32_t width, uint32_t height, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
+    void* instance_workspace, size_t instance_workspace_bytes, float* image, float* alpha, float* depth, lfs_stream_t stream) {
+    if (!depth || !primitive_workspace || workspace_depth_kind(primitive_workspace) == 0) return LFS_E_INVALID;
+    return fastgs_render_impl(N, width, height, n_instances, primitive_workspace, primitive_workspace_bytes, instance_workspace, instance_workspace_bytes, image, alpha,
+                              depth, stream);
 }
 
 static int fastgs_backward_impl(
@@ -286,7 +325,7 @@ static int fastgs_backward_impl(
     void* instance_workspace, size_t instance_workspace_bytes, const float* grad_image, const float* grad_alpha, const float* alpha,
     float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
     float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest, lfs_stream_t stream, const lfs::ShAdamArgs* adam, float* grad_w2c = nullptr,
-    void* w2c_workspace = nullptr) {
+    void* w2c_workspace = nullptr, const float* grad_depth = nullptr, int depth = 0 /* with grad_depth: the workspace's depth kind */) {
     if (!primitive_workspace || !w2c || !cam_position || !grad_image || !grad_alpha || !alpha || width == 0 || height == 0 || n_instances < 0) return LFS_E_INVALID;
 #ifdef LFS_EMULATE
     const bool det = false;   // (the emulated library has no integer-atomic passes)
@@ -314,8 +353,9 @@ static int fastgs_backward_impl(
     if (n_instances > 0 && !keep_acc) {
         lfs::ProfScope prof("fastgs_blend_bwd", s);
         const uint32_t wgrid = cell_grid_blocks(uint64_t(T) * fgs::WPT, fgs::WPT);
-#define LFS_FG_BWD(ACC) hipLaunchKernelGGL(fgs::fg_blend_bwd_kernel<ACC>, dim3(wgrid), dim3(64), 0, s, f.gw, f.gh, width, height, w.rec, w.offsets, iw.cell_count, \
-                                          iw.cell_list, alpha, w.n_contrib, grad_image, grad_alpha, w.acc, w.det64)
+#define LFS_FG_BWD_D(ACC, DEPTH) hipLaunchKernelGGL((fgs::fg_blend_bwd_kernel<ACC, DEPTH>), dim3(wgrid), dim3(64), 0, s, f.gw, f.gh, width, height, w.rec, w.offsets, iw.cell_count, \
+                                                   iw.cell_list, alpha, w.n_contrib, grad_image, grad_alpha, w.acc, w.det64, grad_depth)
+#define LFS_FG_BWD(ACC) do { if (grad_depth) LFS_FG_BWD_D(ACC, true); else LFS_FG_BWD_D(ACC, false); } while (0)
         if (det) { // pass 1: per-slot maxima of |total| (integer atomicMax), pass 2: 64-bit fixed-point sums, then back to float
             const size_t n_acc = ACC_STRIDE * size_t(N);
             hipError_t e = hipMemsetAsync(w.det64, 0, sizeof(unsigned long long) * n_acc, s);
@@ -324,10 +364,11 @@ static int fastgs_backward_impl(
             hipLaunchKernelGGL(fgs::fg_det_resolve_kernel, dim3(uint32_t((n_acc + 255) / 256)), dim3(256), 0, s, n_acc, w.acc, w.det64);
         } else LFS_FG_BWD(0);
 #undef LFS_FG_BWD
+#undef LFS_FG_BWD_D
     }
     return fgs::launch_preprocess_bwd(N, means, scales_raw, rotations_raw, sh_coefficients_0, sh_coefficients_rest, f, w, grad_means, grad_scales_raw, grad_rotations_raw,
                                       grad_opacities_raw, grad_sh_coefficients_0, grad_sh_coefficients_rest, densification_info, s, adam, grad_w2c,
-                                      static_cast<float*>(w2c_workspace));
+                                      static_cast<float*>(w2c_workspace), grad_depth ? depth : 0);
 }
 
 extern "C" int lfs_fastgs_backward(
@@ -361,6 +402,30 @@ extern "C" int lfs_fastgs_backward_w2c(
                                 width, height, fx, fy, cx, cy, near_plane, far_plane, n_instances, primitive_workspace, primitive_workspace_bytes, instance_workspace,
                                 instance_workspace_bytes, grad_image, grad_alpha, alpha, densification_info, grad_means, grad_scales_raw, grad_rotations_raw,
                                 grad_opacities_raw, grad_sh_coefficients_0, grad_sh_coefficients_rest, stream, nullptr, grad_w2c, w2c_workspace);
+}
+
+// lfs_fastgs_backward[_w2c] with a gradient for the depth map of lfs_fastgs_render_depth. Whether the workspace carries d in its records is validated on the HOST (the
+// flags the library remembers by the workspace's address: no device read, no launch on a refusal); the antialiased bit is still picked on the device.
+extern "C" int lfs_fastgs_backward_depth(
+    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* sh_coefficients_0, const float* sh_coefficients_rest,
+    uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position, uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy,
+    float cx, float cy, float near_plane, float far_plane, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
+    void* instance_workspace, size_t instance_workspace_bytes, const float* grad_image, const float* grad_alpha, const float* alpha,
+    float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
+    float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest, const float* grad_depth, float* grad_w2c, void* w2c_workspace, size_t w2c_workspace_bytes,
+    lfs_stream_t stream) {
+    if (!grad_depth || !primitive_workspace) return LFS_E_INVALID;
+    const int depth = workspace_depth_kind(primitive_workspace);
+    if (depth == 0) return LFS_E_INVALID;
+    if (grad_w2c) {
+        if (!w2c_workspace || w2c_workspace_bytes < fgs::w2c_workspace_bytes(N)) return LFS_E_WORKSPACE;
+        if (reinterpret_cast<uintptr_t>(w2c_workspace) % 16 != 0) return LFS_E_INVALID;
+    }
+    return fastgs_backward_impl(N, means, scales_raw, rotations_raw, sh_coefficients_0, sh_coefficients_rest, total_bases_sh_rest, w2c, cam_position, active_sh_bases,
+                                width, height, fx, fy, cx, cy, near_plane, far_plane, n_instances, primitive_workspace, primitive_workspace_bytes, instance_workspace,
+                                instance_workspace_bytes, grad_image, grad_alpha, alpha, densification_info, grad_means, grad_scales_raw, grad_rotations_raw,
+                                grad_opacities_raw, grad_sh_coefficients_0, grad_sh_coefficients_rest, stream, nullptr, grad_w2c, grad_w2c ? w2c_workspace : nullptr,
+                                grad_depth, depth);
 }
 
 // lfs_fastgs_backward for a step with ONE view, fused with the optimizer: sh_coefficients_rest and its Adam moments are updated in place by the SH

@@ -4,6 +4,7 @@
 // scatter straight into per-tile buckets, as intersect.hip does) and the per-primitive backward (preprocess_backward_cu,
 // kernels_backward.cuh:19-233, incl. convert_sh_to_color_backward kernel_utils.cuh:38-106 and densification_info).
 // Streaming, HBM-bound kernels: compiled with -ffp-contract=off so that the tile-membership test rounds like the oracle.
+#include <mutex>
 #include "lfs_fastgs.cuh"
 #include "lfs_prof.h"
 #include "lfs_tilelists.cuh"
@@ -82,15 +83,17 @@ LFS_DI void ewa(const Frame& f, const float* __restrict__ m, const float* __rest
 // AA (LFS_FASTGS_ANTIALIASED): the opacity is multiplied by rho = sqrt(max(0, det(Sigma2d) / det(Sigma2d + DILATION I))) (add_blur, gsplat/Utils.cuh:171-179) before
 // anything looks at it - the 1/255 cut, the power threshold, the extents, the tile tests and the records all see o_eff = sigmoid(raw) * rho. sigmoid(raw) is kept in
 // the record's free r1.w for the backward. Thread 0 writes the mode word of the workspace: the backward reads it there.
+// DEPTH (1: LFS_FASTGS_DEPTH, 2: LFS_FASTGS_INVDEPTH): d = z or 1 / z of the camera-space z the cuts and the sort key already use goes into the record's free r2.w
+// (one dword store; the SH kernel that fills r2.xyz afterwards writes three dwords and leaves it alone). Nothing else changes: the default forms store nothing there.
 // ---------------------------------------------------------------------------
-template <bool LDS_HIST, bool AA>
+template <bool LDS_HIST, bool AA, int DEPTH>
 __global__ void __launch_bounds__(1024) fg_preprocess_kernel(
     const uint32_t N, const uint32_t per_block, const float* __restrict__ means, const float* __restrict__ scales_raw, const float* __restrict__ rot_raw,
     const float* __restrict__ opac_raw, const Frame f,
     GaussRec* __restrict__ rec, float2* __restrict__ mean2d_o, float4* __restrict__ conic_opacity_o, ushort4* __restrict__ bounds_o,
     uint32_t* __restrict__ n_touched_o, uint32_t* __restrict__ depth_bits_o, uint32_t* __restrict__ totals, uint32_t* __restrict__ mode_o) {
     extern __shared__ __attribute__((aligned(16))) uint32_t hist[];
-    if (blockIdx.x == 0 && threadIdx.x == 0) *mode_o = AA ? MODE_ANTIALIASED : 0u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *mode_o = (AA ? MODE_ANTIALIASED : 0u) | depth_mode_bits(DEPTH);
     const uint32_t T = f.gw * f.gh;
     if (LDS_HIST) {
         for (uint32_t t = threadIdx.x; t < T; t += blockDim.x) hist[t] = 0u;
@@ -138,6 +141,7 @@ __global__ void __launch_bounds__(1024) fg_preprocess_kernel(
             float4* r = reinterpret_cast<float4*>(rec + i);
             r[0] = make_float4(mx, my, 0.5f * LOG2E * ca, LOG2E * cb);
             r[1] = make_float4(0.5f * LOG2E * cc, LOG2E * power_threshold, opacity, AA ? sig : 0.f);
+            if constexpr (DEPTH != 0) reinterpret_cast<float*>(rec + i)[11] = DEPTH == 1 ? depth : 1.0f / depth;   // r2.w (depth >= near_plane > 0 here)
             mean2d_o[i] = make_float2(mx, my);
             conic_opacity_o[i] = make_float4(ca, cb, cc, opacity);
             bounds_o[i] = make_ushort4(uint16_t(x0), uint16_t(x1), uint16_t(y0), uint16_t(y1));
@@ -212,7 +216,9 @@ LFS_DI void preprocess_bwd_zero_rows(const uint32_t i, float* __restrict__ g_mea
 // AA: the record's opacity is o_eff = sigmoid(raw) * rho, so the accumulator's S = sum alpha dL/dalpha is o_eff dL/do_eff: dL/draw = S (1 - sigmoid(raw)) with the
 // sigmoid from r1.w, and dL/drho = S / rho reaches the 2-D covariance through rho^2 = det0 / det1: dL/d(a0, b, c0) += S/2 (c0/det0 - c/det1, 2b (1/det1 - 1/det0),
 // a0/det0 - a/det1) - no division by rho (a visible primitive has rho >= 1/255, hence det0 > 0). Everything below dcv is the code both modes share.
-template <bool AA>
+// DEPTH (1 / 2, lfs_fastgs_backward_depth): slot 9 of the row is dL/dd, d = z or 1 / z, and z is the third camera-space coordinate: dL/dz = acc[9] (1 | -1 / z^2) is
+// added to dcam[2] before grad_means and the camera gradient are made of it. densification_info keeps its definition (dL/dmean2d only).
+template <bool AA, int DEPTH>
 LFS_DI void preprocess_bwd_one(
     const uint32_t i, const uint32_t N, const float* __restrict__ means, const float* __restrict__ scales_raw, const float* __restrict__ rot_raw,
     const Frame& f, const GaussRec* __restrict__ rec, const float4* __restrict__ conic_opacity, const float* __restrict__ acc,
@@ -260,6 +266,8 @@ LFS_DI void preprocess_bwd_one(
     const float h1 = dj11 - 2.0f * cv.tx * dj13, h2 = dj22 - 2.0f * cv.ty * dj23;
     dcam[0] = cv.j11 * (dm2[0] - dj13 / cv.depth); dcam[1] = cv.j22 * (dm2[1] - dj23 / cv.depth);
     dcam[2] = -cv.j11 * (cv.x * dm2[0] + h1 / cv.depth) - cv.j22 * (cv.y * dm2[1] + h2 / cv.depth);
+    if constexpr (DEPTH == 1) dcam[2] += a2.y;
+    if constexpr (DEPTH == 2) dcam[2] -= a2.y / (cv.depth * cv.depth);
 #pragma unroll
     for (int c = 0; c < 3; ++c) g_means[3 * size_t(i) + c] = r1[c] * dcam[0] + r2[c] * dcam[1] + r3[c] * dcam[2] + dpos[c];
 #pragma unroll
@@ -311,26 +319,29 @@ LFS_DI float block_sum12(float (&v)[W2C_VALS], float (*s_part)[W2C_VALS]) {
 // no lane leaves before the workgroup sum (rows past N and invisible primitives take part with dcam = 0), and the workgroup's 12 sums go to
 // w2c_partials[blockIdx.x * 12 ..] with plain stores; fg_w2c_reduce_kernel adds the rows up.
 // AA: the instantiation for the antialiased mode. The launcher queues both; the one that does not match the mode word the forward left in the workspace returns at once.
-template <bool W2C, bool AA>
+// DEPTH: 0 = the forms of the three entry points without a depth gradient, which look at the antialiased bit only (a depth-mode workspace is an ordinary workspace to
+// them: slot 9 of the rows is zero and not read); 1 / 2 = the forms of lfs_fastgs_backward_depth, which also require their depth bit in the mode word.
+template <bool W2C, bool AA, int DEPTH>
 __global__ void __launch_bounds__(256) fg_preprocess_bwd_kernel(
     const uint32_t N, const float* __restrict__ means, const float* __restrict__ scales_raw, const float* __restrict__ rot_raw,
     const Frame f, const GaussRec* __restrict__ rec, const float4* __restrict__ conic_opacity,
     const uint32_t* __restrict__ n_touched, const float* __restrict__ acc, float* __restrict__ g_means, float* __restrict__ g_scales_raw, float* __restrict__ g_rot_raw,
     float* __restrict__ g_opac_raw, float* __restrict__ densification_info, float* __restrict__ w2c_partials, const uint32_t* __restrict__ mode) {
     if (((*mode & MODE_ANTIALIASED) != 0u) != AA) return;   // (uniform: before any barrier)
+    if constexpr (DEPTH != 0) { if ((*mode & depth_mode_bits(DEPTH)) == 0u) return; }
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if constexpr (!W2C) {   // the kernel as it was: the same early returns, no operand of the sum below exists
         if (i >= N) return;
         if (n_touched[i] == 0) { preprocess_bwd_zero_rows(i, g_means, g_scales_raw, g_rot_raw, g_opac_raw); return; }
         float dcam[3];
-        preprocess_bwd_one<AA>(i, N, means, scales_raw, rot_raw, f, rec, conic_opacity, acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, dcam);
+        preprocess_bwd_one<AA, DEPTH>(i, N, means, scales_raw, rot_raw, f, rec, conic_opacity, acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, dcam);
     } else {
         __shared__ float s_part[4][W2C_VALS];
         float dcam[3] = {0.f, 0.f, 0.f}, m[3] = {0.f, 0.f, 0.f};
         bool visible = i < N;
         if (visible && n_touched[i] == 0) { preprocess_bwd_zero_rows(i, g_means, g_scales_raw, g_rot_raw, g_opac_raw); visible = false; }
         if (visible) {
-            preprocess_bwd_one<AA>(i, N, means, scales_raw, rot_raw, f, rec, conic_opacity, acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, dcam);
+            preprocess_bwd_one<AA, DEPTH>(i, N, means, scales_raw, rot_raw, f, rec, conic_opacity, acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, dcam);
             m[0] = means[3 * size_t(i)]; m[1] = means[3 * size_t(i) + 1]; m[2] = means[3 * size_t(i) + 2];
         }
         float v[W2C_VALS];
@@ -384,15 +395,26 @@ int launch_scatter(uint32_t N, const Frame& f, const PrimWs& w, int64_t* keys, h
 }
 int launch_preprocess_bwd(uint32_t N, const float* means, const float* scales_raw, const float* rot_raw, const float* sh0, const float* sh_rest, const Frame& f, const PrimWs& w,
                           float* g_means, float* g_scales_raw, float* g_rot_raw, float* g_opac_raw, float* g_sh0, float* g_sh_rest, float* densification_info, hipStream_t s,
-                          const ShAdamArgs* adam, float* grad_w2c, float* w2c_partials) {
+                          const ShAdamArgs* adam, float* grad_w2c, float* w2c_partials, int depth) {
     {
         // the mode of the forward that filled this workspace is a word IN the workspace, which the host does not read: both instantiations are queued, one returns at once
         lfs::ProfScope prof("fastgs_preprocess_bwd", s);
-#define LFS_FG_PREP_BWD(W2C, AA, PARTIALS) hipLaunchKernelGGL((fg_preprocess_bwd_kernel<W2C, AA>), dim3((N + 255) / 256), dim3(256), 0, s, N, means, scales_raw, rot_raw, f, w.rec, \
+        // depth (lfs_fastgs_backward_depth: 1 / 2, the kind the host remembers for this workspace; 0 otherwise) picks the pair of forms that is queued
+#define LFS_FG_PREP_BWD(W2C, AA, PARTIALS) LFS_FG_PREP_BWD_D(W2C, AA, 0, PARTIALS)
+#define LFS_FG_PREP_BWD_D(W2C, AA, DEPTH, PARTIALS) hipLaunchKernelGGL((fg_preprocess_bwd_kernel<W2C, AA, DEPTH>), dim3((N + 255) / 256), dim3(256), 0, s, N, means, scales_raw, rot_raw, f, w.rec, \
                                                               w.conic_opacity, w.n_touched, w.acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, PARTIALS, w.mode)
-        if (grad_w2c != nullptr) { LFS_FG_PREP_BWD(true, false, w2c_partials); LFS_FG_PREP_BWD(true, true, w2c_partials); }
-        else { LFS_FG_PREP_BWD(false, false, static_cast<float*>(nullptr)); LFS_FG_PREP_BWD(false, true, static_cast<float*>(nullptr)); }
+        if (depth == 0) {
+            if (grad_w2c != nullptr) { LFS_FG_PREP_BWD(true, false, w2c_partials); LFS_FG_PREP_BWD(true, true, w2c_partials); }
+            else { LFS_FG_PREP_BWD(false, false, static_cast<float*>(nullptr)); LFS_FG_PREP_BWD(false, true, static_cast<float*>(nullptr)); }
+        } else if (depth == 1) {
+            if (grad_w2c != nullptr) { LFS_FG_PREP_BWD_D(true, false, 1, w2c_partials); LFS_FG_PREP_BWD_D(true, true, 1, w2c_partials); }
+            else { LFS_FG_PREP_BWD_D(false, false, 1, static_cast<float*>(nullptr)); LFS_FG_PREP_BWD_D(false, true, 1, static_cast<float*>(nullptr)); }
+        } else {
+            if (grad_w2c != nullptr) { LFS_FG_PREP_BWD_D(true, false, 2, w2c_partials); LFS_FG_PREP_BWD_D(true, true, 2, w2c_partials); }
+            else { LFS_FG_PREP_BWD_D(false, false, 2, static_cast<float*>(nullptr)); LFS_FG_PREP_BWD_D(false, true, 2, static_cast<float*>(nullptr)); }
+        }
 #undef LFS_FG_PREP_BWD
+#undef LFS_FG_PREP_BWD_D
     }
     if (grad_w2c != nullptr) {
         const int rc = launch_w2c_reduce(N, w2c_partials, grad_w2c, s);
@@ -422,6 +444,38 @@ static Readback& readback() {
     }();
     return rb;
 }
+
+// The flags of the depth-mode preprocess that last filled a primitive workspace, by the workspace's address: what lfs_fastgs_render_depth and lfs_fastgs_backward_depth
+// validate against without reading the mode word back (that would be a host sync). Only workspaces filled WITH a depth flag take an entry; a preprocess without one
+// erases the entry of its address (the workspace stops counting as a depth workspace) and takes none, so ordinary forwards - evaluation renders, other views - never
+// push a depth workspace out. DEPTH_SLOTS depth forwards can be outstanding (filled, their backward still to come); one more evicts the least recently filled, whose
+// depth entry points then return LFS_E_INVALID (fastgs.py names that cause in its error). Device addresses are unique across the devices of a process (one unified
+// address space), so the address alone is the key. A mutex guards the table: the entry points may be called from several host threads.
+constexpr int DEPTH_SLOTS = 256;
+struct DepthSlot { const void* ws = nullptr; uint32_t flags = 0; uint64_t stamp = 0; };
+static DepthSlot g_depth_slots[DEPTH_SLOTS];
+static uint64_t g_depth_stamp = 0;
+static std::mutex g_depth_mutex;
+static void remember_flags(const void* ws, uint32_t flags) {
+    const bool depth = (flags & (MODE_DEPTH | MODE_INVDEPTH)) != 0;
+    std::lock_guard<std::mutex> lock(g_depth_mutex);
+    DepthSlot* pick = &g_depth_slots[0];
+    for (DepthSlot& m : g_depth_slots) {
+        if (m.ws == ws) { pick = &m; break; }
+        if (m.stamp < pick->stamp) pick = &m;
+    }
+    if (!depth) {
+        if (pick->ws == ws) *pick = DepthSlot{};
+        return;
+    }
+    pick->ws = ws; pick->flags = flags; pick->stamp = ++g_depth_stamp;
+}
+uint32_t remembered_flags(const void* ws) {   // 0: a workspace that was not (or not recently enough) filled by a depth-mode preprocess
+    std::lock_guard<std::mutex> lock(g_depth_mutex);
+    for (const DepthSlot& m : g_depth_slots)
+        if (m.ws == ws && m.stamp != 0) return m.flags;
+    return 0u;
+}
 } } // namespace lfs::fgs
 
 // n_instances of the last lfs_fastgs_preprocess call on this process: waits for the read-back event only (not for the SH kernel queued after it)
@@ -445,13 +499,18 @@ extern "C" size_t lfs_fastgs_instance_workspace_bytes(uint32_t width, uint32_t h
 
 // flags bit 0 (LFS_FASTGS_ANTIALIASED): the antialiased mode of fg_preprocess_kernel. The mode is recorded in the primitive workspace (PrimWs::mode), rewritten by
 // every call with N > 0; render and the backward entry points need no flag.
+// bits 2 / 3 (LFS_FASTGS_DEPTH / LFS_FASTGS_INVDEPTH, exclusive): the depth forms of the kernel; the host remembers the flags by the workspace's address for the
+// two depth entry points (remember_flags).
 extern "C" int lfs_fastgs_preprocess_ex(
     uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* opacities_raw,
     const float* sh_coefficients_0, const float* sh_coefficients_rest, uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position,
     uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy, float cx, float cy, float near_plane, float far_plane,
     int64_t* n_instances, void* primitive_workspace, size_t primitive_workspace_bytes, uint32_t flags, lfs_stream_t stream) {
-    if (flags & ~uint32_t(LFS_FASTGS_ANTIALIASED)) return LFS_E_INVALID;
+    if (flags & ~uint32_t(LFS_FASTGS_ANTIALIASED | LFS_FASTGS_DEPTH | LFS_FASTGS_INVDEPTH)) return LFS_E_INVALID;
+    if ((flags & LFS_FASTGS_DEPTH) && (flags & LFS_FASTGS_INVDEPTH)) return LFS_E_INVALID;
+    static_assert(LFS_FASTGS_ANTIALIASED == fgs::MODE_ANTIALIASED && LFS_FASTGS_DEPTH == fgs::MODE_DEPTH && LFS_FASTGS_INVDEPTH == fgs::MODE_INVDEPTH, "the mode word holds the flags");
     const bool aa = (flags & LFS_FASTGS_ANTIALIASED) != 0;
+    const int depth = (flags & LFS_FASTGS_DEPTH) ? 1 : (flags & LFS_FASTGS_INVDEPTH) ? 2 : 0;
     if (!n_instances || !primitive_workspace || !w2c || !cam_position || width == 0 || height == 0) return LFS_E_INVALID;
     if (active_sh_bases == 0 || active_sh_bases > 16 || (active_sh_bases > 1 && total_bases_sh_rest + 1 < active_sh_bases)) return LFS_E_INVALID;
     fgs::PrimWs w = fgs::prim_ws(primitive_workspace, N, width, height);
@@ -469,11 +528,13 @@ extern "C" int lfs_fastgs_preprocess_ex(
         if (N > 0) {
             const uint32_t pb = fgs::per_block_for(N), blocks = (N + pb - 1) / pb;
             const bool lds = size_t(T) * 8 <= 64 * 1024;
-#define LFS_FG_PREP(LDS, AA) hipLaunchKernelGGL((fgs::fg_preprocess_kernel<LDS, AA>), dim3(blocks), dim3(1024), LDS ? size_t(T) * 4 : size_t(0), s, N, pb, means, scales_raw, \
+#define LFS_FG_PREP(LDS, AA) do { if (depth == 0) LFS_FG_PREP_D(LDS, AA, 0); else if (depth == 1) LFS_FG_PREP_D(LDS, AA, 1); else LFS_FG_PREP_D(LDS, AA, 2); } while (0)
+#define LFS_FG_PREP_D(LDS, AA, DEPTH) hipLaunchKernelGGL((fgs::fg_preprocess_kernel<LDS, AA, DEPTH>), dim3(blocks), dim3(1024), LDS ? size_t(T) * 4 : size_t(0), s, N, pb, means, scales_raw, \
                                                 rotations_raw, opacities_raw, f, w.rec, w.mean2d, w.conic_opacity, w.bounds, w.n_touched, w.depth_bits, w.totals, w.mode)
             if (lds) { if (aa) LFS_FG_PREP(true, true); else LFS_FG_PREP(true, false); }
             else { if (aa) LFS_FG_PREP(false, true); else LFS_FG_PREP(false, false); }
 #undef LFS_FG_PREP
+#undef LFS_FG_PREP_D
         }
         hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, s, T, w.totals, w.offsets, n_instances);
     }
@@ -492,7 +553,9 @@ extern "C" int lfs_fastgs_preprocess_ex(
                                       reinterpret_cast<float*>(w.rec) + 8, 16, s);
         if (rc) return rc;
     }
-    return (int)hipGetLastError();
+    const int rc = (int)hipGetLastError();
+    if (rc == 0) fgs::remember_flags(primitive_workspace, flags);
+    return rc;
 }
 
 extern "C" int lfs_fastgs_preprocess(

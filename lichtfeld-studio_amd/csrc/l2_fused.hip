@@ -110,6 +110,55 @@ __global__ void __launch_bounds__(256) mse_loss_masked_kernel(
     mse_loss_body<CHW, true>(H, W, render, target, 0.f, v_render, loss, clamp, mask, sums, wscale, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
+// Depth supervision (lfs_depth_prepare / lfs_depth_l1_loss_fwd_bwd). A target is valid where it is finite and > 0; the prepared plane carries NaN elsewhere, so the
+// loss kernel needs no validity plane. sums[0] = sum_p valid_p M_p (M_p the mask byte, 255 without a mask) = 255 sum_p m_p: integer wave sums and one 64-bit integer
+// atomic per block, as mask_prepare_kernel - exact, the same on every run.
+// (in and out may be the same plane - preparing in place is part of the contract - so neither is __restrict__; every thread touches its own element only)
+__global__ void __launch_bounds__(256) depth_prepare_kernel(const uint32_t P, const float* in, const uint8_t* __restrict__ mask, float* out,
+                                                            unsigned long long* __restrict__ sums) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned int m = 0;
+    if (p < P) {
+        const float t = in[p];
+        const bool valid = t > 0.f && t < __builtin_inff();   // (NaN fails both)
+        out[p] = valid ? t : __builtin_nanf("");
+        m = valid ? (mask ? (unsigned int)mask[p] : 255u) : 0u;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m += __shfl_xor(m, d, 64);
+    __shared__ unsigned int part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned int v = part[0] + part[1] + part[2] + part[3];
+        if (v) atomicAdd(&sums[0], (unsigned long long)v);
+    }
+}
+
+// loss_acc += weight sum_p m_p |D_p - t_p| / max(sum m, 1), grad_depth_p = weight m_p sign(D_p - t_p) / max(sum m, 1), m_p = valid_p M_p / 255. With S = sums[0] =
+// 255 sum m the common factor is scale = weight / max(S, 255) per unit of M_p (a double division rounded to float once, the same value in every thread); the block
+// sums and the atomic are those of mse_loss_body.
+__global__ void __launch_bounds__(256) depth_l1_loss_kernel(const uint32_t P, const float* __restrict__ depth, const float* __restrict__ target, const uint8_t* __restrict__ mask,
+                                                            const long long* __restrict__ sums, const double weight, float* __restrict__ g_depth, float* __restrict__ loss) {
+    const long long S = sums[0];
+    const float scale = float(weight / double(S > 255 ? S : 255));
+    float acc = 0.f;
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) {
+        const float t = target[p];
+        float m = mask ? float(mask[p]) : 255.f;
+        if (!(t > 0.f)) m = 0.f;                                  // the sentinel of depth_prepare_kernel (NaN), or a target that was never prepared
+        const float d = m != 0.f ? depth[p] - t : 0.f;
+        acc += m * fabsf(d);
+        g_depth[p] = d > 0.f ? m * scale : d < 0.f ? -(m * scale) : 0.f;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+    __shared__ float part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(loss, (part[0] + part[1] + part[2] + part[3]) * scale);
+}
+
 } // namespace lfs
 
 extern "C" int lfs_activations_fwd(uint32_t N, const float* raw_quats, const float* raw_scales, const float* raw_opacities,
@@ -187,5 +236,29 @@ extern "C" int lfs_mse_loss_masked_fwd_bwd(uint32_t H, uint32_t W, const float* 
     const double wscale = double(weight) / 3.0;
     if (render_is_chw) hipLaunchKernelGGL(lfs::mse_loss_masked_kernel<true>, dim3(blocks), dim3(256), 0, s, H, W, render, target_chw, mask_u8, (const long long*)mask_sums, wscale, v_render, loss, clamp_render != 0);
     else hipLaunchKernelGGL(lfs::mse_loss_masked_kernel<false>, dim3(blocks), dim3(256), 0, s, H, W, render, target_chw, mask_u8, (const long long*)mask_sums, wscale, v_render, loss, clamp_render != 0);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lfs_depth_prepare(uint32_t H, uint32_t W, const float* target_in, const uint8_t* weights_u8, float* target_out, int64_t* sums, lfs_stream_t stream) {
+    if (!sums || uint64_t(H) * W >= (1ull << 31) || (H != 0 && W != 0 && (!target_in || !target_out))) return LFS_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(sums, 0, sizeof(int64_t), s); // the sum is written, not accumulated
+    if (e != hipSuccess) return (int)e;
+    if (H == 0 || W == 0) return LFS_OK;
+    lfs::ProfScope prof("depth_prepare", s);
+    const uint32_t P = H * W;
+    hipLaunchKernelGGL(lfs::depth_prepare_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, target_in, weights_u8, target_out, (unsigned long long*)sums);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lfs_depth_l1_loss_fwd_bwd(uint32_t H, uint32_t W, const float* depth, const float* target, const uint8_t* weights_u8, const int64_t* sums, float weight,
+                                         float* grad_depth, float* loss_acc, lfs_stream_t stream) {
+    if (H == 0 || W == 0) return LFS_OK;
+    if (!depth || !target || !sums || !grad_depth || !loss_acc || uint64_t(H) * W >= (1ull << 31)) return LFS_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    lfs::ProfScope prof("depth_l1_loss", s);
+    const uint32_t P = H * W;
+    const uint32_t blocks = (P + 255) / 256 < 2048 ? (P + 255) / 256 : 2048;
+    hipLaunchKernelGGL(lfs::depth_l1_loss_kernel, dim3(blocks), dim3(256), 0, s, P, depth, target, weights_u8, (const long long*)sums, double(weight), grad_depth, loss_acc);
     return (int)hipGetLastError();
 }

@@ -23,6 +23,10 @@ constexpr float T_THRESHOLD = 1e-4f;
 constexpr uint32_t TILE = 16;
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr uint32_t MODE_ANTIALIASED = 1u; // PrimWs::mode bit 0 (= LFS_FASTGS_ANTIALIASED of lfs_fastgs_preprocess_ex)
+constexpr uint32_t MODE_DEPTH = 4u;       // bit 2 (= LFS_FASTGS_DEPTH): r2.w of every visible record = camera-space z
+constexpr uint32_t MODE_INVDEPTH = 8u;    // bit 3 (= LFS_FASTGS_INVDEPTH): r2.w = 1 / z
+// the DEPTH template parameter of the per-primitive kernels: 0 none, 1 z, 2 1 / z
+constexpr uint32_t depth_mode_bits(int depth) { return depth == 1 ? MODE_DEPTH : depth == 2 ? MODE_INVDEPTH : 0u; }
 
 struct Frame { // one camera; w2c / cam_position stay device pointers (torch tensors of the caller)
     const float* w2c; const float* cam_pos;
@@ -37,6 +41,7 @@ inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 //            r3 unused; with (A, B, C) = log2(e) * (conic.x / 2, conic.y, conic.z / 2) and thr' = log2(e) *
 //            log(255 * opacity): sigma' = A dx^2 + B dx dy + C dy^2 is the Gaussian exponent in bits (one v_exp_f32).
 //            Antialiased mode: opacity = sigmoid(raw) * rho everywhere, and r1.w = sigmoid(raw) for the backward.
+//            Depth modes: r2.w = d = z or 1 / z (camera space), blended by the depth forms of the blend kernels like a fourth colour channel.
 //   mode     one word of the (otherwise spare) 256-byte n_instances slot: the flags of the preprocess that filled the workspace. The backward picks its
 //            instantiation by it on the device, so the backward entry points carry no flag and nothing outside the workspace remembers the mode.
 struct PrimWs {
@@ -79,6 +84,7 @@ inline InstWs inst_ws(void* base, uint32_t width, uint32_t height, uint64_t n_in
 }
 
 // accumulator row of the blend backward (16 floats per primitive, one 64-B line):
-//   0,1 dL/dmean2d * log2(e) | 2,3,4 dL/dconic (xx, xy, yy) | 5 sum alpha dL/dalpha | 6,7,8 dL/d(clamped colour) | 9..15 unused
+//   0,1 sum h (dx, dy) | 2,3,4 sum h (dx dx, dx dy, dy dy), h = -alpha dL/dalpha | 5,6,7 dL/d(clamped colour) | 8 sum alpha dL/dalpha |
+//   9 dL/dd = sum w g_depth (depth form of the backward only; 0 otherwise) | 10..15 unused
 } // namespace fgs
 } // namespace lfs

@@ -451,12 +451,16 @@ LFS_DI void wave_sum16_atomic_quad(const v2f (&V)[8], float* __restrict__ dst /*
 // The EWA blend backward's NINE sums the same way (a [64][9] block: the odd stride is conflict-free for the row writes and for the column reads alike);
 // lanes 9..15 of every quarter read a duplicate column and are dropped at the atomic. Measured against register swaps + DPP and two atomics:
 // fastgs_blend_bwd 0.452 - 0.457 -> 0.391 - 0.395 ms (profiles/r03/fastgs_blend_bwd_lds_reduce_ab.txt).
-constexpr int RED9_STRIDE = 9;
-constexpr int RED9_SCRATCH_FLOATS = (LFS_RED_ADDTID ? 16 * RED_ROW : 64 * RED9_STRIDE); // per wavefront (value-major form: rows 9..15 are read by the dropped lanes, never written)
+// NV = 10: the depth form of that backward (slot 9 = sum w g_depth) - one more store, one more live column, the same reads, swaps and atomic instruction;
+// its row-major block takes stride 11 (odd again). NV = 9 is the code it always was.
+constexpr int red_n_stride(int nv) { return nv | 1; }
+constexpr int red_n_scratch_floats(int nv) { return LFS_RED_ADDTID ? 16 * RED_ROW : 64 * red_n_stride(nv); } // per wavefront (value-major form: rows NV..15 are read by the dropped lanes, never written)
+constexpr int RED9_SCRATCH_FLOATS = red_n_scratch_floats(9);
 // ACC as for wave_sum16_atomic: 0 float atomics, 1 / 2 the two passes of the deterministic mode (det64 = the int64 accumulator row, 16 per Gaussian).
-template <int ACC = 0>
-LFS_DI void wave_sum9_atomic_lds(const float (&v)[9], float* __restrict__ dst, const uint32_t lane, float* __restrict__ scratch /* this wavefront's [RED9_SCRATCH_FLOATS] */,
+template <int ACC = 0, int NV = 9>
+LFS_DI void wave_sum9_atomic_lds(const float (&v)[NV], float* __restrict__ dst, const uint32_t lane, float* __restrict__ scratch /* this wavefront's [red_n_scratch_floats(NV)] */,
                                  unsigned long long* __restrict__ det64 = nullptr) {
+    static_assert(NV == 9 || NV == 10, "nine sums, or ten in the depth form");
     float c[16];
 #if LFS_RED_ADDTID && !defined(LFS_EMULATE)
     {   // value-major block through ds_write_addtid_b32 / ds_read_b128 (LFS_RED_ADDTID above)
@@ -464,15 +468,20 @@ LFS_DI void wave_sum9_atomic_lds(const float (&v)[9], float* __restrict__ dst, c
         // M0 is a register the compiler manages itself (LLVM does not promise to honour an "m0" clobber): the block saves it, sets it, and puts it back - it leaves no
         // trace in M0, so nothing depends on how the compiler places its own M0 initialisations around the asm. (s_nop: one wait state between the SALU write
         // of M0 and an add-TID LDS instruction; the stores have read M0 when they issue, so the restore needs none.)
-        uint32_t m0_saved;
-        asm volatile("s_mov_b32 %[sv], m0\n\ts_mov_b32 m0, %[base]\n\ts_nop 0\n\t"
-                     "ds_write_addtid_b32 %[a0] offset:0\n\tds_write_addtid_b32 %[a1] offset:288\n\tds_write_addtid_b32 %[a2] offset:576\n\tds_write_addtid_b32 %[a3] offset:864\n\t"
-                     "ds_write_addtid_b32 %[a4] offset:1152\n\tds_write_addtid_b32 %[a5] offset:1440\n\tds_write_addtid_b32 %[a6] offset:1728\n\tds_write_addtid_b32 %[a7] offset:2016\n\t"
-                     "ds_write_addtid_b32 %[a8] offset:2304\n\t"
+        // ONE text for both forms: the nine stores every form has, then TENTH - nothing for NV = 9, the store into row 9 for NV = 10 - between the same M0 frame.
+#define LFS_RED9_ASM(TENTH) "s_mov_b32 %[sv], m0\n\ts_mov_b32 m0, %[base]\n\ts_nop 0\n\t" \
+                     "ds_write_addtid_b32 %[a0] offset:0\n\tds_write_addtid_b32 %[a1] offset:288\n\tds_write_addtid_b32 %[a2] offset:576\n\tds_write_addtid_b32 %[a3] offset:864\n\t" \
+                     "ds_write_addtid_b32 %[a4] offset:1152\n\tds_write_addtid_b32 %[a5] offset:1440\n\tds_write_addtid_b32 %[a6] offset:1728\n\tds_write_addtid_b32 %[a7] offset:2016\n\t" \
+                     "ds_write_addtid_b32 %[a8] offset:2304\n\t" TENTH \
                      "s_mov_b32 m0, %[sv]"
-                     : [sv] "=&s"(m0_saved)
-                     : [a0] "v"(v[0]), [a1] "v"(v[1]), [a2] "v"(v[2]), [a3] "v"(v[3]), [a4] "v"(v[4]), [a5] "v"(v[5]), [a6] "v"(v[6]), [a7] "v"(v[7]), [a8] "v"(v[8]),
-                       [base] "s"(base) : "memory");
+#define LFS_RED9_OPERANDS [a0] "v"(v[0]), [a1] "v"(v[1]), [a2] "v"(v[2]), [a3] "v"(v[3]), [a4] "v"(v[4]), [a5] "v"(v[5]), [a6] "v"(v[6]), [a7] "v"(v[7]), [a8] "v"(v[8])
+        uint32_t m0_saved;
+        if constexpr (NV == 9)
+            asm volatile(LFS_RED9_ASM("") : [sv] "=&s"(m0_saved) : LFS_RED9_OPERANDS, [base] "s"(base) : "memory");
+        else
+            asm volatile(LFS_RED9_ASM("ds_write_addtid_b32 %[a9] offset:2592\n\t") : [sv] "=&s"(m0_saved) : LFS_RED9_OPERANDS, [a9] "v"(v[NV - 1]), [base] "s"(base) : "memory");
+#undef LFS_RED9_ASM
+#undef LFS_RED9_OPERANDS
         __builtin_amdgcn_wave_barrier();
         const float4* rd = reinterpret_cast<const float4*>(scratch + (lane & 15) * RED_ROW + 4 * (lane >> 4));
 #pragma unroll
@@ -480,17 +489,18 @@ LFS_DI void wave_sum9_atomic_lds(const float (&v)[9], float* __restrict__ dst, c
         __builtin_amdgcn_wave_barrier();
     }
 #else
-    float* wr = scratch + lane * RED9_STRIDE;
+    constexpr int STRIDE = red_n_stride(NV);
+    float* wr = scratch + lane * STRIDE;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) wr[k] = v[k];
+    for (int k = 0; k < NV; ++k) wr[k] = v[k];
     LFS_WAVE_LOCKSTEP();
 #ifndef LFS_EMULATE
     __builtin_amdgcn_wave_barrier();
 #endif
-    const uint32_t r = min(lane & 15u, 8u);
-    const float* rd = scratch + (lane >> 4) * (16 * RED9_STRIDE) + r;
+    const uint32_t r = min(lane & 15u, uint32_t(NV - 1));
+    const float* rd = scratch + (lane >> 4) * (16 * STRIDE) + r;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) c[i] = rd[i * RED9_STRIDE];
+    for (int i = 0; i < 16; ++i) c[i] = rd[i * STRIDE];
     LFS_WAVE_LOCKSTEP();
 #ifndef LFS_EMULATE
     __builtin_amdgcn_wave_barrier();
@@ -503,7 +513,7 @@ LFS_DI void wave_sum9_atomic_lds(const float (&v)[9], float* __restrict__ dst, c
     t = __uint_as_float(q[0]) + __uint_as_float(q[1]);
     auto rr = __builtin_amdgcn_permlane32_swap(__float_as_uint(t), __float_as_uint(t), false, false);
     t = __uint_as_float(rr[0]) + __uint_as_float(rr[1]);
-    if (lane < 9) {
+    if (lane < uint32_t(NV)) {
         if (ACC == 0) unsafeAtomicAdd(dst + lane, t);
 #ifndef LFS_EMULATE
         else if (ACC == 1) atomicMax(reinterpret_cast<uint32_t*>(dst) + lane, __float_as_uint(t) & 0x7fffffffu);

@@ -527,13 +527,14 @@ torch::Tensor GutTrainStep::radii() const {
 // ---------------------------------------------------------------------------------------------------------
 // fast_gs::rasterization (rasterization_api.h:27-75, src/rasterization_api.cu) and fusedssim (ssim.cuh:11-30)
 // ---------------------------------------------------------------------------------------------------------
-// the forward of both modes; the mode lives in per_primitive_buffers from here on, so backward_wrapper below serves either
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int>
-lfs::fastgs_forward_wrapper_ex(
+// the forward of every mode (flags of lfs_fastgs_preprocess_ex; depth: also the accumulated depth plane); the mode lives in per_primitive_buffers from here on
+namespace {
+struct FastgsForward { at::Tensor image, alpha, depth, prim, inst; int64_t n_instances; };
+FastgsForward fastgs_forward_impl(
     const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
     const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
     const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane, const bool antialiased) {
+    const float center_y, const float near_plane, const float far_plane, const uint32_t flags, const bool want_depth) {
     LFS_DEVICE_GUARD(means);
     LFS_CHECK_INPUT(means); LFS_CHECK_INPUT(scales_raw); LFS_CHECK_INPUT(rotations_raw); LFS_CHECK_INPUT(opacities_raw);
     LFS_CHECK_INPUT(sh_coefficients_0); LFS_CHECK_INPUT(sh_coefficients_rest);
@@ -547,13 +548,76 @@ lfs::fastgs_forward_wrapper_ex(
                                       sh_coefficients_0.data_ptr<float>(), total_rest ? sh_coefficients_rest.data_ptr<float>() : nullptr, total_rest,
                                       w2c_c.data_ptr<float>(), cam_c.data_ptr<float>(), (uint32_t)active_sh_bases, (uint32_t)width, (uint32_t)height,
                                       focal_x, focal_y, center_x, center_y, near_plane, far_plane, n_inst_dev.data_ptr<int64_t>(), prim.data_ptr(),
-                                      (size_t)prim.numel(), antialiased ? LFS_FASTGS_ANTIALIASED : 0u, cur_stream()), "fast_gs::rasterization::forward (preprocess)");
+                                      (size_t)prim.numel(), flags, cur_stream()), "fast_gs::rasterization::forward (preprocess)");
     const int64_t n_instances = n_inst_dev.item<int64_t>(); // the host sync of forward.cu:114-117
     at::Tensor inst = at::empty({(int64_t)std::max<size_t>(256, lfs_fastgs_instance_workspace_bytes((uint32_t)width, (uint32_t)height, n_instances))}, bopt);
-    check_rc(lfs_fastgs_render(N, (uint32_t)width, (uint32_t)height, n_instances, prim.data_ptr(), (size_t)prim.numel(), inst.data_ptr(), (size_t)inst.numel(),
-                               image.data_ptr<float>(), alpha.data_ptr<float>(), cur_stream()), "fast_gs::rasterization::forward (render)");
-    at::Tensor none = at::empty({0}, bopt);
-    return {image, alpha, prim, none, inst, none.clone(), 0, (int)n_instances, 0, 0, 0};
+    at::Tensor depth;
+    if (want_depth) {
+        depth = at::empty({1, height, width}, fopt);
+        check_rc(lfs_fastgs_render_depth(N, (uint32_t)width, (uint32_t)height, n_instances, prim.data_ptr(), (size_t)prim.numel(), inst.data_ptr(), (size_t)inst.numel(),
+                                         image.data_ptr<float>(), alpha.data_ptr<float>(), depth.data_ptr<float>(), cur_stream()), "lfs::fastgs_forward_wrapper_depth (render)");
+    } else {
+        check_rc(lfs_fastgs_render(N, (uint32_t)width, (uint32_t)height, n_instances, prim.data_ptr(), (size_t)prim.numel(), inst.data_ptr(), (size_t)inst.numel(),
+                                   image.data_ptr<float>(), alpha.data_ptr<float>(), cur_stream()), "fast_gs::rasterization::forward (render)");
+    }
+    return {image, alpha, depth, prim, inst, n_instances};
+}
+} // namespace
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int>
+lfs::fastgs_forward_wrapper_ex(
+    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
+    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
+    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
+    const float center_y, const float near_plane, const float far_plane, const bool antialiased) {
+    const FastgsForward f = fastgs_forward_impl(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c, cam_position, active_sh_bases,
+                                                width, height, focal_x, focal_y, center_x, center_y, near_plane, far_plane, antialiased ? LFS_FASTGS_ANTIALIASED : 0u, false);
+    at::Tensor none = at::empty({0}, means.options().dtype(at::kByte));
+    return {f.image, f.alpha, f.prim, none, f.inst, none.clone(), 0, (int)f.n_instances, 0, 0, 0};
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int> lfs::fastgs_forward_wrapper_depth(
+    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
+    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
+    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
+    const float center_y, const float near_plane, const float far_plane, const bool antialiased, const bool inverse_depth) {
+    const uint32_t flags = (antialiased ? LFS_FASTGS_ANTIALIASED : 0u) | (inverse_depth ? LFS_FASTGS_INVDEPTH : LFS_FASTGS_DEPTH);
+    const FastgsForward f = fastgs_forward_impl(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c, cam_position, active_sh_bases,
+                                                width, height, focal_x, focal_y, center_x, center_y, near_plane, far_plane, flags, true);
+    return {f.image, f.alpha, f.depth, f.prim, f.inst, (int)f.n_instances};
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> lfs::fastgs_backward_wrapper_depth(
+    torch::Tensor& densification_info, const torch::Tensor& grad_image, const torch::Tensor& grad_alpha, const torch::Tensor& grad_depth, const torch::Tensor& alpha,
+    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& sh_coefficients_rest,
+    const torch::Tensor& per_primitive_buffers, const torch::Tensor& per_instance_buffers, const torch::Tensor& w2c, const torch::Tensor& cam_position,
+    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
+    const float center_y, const float near_plane, const float far_plane, const int n_instances) {
+    LFS_DEVICE_GUARD(means);
+    const uint32_t N = (uint32_t)means.size(0), total_rest = (uint32_t)sh_coefficients_rest.size(1);
+    const auto fopt = means.options().dtype(at::kFloat);
+    at::Tensor g_means = at::empty({N, 3}, fopt), g_scales = at::empty({N, 3}, fopt), g_rot = at::empty({N, 4}, fopt), g_opac = at::empty({N, 1}, fopt);
+    at::Tensor g_sh0 = at::empty({N, 1, 3}, fopt), g_shr = at::empty({N, (int64_t)total_rest, 3}, fopt);
+    const at::Tensor gi = grad_image.contiguous(), ga = grad_alpha.contiguous(), gd = grad_depth.contiguous(), al = alpha.contiguous(), w2c_c = w2c.contiguous(),
+                     cam_c = cam_position.contiguous();
+    TORCH_CHECK(gd.numel() == (int64_t)width * height, "grad_depth must hold one [1,H,W] plane");
+    const bool dens = densification_info.defined() && densification_info.dim() > 0 && densification_info.size(0) > 0;
+    at::Tensor g_w2c, ws;
+    if (w2c.requires_grad()) {
+        TORCH_CHECK(w2c.numel() == 16, "w2c must hold one [4,4] transform");
+        g_w2c = at::empty_like(w2c_c);
+        ws = at::empty({(int64_t)lfs_fastgs_w2c_workspace_bytes(N)}, means.options().dtype(at::kByte));
+    }
+    check_rc(lfs_fastgs_backward_depth(N, means.data_ptr<float>(), scales_raw.data_ptr<float>(), rotations_raw.data_ptr<float>(), nullptr,
+                                       total_rest ? sh_coefficients_rest.data_ptr<float>() : nullptr, total_rest, w2c_c.data_ptr<float>(), cam_c.data_ptr<float>(),
+                                       (uint32_t)active_sh_bases, (uint32_t)width, (uint32_t)height, focal_x, focal_y, center_x, center_y, near_plane, far_plane,
+                                       (int64_t)n_instances, per_primitive_buffers.data_ptr(), (size_t)per_primitive_buffers.numel(), per_instance_buffers.data_ptr(),
+                                       (size_t)per_instance_buffers.numel(), gi.data_ptr<float>(), ga.data_ptr<float>(), al.data_ptr<float>(),
+                                       dens ? densification_info.data_ptr<float>() : nullptr, g_means.data_ptr<float>(), g_scales.data_ptr<float>(),
+                                       g_rot.data_ptr<float>(), g_opac.data_ptr<float>(), g_sh0.data_ptr<float>(), total_rest ? g_shr.data_ptr<float>() : nullptr,
+                                       gd.data_ptr<float>(), g_w2c.defined() ? g_w2c.data_ptr<float>() : nullptr, ws.defined() ? ws.data_ptr() : nullptr,
+                                       ws.defined() ? (size_t)ws.numel() : 0, cur_stream()), "lfs::fastgs_backward_wrapper_depth");
+    return {g_means, g_scales, g_rot, g_opac, g_sh0, g_shr, g_w2c};
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int>

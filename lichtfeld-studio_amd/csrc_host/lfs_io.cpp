@@ -594,12 +594,14 @@ void to_rgb(const uint8_t* src, int ch, size_t n, uint8_t* dst) {
 }
 
 // alpha_only: the alpha channel alone, [h,w] (colour types 4 and 6; anything else is LFS_IO_E_UNSUPPORTED), samples reduced as the colour path reduces them
-uint8_t* decode_png(const std::vector<char>& f, int32_t& w, int32_t& h, bool alpha_only = false) {
+// gray16 (lfs_image_load_gray16): a 16-bit greyscale file's samples with both bytes, [h,w], into *gray16; nothing else is decoded and nullptr is returned
+uint8_t* decode_png(const std::vector<char>& f, int32_t& w, int32_t& h, bool alpha_only = false, std::vector<uint16_t>* gray16 = nullptr) {
     const unsigned char* u = (const unsigned char*)f.data();
     w = (int32_t)be32(u + 16); h = (int32_t)be32(u + 20);
     const int depth = u[24], ct = u[25], interlace = u[28];
     if (interlace) fail(LFS_IO_E_UNSUPPORTED, "PNG: interlaced files are not supported");
     if (alpha_only && ct != 4 && ct != 6) fail(LFS_IO_E_UNSUPPORTED, "PNG: colour type %d has no alpha channel", ct);
+    if (gray16 && (ct != 0 || depth != 16)) fail(LFS_IO_E_UNSUPPORTED, "PNG: not a 16-bit greyscale file (colour type %d, bit depth %d)", ct, depth);
     if (ct != 0 && ct != 2 && ct != 3 && ct != 4 && ct != 6) fail(LFS_IO_E_FORMAT, "PNG: bad colour type %d", ct);
     if (depth != 1 && depth != 2 && depth != 4 && depth != 8 && depth != 16) fail(LFS_IO_E_FORMAT, "PNG: bad bit depth %d", depth);
     if ((depth < 8 && ct != 0 && ct != 3) || (depth == 16 && ct == 3)) // PNG spec table 11.1: packed samples only for grey / palette, no 16-bit palette
@@ -625,7 +627,8 @@ uint8_t* decode_png(const std::vector<char>& f, int32_t& w, int32_t& h, bool alp
     if (zr != Z_OK || out_len != raw.size()) fail(LFS_IO_E_FORMAT, "PNG: corrupt image data (zlib %d)", zr);
     // undo the scanline filters in place
     std::vector<unsigned char> prev(row_bytes, 0);
-    std::vector<uint8_t> pix((size_t)w * h * samples); // 8 bit per sample
+    std::vector<uint8_t> pix(gray16 ? 0 : (size_t)w * h * samples); // 8 bit per sample
+    if (gray16) gray16->resize((size_t)w * h);
     for (int y = 0; y < h; ++y) {
         unsigned char* row = raw.data() + (size_t)y * (row_bytes + 1);
         const int ft = row[0];
@@ -644,6 +647,11 @@ uint8_t* decode_png(const std::vector<char>& f, int32_t& w, int32_t& h, bool alp
             cur[i] = (unsigned char)(cur[i] + pred);
         }
         std::memcpy(prev.data(), cur, row_bytes);
+        if (gray16) {
+            uint16_t* d16 = gray16->data() + (size_t)y * w;
+            for (int x = 0; x < w; ++x) d16[x] = (uint16_t)((cur[2 * (size_t)x] << 8) | cur[2 * (size_t)x + 1]);
+            continue;
+        }
         uint8_t* dst = pix.data() + (size_t)y * w * samples;
         if (depth == 8) std::memcpy(dst, cur, (size_t)w * samples);
         else if (depth == 16) for (size_t i = 0; i < (size_t)w * samples; ++i) dst[i] = cur[2 * i]; // high byte
@@ -652,6 +660,7 @@ uint8_t* decode_png(const std::vector<char>& f, int32_t& w, int32_t& h, bool alp
             dst[x] = ct == 3 ? (uint8_t)v : (uint8_t)(v * 255 / ((1 << depth) - 1));
         }
     }
+    if (gray16) return nullptr;
     if (alpha_only) {
         uint8_t* a = (uint8_t*)std::malloc((size_t)w * h);
         if (!a) throw std::bad_alloc();
@@ -1125,6 +1134,21 @@ int lfs_image_load_alpha8(const char* path, uint8_t** data, int32_t* width, int3
         const auto f = slurp(path);
         if (f.size() >= 33 && std::memcmp(f.data(), kPngSig, 8) == 0) { *data = decode_png(f, *width, *height, true); return; }
         fail(LFS_IO_E_UNSUPPORTED, "No alpha channel can be read from %s", path);
+    });
+}
+
+int lfs_image_load_gray16(const char* path, uint16_t** data, int32_t* width, int32_t* height) {
+    return guarded([&] {
+        if (!path || !data || !width || !height) fail(LFS_IO_E_INVALID, "lfs_image_load_gray16: bad arguments");
+        *data = nullptr;
+        const auto f = slurp(path);
+        if (f.size() < 33 || std::memcmp(f.data(), kPngSig, 8) != 0) fail(LFS_IO_E_UNSUPPORTED, "No 16-bit greyscale samples can be read from %s", path);
+        std::vector<uint16_t> px;
+        decode_png(f, *width, *height, false, &px);
+        uint16_t* out = (uint16_t*)std::malloc(px.size() * sizeof(uint16_t));
+        if (!out) throw std::bad_alloc();
+        std::memcpy(out, px.data(), px.size() * sizeof(uint16_t));
+        *data = out;
     });
 }
 

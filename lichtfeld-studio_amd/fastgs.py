@@ -15,7 +15,7 @@ from typing import Optional, Tuple
 import torch
 
 from .capi import LfsError, check, load_library, ptr, require_gpu, stream, workspace
-from .rasterizer import Camera, RenderOutput, SplatModel
+from .rasterizer import Camera, RenderMode, RenderOutput, SplatModel
 
 
 @dataclass
@@ -31,9 +31,11 @@ class FastGSSettings:  # rasterization_api.h:12-24
     near_plane: float
     far_plane: float
     antialiased: bool = False   # opacity * sqrt(det(Sigma2d) / det(Sigma2d + 0.3 I)) (LFS_FASTGS_ANTIALIASED; the reference's OptimizationParameters::antialiasing)
+    depth: str = "none"         # "depth" | "invdepth": the records also carry z | 1 / z (LFS_FASTGS_DEPTH | LFS_FASTGS_INVDEPTH) for forward_wrapper_depth
 
 
 ANTIALIASED = 1         # LFS_FASTGS_ANTIALIASED
+DEPTH_FLAGS = {"none": 0, "depth": 4, "invdepth": 8}   # LFS_FASTGS_DEPTH, LFS_FASTGS_INVDEPTH
 ASYNC_READBACK = True   # False: n_instances via a stream synchronisation (A/B timing)
 
 
@@ -44,7 +46,20 @@ def _frame_args(s: FastGSSettings):
 
 def forward_wrapper(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c, s: FastGSSettings):
     """-> (image [3,H,W], alpha [1,H,W], primitive_workspace, instance_workspace, n_instances). s.antialiased: the antialiased mode; the primitive workspace
-    remembers it, so backward_wrapper takes the same arguments in both modes."""
+    remembers it, so backward_wrapper takes the same arguments in both modes. (s.depth is honoured in the preprocess, but this function returns no depth plane:
+    forward_wrapper_depth does.)"""
+    return _forward(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c, s, False)
+
+
+def forward_wrapper_depth(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c, s: FastGSSettings):
+    """-> (image, alpha, depth [1,H,W], primitive_workspace, instance_workspace, n_instances) with s.depth "depth" | "invdepth": depth = sum_i w_i d_i, d_i = z_i or
+    1 / z_i in camera space - the ACCUMULATED value (the reference's D / RGB_D); image and alpha are forward_wrapper's bit for bit."""
+    if s.depth not in ("depth", "invdepth"):
+        raise LfsError(f"forward_wrapper_depth needs FastGSSettings.depth 'depth' or 'invdepth' (got {s.depth!r})")
+    return _forward(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c, s, True)
+
+
+def _forward(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c, s: FastGSSettings, want_depth: bool):
     w2c = w2c.reshape(-1, 4, 4)[0].contiguous()
     cam_position = s.cam_position.reshape(-1)[:3].contiguous()
     opac = opacities_raw.reshape(-1)
@@ -59,9 +74,12 @@ def forward_wrapper(means, scales_raw, rotations_raw, opacities_raw, sh_coeffici
     lib, dev = load_library(), means.device
     pws = torch.empty(lib.lfs_fastgs_primitive_workspace_bytes(C.c_uint32(N), C.c_uint32(s.width), C.c_uint32(s.height)), dtype=torch.uint8, device=dev)
     n_inst_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-    if s.antialiased:
+    if s.depth not in DEPTH_FLAGS:
+        raise LfsError(f"FastGSSettings.depth must be 'none', 'depth' or 'invdepth' (got {s.depth!r})")
+    flags = (ANTIALIASED if s.antialiased else 0) | DEPTH_FLAGS[s.depth]
+    if flags:
         check(lib.lfs_fastgs_preprocess_ex(C.c_uint32(N), ptr(means), ptr(scales_raw), ptr(rotations_raw), ptr(opac), ptr(sh0), ptr(shr), C.c_uint32(total_rest),
-                                           ptr(w2c), ptr(cam_position), *_frame_args(s), ptr(n_inst_dev), ptr(pws), C.c_size_t(pws.numel()), C.c_uint32(ANTIALIASED),
+                                           ptr(w2c), ptr(cam_position), *_frame_args(s), ptr(n_inst_dev), ptr(pws), C.c_size_t(pws.numel()), C.c_uint32(flags),
                                            stream()), "fastgs_preprocess_ex")
     else:
         check(lib.lfs_fastgs_preprocess(C.c_uint32(N), ptr(means), ptr(scales_raw), ptr(rotations_raw), ptr(opac), ptr(sh0), ptr(shr), C.c_uint32(total_rest),
@@ -77,6 +95,11 @@ def forward_wrapper(means, scales_raw, rotations_raw, opacities_raw, sh_coeffici
     iws = torch.empty(max(256, lib.lfs_fastgs_instance_workspace_bytes(C.c_uint32(s.width), C.c_uint32(s.height), C.c_int64(n_instances))), dtype=torch.uint8, device=dev)
     image = torch.empty((3, s.height, s.width), dtype=means.dtype, device=dev)
     alpha = torch.empty((1, s.height, s.width), dtype=means.dtype, device=dev)
+    if want_depth:
+        depth = torch.empty((1, s.height, s.width), dtype=means.dtype, device=dev)
+        check(lib.lfs_fastgs_render_depth(C.c_uint32(N), C.c_uint32(s.width), C.c_uint32(s.height), C.c_int64(n_instances), ptr(pws), C.c_size_t(pws.numel()),
+                                          ptr(iws), C.c_size_t(iws.numel()), ptr(image), ptr(alpha), ptr(depth), stream()), "fastgs_render_depth")
+        return image, alpha, depth, pws, iws, n_instances
     check(lib.lfs_fastgs_render(C.c_uint32(N), C.c_uint32(s.width), C.c_uint32(s.height), C.c_int64(n_instances), ptr(pws), C.c_size_t(pws.numel()),
                                 ptr(iws), C.c_size_t(iws.numel()), ptr(image), ptr(alpha), stream()), "fastgs_render")
     return image, alpha, pws, iws, n_instances
@@ -84,14 +107,16 @@ def forward_wrapper(means, scales_raw, rotations_raw, opacities_raw, sh_coeffici
 
 def backward_wrapper(densification_info: Optional[torch.Tensor], grad_image, grad_alpha, image, alpha, means, scales_raw, rotations_raw,
                      sh_coefficients_0, sh_coefficients_rest, primitive_workspace, instance_workspace, w2c, s: FastGSSettings, n_instances: int, out=None,
-                     adam_sh_rest: Optional[dict] = None, grad_w2c: Optional[torch.Tensor] = None):
+                     adam_sh_rest: Optional[dict] = None, grad_w2c: Optional[torch.Tensor] = None, grad_depth: Optional[torch.Tensor] = None):
     """-> (grad_means, grad_scales_raw, grad_rotations_raw, grad_opacities_raw [N,1], grad_sh_coefficients_0, grad_sh_coefficients_rest);
     densification_info [2,N] (when given and non-empty) is accumulated into in place (kernels_backward.cuh:229-232).
     Extension `adam_sh_rest` (FusedAdam.prepare_inline of sh_coefficients_rest; single-view steps): the rest-coefficient gradient is not
     written, the coefficients and their moments are updated in place by the SH backward (lfs_fastgs_backward_adam).
     `grad_w2c` (pose optimisation; a contiguous float32 out buffer of 16 elements, e.g. zeros_like(w2c)): the camera gradient the reference's backward returns
     when w2c requires grad (rasterization_api.cu:133-136) is WRITTEN into it - rows 0-2 = sum over the visible primitives of dL/d(mean in camera space) (x) (mean, 1),
-    row 3 = 0 (lfs_fastgs_backward_w2c). None: today's entry points. Not combined with adam_sh_rest."""
+    row 3 = 0 (lfs_fastgs_backward_w2c). None: today's entry points. Not combined with adam_sh_rest.
+    `grad_depth` ([1,H,W] or [H,W]; the workspace of a forward with s.depth on): the gradient of forward_wrapper_depth's depth plane (lfs_fastgs_backward_depth) - depth
+    is blended as a fourth channel, and dL/dz reaches grad_means and, with grad_w2c, row 2 of the camera gradient. Not combined with adam_sh_rest."""
     w2c = w2c.reshape(-1, 4, 4)[0].contiguous()
     cam_position = s.cam_position.reshape(-1)[:3].contiguous()
     grad_image, grad_alpha, alpha = grad_image.contiguous(), grad_alpha.contiguous(), alpha.contiguous()
@@ -111,12 +136,30 @@ def backward_wrapper(densification_info: Optional[torch.Tensor], grad_image, gra
         g_opac = torch.empty((N, 1), dtype=means.dtype, device=means.device)
         g_sh0 = torch.empty((N, 1, 3), dtype=means.dtype, device=means.device)
         g_shr = torch.empty_like(shr)
+    if grad_depth is not None and adam_sh_rest is not None:
+        raise LfsError("grad_depth is not available together with adam_sh_rest: depth supervision takes the separate optimizer")
     if grad_w2c is not None:
         if adam_sh_rest is not None:
             raise LfsError("grad_w2c is not available together with adam_sh_rest: pose optimisation takes the separate optimizer")
         if grad_w2c.numel() != 16 or grad_w2c.dtype != torch.float32 or not grad_w2c.is_contiguous():
             raise LfsError("grad_w2c must be a contiguous float32 buffer of 16 elements ([4,4] or [1,4,4])")
         require_gpu(grad_w2c)
+    if grad_depth is not None:
+        grad_depth = grad_depth.contiguous()
+        require_gpu(grad_depth)
+        if grad_depth.numel() != s.width * s.height or grad_depth.dtype != torch.float32:
+            raise LfsError("grad_depth must be a float32 [1,H,W] tensor")
+        lib = load_library()
+        ws = workspace(lib.lfs_fastgs_w2c_workspace_bytes(C.c_uint32(N)), means.device, "fastgs_w2c") if grad_w2c is not None else None
+        check(lib.lfs_fastgs_backward_depth(
+            C.c_uint32(N), ptr(means), ptr(scales_raw), ptr(rotations_raw), ptr(sh0), ptr(shr), C.c_uint32(total_rest), ptr(w2c), ptr(cam_position), *_frame_args(s),
+            C.c_int64(n_instances), ptr(primitive_workspace), C.c_size_t(primitive_workspace.numel()), ptr(instance_workspace), C.c_size_t(instance_workspace.numel()),
+            ptr(grad_image), ptr(grad_alpha), ptr(alpha), ptr(dens), ptr(g_means), ptr(g_scales), ptr(g_rot), ptr(g_opac), ptr(g_sh0), ptr(g_shr),
+            ptr(grad_depth), ptr(grad_w2c), ptr(ws), C.c_size_t(ws.numel() if ws is not None else 0), stream()),
+            "fastgs_backward_depth (LFS_E_INVALID here also means: this workspace is not known as a depth-mode workspace - its forward ran without FastGSSettings.depth, "
+            "or more than 256 depth-mode forwards were started since without their backward and it was forgotten)")
+        return g_means, g_scales, g_rot, g_opac, g_sh0, g_shr
+    if grad_w2c is not None:
         lib = load_library()
         ws = workspace(lib.lfs_fastgs_w2c_workspace_bytes(C.c_uint32(N)), means.device, "fastgs_w2c")
         check(lib.lfs_fastgs_backward_w2c(
@@ -148,33 +191,49 @@ class FastGSRasterize(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest, w2c, densification_info, settings: FastGSSettings):
-        image, alpha, pws, iws, n_instances = forward_wrapper(means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest, w2c, settings)
+        depth = None
+        if settings.depth != "none":   # (image, alpha, depth): the accumulated depth, so that autograd can divide by alpha outside the op
+            image, alpha, depth, pws, iws, n_instances = forward_wrapper_depth(means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest, w2c, settings)
+        else:
+            image, alpha, pws, iws, n_instances = forward_wrapper(means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest, w2c, settings)
         ctx.save_for_backward(image, alpha, means, scales_raw, rotations_raw, sh0, sh_rest, w2c)
         ctx.state = (pws, iws, n_instances, settings, densification_info, opacities_raw.shape)
-        return image, alpha
+        return (image, alpha) if depth is None else (image, alpha, depth)
 
     @staticmethod
-    def backward(ctx, grad_image, grad_alpha):
+    def backward(ctx, grad_image, grad_alpha, grad_depth=None):
         image, alpha, means, scales_raw, rotations_raw, sh0, sh_rest, w2c = ctx.saved_tensors
         pws, iws, n_instances, settings, dens, opac_shape = ctx.state
         g_w2c = torch.empty_like(w2c, memory_format=torch.contiguous_format) if ctx.needs_input_grad[6] else None   # pose optimisation: fast_rasterizer_autograd.cpp hands grad_w2c on
         g = backward_wrapper(dens, grad_image, grad_alpha, image, alpha, means, scales_raw, rotations_raw, sh0, sh_rest, pws, iws, w2c, settings, n_instances,
-                             grad_w2c=g_w2c)
+                             grad_w2c=g_w2c, grad_depth=grad_depth)
         return g[0], g[1], g[2], g[3].reshape(opac_shape), g[4], g[5], g_w2c, None, None
 
 
-def fast_rasterize(camera: Camera, model: SplatModel, bg_color: torch.Tensor, densification_info: Optional[torch.Tensor] = None, antialiased: bool = False) -> RenderOutput:
-    """fast_rasterizer.cpp:12-68; antialiased: FastGSSettings.antialiased (an extension: the reference's fast_rasterize has no such argument)"""
+def fast_rasterize(camera: Camera, model: SplatModel, bg_color: torch.Tensor, densification_info: Optional[torch.Tensor] = None, antialiased: bool = False,
+                   render_mode: RenderMode = RenderMode.RGB, depth_kind: str = "depth") -> RenderOutput:
+    """fast_rasterizer.cpp:12-68; antialiased: FastGSSettings.antialiased (an extension: the reference's fast_rasterize has no such argument).
+    render_mode (the reference's RenderMode, which its EWA path ignores): D / RGB_D fill RenderOutput.depth [1,H,W] with the accumulated sum w_i d_i, ED / RGB_ED with
+    that over alpha.clamp_min(1e-10) (rasterizer.py's rule); D / ED return image None (the colour is still rendered inside). depth_kind "depth": d = z,
+    "invdepth": d = 1 / z. RGB: everything as before."""
+    render_mode = RenderMode(render_mode)
+    if depth_kind not in ("depth", "invdepth"):
+        raise ValueError(f"depth_kind must be 'depth' or 'invdepth' (got {depth_kind!r})")
     W, H = int(camera.image_width), int(camera.image_height)
     K = camera.K.reshape(-1, 3, 3)[0]
     w2c = camera.world_view_transform
     R, t = w2c.reshape(-1, 4, 4)[0][:3, :3], w2c.reshape(-1, 4, 4)[0][:3, 3]
     deg = model.get_active_sh_degree()
     settings = FastGSSettings(cam_position=(-(R.T @ t)).contiguous(), active_sh_bases=(deg + 1) ** 2, width=W, height=H,
-                              focal_x=float(K[0, 0]), focal_y=float(K[1, 1]), center_x=float(K[0, 2]), center_y=float(K[1, 2]), near_plane=0.01, far_plane=1e10, antialiased=bool(antialiased))
-    image, alpha = FastGSRasterize.apply(model.means, model.raw_scales, model.raw_quats, model.raw_opacities, model.sh0, model.shN, w2c, densification_info, settings)
-    image = image + (1.0 - alpha) * bg_color.view(3, 1, 1)
-    return RenderOutput(image=image, alpha=alpha, depth=None, means2d=None, depths=None, radii=None, visibility=None, width=W, height=H, n_isects=0)
+                              focal_x=float(K[0, 0]), focal_y=float(K[1, 1]), center_x=float(K[0, 2]), center_y=float(K[1, 2]), near_plane=0.01, far_plane=1e10, antialiased=bool(antialiased),
+                              depth="none" if render_mode == RenderMode.RGB else depth_kind)
+    out = FastGSRasterize.apply(model.means, model.raw_scales, model.raw_quats, model.raw_opacities, model.sh0, model.shN, w2c, densification_info, settings)
+    image, alpha = out[0], out[1]
+    depth = None
+    if render_mode != RenderMode.RGB:
+        depth = out[2] if render_mode in (RenderMode.D, RenderMode.RGB_D) else out[2] / alpha.clamp_min(1e-10)
+    image = image + (1.0 - alpha) * bg_color.view(3, 1, 1) if render_mode in (RenderMode.RGB, RenderMode.RGB_D, RenderMode.RGB_ED) else None
+    return RenderOutput(image=image, alpha=alpha, depth=depth, means2d=None, depths=None, radii=None, visibility=None, width=W, height=H, n_isects=0)
 
 
 def mse_loss_chw_fwd_bwd(render_chw: torch.Tensor, target_chw: torch.Tensor, weight: float, loss_acc: torch.Tensor) -> torch.Tensor:
@@ -190,17 +249,26 @@ def mse_loss_chw_fwd_bwd(render_chw: torch.Tensor, target_chw: torch.Tensor, wei
 
 def render_and_backward(settings: FastGSSettings, w2c: torch.Tensor, model: SplatModel, target_chw: torch.Tensor, weight: float, grads, loss_acc: torch.Tensor,
                         densification_info: Optional[torch.Tensor] = None, loss: str = "mse", lambda_dssim: float = 0.2, bilateral=None, image_idx: int = 0,
-                        adam_shN: Optional[dict] = None, grad_w2c: Optional[torch.Tensor] = None, mask=None, mask_alpha_weight: float = 0.0):
+                        adam_shN: Optional[dict] = None, grad_w2c: Optional[torch.Tensor] = None, mask=None, mask_alpha_weight: float = 0.0,
+                        depth_target=None, depth_weight: float = 0.0):
     """One training view without an autograd graph (black background; loss "mse" or the trainer's "l1_ssim", trainer.cpp:122-125):
     forward, [bilateral-grid slice, trainer.cpp:662-664,] loss, backward; the gradients of (means, sh0, shN, raw_scales, raw_quats,
     raw_opacities) are WRITTEN into `grads` (param-group order); the bilateral grid's gradient is accumulated into its .grad;
     `grad_w2c` (optional out buffer, pose optimisation): the camera gradient is written into it (backward_wrapper).
     mask (a losses.PreparedMask): the masked loss on `shown`; with mask_alpha_weight > 0 ("segment", l1_ssim) the opacity penalty outside the mask, whose
-    gradient replaces the zero alpha gradient of the backward."""
+    gradient replaces the zero alpha gradient of the backward.
+    depth_target (a losses.PreparedDepth; settings.depth "depth" | "invdepth" says what it holds): loss_acc += weight * depth_weight * the masked L1 between the
+    accumulated depth map and the target (lfs_depth_l1_loss_fwd_bwd), and the backward is the depth one. None: everything as before."""
     means, sh0, shN, raw_scales, raw_quats, raw_opac = [p.detach() for p in model.parameters()]
     g_means, g_sh0, g_shN, g_scales, g_quats, g_opac = grads
     with torch.no_grad():
-        image, alpha, pws, iws, n_inst = forward_wrapper(means, raw_scales, raw_quats, raw_opac, sh0, shN, w2c, settings)
+        v_depth = None
+        if depth_target is not None:
+            from .losses import depth_l1_loss_fwd_bwd
+            image, alpha, depth, pws, iws, n_inst = forward_wrapper_depth(means, raw_scales, raw_quats, raw_opac, sh0, shN, w2c, settings)
+            v_depth = depth_l1_loss_fwd_bwd(depth, depth_target, weight * depth_weight, loss_acc)
+        else:
+            image, alpha, pws, iws, n_inst = forward_wrapper(means, raw_scales, raw_quats, raw_opac, sh0, shN, w2c, settings)
         shown = image if bilateral is None else bilateral.apply_fused(image, image_idx, chw=True)
         v_alpha = None
         if mask is not None:
@@ -222,5 +290,5 @@ def render_and_backward(settings: FastGSSettings, w2c: torch.Tensor, model: Spla
         if not hasattr(render_and_backward, "_zero") or render_and_backward._zero.shape != alpha.shape or render_and_backward._zero.device != alpha.device:
             render_and_backward._zero = torch.zeros_like(alpha)
         backward_wrapper(densification_info, v_image, render_and_backward._zero if v_alpha is None else v_alpha, image, alpha, means, raw_scales, raw_quats, sh0, shN, pws, iws, w2c, settings, n_inst,
-                         out=(g_means, g_scales, g_quats, g_opac.view(-1, 1), g_sh0, g_shN), adam_sh_rest=adam_shN, grad_w2c=grad_w2c)
+                         out=(g_means, g_scales, g_quats, g_opac.view(-1, 1), g_sh0, g_shN), adam_sh_rest=adam_shN, grad_w2c=grad_w2c, grad_depth=v_depth)
     return image, alpha, n_inst

@@ -33,7 +33,7 @@ IO_EXPORTS = [
     "lfs_colmap_image_name", "lfs_colmap_image_path", "lfs_colmap_scene_center", "lfs_colmap_points_open", "lfs_point_cloud_size",
     "lfs_point_cloud_copy", "lfs_point_cloud_close", "lfs_ply_write_splat", "lfs_ply_open", "lfs_ply_num_vertices", "lfs_ply_num_properties",
     "lfs_ply_property_name", "lfs_ply_read", "lfs_ply_close", "lfs_image_info", "lfs_image_target_size", "lfs_image_load_rgb8",
-    "lfs_image_write_png_rgb8", "lfs_image_load_alpha8",
+    "lfs_image_write_png_rgb8", "lfs_image_load_alpha8", "lfs_image_load_gray16",
 ]
 IO_E_UNSUPPORTED = -4
 
@@ -286,6 +286,65 @@ def load_mask8(image_path: str, source: Tuple[str, bool]) -> np.ndarray:
     return m
 
 
+def decode_gray16(path: str) -> np.ndarray:
+    """-> uint16 [h,w]: a 16-bit greyscale PNG with both bytes of every sample (lfs_image_load_gray16; the 8-bit decoders keep the high byte only)"""
+    lib = io_library()
+    data, w, h = C.POINTER(C.c_uint16)(), C.c_int32(), C.c_int32()
+    _check(lib.lfs_image_load_gray16(os.fsencode(path), C.byref(data), C.byref(w), C.byref(h)))
+    try:
+        return np.ctypeslib.as_array(data, shape=(h.value, w.value)).copy()
+    finally:
+        lib.lfs_io_free(data)
+
+
+def find_depth(image_path: str, data_path: Optional[str], depths_folder: Optional[str] = "depths") -> Optional[str]:
+    """The depth file of an image, or None: <data>/<depths folder>/<stem>.npy (float32 [H,W]) first, then <stem>.png (16-bit greyscale, value / 65536 - the Inria
+    convention for monocular inverse depth)."""
+    if not data_path or not depths_folder:
+        return None
+    stem = os.path.splitext(os.path.basename(image_path))[0]
+    for cand in (stem + ".npy", stem + ".png"):
+        p = os.path.join(data_path, depths_folder, cand)
+        if os.path.isfile(p):
+            return p
+    return None
+
+
+def load_depth_params(path: Optional[str]) -> Optional[dict]:
+    """depth_params.json of the Inria pipeline: {<image stem>: {"scale": s, "offset": o, ...}} -> {stem: (s, o)}; None when there is no file"""
+    if not path or not os.path.isfile(path):
+        return None
+    import json
+    with open(path) as f:
+        raw = json.load(f)
+    return {k: (float(v["scale"]), float(v["offset"])) for k, v in raw.items() if isinstance(v, dict) and "scale" in v and "offset" in v}
+
+
+def load_depth(path: str) -> np.ndarray:
+    """-> float32 [h,w]: a .npy as it is, a 16-bit greyscale PNG as value / 65536"""
+    if path.lower().endswith(".npy"):
+        a = np.load(path, allow_pickle=False)
+        if a.ndim == 3 and a.shape[0] == 1:      # [1,H,W]: the channel axis alone is dropped (H or W may be 1 themselves)
+            a = a[0]
+        elif a.ndim == 3 and a.shape[-1] == 1:   # [H,W,1]
+            a = a[..., 0]
+        if a.ndim != 2:
+            raise LoaderError(f"depth file {path} is not a [H,W] array (shape {a.shape})")
+        return np.ascontiguousarray(a, dtype=np.float32)
+    return (decode_gray16(path).astype(np.float64) / 65536.0).astype(np.float32)
+
+
+def depth_target(path: str, stem: str, params: Optional[dict]) -> Optional[np.ndarray]:
+    """The view's target t = v * scale + offset as float32 [h,w] at the file's size. With a params table (load_depth_params) a view without an entry or with
+    scale <= 0 has no reliable alignment and gets None - no target; without a table the file's values are the target."""
+    if params is None:
+        return load_depth(path)
+    so = params.get(stem)
+    if so is None or not so[0] > 0:
+        return None
+    return (load_depth(path).astype(np.float64) * so[0] + so[1]).astype(np.float32)
+
+
 def u8_to_chw_f32(image_u8: torch.Tensor, out_width: Optional[int] = None, out_height: Optional[int] = None) -> torch.Tensor:
     """GPU: u8 [h,w,3] -> f32 [3,oh,ow] in [0,1] (bilinear resample + 8-bit requantisation when the size changes)."""
     from .capi import check, load_library, ptr, require_gpu, stream
@@ -444,6 +503,11 @@ class CameraDataset:
     indices: List[int] = field(default_factory=list)
     data_path: Optional[str] = None     # the scene's directory: where the masks folder is looked for
     masks_folder: Optional[str] = "masks"
+    depths_folder: Optional[str] = "depths"
+
+    def depth_source(self, index: int) -> Optional[str]:
+        """the view's depth file (find_depth), or None"""
+        return find_depth(self.cameras[self.indices[index]].image_path, self.data_path, self.depths_folder)
 
     def mask_source(self, index: int) -> Optional[Tuple[str, bool]]:
         """(path, is_alpha) of the view's mask (find_mask), or None: that view trains unmasked"""
@@ -506,6 +570,30 @@ def preload_masks(ds: "CameraDataset", device="cuda:0", invert: bool = False, th
     return out
 
 
+def preload_depths(ds: "CameraDataset", device="cuda:0", kind: str = "invdepth", params: Optional[dict] = None, masks: Optional[list] = None) -> list:
+    """The depth targets of the split, parallel to preload(): a losses.PreparedDepth at image_target_size per view that has a depth file (and, with a params
+    table, a reliable scale), None for the others. The file holds what `kind` names ("invdepth": the Inria convention; "depth"); params = load_depth_params(...)
+    applies t = v * scale + offset per image. Resampled once, here, to the training resolution (nearest neighbour). masks (preload_masks' list): a view's mask is
+    baked into its target's weights."""
+    from .losses import prepare_depth
+    if kind not in ("invdepth", "depth"):
+        raise ValueError(f"preload_depths: kind must be 'invdepth' or 'depth' (got {kind!r})")
+    out = []
+    for i in range(len(ds)):
+        src = ds.depth_source(i)
+        cam = ds.cameras[ds.indices[i]]
+        t = None if src is None else depth_target(src, os.path.splitext(os.path.basename(cam.image_path))[0], params)
+        if t is None:
+            out.append(None)
+            continue
+        ow, oh = ds.image_size(i)
+        dev = torch.from_numpy(t).to(device)
+        if tuple(dev.shape) != (oh, ow):
+            dev = torch.nn.functional.interpolate(dev[None, None], size=(oh, ow), mode="nearest")[0, 0].contiguous()
+        out.append(prepare_depth(dev, None if masks is None else masks[i]))
+    return out
+
+
 def world_to_view(cam: CameraData) -> np.ndarray:
     """camera.cpp:15-23: [R | t] with the COLMAP translation as is."""
     m = np.eye(4, dtype=np.float32)
@@ -523,13 +611,14 @@ def intrinsics(cam: CameraData, image_width: int, image_height: int) -> np.ndarr
 
 
 def colmap_scene(base: str, images_folder: str = "images", split: str = "train", test_every: int = 8, resize_factor: int = -1, max_width: int = 0,
-                 sh_degree: int = 3, init_scaling: float = 1.0, init_opacity: float = 0.1, text: bool = False, device="cuda:0", masks_folder: Optional[str] = "masks"):
+                 sh_degree: int = 3, init_scaling: float = 1.0, init_opacity: float = 0.1, text: bool = False, device="cuda:0", masks_folder: Optional[str] = "masks",
+                 depths_folder: Optional[str] = "depths"):
     """COLMAP directory -> (Scene for GutTrainer, CameraDataset, scene_scale). All views must share one image size (the trainer's
     view batches are rectangular)."""
     from .scenes import Scene
     cams, center = (read_colmap_cameras_and_images_text if text else read_colmap_cameras_and_images)(base, images_folder)
     pcd = (read_colmap_point_cloud_text if text else read_colmap_point_cloud)(base)
-    ds = CameraDataset(cams, split, test_every, resize_factor, max_width, data_path=base, masks_folder=masks_folder)
+    ds = CameraDataset(cams, split, test_every, resize_factor, max_width, data_path=base, masks_folder=masks_folder, depths_folder=depths_folder)
     if not len(ds):
         raise LoaderError("the requested split has no images")
     w, h = ds.image_size(0)

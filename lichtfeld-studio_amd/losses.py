@@ -153,6 +153,50 @@ def prepare_mask(mask_u8_device: torch.Tensor, out_width: int, out_height: int, 
     return PreparedMask(dst, sums)
 
 
+class PreparedDepth(NamedTuple):
+    """A depth (or inverse-depth) target at the training resolution on the device: target float32 [H,W] with NaN where the source was not finite and > 0, the
+    optional mask it was prepared with (uint8 [H,W], or None) and sums int64[1] = sum over the valid pixels of the mask byte (255 without a mask) - 255 x the sum
+    of the per-pixel weights, the exact integer the depth loss normalises with (read on the device)."""
+    target: torch.Tensor
+    mask_u8: torch.Tensor | None
+    sums: torch.Tensor
+
+
+def prepare_depth(target_f32: torch.Tensor, mask: PreparedMask | torch.Tensor | None = None) -> PreparedDepth:
+    """lfs_depth_prepare: a float32 [H,W] plane (device) -> PreparedDepth. mask: a PreparedMask or a uint8 [H,W] device tensor of the same size. Asynchronous."""
+    src = target_f32.contiguous()
+    require_gpu(src)
+    if src.dim() == 3 and src.shape[0] == 1:
+        src = src[0]
+    if src.dim() != 2 or src.dtype != torch.float32:
+        raise LfsError("prepare_depth expects a float32 [H,W] tensor")
+    H, W = src.shape
+    m = mask.mask_u8 if isinstance(mask, PreparedMask) else mask
+    if m is not None:
+        m = m.contiguous()
+        require_gpu(m)
+        if tuple(m.shape) != (H, W) or m.dtype != torch.uint8:
+            raise LfsError(f"prepare_depth: the mask must be uint8 [{H},{W}] (got {tuple(m.shape)})")
+    out = torch.empty_like(src)
+    sums = torch.empty(1, dtype=torch.int64, device=src.device)
+    check(load_library().lfs_depth_prepare(C.c_uint32(H), C.c_uint32(W), ptr(src), ptr(m), ptr(out), ptr(sums), stream()), "depth_prepare")
+    return PreparedDepth(out, m, sums)
+
+
+def depth_l1_loss_fwd_bwd(depth: torch.Tensor, target: PreparedDepth, weight: float, loss_acc: torch.Tensor) -> torch.Tensor:
+    """lfs_depth_l1_loss_fwd_bwd: loss_acc += weight * sum m |D - t| / max(sum m, 1) over the valid (and masked-in) pixels; returns dL/d(depth), shaped like depth
+    ([1,H,W] or [H,W])."""
+    depth = depth.contiguous()
+    require_gpu(depth, target.target, target.mask_u8, target.sums, loss_acc)
+    H, W = target.target.shape
+    if depth.numel() != H * W or depth.dtype != torch.float32:
+        raise LfsError(f"depth_l1_loss_fwd_bwd: the depth map must be float32 with {H}x{W} elements (got {tuple(depth.shape)})")
+    g = torch.empty_like(depth)
+    check(load_library().lfs_depth_l1_loss_fwd_bwd(C.c_uint32(H), C.c_uint32(W), ptr(depth), ptr(target.target), ptr(target.mask_u8), ptr(target.sums),
+                                                   C.c_float(weight), ptr(g), ptr(loss_acc), stream()), "depth_l1_loss_fwd_bwd")
+    return g
+
+
 def loss_fwd_bwd(kind: str, render: torch.Tensor, target_chw: torch.Tensor, weight: float, loss_acc: torch.Tensor, chw: bool, clamp: bool,
                  lambda_dssim: float = 0.2, mask: PreparedMask | None = None, alpha: torch.Tensor | None = None, alpha_weight: float = 0.0):
     """General fused loss: kind "mse" | "l1_ssim"; render [H,W,3] (chw False) or [3,H,W]; clamp = clamp(render, 0, 1) first (gradient masked).

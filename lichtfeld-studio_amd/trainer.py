@@ -5,6 +5,8 @@ scope; the loss here is the rasterizer-only MSE of SURVEY.md §8
 """
 from __future__ import annotations
 
+import math
+
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -88,7 +90,7 @@ class GutTrainer:
                  use_bilateral_grid: bool = False, bilateral_grid_dims=(16, 16, 8), bilateral_grid_lr: float = 2e-3, tv_loss_weight: float = 10.0,
                  sh_sharded: Optional[bool] = None, factored_sh: bool = False, one_call: bool = False, pose_optimization: str = "none", pose_lr: float = 1e-5,
                  enable_sparsity: bool = False, sparsify_steps: int = 15000, init_rho: float = 0.0005, prune_ratio: float = 0.6, sparsity_update_every: int = 50,
-                 mask_mode: str = "none", mask_alpha_weight: float = 1.0, antialiasing: bool = False):
+                 mask_mode: str = "none", mask_alpha_weight: float = 1.0, antialiasing: bool = False, depth_loss: str = "none", depth_weight=(1.0, 0.01)):
         """strategy: None (fixed set of Gaussians: the benchmark), "mcmc" (strategies.MCMC: relocation + growth + SGLD noise, with
         the scale / opacity regularisers of trainer.cpp:132-158) or "default" (ADC; needs densification_info, see strategies.py).
         `seed` seeds the strategy's generator: the same on every rank, so replicas densify identically.
@@ -105,7 +107,23 @@ class GutTrainer:
         pixel by its mask byte (the masked loss kernels). "segment": additionally the rendered opacity outside the mask is penalised with mask_alpha_weight (L1 + D-SSIM
         on the fastgs rasterizer, whose backward takes an alpha gradient; the autograd form of the 3DGUT rasterizer as well).
         antialiasing (OptimizationParameters::antialiasing; DESIGN.md 8f): every fastgs render of the trainer runs in the antialiased mode (FastGSSettings.antialiased).
-        fastgs rasterizer only."""
+        fastgs rasterizer only.
+        depth_loss: "none" | "invdepth" | "depth" (DESIGN.md 8g): what train_step(depths=...) supervises - the accumulated inverse depth (the Inria trainer's
+        convention: monocular depth, scale and offset fitted per image) or the accumulated depth of the view against a losses.PreparedDepth, by a masked L1 whose weight
+        decays exponentially from depth_weight[0] (first iteration) to depth_weight[1] (iteration `iterations`) - the log-linear interpolation of the Inria trainer's
+        depth_l1_weight. fastgs rasterizer, one rank. With "none" (and on steps without depths) the trainer plans and computes what it always did."""
+        if depth_loss not in ("none", "invdepth", "depth"):
+            raise ValueError(f"Invalid depth loss: {depth_loss}")
+        if depth_loss != "none":
+            if rasterizer == "gut":
+                raise ValueError("depth supervision is not wired into the 3DGUT route (rasterizer='gut'): its step forms render and differentiate colour only. "
+                                 "Use rasterizer='fastgs'.")
+            if world > 1:
+                raise ValueError("depth supervision is implemented for one rank (world == 1)")
+            if len(depth_weight) != 2 or not (float(depth_weight[0]) > 0 and float(depth_weight[1]) > 0):
+                raise ValueError("depth_weight is (initial, final), both > 0: the weight is interpolated in the logarithm")
+        self.depth_loss, self.depth_weight = depth_loss, (float(depth_weight[0]), float(depth_weight[1]))
+        self._depths = None
         if antialiasing and rasterizer == "gut":
             raise ValueError("antialiasing is not wired into the 3DGUT route (rasterizer='gut'): its fused and autograd steps render without the opacity compensation. "
                              "Use rasterizer='fastgs'.")
@@ -315,7 +333,14 @@ class GutTrainer:
             st = FastGSSettings(cam_pos, (deg + 1) ** 2, sc.width, sc.height, float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), 0.01, 1e10, self.antialiasing)
             self._fg_settings[view] = st
         st.active_sh_bases = (self.model.get_active_sh_degree() + 1) ** 2
+        st.depth = "none"   # (_train_step_fastgs switches a view with a depth target to the trainer's depth kind)
         return st
+
+    def depth_weight_at(self, iteration: int) -> float:
+        """the depth loss weight of (1-based) iteration `iteration`: depth_weight[0] at the first, depth_weight[1] at iteration `iterations` and after, log-linear between"""
+        w0, w1 = self.depth_weight
+        tt = min(max((iteration - 1) / max(self.base_iterations - 1, 1), 0.0), 1.0)
+        return float(math.exp((1.0 - tt) * math.log(w0) + tt * math.log(w1)))
 
     def _train_step_fastgs(self, targets, views, total_views):
         """The same step through the fastgs (EWA) rasterizer - the reference's default training path (trainer.cpp:656-760): fused
@@ -337,7 +362,8 @@ class GutTrainer:
             self._fg_tmp = [torch.empty_like(v) for v in self.bucket.views]
         inline = None   # one view on one rank, Adam reading shN: the SH backward inside lfs_fastgs_backward_adam updates shN itself
         if (self.inline_shN_adam and self.world == 1 and len(views) == 1 and self.strategy is None and self.iteration > 1000 and self.model.shN.shape[1] > 0
-                and getattr(self.optimizer, "fused", False) and self.pose_module is None):   # (lfs_fastgs_backward_adam has no camera gradient)
+                and getattr(self.optimizer, "fused", False) and self.pose_module is None   # (lfs_fastgs_backward_adam has no camera gradient)
+                and self._depths is None):                                                   # (... and no depth gradient)
             inline = self.optimizer.prepare_inline(self.model.shN)
         for k, v in enumerate(views):
             dst = self.bucket.views if k == 0 else self._fg_tmp
@@ -346,10 +372,14 @@ class GutTrainer:
                 # trainer.cpp:648-649: the adjusted transform under autograd; cam_position stays the stored camera's (Camera(const Camera&, transform) copies it)
                 w2c_adj = self.pose_module(w2c, [v])
                 w2c, g_w2c = w2c_adj.detach().contiguous(), torch.empty_like(w2c)
-            _, _, self.last_n_isects = fg_step(self._fastgs_settings(v), w2c, self.model, targets[k % len(targets)],
+            st, depth_args = self._fastgs_settings(v), {}
+            if self._depths is not None and self._depths[k % len(self._depths)] is not None:
+                st.depth = self.depth_loss
+                depth_args = {"depth_target": self._depths[k % len(self._depths)], "depth_weight": self.depth_weight_at(self.iteration)}
+            _, _, self.last_n_isects = fg_step(st, w2c, self.model, targets[k % len(targets)],
                                                1.0 / total_views, dst, self.loss_acc, densification_info=dens, loss=self.loss_kind,
                                                lambda_dssim=self.lambda_dssim, bilateral=self.bilateral, image_idx=v, adam_shN=inline, grad_w2c=g_w2c,
-                                               **self._fastgs_mask_args(k))
+                                               **self._fastgs_mask_args(k), **depth_args)
             if w2c_adj is not None:
                 w2c_adj.backward(g_w2c)   # accumulates into the module's parameters over the views of the step
                 self.last_grad_w2c = g_w2c
@@ -461,8 +491,10 @@ class GutTrainer:
         return Camera(sc.viewmats[view:view + 1].contiguous(), sc.Ks[view:view + 1].contiguous(), sc.width, sc.height)
 
     def train_step(self, targets: List[torch.Tensor], views: Optional[List[int]] = None, views_all: Optional[List[List[int]]] = None,
-                   next_views: Optional[List[int]] = None, masks: Optional[List] = None) -> float:
-        """masks: a list parallel to `targets` of losses.PreparedMask (at the training resolution) or None (that view is unmasked); needs mask_mode "ignore" or
+                   next_views: Optional[List[int]] = None, masks: Optional[List] = None, depths: Optional[List] = None) -> float:
+        """depths: a list parallel to `targets` of losses.PreparedDepth (at the training resolution; what depth_loss names: inverse depth or depth) or None (that
+        view has no depth target); needs depth_loss "invdepth" or "depth". A step whose depths are all None is the step without the argument.
+        masks: a list parallel to `targets` of losses.PreparedMask (at the training resolution) or None (that view is unmasked); needs mask_mode "ignore" or
         "segment". A step whose masks are all None is the unmasked step.
         next_views: with an explicit `views`, the views the NEXT call will pass (a data loader knows them: src/training/dataloader.cpp prefetches) - the one-call step's
         fused tail then evaluates their SH colours on the side. Without `views` the round-robin schedule names them."""
@@ -479,10 +511,18 @@ class GutTrainer:
             if len(masks) != len(targets):
                 raise ValueError("masks must be parallel to targets")
             self._masks = list(masks)
+        self._depths = None
+        if depths is not None and any(d is not None for d in depths):
+            if self.depth_loss == "none":
+                raise ValueError("train_step(depths=...) needs GutTrainer(depth_loss='invdepth' | 'depth') (depth_loss='none')")
+            if len(depths) != len(targets):
+                raise ValueError("depths must be parallel to targets")
+            self._depths = list(depths)
         try:
             out = self._train_step(targets, views, views_all)
         finally:
             self._masks = None
+            self._depths = None
         # the SH schedule, AFTER the backward / optimizer step of the iteration, where the strategies keep it (post_backward: mcmc.cpp:366-368,
         # default_strategy.cpp) - iteration 1000, 2000, ... still renders with the old degree, as the reference does; without a strategy the trainer does it
         if (self.strategy is None and self.iteration % self.sh_degree_interval == 0 and self.model.active_sh_degree < self.model.max_sh_degree
@@ -515,6 +555,8 @@ class GutTrainer:
             raise ValueError(f"masked training is not wired into the {plan.path} step form (rasterizer={self.rasterizer!r}, world={self.world}, views per step="
                              f"{len(views)}, sh_sharded={self.sh_exchange is not None}, cxx_step={self.cxx_step}): masks run in the fastgs, autograd, cxx_views and "
                              "cxx_factored forms")
+        if self._depths is not None and plan.path != "fastgs":
+            raise ValueError(f"depth supervision is not wired into the {plan.path} step form: it runs in the fastgs form only")
         if plan.path != "cxx_all" and self._gut_step is not None:
             self._gut_step.colors_for = None   # (another step form is about to change the parameters: colours a fused tail left for this step are void)
         if plan.path == "fastgs":

@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("-d", "--data-path", required=True)
     ap.add_argument("--images", default="images")
@@ -30,7 +30,7 @@ def main():
     ap.add_argument("--max-width", type=int, default=3840)
     ap.add_argument("--sh-degree", type=int, default=3)
     ap.add_argument("--bilateral-grid", action="store_true")
-    ap.add_argument("--eval", action="store_true")
+    ap.add_argument("--eval", action="store_true", help="PSNR / SSIM on the held-out views (every --test-every-th); with --depth-loss also saves their renders and depth maps")
     ap.add_argument("-o", "--output-path", default="output")
     ap.add_argument("--text", action="store_true", help="read cameras.txt / images.txt / points3D.txt")
     ap.add_argument("--eval-every", type=int, default=0, help="with --eval: held-out PSNR (the renderer the model trains with) every N iterations -> 'psnr_curve' (the turbulence of an MCMC run)")
@@ -50,11 +50,43 @@ def main():
     ap.add_argument("--mask-threshold", type=int, default=-1, help="binarise: mask byte >= N counts fully, below it not at all (default: keep soft values)")
     ap.add_argument("--mask-alpha-weight", type=float, default=1.0, help="weight of the opacity penalty of --mask-mode segment")
     ap.add_argument("--antialiasing", action="store_true", help="antialiased mode of the EWA rasterizer for training and --eval renders (the reference's antialiasing parameter)")
-    args = ap.parse_args()
+    ap.add_argument("--depth-loss", default="none", choices=["none", "invdepth", "depth"],
+                    help="depth-regularised training (fastgs rasterizer): L1 between the accumulated inverse depth (invdepth: monocular depth, the Inria convention) or depth of a view "
+                         "and <data>/<depths folder>/<image stem>.npy (float32 [H,W]) or .png (16-bit greyscale, value / 65536). With --eval, every held-out render is then saved as "
+                         "<output>/renders/val_NNNN.png with its expected-depth map val_NNNN_depth.png beside it (without --depth-loss no renders are saved)")
+    ap.add_argument("--depths-folder", default="depths")
+    ap.add_argument("--depth-params", default=None, help="depth_params.json: per image {scale, offset}, target = value * scale + offset; a view without an entry or with "
+                                                         "scale <= 0 trains without a depth target (default: <data>/sparse/0/depth_params.json when it exists)")
+    ap.add_argument("--depth-weight-init", type=float, default=1.0, help="weight of the depth loss at the first iteration")
+    ap.add_argument("--depth-weight-final", type=float, default=0.01, help="... and at the last: exponential decay between the two")
+    return ap
+
+
+def check_args(args) -> None:
+    """the combinations the tool refuses, before anything is loaded"""
     if args.antialiasing and args.gut:
         raise SystemExit("--antialiasing is not wired into the 3DGUT route. Please disable antialiasing or disable gut.")
+    if args.depth_loss != "none" and args.gut:
+        raise SystemExit("--depth-loss is not wired into the 3DGUT route. Please disable the depth loss or disable gut.")
+    if args.depth_loss != "none" and not (args.depth_weight_init > 0 and args.depth_weight_final > 0):
+        raise SystemExit("--depth-weight-init and --depth-weight-final must be > 0 (the weight is interpolated in the logarithm)")
     if args.pose_optimization != "none" and args.eval:   # trainer.cpp:367-370
         raise SystemExit("Evaluating with pose optimization is not supported yet. Please disable pose optimization or evaluation.")
+
+
+def depth_params_path(args):
+    """--depth-params, or the Inria pipeline's default location when that file exists, or None (the files' values are the targets)"""
+    if args.depth_params:
+        return args.depth_params
+    for cand in (os.path.join(args.data_path, "sparse", "0", "depth_params.json"), os.path.join(args.data_path, "depth_params.json")):
+        if os.path.isfile(cand):
+            return cand
+    return None
+
+
+def main():
+    args = build_parser().parse_args()
+    check_args(args)
 
     import lichtfeld_studio_amd  # noqa: F401
     from lichtfeld_studio_amd import evaluate, loader, strategies
@@ -69,8 +101,13 @@ def main():
     split = "train" if args.eval else "all"
     scene, ds, scene_scale = loader.colmap_scene(args.data_path, args.images, split=split, test_every=args.test_every, resize_factor=args.resize_factor,
                                                  max_width=args.max_width, sh_degree=args.sh_degree, init_scaling=init_scaling, init_opacity=init_opacity,
-                                                 text=args.text, device=dev, masks_folder=args.masks_folder)
+                                                 text=args.text, device=dev, masks_folder=args.masks_folder, depths_folder=args.depths_folder)
     masks = loader.preload_masks(ds, dev, args.invert_masks, args.mask_threshold) if args.mask_mode != "none" else None
+    depths = None
+    if args.depth_loss != "none":
+        depths = loader.preload_depths(ds, dev, args.depth_loss, loader.load_depth_params(depth_params_path(args)), masks)
+        if not any(d is not None for d in depths):
+            raise SystemExit(f"--depth-loss {args.depth_loss}: no view has a usable depth target under {os.path.join(args.data_path, args.depths_folder)}")
     targets = loader.preload(ds, dev, workers=os.cpu_count() or 8)          # resident in HBM: 288 GB hold a Mip-NeRF360 scene at full resolution
     t_load = time.time() - t0
     rast = "gut" if args.gut else "fastgs"
@@ -79,7 +116,8 @@ def main():
     tr = GutTrainer(scene, dev, iterations=args.iterations, loss="l1_ssim", strategy=None if args.strategy == "none" else args.strategy, opt_params=op,
                     scene_scale=scene_scale, rasterizer=rast, use_bilateral_grid=args.bilateral_grid, pose_optimization=args.pose_optimization,
                     enable_sparsity=args.enable_sparsity, sparsify_steps=args.sparsify_steps, init_rho=args.init_rho, prune_ratio=args.prune_ratio,
-                    mask_mode=args.mask_mode, mask_alpha_weight=args.mask_alpha_weight, antialiasing=args.antialiasing)
+                    mask_mode=args.mask_mode, mask_alpha_weight=args.mask_alpha_weight, antialiasing=args.antialiasing,
+                    depth_loss=args.depth_loss, depth_weight=(args.depth_weight_init, args.depth_weight_final))
     total = tr.total_iterations                                             # --iterations, plus the sparsification phase
     os.makedirs(args.output_path, exist_ok=True)
     g = torch.Generator().manual_seed(0)
@@ -102,7 +140,7 @@ def main():
         if not order:
             order = torch.randperm(len(ds), generator=g).tolist()          # infinite random sampler, one view per step
         v = order.pop()
-        tr.train_step([targets[v]], views=[v], masks=None if masks is None else [masks[v]])
+        tr.train_step([targets[v]], views=[v], masks=None if masks is None else [masks[v]], depths=None if depths is None else [depths[v]])
         if args.enable_sparsity and it + 1 == args.iterations:              # the model of the base run, before sparsification touches it
             loader.save_ply(tr.model, os.path.join(args.output_path, f"splat_{args.iterations}.ply"))
         if val_set is not None and (it + 1) % args.eval_every == 0:
@@ -133,6 +171,8 @@ def main():
            "iters_per_s": round(total / max(t_train, 1e-9), 1)}
     if masks is not None:
         out.update(mask_mode=args.mask_mode, masked_views=sum(m is not None for m in masks))
+    if depths is not None:
+        out.update(depth_loss=args.depth_loss, depth_views=sum(d is not None for d in depths), depth_weight=[args.depth_weight_init, args.depth_weight_final])
     if args.enable_sparsity:
         out.update(base_iterations=args.iterations, sparsify_steps=args.sparsify_steps, prune_ratio=args.prune_ratio, init_rho=args.init_rho)
     if args.eval:
@@ -147,6 +187,21 @@ def main():
             images.append(img)
         m = evaluate.evaluate(tr.model, cameras, images, total, masks=val_masks, antialiased=args.antialiasing)
         out.update(psnr=round(m.psnr, 4), ssim=round(m.ssim, 5), val_images=m.n_images)
+        if args.depth_loss != "none":   # the held-out renders and, beside each, its expected depth map (D / alpha; grey, scaled to the view's own range)
+            from lichtfeld_studio_amd import fastgs
+            from lichtfeld_studio_amd.rasterizer import RenderMode
+            rdir = os.path.join(args.output_path, "renders")
+            os.makedirs(rdir, exist_ok=True)
+            for k, cam in enumerate(cameras):
+                with torch.no_grad():
+                    r = fastgs.fast_rasterize(cam, tr.model, torch.zeros(3, device=dev), antialiased=args.antialiasing, render_mode=RenderMode.RGB_ED, depth_kind=args.depth_loss)
+                rgb = (r.image.clamp(0, 1) * 255.0 + 0.5).to(torch.uint8).permute(1, 2, 0).contiguous().cpu().numpy()
+                d = r.depth[0]
+                lo, hi = float(d[r.alpha[0] > 0.5].min()) if bool((r.alpha[0] > 0.5).any()) else 0.0, float(d.max())
+                grey = (((d - lo) / max(hi - lo, 1e-12)).clamp(0, 1) * 255.0 + 0.5).to(torch.uint8).cpu().numpy()
+                loader.write_png(os.path.join(rdir, f"val_{k:04d}.png"), rgb)
+                loader.write_png(os.path.join(rdir, f"val_{k:04d}_depth.png"), grey[..., None].repeat(3, axis=2))
+            out["renders"] = rdir
         if args.gut:   # the reference's protocol above renders with the EWA rasterizer; this is the renderer the model was trained with
             mg = evaluate.evaluate(tr.model, cameras, images, total, rasterizer="gut", masks=val_masks)
             out.update(psnr_gut=round(mg.psnr, 4), ssim_gut=round(mg.ssim, 5))
