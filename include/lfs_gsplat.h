@@ -263,102 +263,94 @@ LFS_API int lfs_mse_loss_chw_fwd_bwd(uint32_t H, uint32_t W, const float* render
  *      src/rasterization_api.cu, forward.cu, backward.cu, kernels_{forward,backward}.cuh). Inputs are the RAW parameters
  *      (log-scales, un-normalised quaternions wxyz, opacity logits, sh0 [N,1,3], sh_rest [N,total_bases_sh_rest,3]); w2c is a
  *      row-major [4,4] (rows 0-2 used) and cam_position [3], both on the device. image [3,H,W], alpha [1,H,W] (CHW, no background).
- *      The reference's four opaque buffer tensors become two caller-owned workspaces that must survive until the backward:
- *        1) lfs_fastgs_preprocess   : per-primitive stage + per-tile counts; *n_instances (device int64) = list length
+ *      The reference's four opaque buffer tensors become two caller-owned workspaces that must survive until the backward.
+ *      One entry point per stage, each on the same lfs_fastgs_view (the scene's raw parameters, one camera, the primitive workspace);
+ *      every optional output or operand is a field that may be NULL:
+ *        1) lfs_fastgs_view_preprocess : per-primitive stage + per-tile counts; *n_instances (device int64) = list length
  *        2) (host reads n_instances: the reference syncs at the same place, forward.cu:114-117)
- *        3) lfs_fastgs_render       : instance lists (scatter + per-tile depth sort), per-cell culling, blending
- *        4) lfs_fastgs_backward     : blending backward + per-primitive backward; gradients FULLY written; sh_coefficients_0 may be
- *                                     NULL (the reference's backward does not take it either); densification_info
- *                                     [2,N] (or NULL) is accumulated into (visibility count, screen-space gradient norm). */
+ *        3) lfs_fastgs_view_render     : instance lists (scatter + per-tile depth sort), per-cell culling, blending
+ *        4) lfs_fastgs_view_backward   : blending backward + per-primitive backward; gradients FULLY written */
 LFS_API size_t lfs_fastgs_primitive_workspace_bytes(uint32_t N, uint32_t width, uint32_t height);
 LFS_API size_t lfs_fastgs_instance_workspace_bytes(uint32_t width, uint32_t height, int64_t n_instances);
-LFS_API int lfs_fastgs_preprocess(
-    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* opacities_raw,
-    const float* sh_coefficients_0, const float* sh_coefficients_rest, uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position,
-    uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy, float cx, float cy, float near_plane, float far_plane,
-    int64_t* n_instances, void* primitive_workspace, size_t primitive_workspace_bytes, lfs_stream_t stream);
-/* lfs_fastgs_preprocess with flags; lfs_fastgs_preprocess is flags = 0. A bit that is not defined here: LFS_E_INVALID before any launch.
+typedef struct lfs_fastgs_view {
+    uint32_t N;
+    const float *means, *scales_raw, *rotations_raw;
+    const float* opacities_raw;             /* read by the preprocess only */
+    const float* sh_coefficients_0;         /* the backward takes NULL (the reference's backward does not take it either) */
+    const float* sh_coefficients_rest;      /* NULL when total_bases_sh_rest == 0 */
+    uint32_t total_bases_sh_rest;
+    const float *w2c, *cam_position;
+    uint32_t active_sh_bases, width, height;
+    float fx, fy, cx, cy, near_plane, far_plane;
+    void* primitive_workspace;              /* lfs_fastgs_primitive_workspace_bytes(N, width, height) */
+    size_t primitive_workspace_bytes;
+} lfs_fastgs_view;
+/* flags of lfs_fastgs_view_preprocess. A bit that is not defined here: LFS_E_INVALID before any launch.
  * LFS_FASTGS_ANTIALIASED (the reference's OptimizationParameters::antialiasing, which it connects to nothing): with (a0, b, c0) the projected covariance before the
  * 0.3 px^2 dilation and (a, b, c) after it, rho = sqrt(max(0, (a0 c0 - b^2) / (a c - b^2))) (add_blur, gsplat/Utils.cuh:171-179) and the opacity of the primitive is
  * sigmoid(raw) * rho wherever the default mode uses sigmoid(raw): the 1/255 cut (after the cuts on sigmoid(raw), the quaternion and a c - b^2), the power threshold,
- * the extents, the tile tests, the blend. The mode is recorded in the primitive workspace: lfs_fastgs_render and the three backward entry points take the same
- * arguments in both modes, and the backward is the full derivative (through rho into means, scales, rotations and grad_w2c). */
+ * the extents, the tile tests, the blend. The mode is recorded in the primitive workspace, rewritten by every preprocess with N > 0: render and backward take the
+ * same arguments in both modes, and the backward is the full derivative (through rho into means, scales, rotations and grad_w2c). */
 #define LFS_FASTGS_ANTIALIASED 1u
 /* Depth modes (the reference's render_mode D / ED / RGB_D / RGB_ED on the EWA path). With z_i the camera-space z of primitive i (>= near_plane when visible):
  * LFS_FASTGS_DEPTH blends d_i = z_i, LFS_FASTGS_INVDEPTH d_i = 1 / z_i. The two exclude each other (both: LFS_E_INVALID), each combines with LFS_FASTGS_ANTIALIASED.
- * The preprocess writes d_i into a free word of the blend record and the flag into the workspace's mode word; the workspace size does not change, and colour, alpha
- * and the three backward entry points above treat such a workspace as an ordinary one. (Bit 1, value 2, stays undefined.) */
+ * The preprocess writes d_i into a free word of the blend record and the flag into the workspace's mode word; the workspace size does not change, and a render
+ * without a depth plane and a backward without grad_depth treat such a workspace as an ordinary one. (Bit 1, value 2, stays undefined.)
+ * The library remembers, by address and without a device read, the workspaces filled in a depth mode: up to 256 whose backward is still to come (a preprocess
+ * without a depth flag takes no entry and only clears its own address); with more outstanding, the least recently filled one is forgotten and from then on
+ * counts as a default-mode workspace. */
 #define LFS_FASTGS_DEPTH 4u
 #define LFS_FASTGS_INVDEPTH 8u
-LFS_API int lfs_fastgs_preprocess_ex(
-    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* opacities_raw,
-    const float* sh_coefficients_0, const float* sh_coefficients_rest, uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position,
-    uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy, float cx, float cy, float near_plane, float far_plane,
-    int64_t* n_instances, void* primitive_workspace, size_t primitive_workspace_bytes, uint32_t flags, lfs_stream_t stream);
-/* n_instances of this process's last lfs_fastgs_preprocess call, read back asynchronously: blocks until the 8-byte copy (queued before the SH kernel)
+LFS_API int lfs_fastgs_view_preprocess(const lfs_fastgs_view* view, uint32_t flags, int64_t* n_instances /* device */, lfs_stream_t stream);
+/* n_instances of this process's last lfs_fastgs_view_preprocess call, read back asynchronously: blocks until the 8-byte copy (queued before the SH kernel)
  * has landed, not until the stream is idle. Alternative to reading the device value with a stream synchronisation. */
 LFS_API int lfs_fastgs_wait_n_instances(int64_t* n_instances);
-LFS_API int lfs_fastgs_render(
-    uint32_t N, uint32_t width, uint32_t height, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
-    void* instance_workspace, size_t instance_workspace_bytes, float* image, float* alpha, lfs_stream_t stream);
-/* lfs_fastgs_render + depth [1,H,W] = sum_i w_i d_i over exactly the instances that contribute to the colour (w_i = T_i alpha_i): the ACCUMULATED value, the
- * reference's D / RGB_D; the expected value (ED) is depth / alpha, the caller's business. image and alpha are bit-identical to lfs_fastgs_render's.
- * LFS_E_INVALID: depth NULL, or the primitive workspace was not last filled by a preprocess with a depth flag in this process. The library remembers, by
- * address and without a device read, the workspaces filled in a depth mode: up to 256 whose backward is still to come (a preprocess without a depth flag takes no
- * entry and only clears its own address); with more outstanding, the least recently filled one is forgotten and refused here like a default-mode workspace. */
-LFS_API int lfs_fastgs_render_depth(
-    uint32_t N, uint32_t width, uint32_t height, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
-    void* instance_workspace, size_t instance_workspace_bytes, float* image, float* alpha, float* depth, lfs_stream_t stream);
-LFS_API int lfs_fastgs_backward(
-    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* sh_coefficients_0, const float* sh_coefficients_rest,
-    uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position, uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy,
-    float cx, float cy, float near_plane, float far_plane, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
-    void* instance_workspace, size_t instance_workspace_bytes, const float* grad_image, const float* grad_alpha, const float* alpha,
-    float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
-    float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest, lfs_stream_t stream);
-/* lfs_fastgs_backward + grad_w2c, the camera gradient of the reference's pose optimisation (rasterization_api.cu:133-136: requested when w2c requires grad).
- * grad_w2c [4,4] row-major, device, FULLY written: rows 0-2 = sum over the primitives with n_touched > 0 of dL/d(mean in camera space) (x) (mean, 1)
- * (kernels_backward.cuh:165-183: no term through cam_position, none for the direct dependence of the EWA Jacobian on w2c, none from the SH colours), row 3 = 0.
- * Summed without float atomics, in a fixed order: the same bits on every run for the same dL/d(mean in camera space). w2c_workspace (16-byte aligned,
- * lfs_fastgs_w2c_workspace_bytes(N) bytes) holds one row of partial sums per 256 primitives. LFS_E_INVALID: grad_w2c NULL or a workspace that is not 16-byte aligned; LFS_E_WORKSPACE: workspace NULL / short. */
+/* Reads N, width, height and the primitive workspace of the view. depth (NULL, or [1,H,W]) = sum_i w_i d_i over exactly the instances that contribute to the
+ * colour (w_i = T_i alpha_i): the ACCUMULATED value, the reference's D / RGB_D; the expected value (ED) is depth / alpha, the caller's business. image and alpha
+ * are the same bits with and without it. LFS_E_INVALID, nothing launched: depth given on a workspace that was not last filled by a preprocess with a depth flag in
+ * this process (the library's memory of them: above). */
+LFS_API int lfs_fastgs_view_render(const lfs_fastgs_view* view, int64_t n_instances, void* instance_workspace, size_t instance_workspace_bytes,
+                                   float* image, float* alpha, float* depth, lfs_stream_t stream);
+/* Extension for a step with ONE view, the backward fused with the optimizer: sh_coefficients_rest (the parameter itself; the view's pointer is not read) and its
+ * Adam moments are updated in place by the SH backward (fast_gs::optimizer::adam_step arithmetic); the [N,total_rest,3] gradient is never stored. */
+typedef struct lfs_fastgs_sh_rest_adam {
+    float *sh_coefficients_rest, *exp_avg, *exp_avg_sq;
+    float lr, beta1, beta2, eps, bias_correction1_rcp, bias_correction2_sqrt_rcp;
+} lfs_fastgs_sh_rest_adam;
+typedef struct lfs_fastgs_view_backward_args {
+    int64_t n_instances;
+    void* instance_workspace;
+    size_t instance_workspace_bytes;
+    const float *grad_image, *grad_alpha, *alpha;
+    /* NULL, or the gradient [1,H,W] of lfs_fastgs_view_render's depth plane. Depth is a fourth blended channel of the blending backward (dL/dalpha and the
+     * colour-behind recurrence see d_i g_depth next to c_i . g_image), dL/dd_i = sum w g_depth is one more slot of the accumulator row, and dL/dz_i = dL/dd_i
+     * (1 | -1 / z_i^2) is added to the camera-space mean gradient: it reaches grad_means and row 2 of grad_w2c. LFS_E_INVALID, nothing launched: given on a workspace
+     * the library does not know as a depth-mode one (as the render's depth). */
+    const float* grad_depth;
+    float* densification_info;              /* NULL, or [2,N] accumulated into: (visibility count, screen-space gradient norm) */
+    float *grad_means, *grad_scales_raw, *grad_rotations_raw, *grad_opacities_raw, *grad_sh_coefficients_0;
+    float* grad_sh_coefficients_rest;       /* not written when adam is given (may be NULL then, and when total_bases_sh_rest == 0) */
+    /* NULL, or the camera gradient of the reference's pose optimisation (rasterization_api.cu:133-136: requested when w2c requires grad): [4,4] row-major, FULLY
+     * written whatever N and n_instances are: rows 0-2 = sum over the primitives with n_touched > 0 of dL/d(mean in camera space) (x) (mean, 1)
+     * (kernels_backward.cuh:165-183: no term through cam_position, none for the direct dependence of the EWA Jacobian on w2c, none from the SH colours), row 3 = 0.
+     * Summed without float atomics, in a fixed order: the same bits on every run for the same dL/d(mean in camera space). w2c_workspace (16-byte aligned,
+     * lfs_fastgs_w2c_workspace_bytes(N) bytes) holds one row of partial sums per 256 primitives. With grad_w2c: LFS_E_WORKSPACE for a NULL or short workspace,
+     * LFS_E_INVALID for one that is not 16-byte aligned. Without: w2c_workspace must be NULL and its size 0 (LFS_E_INVALID). */
+    float* grad_w2c;
+    void* w2c_workspace;
+    size_t w2c_workspace_bytes;
+    /* NULL: the gradient tensors above. Given: LFS_E_INVALID when total_bases_sh_rest == 0 or a pointer of it is NULL, and - before any launch - together with
+     * grad_w2c or grad_depth (pose optimisation and depth supervision take the separate optimizer). */
+    const lfs_fastgs_sh_rest_adam* adam;
+} lfs_fastgs_view_backward_args;
 LFS_API size_t lfs_fastgs_w2c_workspace_bytes(uint32_t N);
-LFS_API int lfs_fastgs_backward_w2c(
-    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* sh_coefficients_0, const float* sh_coefficients_rest,
-    uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position, uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy,
-    float cx, float cy, float near_plane, float far_plane, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
-    void* instance_workspace, size_t instance_workspace_bytes, const float* grad_image, const float* grad_alpha, const float* alpha,
-    float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
-    float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest, float* grad_w2c /* [4,4], fully written */, void* w2c_workspace, size_t w2c_workspace_bytes,
-    lfs_stream_t stream);
-/* lfs_fastgs_backward with a gradient for the depth map of lfs_fastgs_render_depth: grad_depth [1,H,W]. Depth is a fourth blended channel of the blending
- * backward (dL/dalpha and the colour-behind recurrence see d_i g_depth next to c_i . g_image), dL/dd_i = sum w g_depth is one more slot of the accumulator row, and
- * dL/dz_i = dL/dd_i (1 | -1 / z_i^2) is added to the camera-space mean gradient: it reaches grad_means and, when grad_w2c is given, row 2 of the camera gradient.
- * grad_w2c NULL: as lfs_fastgs_backward (w2c_workspace is not used); otherwise as lfs_fastgs_backward_w2c. densification_info keeps its definition.
- * LFS_E_INVALID: grad_depth NULL, or a workspace without a depth flag (as lfs_fastgs_render_depth). */
-LFS_API int lfs_fastgs_backward_depth(
-    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* sh_coefficients_0, const float* sh_coefficients_rest,
-    uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position, uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy,
-    float cx, float cy, float near_plane, float far_plane, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
-    void* instance_workspace, size_t instance_workspace_bytes, const float* grad_image, const float* grad_alpha, const float* alpha,
-    float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
-    float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest, const float* grad_depth, float* grad_w2c /* NULL or [4,4], fully written */, void* w2c_workspace,
-    size_t w2c_workspace_bytes, lfs_stream_t stream);
-/* lfs_fastgs_backward for a step with ONE view, fused with the optimizer (extension): sh_coefficients_rest and its Adam moments are updated in
- * place by the SH backward (fast_gs::optimizer::adam_step arithmetic); the [N,total_rest,3] gradient is never stored. */
-LFS_API int lfs_fastgs_backward_adam(
-    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* sh_coefficients_0, float* sh_coefficients_rest,
-    uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position, uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy,
-    float cx, float cy, float near_plane, float far_plane, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
-    void* instance_workspace, size_t instance_workspace_bytes, const float* grad_image, const float* grad_alpha, const float* alpha,
-    float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
-    float* grad_sh_coefficients_0, float* sh_rest_exp_avg, float* sh_rest_exp_avg_sq, float lr, float beta1, float beta2, float eps,
-    float bias_correction1_rcp, float bias_correction2_sqrt_rcp, lfs_stream_t stream);
-LFS_API void lfs_fastgs_set_debug_flags(uint32_t flags); /* bit 0: no per-cell culling (bit-identity test); bit 1: the backward entry points skip the blending
-                                                           * backward and reuse the accumulator rows the previous backward left in the primitive workspace (its float
+LFS_API int lfs_fastgs_view_backward(const lfs_fastgs_view* view, const lfs_fastgs_view_backward_args* args, lfs_stream_t stream);
+LFS_API void lfs_fastgs_set_debug_flags(uint32_t flags); /* bit 0: no per-cell culling (bit-identity test); bit 1: the backward skips the blending
+                                                           * backward and reuses the accumulator rows the previous backward left in the primitive workspace (its float
                                                            * atomics round differently from run to run: bit-identity tests of the per-primitive stage hold them fixed).
                                                            * Bit 1 is for tests ONLY and must never be set elsewhere: while it is set, every gradient of
-                                                           * lfs_fastgs_backward / lfs_fastgs_backward_w2c comes from stale accumulator rows. lfs_fastgs_backward_adam,
-                                                           * which updates parameters in place, ignores it. */
+                                                           * lfs_fastgs_view_backward comes from stale accumulator rows. With args->adam, which updates parameters in
+                                                           * place, the bit is ignored. */
 
 /* ---- "next" row 2 of SURVEY.md §8f: fused SSIM (fusedssim / fusedssim_backward, include/kernels/ssim.cuh:11-30,
  *      src/training/kernels/ssim.cu:64-510) and the trainer's photometric loss (trainer.cpp:122-125).

@@ -75,6 +75,26 @@ class ParamRows(C.Structure):  # lfs_param_rows
     _fields_ = [("param", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("width", C.c_uint32)]
 
 
+class FastgsView(C.Structure):  # lfs_fastgs_view
+    _fields_ = [("N", C.c_uint32), ("means", C.c_void_p), ("scales_raw", C.c_void_p), ("rotations_raw", C.c_void_p), ("opacities_raw", C.c_void_p),
+                ("sh_coefficients_0", C.c_void_p), ("sh_coefficients_rest", C.c_void_p), ("total_bases_sh_rest", C.c_uint32), ("w2c", C.c_void_p), ("cam_position", C.c_void_p),
+                ("active_sh_bases", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("near_plane", C.c_float), ("far_plane", C.c_float), ("primitive_workspace", C.c_void_p), ("primitive_workspace_bytes", C.c_size_t)]
+
+
+class FastgsShRestAdam(C.Structure):  # lfs_fastgs_sh_rest_adam
+    _fields_ = [("sh_coefficients_rest", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("eps", C.c_float), ("bias_correction1_rcp", C.c_float), ("bias_correction2_sqrt_rcp", C.c_float)]
+
+
+class FastgsBackwardArgs(C.Structure):  # lfs_fastgs_view_backward_args
+    _fields_ = [("n_instances", C.c_int64), ("instance_workspace", C.c_void_p), ("instance_workspace_bytes", C.c_size_t), ("grad_image", C.c_void_p),
+                ("grad_alpha", C.c_void_p), ("alpha", C.c_void_p), ("grad_depth", C.c_void_p), ("densification_info", C.c_void_p), ("grad_means", C.c_void_p),
+                ("grad_scales_raw", C.c_void_p), ("grad_rotations_raw", C.c_void_p), ("grad_opacities_raw", C.c_void_p), ("grad_sh_coefficients_0", C.c_void_p),
+                ("grad_sh_coefficients_rest", C.c_void_p), ("grad_w2c", C.c_void_p), ("w2c_workspace", C.c_void_p), ("w2c_workspace_bytes", C.c_size_t),
+                ("adam", C.POINTER(FastgsShRestAdam))]
+
+
 ADAM_MAX_TENSORS = 8
 
 # every symbol include/lfs_gsplat.h declares
@@ -83,7 +103,7 @@ EXPORTS = [
     "lfs_intersect_tile_workspace_bytes", "lfs_intersect_tile_count", "lfs_intersect_tile_emit", "lfs_intersect_tile_count_ex", "lfs_intersect_tile_emit_ex", "lfs_get_debug_flags", "lfs_intersect_offset",
     "lfs_rasterize_workspace_bytes", "lfs_set_debug_flags", "lfs_rasterize_to_pixels_from_world_3dgs_fwd", "lfs_rasterize_to_pixels_from_world_3dgs_bwd", "lfs_rasterize_to_pixels_from_world_3dgs_bwd_prepared", "lfs_rasterize_to_pixels_from_world_3dgs_bwd_prepared_mse",
     "lfs_sh_model_fwd", "lfs_sh_model_bwd", "lfs_sh_model_bwd_adam", "lfs_sh_model_fwd_views", "lfs_sh_model_bwd_views", "lfs_activations_fwd", "lfs_activations_bwd", "lfs_mse_loss_fwd_bwd", "lfs_mse_loss_chw_fwd_bwd",
-    "lfs_fastgs_primitive_workspace_bytes", "lfs_fastgs_instance_workspace_bytes", "lfs_fastgs_preprocess", "lfs_fastgs_preprocess_ex", "lfs_fastgs_wait_n_instances", "lfs_fastgs_render", "lfs_fastgs_backward", "lfs_fastgs_backward_adam", "lfs_fastgs_w2c_workspace_bytes", "lfs_fastgs_backward_w2c",
+    "lfs_fastgs_primitive_workspace_bytes", "lfs_fastgs_instance_workspace_bytes", "lfs_fastgs_view_preprocess", "lfs_fastgs_wait_n_instances", "lfs_fastgs_view_render", "lfs_fastgs_view_backward", "lfs_fastgs_w2c_workspace_bytes",
     "lfs_fastgs_set_debug_flags", "lfs_fused_ssim_fwd", "lfs_fused_ssim_bwd", "lfs_photometric_loss_workspace_bytes", "lfs_photometric_loss_fwd_bwd", "lfs_photometric_loss_chw_fwd_bwd", "lfs_photometric_loss_ex_fwd_bwd", "lfs_mse_loss_ex_fwd_bwd",
     "lfs_bilateral_slice_fwd", "lfs_bilateral_slice_bwd", "lfs_bilateral_slice_plan", "lfs_bilateral_tv_loss_fwd", "lfs_bilateral_tv_loss_bwd", "lfs_image_u8_to_chw_f32", "lfs_mean_neighbor_distances", "lfs_mean_neighbor_distances_exact",
     "lfs_quats_to_rotmats", "lfs_relocation", "lfs_add_noise", "lfs_mcmc_relocate_workspace_bytes", "lfs_mcmc_relocate",
@@ -93,7 +113,7 @@ EXPORTS = [
     "lfs_select_kth_workspace_bytes", "lfs_select_kth_f32", "lfs_admm_update_workspace_bytes", "lfs_admm_update", "lfs_admm_loss_grad_workspace_bytes", "lfs_admm_loss_grad",
     "lfs_admm_prune_mask_workspace_bytes", "lfs_admm_prune_mask",
     "lfs_mask_prepare", "lfs_photometric_loss_masked_fwd_bwd", "lfs_mse_loss_masked_fwd_bwd",
-    "lfs_fastgs_render_depth", "lfs_fastgs_backward_depth", "lfs_depth_prepare", "lfs_depth_l1_loss_fwd_bwd",
+    "lfs_depth_prepare", "lfs_depth_l1_loss_fwd_bwd",
 ]
 
 
@@ -129,6 +149,8 @@ def load_library():
         for name in ("lfs_select_kth_workspace_bytes", "lfs_admm_update_workspace_bytes", "lfs_admm_loss_grad_workspace_bytes", "lfs_admm_prune_mask_workspace_bytes"):
             getattr(lib, name).restype = C.c_size_t
         lib.lfs_version.restype = C.c_char_p
+        for name in ("lfs_fastgs_view_preprocess", "lfs_fastgs_view_render", "lfs_fastgs_view_backward"):
+            getattr(lib, name).restype = C.c_int
         if os.environ.get("LFS_DEBUG_FLAGS"):   # measurement / debugging only (tools/*.sh): e.g. 64 = the reference's tile lists + pack + cull kernels inside the step
             lib.lfs_set_debug_flags(C.c_uint32(int(os.environ["LFS_DEBUG_FLAGS"], 0)))
         _LIB = lib

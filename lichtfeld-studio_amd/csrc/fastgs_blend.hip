@@ -15,9 +15,9 @@ namespace lfs {
 namespace fgs {
 
 int launch_scatter(uint32_t N, const Frame& f, const PrimWs& w, int64_t* keys, hipStream_t s);
-int launch_preprocess_bwd(uint32_t N, const float* means, const float* scales_raw, const float* rot_raw, const float* sh0, const float* sh_rest, const Frame& f, const PrimWs& w,
-                          float* g_means, float* g_scales_raw, float* g_rot_raw, float* g_opac_raw, float* g_sh0, float* g_sh_rest, float* densification_info, hipStream_t s,
-                          const ShAdamArgs* adam, float* grad_w2c, float* w2c_partials, int depth);
+Frame make_frame(const lfs_fastgs_view& v);
+int launch_preprocess_bwd(const lfs_fastgs_view& v, const Frame& f, const PrimWs& w, const lfs_fastgs_view_backward_args& a, const float* sh_rest, const ShAdamArgs* adam,
+                          int depth, hipStream_t s);
 uint32_t remembered_flags(const void* primitive_workspace);
 size_t w2c_workspace_bytes(uint32_t N);
 int launch_w2c_reduce(uint32_t N, const float* w2c_partials, float* grad_w2c, hipStream_t s);
@@ -110,7 +110,7 @@ LFS_DI Frag frag_eval(const GaussRec& rec, const float px, const float py) {
 }
 
 // fwd / bwd: ONE wavefront per workgroup (the cells of a tile never cooperate here; a finished cell frees its slot at once - as raster.hip's wave_geom)
-// DEPTH (lfs_fastgs_render_depth): one more accumulator D += r2.w T alpha over exactly the instances the colour takes, stored to depth_map [1,H,W]; r2.w arrives with
+// DEPTH (lfs_fastgs_view_render with a depth plane): one more accumulator D += r2.w T alpha over exactly the instances the colour takes, stored to depth_map [1,H,W]; r2.w arrives with
 // the record. The default form does not read r2.w or depth_map.
 template <bool DEPTH>
 __global__ void __launch_bounds__(64) fg_blend_fwd_kernel(
@@ -156,7 +156,7 @@ __global__ void __launch_bounds__(64) fg_blend_fwd_kernel(
 
 // ACC 0: the rows are summed with float atomics, whose arrival order - and so the last bits of every gradient - differs from run to run. ACC 1 / 2: the two passes of
 // the deterministic mode (lfs_set_debug_flags bit 4, as the 3DGUT backward's: wave_sum16_atomic in lfs_raster_common.cuh), fg_det_resolve_kernel turns the sums back into floats.
-// DEPTH (lfs_fastgs_backward_depth): depth is a fourth blended channel - cv = c . g_image + r2.w g_depth feeds dL/dalpha and the colour-behind recurrence - and slot 9
+// DEPTH (lfs_fastgs_view_backward with grad_depth): depth is a fourth blended channel - cv = c . g_image + r2.w g_depth feeds dL/dalpha and the colour-behind recurrence - and slot 9
 // of the row takes sum w g_depth = dL/dd; the reduction carries ten values instead of nine (wave_sum9_atomic_lds<ACC, 10>), through the same block and atomic.
 template <int ACC, bool DEPTH>
 __global__ void __launch_bounds__(64) fg_blend_bwd_kernel(
@@ -247,23 +247,30 @@ using namespace lfs;
 
 extern "C" void lfs_fastgs_set_debug_flags(uint32_t flags) { fgs::g_fastgs_debug = flags; }
 
-static fgs::Frame make_frame(const float* w2c, const float* cam_position, uint32_t active_sh_bases, uint32_t total_rest, uint32_t width, uint32_t height,
-                             float fx, float fy, float cx, float cy, float near_plane, float far_plane) {
-    return fgs::Frame{w2c, cam_position, active_sh_bases, total_rest, width, height, (width + fgs::TILE - 1) / fgs::TILE, (height + fgs::TILE - 1) / fgs::TILE,
-                      fx, fy, cx, cy, near_plane, far_plane};
+static_assert(sizeof(lfs_fastgs_sh_rest_adam) == 48 && sizeof(lfs_fastgs_view_backward_args) == 144, "the ctypes mirrors (capi.py) are laid out by hand");
+
+// the depth kind (1: z, 2: 1 / z) of the preprocess that last filled this workspace, 0 when it carried no depth flag (fastgs_prep.hip: remember_flags)
+static int workspace_depth_kind(const void* primitive_workspace) {
+    const uint32_t flags = fgs::remembered_flags(primitive_workspace);
+    return (flags & LFS_FASTGS_DEPTH) ? 1 : (flags & LFS_FASTGS_INVDEPTH) ? 2 : 0;
 }
 
-static int fastgs_render_impl(
-    uint32_t N, uint32_t width, uint32_t height, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
-    void* instance_workspace, size_t instance_workspace_bytes, float* image, float* alpha, float* depth, lfs_stream_t stream) {
+// Whether the workspace carries d in its records is validated on the HOST (the flags the library remembers by the workspace's address: no device read, no launch on
+// a refusal); the antialiased bit is picked on the device.
+extern "C" int lfs_fastgs_view_render(const lfs_fastgs_view* view, int64_t n_instances, void* instance_workspace, size_t instance_workspace_bytes,
+                                      float* image, float* alpha, float* depth, lfs_stream_t stream) {
+    if (!view) return LFS_E_INVALID;
+    const uint32_t N = view->N, width = view->width, height = view->height;
+    void* const primitive_workspace = view->primitive_workspace;
+    if (depth && (!primitive_workspace || workspace_depth_kind(primitive_workspace) == 0)) return LFS_E_INVALID;
     if (!primitive_workspace || !image || !alpha || width == 0 || height == 0 || n_instances < 0 || n_instances > 0x7FFFFFFFll) return LFS_E_INVALID;
     if (N >= (1u << 26) || uint64_t(n_instances) >= (1ull << 29)) return LFS_E_UNSUPPORTED; // 32-bit byte offsets of the record walker
     fgs::PrimWs w = fgs::prim_ws(primitive_workspace, N, width, height);
-    if (primitive_workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
+    if (view->primitive_workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
     fgs::InstWs iw = fgs::inst_ws(instance_workspace, width, height, uint64_t(n_instances));
     if (!instance_workspace || instance_workspace_bytes < iw.bytes) return LFS_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const fgs::Frame f = make_frame(nullptr, nullptr, 1, 0, width, height, 0, 0, 0, 0, 0, 0);
+    const fgs::Frame f = fgs::make_frame(*view);   // (the kernels of this stage read the image and grid extents only)
     const uint32_t T = f.gw * f.gh;
     if (n_instances > 0) {
         int rc = fgs::launch_scatter(N, f, w, iw.keys, s);
@@ -297,65 +304,66 @@ static int fastgs_render_impl(
     return (int)hipGetLastError();
 }
 
-extern "C" int lfs_fastgs_render(
-    uint32_t N, uint32_t width, uint32_t height, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
-    void* instance_workspace, size_t instance_workspace_bytes, float* image, float* alpha, lfs_stream_t stream) {
-    return fastgs_render_impl(N, width, height, n_instances, primitive_workspace, primitive_workspace_bytes, instance_workspace, instance_workspace_bytes, image, alpha,
-                              nullptr, stream);
-}
+extern "C" size_t lfs_fastgs_w2c_workspace_bytes(uint32_t N) { return fgs::w2c_workspace_bytes(N); }
 
-// the depth kind (1: z, 2: 1 / z) of the preprocess that last filled this workspace, 0 when it carried no depth flag (fastgs_prep.hip: remember_flags)
-static int workspace_depth_kind(const void* primitive_workspace) {
-    const uint32_t flags = fgs::remembered_flags(primitive_workspace);
-    return (flags & LFS_FASTGS_DEPTH) ? 1 : (flags & LFS_FASTGS_INVDEPTH) ? 2 : 0;
-}
-
-extern "C" int lfs_fastgs_render_depth(
-    uint32_t N, uint32_t width, uint32_t height, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
-    void* instance_workspace, size_t instance_workspace_bytes, float* image, float* alpha, float* depth, lfs_stream_t stream) {
-    if (!depth || !primitive_workspace || workspace_depth_kind(primitive_workspace) == 0) return LFS_E_INVALID;
-    return fastgs_render_impl(N, width, height, n_instances, primitive_workspace, primitive_workspace_bytes, instance_workspace, instance_workspace_bytes, image, alpha,
-                              depth, stream);
-}
-
-static int fastgs_backward_impl(
-    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* sh_coefficients_0, const float* sh_coefficients_rest,
-    uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position, uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy,
-    float cx, float cy, float near_plane, float far_plane, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
-    void* instance_workspace, size_t instance_workspace_bytes, const float* grad_image, const float* grad_alpha, const float* alpha,
-    float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
-    float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest, lfs_stream_t stream, const lfs::ShAdamArgs* adam, float* grad_w2c = nullptr,
-    void* w2c_workspace = nullptr, const float* grad_depth = nullptr, int depth = 0 /* with grad_depth: the workspace's depth kind */) {
-    if (!primitive_workspace || !w2c || !cam_position || !grad_image || !grad_alpha || !alpha || width == 0 || height == 0 || n_instances < 0) return LFS_E_INVALID;
+extern "C" int lfs_fastgs_view_backward(const lfs_fastgs_view* view, const lfs_fastgs_view_backward_args* args, lfs_stream_t stream) {
+    if (!view || !args) return LFS_E_INVALID;
+    const lfs_fastgs_view& v = *view;
+    const lfs_fastgs_view_backward_args& a = *args;
+    const uint32_t N = v.N;
+    // the optimizer-fused form: the parameter it updates replaces the view's sh_coefficients_rest; it has no camera gradient and no depth gradient
+    const float* sh_rest = v.sh_coefficients_rest;
+    lfs::ShAdamArgs adam_args{};
+    const lfs::ShAdamArgs* adam = nullptr;
+    if (a.adam) {
+        if (v.total_bases_sh_rest == 0 || !a.adam->exp_avg || !a.adam->exp_avg_sq) return LFS_E_INVALID;
+        if (a.grad_w2c || a.grad_depth) return LFS_E_INVALID;
+        adam_args = lfs::ShAdamArgs{a.adam->exp_avg, a.adam->exp_avg_sq, a.adam->lr, a.adam->beta1, a.adam->beta2, a.adam->eps, a.adam->bias_correction1_rcp,
+                                    a.adam->bias_correction2_sqrt_rcp};
+        adam = &adam_args;
+        sh_rest = a.adam->sh_coefficients_rest;
+    }
+    int depth = 0;   // with grad_depth: the workspace's depth kind
+    if (a.grad_depth) {
+        if (!v.primitive_workspace) return LFS_E_INVALID;
+        depth = workspace_depth_kind(v.primitive_workspace);
+        if (depth == 0) return LFS_E_INVALID;
+    }
+    if (a.grad_w2c) {
+        if (!a.w2c_workspace || a.w2c_workspace_bytes < fgs::w2c_workspace_bytes(N)) return LFS_E_WORKSPACE;
+        if (reinterpret_cast<uintptr_t>(a.w2c_workspace) % 16 != 0) return LFS_E_INVALID;   // fg_w2c_reduce_kernel reads the partial rows as float4
+    } else if (a.w2c_workspace || a.w2c_workspace_bytes != 0) return LFS_E_INVALID;
+    if (!v.primitive_workspace || !v.w2c || !v.cam_position || !a.grad_image || !a.grad_alpha || !a.alpha || v.width == 0 || v.height == 0 || a.n_instances < 0)
+        return LFS_E_INVALID;
 #ifdef LFS_EMULATE
     const bool det = false;   // (the emulated library has no integer-atomic passes)
 #else
     const bool det = (lfs_get_debug_flags() & 16u) != 0;   // the workspace then carries the int64 rows: it was sized with the bit set, or it is refused here
 #endif
-    fgs::PrimWs w = fgs::prim_ws(primitive_workspace, N, width, height, det);
-    if (primitive_workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
-    fgs::InstWs iw = fgs::inst_ws(instance_workspace, width, height, uint64_t(n_instances));
-    if (!instance_workspace || instance_workspace_bytes < iw.bytes) return LFS_E_WORKSPACE;
-    if (N == 0) return grad_w2c ? fgs::launch_w2c_reduce(0, static_cast<const float*>(w2c_workspace), grad_w2c, (hipStream_t)stream) : LFS_OK;   // (grad_w2c is fully written: zeros)
-    if (!means || !scales_raw || !rotations_raw || !grad_means || !grad_scales_raw || !grad_rotations_raw || !grad_opacities_raw || !grad_sh_coefficients_0 ||
-        (total_bases_sh_rest > 0 && (!sh_coefficients_rest || (!grad_sh_coefficients_rest && !adam)))) return LFS_E_INVALID;
+    fgs::PrimWs w = fgs::prim_ws(v.primitive_workspace, N, v.width, v.height, det);
+    if (v.primitive_workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
+    fgs::InstWs iw = fgs::inst_ws(a.instance_workspace, v.width, v.height, uint64_t(a.n_instances));
+    if (!a.instance_workspace || a.instance_workspace_bytes < iw.bytes) return LFS_E_WORKSPACE;
+    if (N == 0) return a.grad_w2c ? fgs::launch_w2c_reduce(0, static_cast<const float*>(a.w2c_workspace), a.grad_w2c, (hipStream_t)stream) : LFS_OK;   // (grad_w2c is fully written: zeros)
+    if (!v.means || !v.scales_raw || !v.rotations_raw || !a.grad_means || !a.grad_scales_raw || !a.grad_rotations_raw || !a.grad_opacities_raw || !a.grad_sh_coefficients_0 ||
+        (v.total_bases_sh_rest > 0 && (!sh_rest || (!a.grad_sh_coefficients_rest && !adam)))) return LFS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    const fgs::Frame f = make_frame(w2c, cam_position, active_sh_bases, total_bases_sh_rest, width, height, fx, fy, cx, cy, near_plane, far_plane);
+    const fgs::Frame f = fgs::make_frame(v);
     // debug bit 1: the accumulator rows of the previous backward on this workspace are kept (no blending backward). Its float atomics arrive in a different order on
     // every run; with the rows held fixed, the per-primitive stage of two calls can be compared bit for bit (tests/test_gpu_fastgs_w2c.py)
-    // TEST-ONLY: with the bit left set every gradient is computed from stale rows. The optimizer-fused entry point (adam != nullptr) ignores it.
+    // TEST-ONLY: with the bit left set every gradient is computed from stale rows. The optimizer-fused form (adam != nullptr) ignores it.
     const bool keep_acc = (fgs::g_fastgs_debug & 2u) != 0 && adam == nullptr;
     if (!keep_acc) {
         hipError_t e = hipMemsetAsync(w.acc, 0, sizeof(float) * ACC_STRIDE * size_t(N), s);
         if (e != hipSuccess) return (int)e;
     }
     const uint32_t T = f.gw * f.gh;
-    if (n_instances > 0 && !keep_acc) {
+    if (a.n_instances > 0 && !keep_acc) {
         lfs::ProfScope prof("fastgs_blend_bwd", s);
         const uint32_t wgrid = cell_grid_blocks(uint64_t(T) * fgs::WPT, fgs::WPT);
-#define LFS_FG_BWD_D(ACC, DEPTH) hipLaunchKernelGGL((fgs::fg_blend_bwd_kernel<ACC, DEPTH>), dim3(wgrid), dim3(64), 0, s, f.gw, f.gh, width, height, w.rec, w.offsets, iw.cell_count, \
-                                                   iw.cell_list, alpha, w.n_contrib, grad_image, grad_alpha, w.acc, w.det64, grad_depth)
-#define LFS_FG_BWD(ACC) do { if (grad_depth) LFS_FG_BWD_D(ACC, true); else LFS_FG_BWD_D(ACC, false); } while (0)
+#define LFS_FG_BWD_D(ACC, DEPTH) hipLaunchKernelGGL((fgs::fg_blend_bwd_kernel<ACC, DEPTH>), dim3(wgrid), dim3(64), 0, s, f.gw, f.gh, v.width, v.height, w.rec, w.offsets, iw.cell_count, \
+                                                   iw.cell_list, a.alpha, w.n_contrib, a.grad_image, a.grad_alpha, w.acc, w.det64, a.grad_depth)
+#define LFS_FG_BWD(ACC) do { if (a.grad_depth) LFS_FG_BWD_D(ACC, true); else LFS_FG_BWD_D(ACC, false); } while (0)
         if (det) { // pass 1: per-slot maxima of |total| (integer atomicMax), pass 2: 64-bit fixed-point sums, then back to float
             const size_t n_acc = ACC_STRIDE * size_t(N);
             hipError_t e = hipMemsetAsync(w.det64, 0, sizeof(unsigned long long) * n_acc, s);
@@ -366,82 +374,5 @@ static int fastgs_backward_impl(
 #undef LFS_FG_BWD
 #undef LFS_FG_BWD_D
     }
-    return fgs::launch_preprocess_bwd(N, means, scales_raw, rotations_raw, sh_coefficients_0, sh_coefficients_rest, f, w, grad_means, grad_scales_raw, grad_rotations_raw,
-                                      grad_opacities_raw, grad_sh_coefficients_0, grad_sh_coefficients_rest, densification_info, s, adam, grad_w2c,
-                                      static_cast<float*>(w2c_workspace), grad_depth ? depth : 0);
-}
-
-extern "C" int lfs_fastgs_backward(
-    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* sh_coefficients_0, const float* sh_coefficients_rest,
-    uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position, uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy,
-    float cx, float cy, float near_plane, float far_plane, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
-    void* instance_workspace, size_t instance_workspace_bytes, const float* grad_image, const float* grad_alpha, const float* alpha,
-    float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
-    float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest, lfs_stream_t stream) {
-    return fastgs_backward_impl(N, means, scales_raw, rotations_raw, sh_coefficients_0, sh_coefficients_rest, total_bases_sh_rest, w2c, cam_position, active_sh_bases,
-                                width, height, fx, fy, cx, cy, near_plane, far_plane, n_instances, primitive_workspace, primitive_workspace_bytes, instance_workspace,
-                                instance_workspace_bytes, grad_image, grad_alpha, alpha, densification_info, grad_means, grad_scales_raw, grad_rotations_raw,
-                                grad_opacities_raw, grad_sh_coefficients_0, grad_sh_coefficients_rest, stream, nullptr);
-}
-
-extern "C" size_t lfs_fastgs_w2c_workspace_bytes(uint32_t N) { return fgs::w2c_workspace_bytes(N); }
-
-// lfs_fastgs_backward + the camera gradient of pose optimisation (rasterization_api.cu:133-136, 163, 180): grad_w2c [4,4] = sum over the primitives with
-// n_touched > 0 of dL/d(mean in camera space) (x) (mean, 1) in rows 0-2, row 3 = 0; all 16 floats are written, whatever N and n_instances are.
-extern "C" int lfs_fastgs_backward_w2c(
-    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* sh_coefficients_0, const float* sh_coefficients_rest,
-    uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position, uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy,
-    float cx, float cy, float near_plane, float far_plane, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
-    void* instance_workspace, size_t instance_workspace_bytes, const float* grad_image, const float* grad_alpha, const float* alpha,
-    float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
-    float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest, float* grad_w2c, void* w2c_workspace, size_t w2c_workspace_bytes, lfs_stream_t stream) {
-    if (!grad_w2c) return LFS_E_INVALID;
-    if (!w2c_workspace || w2c_workspace_bytes < fgs::w2c_workspace_bytes(N)) return LFS_E_WORKSPACE;
-    if (reinterpret_cast<uintptr_t>(w2c_workspace) % 16 != 0) return LFS_E_INVALID;   // fg_w2c_reduce_kernel reads the partial rows as float4
-    return fastgs_backward_impl(N, means, scales_raw, rotations_raw, sh_coefficients_0, sh_coefficients_rest, total_bases_sh_rest, w2c, cam_position, active_sh_bases,
-                                width, height, fx, fy, cx, cy, near_plane, far_plane, n_instances, primitive_workspace, primitive_workspace_bytes, instance_workspace,
-                                instance_workspace_bytes, grad_image, grad_alpha, alpha, densification_info, grad_means, grad_scales_raw, grad_rotations_raw,
-                                grad_opacities_raw, grad_sh_coefficients_0, grad_sh_coefficients_rest, stream, nullptr, grad_w2c, w2c_workspace);
-}
-
-// lfs_fastgs_backward[_w2c] with a gradient for the depth map of lfs_fastgs_render_depth. Whether the workspace carries d in its records is validated on the HOST (the
-// flags the library remembers by the workspace's address: no device read, no launch on a refusal); the antialiased bit is still picked on the device.
-extern "C" int lfs_fastgs_backward_depth(
-    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* sh_coefficients_0, const float* sh_coefficients_rest,
-    uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position, uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy,
-    float cx, float cy, float near_plane, float far_plane, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
-    void* instance_workspace, size_t instance_workspace_bytes, const float* grad_image, const float* grad_alpha, const float* alpha,
-    float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
-    float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest, const float* grad_depth, float* grad_w2c, void* w2c_workspace, size_t w2c_workspace_bytes,
-    lfs_stream_t stream) {
-    if (!grad_depth || !primitive_workspace) return LFS_E_INVALID;
-    const int depth = workspace_depth_kind(primitive_workspace);
-    if (depth == 0) return LFS_E_INVALID;
-    if (grad_w2c) {
-        if (!w2c_workspace || w2c_workspace_bytes < fgs::w2c_workspace_bytes(N)) return LFS_E_WORKSPACE;
-        if (reinterpret_cast<uintptr_t>(w2c_workspace) % 16 != 0) return LFS_E_INVALID;
-    }
-    return fastgs_backward_impl(N, means, scales_raw, rotations_raw, sh_coefficients_0, sh_coefficients_rest, total_bases_sh_rest, w2c, cam_position, active_sh_bases,
-                                width, height, fx, fy, cx, cy, near_plane, far_plane, n_instances, primitive_workspace, primitive_workspace_bytes, instance_workspace,
-                                instance_workspace_bytes, grad_image, grad_alpha, alpha, densification_info, grad_means, grad_scales_raw, grad_rotations_raw,
-                                grad_opacities_raw, grad_sh_coefficients_0, grad_sh_coefficients_rest, stream, nullptr, grad_w2c, grad_w2c ? w2c_workspace : nullptr,
-                                grad_depth, depth);
-}
-
-// lfs_fastgs_backward for a step with ONE view, fused with the optimizer: sh_coefficients_rest and its Adam moments are updated in place by the SH
-// backward (fast_gs::optimizer::adam_step arithmetic), its gradient is never stored. Everything else as lfs_fastgs_backward.
-extern "C" int lfs_fastgs_backward_adam(
-    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* sh_coefficients_0, float* sh_coefficients_rest,
-    uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position, uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy,
-    float cx, float cy, float near_plane, float far_plane, int64_t n_instances, void* primitive_workspace, size_t primitive_workspace_bytes,
-    void* instance_workspace, size_t instance_workspace_bytes, const float* grad_image, const float* grad_alpha, const float* alpha,
-    float* densification_info, float* grad_means, float* grad_scales_raw, float* grad_rotations_raw, float* grad_opacities_raw,
-    float* grad_sh_coefficients_0, float* sh_rest_exp_avg, float* sh_rest_exp_avg_sq, float lr, float beta1, float beta2, float eps,
-    float bias_correction1_rcp, float bias_correction2_sqrt_rcp, lfs_stream_t stream) {
-    if (total_bases_sh_rest == 0 || !sh_rest_exp_avg || !sh_rest_exp_avg_sq) return LFS_E_INVALID;
-    const lfs::ShAdamArgs adam{sh_rest_exp_avg, sh_rest_exp_avg_sq, lr, beta1, beta2, eps, bias_correction1_rcp, bias_correction2_sqrt_rcp};
-    return fastgs_backward_impl(N, means, scales_raw, rotations_raw, sh_coefficients_0, sh_coefficients_rest, total_bases_sh_rest, w2c, cam_position, active_sh_bases,
-                                width, height, fx, fy, cx, cy, near_plane, far_plane, n_instances, primitive_workspace, primitive_workspace_bytes, instance_workspace,
-                                instance_workspace_bytes, grad_image, grad_alpha, alpha, densification_info, grad_means, grad_scales_raw, grad_rotations_raw,
-                                grad_opacities_raw, grad_sh_coefficients_0, nullptr, stream, &adam);
+    return fgs::launch_preprocess_bwd(v, f, w, a, sh_rest, adam, depth, s);
 }

@@ -216,7 +216,7 @@ LFS_DI void preprocess_bwd_zero_rows(const uint32_t i, float* __restrict__ g_mea
 // AA: the record's opacity is o_eff = sigmoid(raw) * rho, so the accumulator's S = sum alpha dL/dalpha is o_eff dL/do_eff: dL/draw = S (1 - sigmoid(raw)) with the
 // sigmoid from r1.w, and dL/drho = S / rho reaches the 2-D covariance through rho^2 = det0 / det1: dL/d(a0, b, c0) += S/2 (c0/det0 - c/det1, 2b (1/det1 - 1/det0),
 // a0/det0 - a/det1) - no division by rho (a visible primitive has rho >= 1/255, hence det0 > 0). Everything below dcv is the code both modes share.
-// DEPTH (1 / 2, lfs_fastgs_backward_depth): slot 9 of the row is dL/dd, d = z or 1 / z, and z is the third camera-space coordinate: dL/dz = acc[9] (1 | -1 / z^2) is
+// DEPTH (1 / 2, a backward with grad_depth): slot 9 of the row is dL/dd, d = z or 1 / z, and z is the third camera-space coordinate: dL/dz = acc[9] (1 | -1 / z^2) is
 // added to dcam[2] before grad_means and the camera gradient are made of it. densification_info keeps its definition (dL/dmean2d only).
 template <bool AA, int DEPTH>
 LFS_DI void preprocess_bwd_one(
@@ -319,8 +319,8 @@ LFS_DI float block_sum12(float (&v)[W2C_VALS], float (*s_part)[W2C_VALS]) {
 // no lane leaves before the workgroup sum (rows past N and invisible primitives take part with dcam = 0), and the workgroup's 12 sums go to
 // w2c_partials[blockIdx.x * 12 ..] with plain stores; fg_w2c_reduce_kernel adds the rows up.
 // AA: the instantiation for the antialiased mode. The launcher queues both; the one that does not match the mode word the forward left in the workspace returns at once.
-// DEPTH: 0 = the forms of the three entry points without a depth gradient, which look at the antialiased bit only (a depth-mode workspace is an ordinary workspace to
-// them: slot 9 of the rows is zero and not read); 1 / 2 = the forms of lfs_fastgs_backward_depth, which also require their depth bit in the mode word.
+// DEPTH: 0 = the forms of a backward without a depth gradient, which look at the antialiased bit only (a depth-mode workspace is an ordinary workspace to
+// them: slot 9 of the rows is zero and not read); 1 / 2 = the forms of a backward with grad_depth, which also require their depth bit in the mode word.
 template <bool W2C, bool AA, int DEPTH>
 __global__ void __launch_bounds__(256) fg_preprocess_bwd_kernel(
     const uint32_t N, const float* __restrict__ means, const float* __restrict__ scales_raw, const float* __restrict__ rot_raw,
@@ -393,38 +393,38 @@ int launch_scatter(uint32_t N, const Frame& f, const PrimWs& w, int64_t* keys, h
         hipLaunchKernelGGL(fg_scatter_kernel<false>, dim3(blocks), dim3(1024), 0, s, N, pb, f, w.mean2d, w.conic_opacity, w.bounds, w.n_touched, w.depth_bits, w.offsets, w.cursor, keys);
     return (int)hipGetLastError();
 }
-int launch_preprocess_bwd(uint32_t N, const float* means, const float* scales_raw, const float* rot_raw, const float* sh0, const float* sh_rest, const Frame& f, const PrimWs& w,
-                          float* g_means, float* g_scales_raw, float* g_rot_raw, float* g_opac_raw, float* g_sh0, float* g_sh_rest, float* densification_info, hipStream_t s,
-                          const ShAdamArgs* adam, float* grad_w2c, float* w2c_partials, int depth) {
+Frame make_frame(const lfs_fastgs_view& v) {
+    return Frame{v.w2c, v.cam_position, v.active_sh_bases, v.total_bases_sh_rest, v.width, v.height, (v.width + TILE - 1) / TILE, (v.height + TILE - 1) / TILE,
+                 v.fx, v.fy, v.cx, v.cy, v.near_plane, v.far_plane};
+}
+// sh_rest / adam: the view's coefficients and no optimizer, or the optimizer-fused form's parameter; depth: with grad_depth 1 / 2, the kind the host remembers for
+// this workspace, 0 otherwise
+int launch_preprocess_bwd(const lfs_fastgs_view& v, const Frame& f, const PrimWs& w, const lfs_fastgs_view_backward_args& a, const float* sh_rest, const ShAdamArgs* adam,
+                          int depth, hipStream_t s) {
+    const uint32_t N = v.N;
+    float* const w2c_partials = a.grad_w2c ? static_cast<float*>(a.w2c_workspace) : nullptr;
     {
-        // the mode of the forward that filled this workspace is a word IN the workspace, which the host does not read: both instantiations are queued, one returns at once
+        // the mode of the forward that filled this workspace is a word IN the workspace, which the host does not read: both AA instantiations are queued, one returns
+        // at once. (depth, w2c) pick the pair on the host. (The table lists the kernels in the order the code object has always had them: with W2C first.)
         lfs::ProfScope prof("fastgs_preprocess_bwd", s);
-        // depth (lfs_fastgs_backward_depth: 1 / 2, the kind the host remembers for this workspace; 0 otherwise) picks the pair of forms that is queued
-#define LFS_FG_PREP_BWD(W2C, AA, PARTIALS) LFS_FG_PREP_BWD_D(W2C, AA, 0, PARTIALS)
-#define LFS_FG_PREP_BWD_D(W2C, AA, DEPTH, PARTIALS) hipLaunchKernelGGL((fg_preprocess_bwd_kernel<W2C, AA, DEPTH>), dim3((N + 255) / 256), dim3(256), 0, s, N, means, scales_raw, rot_raw, f, w.rec, \
-                                                              w.conic_opacity, w.n_touched, w.acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, PARTIALS, w.mode)
-        if (depth == 0) {
-            if (grad_w2c != nullptr) { LFS_FG_PREP_BWD(true, false, w2c_partials); LFS_FG_PREP_BWD(true, true, w2c_partials); }
-            else { LFS_FG_PREP_BWD(false, false, static_cast<float*>(nullptr)); LFS_FG_PREP_BWD(false, true, static_cast<float*>(nullptr)); }
-        } else if (depth == 1) {
-            if (grad_w2c != nullptr) { LFS_FG_PREP_BWD_D(true, false, 1, w2c_partials); LFS_FG_PREP_BWD_D(true, true, 1, w2c_partials); }
-            else { LFS_FG_PREP_BWD_D(false, false, 1, static_cast<float*>(nullptr)); LFS_FG_PREP_BWD_D(false, true, 1, static_cast<float*>(nullptr)); }
-        } else {
-            if (grad_w2c != nullptr) { LFS_FG_PREP_BWD_D(true, false, 2, w2c_partials); LFS_FG_PREP_BWD_D(true, true, 2, w2c_partials); }
-            else { LFS_FG_PREP_BWD_D(false, false, 2, static_cast<float*>(nullptr)); LFS_FG_PREP_BWD_D(false, true, 2, static_cast<float*>(nullptr)); }
-        }
-#undef LFS_FG_PREP_BWD
-#undef LFS_FG_PREP_BWD_D
+#define LFS_FG_PREP_BWD_PAIR(W2C, DEPTH) {&fg_preprocess_bwd_kernel<W2C, false, DEPTH>, &fg_preprocess_bwd_kernel<W2C, true, DEPTH>}
+        static constexpr decltype(&fg_preprocess_bwd_kernel<false, false, 0>) kernels[3][2][2] = {   // [depth][without grad_w2c][antialiased]
+            {LFS_FG_PREP_BWD_PAIR(true, 0), LFS_FG_PREP_BWD_PAIR(false, 0)}, {LFS_FG_PREP_BWD_PAIR(true, 1), LFS_FG_PREP_BWD_PAIR(false, 1)},
+            {LFS_FG_PREP_BWD_PAIR(true, 2), LFS_FG_PREP_BWD_PAIR(false, 2)}};
+#undef LFS_FG_PREP_BWD_PAIR
+        for (const auto kernel : kernels[depth][a.grad_w2c == nullptr])
+            hipLaunchKernelGGL(kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, v.means, v.scales_raw, v.rotations_raw, f, w.rec, w.conic_opacity, w.n_touched, w.acc,
+                               a.grad_means, a.grad_scales_raw, a.grad_rotations_raw, a.grad_opacities_raw, a.densification_info, w2c_partials, w.mode);
     }
-    if (grad_w2c != nullptr) {
-        const int rc = launch_w2c_reduce(N, w2c_partials, grad_w2c, s);
+    if (a.grad_w2c != nullptr) {
+        const int rc = launch_w2c_reduce(N, w2c_partials, a.grad_w2c, s);
         if (rc) return rc;
     }
     // SH backward (convert_sh_to_color_backward, kernel_utils.cuh:38-106) with the coalesced three-phase kernel of sh.hip: reads dL/d(clamped colour) from the
     // accumulator rows (floats 6..8 of 16), the clamp mask from the record's colour (floats 8..10 of 16), writes g_sh0 / g_sh_rest fully, adds dL/dposition to g_means
     const uint32_t degree = f.active_sh_bases >= 16 ? 3 : f.active_sh_bases >= 9 ? 2 : f.active_sh_bases >= 4 ? 1 : 0;
-    return sh_records_bwd(N, 1 + f.total_rest, degree, means, f.cam_pos, sh0, sh_rest, w.n_touched, reinterpret_cast<const float*>(w.rec) + 8, 16, w.acc + 5, 16,
-                          g_sh0, g_sh_rest, g_means, s, adam);
+    return sh_records_bwd(N, 1 + f.total_rest, degree, v.means, f.cam_pos, v.sh_coefficients_0, sh_rest, w.n_touched, reinterpret_cast<const float*>(w.rec) + 8, 16,
+                          w.acc + 5, 16, a.grad_sh_coefficients_0, adam ? nullptr : a.grad_sh_coefficients_rest, a.grad_means, s, adam);
 }
 
 } // namespace fgs
@@ -445,11 +445,11 @@ static Readback& readback() {
     return rb;
 }
 
-// The flags of the depth-mode preprocess that last filled a primitive workspace, by the workspace's address: what lfs_fastgs_render_depth and lfs_fastgs_backward_depth
-// validate against without reading the mode word back (that would be a host sync). Only workspaces filled WITH a depth flag take an entry; a preprocess without one
+// The flags of the depth-mode preprocess that last filled a primitive workspace, by the workspace's address: what a render with a depth plane and a backward with
+// grad_depth validate against without reading the mode word back (that would be a host sync). Only workspaces filled WITH a depth flag take an entry; a preprocess without one
 // erases the entry of its address (the workspace stops counting as a depth workspace) and takes none, so ordinary forwards - evaluation renders, other views - never
 // push a depth workspace out. DEPTH_SLOTS depth forwards can be outstanding (filled, their backward still to come); one more evicts the least recently filled, whose
-// depth entry points then return LFS_E_INVALID (fastgs.py names that cause in its error). Device addresses are unique across the devices of a process (one unified
+// depth plane and grad_depth are then refused with LFS_E_INVALID (fastgs.py names that cause in its error). Device addresses are unique across the devices of a process (one unified
 // address space), so the address alone is the key. A mutex guards the table: the entry points may be called from several host threads.
 constexpr int DEPTH_SLOTS = 256;
 struct DepthSlot { const void* ws = nullptr; uint32_t flags = 0; uint64_t stamp = 0; };
@@ -478,7 +478,7 @@ uint32_t remembered_flags(const void* ws) {   // 0: a workspace that was not (or
 }
 } } // namespace lfs::fgs
 
-// n_instances of the last lfs_fastgs_preprocess call on this process: waits for the read-back event only (not for the SH kernel queued after it)
+// n_instances of the last lfs_fastgs_view_preprocess call on this process: waits for the read-back event only (not for the SH kernel queued after it)
 extern "C" int lfs_fastgs_wait_n_instances(int64_t* n_instances) {
     if (!n_instances) return LFS_E_INVALID;
     lfs::fgs::Readback& rb = lfs::fgs::readback();
@@ -498,27 +498,27 @@ extern "C" size_t lfs_fastgs_instance_workspace_bytes(uint32_t width, uint32_t h
 }
 
 // flags bit 0 (LFS_FASTGS_ANTIALIASED): the antialiased mode of fg_preprocess_kernel. The mode is recorded in the primitive workspace (PrimWs::mode), rewritten by
-// every call with N > 0; render and the backward entry points need no flag.
+// every call with N > 0; render and the backward need no flag.
 // bits 2 / 3 (LFS_FASTGS_DEPTH / LFS_FASTGS_INVDEPTH, exclusive): the depth forms of the kernel; the host remembers the flags by the workspace's address for the
-// two depth entry points (remember_flags).
-extern "C" int lfs_fastgs_preprocess_ex(
-    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* opacities_raw,
-    const float* sh_coefficients_0, const float* sh_coefficients_rest, uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position,
-    uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy, float cx, float cy, float near_plane, float far_plane,
-    int64_t* n_instances, void* primitive_workspace, size_t primitive_workspace_bytes, uint32_t flags, lfs_stream_t stream) {
+// render's depth plane and the backward's grad_depth (remember_flags).
+static_assert(sizeof(lfs_fastgs_view) == 136, "the ctypes mirror (capi.py) is laid out by hand");
+extern "C" int lfs_fastgs_view_preprocess(const lfs_fastgs_view* view, uint32_t flags, int64_t* n_instances, lfs_stream_t stream) {
+    if (!view) return LFS_E_INVALID;
+    const lfs_fastgs_view& v = *view;
     if (flags & ~uint32_t(LFS_FASTGS_ANTIALIASED | LFS_FASTGS_DEPTH | LFS_FASTGS_INVDEPTH)) return LFS_E_INVALID;
     if ((flags & LFS_FASTGS_DEPTH) && (flags & LFS_FASTGS_INVDEPTH)) return LFS_E_INVALID;
     static_assert(LFS_FASTGS_ANTIALIASED == fgs::MODE_ANTIALIASED && LFS_FASTGS_DEPTH == fgs::MODE_DEPTH && LFS_FASTGS_INVDEPTH == fgs::MODE_INVDEPTH, "the mode word holds the flags");
     const bool aa = (flags & LFS_FASTGS_ANTIALIASED) != 0;
     const int depth = (flags & LFS_FASTGS_DEPTH) ? 1 : (flags & LFS_FASTGS_INVDEPTH) ? 2 : 0;
-    if (!n_instances || !primitive_workspace || !w2c || !cam_position || width == 0 || height == 0) return LFS_E_INVALID;
-    if (active_sh_bases == 0 || active_sh_bases > 16 || (active_sh_bases > 1 && total_bases_sh_rest + 1 < active_sh_bases)) return LFS_E_INVALID;
-    fgs::PrimWs w = fgs::prim_ws(primitive_workspace, N, width, height);
-    if (primitive_workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
-    if (N > 0 && (!means || !scales_raw || !rotations_raw || !opacities_raw || !sh_coefficients_0 || (total_bases_sh_rest > 0 && !sh_coefficients_rest))) return LFS_E_INVALID;
+    const uint32_t N = v.N;
+    if (!n_instances || !v.primitive_workspace || !v.w2c || !v.cam_position || v.width == 0 || v.height == 0) return LFS_E_INVALID;
+    if (v.active_sh_bases == 0 || v.active_sh_bases > 16 || (v.active_sh_bases > 1 && v.total_bases_sh_rest + 1 < v.active_sh_bases)) return LFS_E_INVALID;
+    fgs::PrimWs w = fgs::prim_ws(v.primitive_workspace, N, v.width, v.height);
+    if (v.primitive_workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
+    if (N > 0 && (!v.means || !v.scales_raw || !v.rotations_raw || !v.opacities_raw || !v.sh_coefficients_0 || (v.total_bases_sh_rest > 0 && !v.sh_coefficients_rest)))
+        return LFS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    fgs::Frame f{w2c, cam_position, active_sh_bases, total_bases_sh_rest, width, height, (width + fgs::TILE - 1) / fgs::TILE, (height + fgs::TILE - 1) / fgs::TILE,
-                 fx, fy, cx, cy, near_plane, far_plane};
+    const fgs::Frame f = fgs::make_frame(v);
     const uint32_t T = f.gw * f.gh;
     if (T > 65535u) return LFS_E_UNSUPPORTED; // bounds are ushort4 (as in the reference: ushort tile keys)
     hipError_t e = hipMemsetAsync(w.totals, 0, (char*)w.offsets - (char*)w.totals, s); // totals + cursor
@@ -528,13 +528,12 @@ extern "C" int lfs_fastgs_preprocess_ex(
         if (N > 0) {
             const uint32_t pb = fgs::per_block_for(N), blocks = (N + pb - 1) / pb;
             const bool lds = size_t(T) * 8 <= 64 * 1024;
-#define LFS_FG_PREP(LDS, AA) do { if (depth == 0) LFS_FG_PREP_D(LDS, AA, 0); else if (depth == 1) LFS_FG_PREP_D(LDS, AA, 1); else LFS_FG_PREP_D(LDS, AA, 2); } while (0)
-#define LFS_FG_PREP_D(LDS, AA, DEPTH) hipLaunchKernelGGL((fgs::fg_preprocess_kernel<LDS, AA, DEPTH>), dim3(blocks), dim3(1024), LDS ? size_t(T) * 4 : size_t(0), s, N, pb, means, scales_raw, \
-                                                rotations_raw, opacities_raw, f, w.rec, w.mean2d, w.conic_opacity, w.bounds, w.n_touched, w.depth_bits, w.totals, w.mode)
-            if (lds) { if (aa) LFS_FG_PREP(true, true); else LFS_FG_PREP(true, false); }
-            else { if (aa) LFS_FG_PREP(false, true); else LFS_FG_PREP(false, false); }
-#undef LFS_FG_PREP
-#undef LFS_FG_PREP_D
+#define LFS_FG_PREP_ROW(LDS, AA) {&fgs::fg_preprocess_kernel<LDS, AA, 0>, &fgs::fg_preprocess_kernel<LDS, AA, 1>, &fgs::fg_preprocess_kernel<LDS, AA, 2>}
+            static constexpr decltype(&fgs::fg_preprocess_kernel<false, false, 0>) kernels[2][2][3] = {   // [no LDS][default mode][depth]: the code object's order
+                {LFS_FG_PREP_ROW(true, true), LFS_FG_PREP_ROW(true, false)}, {LFS_FG_PREP_ROW(false, true), LFS_FG_PREP_ROW(false, false)}};
+#undef LFS_FG_PREP_ROW
+            hipLaunchKernelGGL(kernels[!lds][!aa][depth], dim3(blocks), dim3(1024), lds ? size_t(T) * 4 : size_t(0), s, N, pb, v.means, v.scales_raw, v.rotations_raw,
+                               v.opacities_raw, f, w.rec, w.mean2d, w.conic_opacity, w.bounds, w.n_touched, w.depth_bits, w.totals, w.mode);
         }
         hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, s, T, w.totals, w.offsets, n_instances);
     }
@@ -548,21 +547,12 @@ extern "C" int lfs_fastgs_preprocess_ex(
         }
     }
     if (N > 0) { // SH colour (convert_sh_to_color, kernel_utils.cuh:15-36) of the visible primitives, written into the records
-        const uint32_t degree = active_sh_bases >= 16 ? 3 : active_sh_bases >= 9 ? 2 : active_sh_bases >= 4 ? 1 : 0;
-        const int rc = sh_records_fwd(N, 1 + total_bases_sh_rest, degree, means, cam_position, sh_coefficients_0, sh_coefficients_rest, w.n_touched,
+        const uint32_t degree = v.active_sh_bases >= 16 ? 3 : v.active_sh_bases >= 9 ? 2 : v.active_sh_bases >= 4 ? 1 : 0;
+        const int rc = sh_records_fwd(N, 1 + v.total_bases_sh_rest, degree, v.means, v.cam_position, v.sh_coefficients_0, v.sh_coefficients_rest, w.n_touched,
                                       reinterpret_cast<float*>(w.rec) + 8, 16, s);
         if (rc) return rc;
     }
     const int rc = (int)hipGetLastError();
-    if (rc == 0) fgs::remember_flags(primitive_workspace, flags);
+    if (rc == 0) fgs::remember_flags(v.primitive_workspace, flags);
     return rc;
-}
-
-extern "C" int lfs_fastgs_preprocess(
-    uint32_t N, const float* means, const float* scales_raw, const float* rotations_raw, const float* opacities_raw,
-    const float* sh_coefficients_0, const float* sh_coefficients_rest, uint32_t total_bases_sh_rest, const float* w2c, const float* cam_position,
-    uint32_t active_sh_bases, uint32_t width, uint32_t height, float fx, float fy, float cx, float cy, float near_plane, float far_plane,
-    int64_t* n_instances, void* primitive_workspace, size_t primitive_workspace_bytes, lfs_stream_t stream) {
-    return lfs_fastgs_preprocess_ex(N, means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, total_bases_sh_rest, w2c, cam_position,
-                                    active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane, n_instances, primitive_workspace, primitive_workspace_bytes, 0u, stream);
 }

@@ -22,7 +22,7 @@ constexpr float MAX_ALPHA = 0.999f;
 constexpr float T_THRESHOLD = 1e-4f;
 constexpr uint32_t TILE = 16;
 constexpr float LOG2E = 1.4426950408889634f;
-constexpr uint32_t MODE_ANTIALIASED = 1u; // PrimWs::mode bit 0 (= LFS_FASTGS_ANTIALIASED of lfs_fastgs_preprocess_ex)
+constexpr uint32_t MODE_ANTIALIASED = 1u; // PrimWs::mode bit 0 (= LFS_FASTGS_ANTIALIASED of lfs_fastgs_view_preprocess)
 constexpr uint32_t MODE_DEPTH = 4u;       // bit 2 (= LFS_FASTGS_DEPTH): r2.w of every visible record = camera-space z
 constexpr uint32_t MODE_INVDEPTH = 8u;    // bit 3 (= LFS_FASTGS_INVDEPTH): r2.w = 1 / z
 // the DEPTH template parameter of the per-primitive kernels: 0 none, 1 z, 2 1 / z
@@ -42,8 +42,10 @@ inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 //            log(255 * opacity): sigma' = A dx^2 + B dx dy + C dy^2 is the Gaussian exponent in bits (one v_exp_f32).
 //            Antialiased mode: opacity = sigmoid(raw) * rho everywhere, and r1.w = sigmoid(raw) for the backward.
 //            Depth modes: r2.w = d = z or 1 / z (camera space), blended by the depth forms of the blend kernels like a fourth colour channel.
-//   mode     one word of the (otherwise spare) 256-byte n_instances slot: the flags of the preprocess that filled the workspace. The backward picks its
-//            instantiation by it on the device, so the backward entry points carry no flag and nothing outside the workspace remembers the mode.
+//   mode     one word of the (otherwise spare) 256-byte n_instances slot: the flags of the preprocess that filled the workspace. The per-primitive backward
+//            picks its antialiased or default instantiation by it on the device, so render and backward carry no flag. The depth bits are ALSO remembered on the
+//            host, by the workspace's address (fastgs_prep.hip: remember_flags): a depth plane or a depth gradient on a workspace without them is refused
+//            before any launch, and the depth forms of the kernels are chosen on the host from that table; they check their bit in this word again.
 struct PrimWs {
     GaussRec* rec; float2* mean2d; float4* conic_opacity; ushort4* bounds; uint32_t* n_touched; uint32_t* depth_bits;
     uint32_t* totals; uint32_t* cursor; int32_t* offsets; int64_t* n_instances; uint32_t* mode; int32_t* n_contrib; float* acc; unsigned long long* det64; size_t bytes;

@@ -527,8 +527,21 @@ torch::Tensor GutTrainStep::radii() const {
 // ---------------------------------------------------------------------------------------------------------
 // fast_gs::rasterization (rasterization_api.h:27-75, src/rasterization_api.cu) and fusedssim (ssim.cuh:11-30)
 // ---------------------------------------------------------------------------------------------------------
-// the forward of every mode (flags of lfs_fastgs_preprocess_ex; depth: also the accumulated depth plane); the mode lives in per_primitive_buffers from here on
 namespace {
+// lfs_fastgs_view of (contiguous) tensors, which the caller holds for the duration of the call; opacities_raw / sh_coefficients_0 / prim: undefined -> NULL
+lfs_fastgs_view fastgs_view(const at::Tensor& means, const at::Tensor& scales_raw, const at::Tensor& rotations_raw, const at::Tensor& opacities_raw,
+                            const at::Tensor& sh_coefficients_0, const at::Tensor& sh_coefficients_rest, const at::Tensor& w2c_c, const at::Tensor& cam_c,
+                            int active_sh_bases, int width, int height, float focal_x, float focal_y, float center_x, float center_y, float near_plane, float far_plane,
+                            const at::Tensor& prim) {
+    const uint32_t total_rest = (uint32_t)sh_coefficients_rest.size(1);
+    return lfs_fastgs_view{(uint32_t)means.size(0), means.data_ptr<float>(), scales_raw.data_ptr<float>(), rotations_raw.data_ptr<float>(),
+                           opacities_raw.defined() ? opacities_raw.data_ptr<float>() : nullptr, sh_coefficients_0.defined() ? sh_coefficients_0.data_ptr<float>() : nullptr,
+                           total_rest ? sh_coefficients_rest.data_ptr<float>() : nullptr, total_rest, w2c_c.data_ptr<float>(), cam_c.data_ptr<float>(),
+                           (uint32_t)active_sh_bases, (uint32_t)width, (uint32_t)height, focal_x, focal_y, center_x, center_y, near_plane, far_plane,
+                           prim.data_ptr(), (size_t)prim.numel()};
+}
+
+// the forward of every mode (flags of lfs_fastgs_view_preprocess; depth: also the accumulated depth plane); the mode lives in per_primitive_buffers from here on
 struct FastgsForward { at::Tensor image, alpha, depth, prim, inst; int64_t n_instances; };
 FastgsForward fastgs_forward_impl(
     const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
@@ -538,29 +551,66 @@ FastgsForward fastgs_forward_impl(
     LFS_DEVICE_GUARD(means);
     LFS_CHECK_INPUT(means); LFS_CHECK_INPUT(scales_raw); LFS_CHECK_INPUT(rotations_raw); LFS_CHECK_INPUT(opacities_raw);
     LFS_CHECK_INPUT(sh_coefficients_0); LFS_CHECK_INPUT(sh_coefficients_rest);
-    const uint32_t N = (uint32_t)means.size(0), total_rest = (uint32_t)sh_coefficients_rest.size(1);
+    const uint32_t N = (uint32_t)means.size(0);
     const at::Tensor w2c_c = w2c.contiguous(), cam_c = cam_position.contiguous();
     const auto fopt = means.options().dtype(at::kFloat), bopt = means.options().dtype(at::kByte);
     at::Tensor image = at::empty({3, height, width}, fopt), alpha = at::empty({1, height, width}, fopt);
     at::Tensor prim = at::empty({(int64_t)lfs_fastgs_primitive_workspace_bytes(N, (uint32_t)width, (uint32_t)height)}, bopt);
     at::Tensor n_inst_dev = at::zeros({1}, means.options().dtype(at::kLong));
-    check_rc(lfs_fastgs_preprocess_ex(N, means.data_ptr<float>(), scales_raw.data_ptr<float>(), rotations_raw.data_ptr<float>(), opacities_raw.data_ptr<float>(),
-                                      sh_coefficients_0.data_ptr<float>(), total_rest ? sh_coefficients_rest.data_ptr<float>() : nullptr, total_rest,
-                                      w2c_c.data_ptr<float>(), cam_c.data_ptr<float>(), (uint32_t)active_sh_bases, (uint32_t)width, (uint32_t)height,
-                                      focal_x, focal_y, center_x, center_y, near_plane, far_plane, n_inst_dev.data_ptr<int64_t>(), prim.data_ptr(),
-                                      (size_t)prim.numel(), flags, cur_stream()), "fast_gs::rasterization::forward (preprocess)");
+    const lfs_fastgs_view view = fastgs_view(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c_c, cam_c, active_sh_bases, width,
+                                             height, focal_x, focal_y, center_x, center_y, near_plane, far_plane, prim);
+    check_rc(lfs_fastgs_view_preprocess(&view, flags, n_inst_dev.data_ptr<int64_t>(), cur_stream()), "fast_gs::rasterization::forward (preprocess)");
     const int64_t n_instances = n_inst_dev.item<int64_t>(); // the host sync of forward.cu:114-117
     at::Tensor inst = at::empty({(int64_t)std::max<size_t>(256, lfs_fastgs_instance_workspace_bytes((uint32_t)width, (uint32_t)height, n_instances))}, bopt);
     at::Tensor depth;
-    if (want_depth) {
-        depth = at::empty({1, height, width}, fopt);
-        check_rc(lfs_fastgs_render_depth(N, (uint32_t)width, (uint32_t)height, n_instances, prim.data_ptr(), (size_t)prim.numel(), inst.data_ptr(), (size_t)inst.numel(),
-                                         image.data_ptr<float>(), alpha.data_ptr<float>(), depth.data_ptr<float>(), cur_stream()), "lfs::fastgs_forward_wrapper_depth (render)");
-    } else {
-        check_rc(lfs_fastgs_render(N, (uint32_t)width, (uint32_t)height, n_instances, prim.data_ptr(), (size_t)prim.numel(), inst.data_ptr(), (size_t)inst.numel(),
-                                   image.data_ptr<float>(), alpha.data_ptr<float>(), cur_stream()), "fast_gs::rasterization::forward (render)");
-    }
+    if (want_depth) depth = at::empty({1, height, width}, fopt);
+    check_rc(lfs_fastgs_view_render(&view, n_instances, inst.data_ptr(), (size_t)inst.numel(), image.data_ptr<float>(), alpha.data_ptr<float>(),
+                                    want_depth ? depth.data_ptr<float>() : nullptr, cur_stream()),
+             want_depth ? "lfs::fastgs_forward_wrapper_depth (render)" : "fast_gs::rasterization::forward (render)");
     return {image, alpha, depth, prim, inst, n_instances};
+}
+
+// the backward of every mode: grad_depth undefined -> no depth gradient; grad_w2c is asked for when w2c requires grad (pose optimisation,
+// rasterization_api.cu:133-136) and returned as the 7th element, shaped like w2c, otherwise that element stays an undefined tensor
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> fastgs_backward_impl(
+    torch::Tensor& densification_info, const torch::Tensor& grad_image, const torch::Tensor& grad_alpha, const torch::Tensor& grad_depth, const torch::Tensor& alpha,
+    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& sh_coefficients_rest,
+    const torch::Tensor& per_primitive_buffers, const torch::Tensor& per_instance_buffers, const torch::Tensor& w2c, const torch::Tensor& cam_position,
+    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
+    const float center_y, const float near_plane, const float far_plane, const int n_instances, const char* what) {
+    LFS_DEVICE_GUARD(means);
+    const uint32_t N = (uint32_t)means.size(0), total_rest = (uint32_t)sh_coefficients_rest.size(1);
+    const auto fopt = means.options().dtype(at::kFloat);
+    at::Tensor g_means = at::empty({N, 3}, fopt), g_scales = at::empty({N, 3}, fopt), g_rot = at::empty({N, 4}, fopt), g_opac = at::empty({N, 1}, fopt);
+    at::Tensor g_sh0 = at::empty({N, 1, 3}, fopt), g_shr = at::empty({N, (int64_t)total_rest, 3}, fopt);
+    const at::Tensor gi = grad_image.contiguous(), ga = grad_alpha.contiguous(), al = alpha.contiguous(), w2c_c = w2c.contiguous(), cam_c = cam_position.contiguous();
+    at::Tensor gd;
+    if (grad_depth.defined()) {
+        gd = grad_depth.contiguous();
+        TORCH_CHECK(gd.numel() == (int64_t)width * height, "grad_depth must hold one [1,H,W] plane");
+    }
+    const bool dens = densification_info.defined() && densification_info.dim() > 0 && densification_info.size(0) > 0;
+    at::Tensor g_w2c, ws;
+    if (w2c.requires_grad()) {
+        TORCH_CHECK(w2c.numel() == 16, "w2c must hold one [4,4] transform");
+        g_w2c = at::empty_like(w2c_c);
+        ws = at::empty({(int64_t)lfs_fastgs_w2c_workspace_bytes(N)}, means.options().dtype(at::kByte));
+    }
+    const lfs_fastgs_view view = fastgs_view(means, scales_raw, rotations_raw, at::Tensor(), at::Tensor(), sh_coefficients_rest, w2c_c, cam_c, active_sh_bases, width, height,
+                                             focal_x, focal_y, center_x, center_y, near_plane, far_plane, per_primitive_buffers);
+    lfs_fastgs_view_backward_args args{};
+    args.n_instances = n_instances;
+    args.instance_workspace = per_instance_buffers.data_ptr();
+    args.instance_workspace_bytes = (size_t)per_instance_buffers.numel();
+    args.grad_image = gi.data_ptr<float>(); args.grad_alpha = ga.data_ptr<float>(); args.alpha = al.data_ptr<float>();
+    args.grad_depth = gd.defined() ? gd.data_ptr<float>() : nullptr;
+    args.densification_info = dens ? densification_info.data_ptr<float>() : nullptr;
+    args.grad_means = g_means.data_ptr<float>(); args.grad_scales_raw = g_scales.data_ptr<float>(); args.grad_rotations_raw = g_rot.data_ptr<float>();
+    args.grad_opacities_raw = g_opac.data_ptr<float>(); args.grad_sh_coefficients_0 = g_sh0.data_ptr<float>();
+    args.grad_sh_coefficients_rest = total_rest ? g_shr.data_ptr<float>() : nullptr;
+    if (g_w2c.defined()) { args.grad_w2c = g_w2c.data_ptr<float>(); args.w2c_workspace = ws.data_ptr(); args.w2c_workspace_bytes = (size_t)ws.numel(); }
+    check_rc(lfs_fastgs_view_backward(&view, &args, cur_stream()), what);
+    return {g_means, g_scales, g_rot, g_opac, g_sh0, g_shr, g_w2c};
 }
 } // namespace
 
@@ -593,31 +643,10 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Te
     const torch::Tensor& per_primitive_buffers, const torch::Tensor& per_instance_buffers, const torch::Tensor& w2c, const torch::Tensor& cam_position,
     const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
     const float center_y, const float near_plane, const float far_plane, const int n_instances) {
-    LFS_DEVICE_GUARD(means);
-    const uint32_t N = (uint32_t)means.size(0), total_rest = (uint32_t)sh_coefficients_rest.size(1);
-    const auto fopt = means.options().dtype(at::kFloat);
-    at::Tensor g_means = at::empty({N, 3}, fopt), g_scales = at::empty({N, 3}, fopt), g_rot = at::empty({N, 4}, fopt), g_opac = at::empty({N, 1}, fopt);
-    at::Tensor g_sh0 = at::empty({N, 1, 3}, fopt), g_shr = at::empty({N, (int64_t)total_rest, 3}, fopt);
-    const at::Tensor gi = grad_image.contiguous(), ga = grad_alpha.contiguous(), gd = grad_depth.contiguous(), al = alpha.contiguous(), w2c_c = w2c.contiguous(),
-                     cam_c = cam_position.contiguous();
-    TORCH_CHECK(gd.numel() == (int64_t)width * height, "grad_depth must hold one [1,H,W] plane");
-    const bool dens = densification_info.defined() && densification_info.dim() > 0 && densification_info.size(0) > 0;
-    at::Tensor g_w2c, ws;
-    if (w2c.requires_grad()) {
-        TORCH_CHECK(w2c.numel() == 16, "w2c must hold one [4,4] transform");
-        g_w2c = at::empty_like(w2c_c);
-        ws = at::empty({(int64_t)lfs_fastgs_w2c_workspace_bytes(N)}, means.options().dtype(at::kByte));
-    }
-    check_rc(lfs_fastgs_backward_depth(N, means.data_ptr<float>(), scales_raw.data_ptr<float>(), rotations_raw.data_ptr<float>(), nullptr,
-                                       total_rest ? sh_coefficients_rest.data_ptr<float>() : nullptr, total_rest, w2c_c.data_ptr<float>(), cam_c.data_ptr<float>(),
-                                       (uint32_t)active_sh_bases, (uint32_t)width, (uint32_t)height, focal_x, focal_y, center_x, center_y, near_plane, far_plane,
-                                       (int64_t)n_instances, per_primitive_buffers.data_ptr(), (size_t)per_primitive_buffers.numel(), per_instance_buffers.data_ptr(),
-                                       (size_t)per_instance_buffers.numel(), gi.data_ptr<float>(), ga.data_ptr<float>(), al.data_ptr<float>(),
-                                       dens ? densification_info.data_ptr<float>() : nullptr, g_means.data_ptr<float>(), g_scales.data_ptr<float>(),
-                                       g_rot.data_ptr<float>(), g_opac.data_ptr<float>(), g_sh0.data_ptr<float>(), total_rest ? g_shr.data_ptr<float>() : nullptr,
-                                       gd.data_ptr<float>(), g_w2c.defined() ? g_w2c.data_ptr<float>() : nullptr, ws.defined() ? ws.data_ptr() : nullptr,
-                                       ws.defined() ? (size_t)ws.numel() : 0, cur_stream()), "lfs::fastgs_backward_wrapper_depth");
-    return {g_means, g_scales, g_rot, g_opac, g_sh0, g_shr, g_w2c};
+    TORCH_CHECK(grad_depth.defined(), "grad_depth must hold one [1,H,W] plane");
+    return fastgs_backward_impl(densification_info, grad_image, grad_alpha, grad_depth, alpha, means, scales_raw, rotations_raw, sh_coefficients_rest, per_primitive_buffers,
+                                per_instance_buffers, w2c, cam_position, active_sh_bases, width, height, focal_x, focal_y, center_x, center_y, near_plane, far_plane,
+                                n_instances, "lfs::fastgs_backward_wrapper_depth");
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int>
@@ -641,35 +670,9 @@ fast_gs::rasterization::backward_wrapper(
     const int n_buckets, const int primitive_primitive_indices_selector, const int instance_primitive_indices_selector) {
     (void)image; (void)per_tile_buffers; (void)per_bucket_buffers; (void)n_visible_primitives; (void)n_buckets;
     (void)primitive_primitive_indices_selector; (void)instance_primitive_indices_selector;
-    LFS_DEVICE_GUARD(means);
-    const uint32_t N = (uint32_t)means.size(0), total_rest = (uint32_t)sh_coefficients_rest.size(1);
-    const auto fopt = means.options().dtype(at::kFloat);
-    at::Tensor g_means = at::empty({N, 3}, fopt), g_scales = at::empty({N, 3}, fopt), g_rot = at::empty({N, 4}, fopt), g_opac = at::empty({N, 1}, fopt);
-    at::Tensor g_sh0 = at::empty({N, 1, 3}, fopt), g_shr = at::empty({N, (int64_t)total_rest, 3}, fopt);
-    const at::Tensor gi = grad_image.contiguous(), ga = grad_alpha.contiguous(), al = alpha.contiguous(), w2c_c = w2c.contiguous(), cam_c = cam_position.contiguous();
-    const bool dens = densification_info.defined() && densification_info.dim() > 0 && densification_info.size(0) > 0;
-    if (w2c.requires_grad()) {   // pose optimisation (rasterization_api.cu:133-136): the camera gradient as the 7th element, shaped like w2c
-        TORCH_CHECK(w2c.numel() == 16, "w2c must hold one [4,4] transform");
-        at::Tensor g_w2c = at::empty_like(w2c_c), ws = at::empty({(int64_t)lfs_fastgs_w2c_workspace_bytes(N)}, means.options().dtype(at::kByte));
-        check_rc(lfs_fastgs_backward_w2c(N, means.data_ptr<float>(), scales_raw.data_ptr<float>(), rotations_raw.data_ptr<float>(), nullptr,
-                                         total_rest ? sh_coefficients_rest.data_ptr<float>() : nullptr, total_rest, w2c_c.data_ptr<float>(), cam_c.data_ptr<float>(),
-                                         (uint32_t)active_sh_bases, (uint32_t)width, (uint32_t)height, focal_x, focal_y, center_x, center_y, near_plane, far_plane,
-                                         (int64_t)n_instances, per_primitive_buffers.data_ptr(), (size_t)per_primitive_buffers.numel(), per_instance_buffers.data_ptr(),
-                                         (size_t)per_instance_buffers.numel(), gi.data_ptr<float>(), ga.data_ptr<float>(), al.data_ptr<float>(),
-                                         dens ? densification_info.data_ptr<float>() : nullptr, g_means.data_ptr<float>(), g_scales.data_ptr<float>(),
-                                         g_rot.data_ptr<float>(), g_opac.data_ptr<float>(), g_sh0.data_ptr<float>(), total_rest ? g_shr.data_ptr<float>() : nullptr,
-                                         g_w2c.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(), cur_stream()), "fast_gs::rasterization::backward (grad_w2c)");
-        return {g_means, g_scales, g_rot, g_opac, g_sh0, g_shr, g_w2c};
-    }
-    check_rc(lfs_fastgs_backward(N, means.data_ptr<float>(), scales_raw.data_ptr<float>(), rotations_raw.data_ptr<float>(), nullptr,
-                                 total_rest ? sh_coefficients_rest.data_ptr<float>() : nullptr, total_rest, w2c_c.data_ptr<float>(), cam_c.data_ptr<float>(),
-                                 (uint32_t)active_sh_bases, (uint32_t)width, (uint32_t)height, focal_x, focal_y, center_x, center_y, near_plane, far_plane,
-                                 (int64_t)n_instances, per_primitive_buffers.data_ptr(), (size_t)per_primitive_buffers.numel(), per_instance_buffers.data_ptr(),
-                                 (size_t)per_instance_buffers.numel(), gi.data_ptr<float>(), ga.data_ptr<float>(), al.data_ptr<float>(),
-                                 dens ? densification_info.data_ptr<float>() : nullptr, g_means.data_ptr<float>(), g_scales.data_ptr<float>(),
-                                 g_rot.data_ptr<float>(), g_opac.data_ptr<float>(), g_sh0.data_ptr<float>(), total_rest ? g_shr.data_ptr<float>() : nullptr,
-                                 cur_stream()), "fast_gs::rasterization::backward");
-    return {g_means, g_scales, g_rot, g_opac, g_sh0, g_shr, torch::Tensor()};
+    return fastgs_backward_impl(densification_info, grad_image, grad_alpha, torch::Tensor(), alpha, means, scales_raw, rotations_raw, sh_coefficients_rest,
+                                per_primitive_buffers, per_instance_buffers, w2c, cam_position, active_sh_bases, width, height, focal_x, focal_y, center_x, center_y,
+                                near_plane, far_plane, n_instances, w2c.requires_grad() ? "fast_gs::rasterization::backward (grad_w2c)" : "fast_gs::rasterization::backward");
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> fusedssim(float C1, float C2, torch::Tensor& img1, torch::Tensor& img2, bool train) {

@@ -4,4 +4,4 @@
 #ifndef LFS_SRC_HASH
 #define LFS_SRC_HASH "unknown"
 #endif
-extern "C" const char* lfs_version(void) { return "lfs_gsplat gfx950 abi-3 src-" LFS_SRC_HASH; }
+extern "C" const char* lfs_version(void) { return "lfs_gsplat gfx950 abi-4 src-" LFS_SRC_HASH; }

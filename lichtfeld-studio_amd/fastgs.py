@@ -14,7 +14,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from .capi import LfsError, check, load_library, ptr, require_gpu, stream, workspace
+from .capi import FastgsBackwardArgs, FastgsShRestAdam, FastgsView, LfsError, check, load_library, ptr, require_gpu, stream, workspace
 from .rasterizer import Camera, RenderMode, RenderOutput, SplatModel
 
 
@@ -39,9 +39,11 @@ DEPTH_FLAGS = {"none": 0, "depth": 4, "invdepth": 8}   # LFS_FASTGS_DEPTH, LFS_F
 ASYNC_READBACK = True   # False: n_instances via a stream synchronisation (A/B timing)
 
 
-def _frame_args(s: FastGSSettings):
-    return (C.c_uint32(s.active_sh_bases), C.c_uint32(s.width), C.c_uint32(s.height), C.c_float(s.focal_x), C.c_float(s.focal_y),
-            C.c_float(s.center_x), C.c_float(s.center_y), C.c_float(s.near_plane), C.c_float(s.far_plane))
+def view_struct(s: FastGSSettings, means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest, w2c, cam_position, primitive_workspace) -> FastgsView:
+    """lfs_fastgs_view of contiguous device tensors (opacities_raw: None for the backward). Keeps no reference to them: callers hold them for the duration of the call."""
+    return FastgsView(means.shape[0], ptr(means), ptr(scales_raw), ptr(rotations_raw), ptr(opacities_raw), ptr(sh0), ptr(sh_rest), sh_rest.shape[1] if sh_rest.dim() == 3 else 0,
+                      ptr(w2c), ptr(cam_position), s.active_sh_bases, s.width, s.height, s.focal_x, s.focal_y, s.center_x, s.center_y, s.near_plane, s.far_plane,
+                      ptr(primitive_workspace), primitive_workspace.numel())
 
 
 def forward_wrapper(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c, s: FastGSSettings):
@@ -77,13 +79,8 @@ def _forward(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0,
     if s.depth not in DEPTH_FLAGS:
         raise LfsError(f"FastGSSettings.depth must be 'none', 'depth' or 'invdepth' (got {s.depth!r})")
     flags = (ANTIALIASED if s.antialiased else 0) | DEPTH_FLAGS[s.depth]
-    if flags:
-        check(lib.lfs_fastgs_preprocess_ex(C.c_uint32(N), ptr(means), ptr(scales_raw), ptr(rotations_raw), ptr(opac), ptr(sh0), ptr(shr), C.c_uint32(total_rest),
-                                           ptr(w2c), ptr(cam_position), *_frame_args(s), ptr(n_inst_dev), ptr(pws), C.c_size_t(pws.numel()), C.c_uint32(flags),
-                                           stream()), "fastgs_preprocess_ex")
-    else:
-        check(lib.lfs_fastgs_preprocess(C.c_uint32(N), ptr(means), ptr(scales_raw), ptr(rotations_raw), ptr(opac), ptr(sh0), ptr(shr), C.c_uint32(total_rest),
-                                        ptr(w2c), ptr(cam_position), *_frame_args(s), ptr(n_inst_dev), ptr(pws), C.c_size_t(pws.numel()), stream()), "fastgs_preprocess")
+    view = view_struct(s, means, scales_raw, rotations_raw, opac, sh0, shr, w2c, cam_position, pws)
+    check(lib.lfs_fastgs_view_preprocess(C.byref(view), C.c_uint32(flags), ptr(n_inst_dev), stream()), "fastgs_view_preprocess")
     # the one host sync (forward.cu:114-117 reads n_visible_primitives and n_instances): waits for the read-back event the library queued before
     # its SH kernel, so the GPU keeps working through the host round trip
     if ASYNC_READBACK:
@@ -95,14 +92,9 @@ def _forward(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0,
     iws = torch.empty(max(256, lib.lfs_fastgs_instance_workspace_bytes(C.c_uint32(s.width), C.c_uint32(s.height), C.c_int64(n_instances))), dtype=torch.uint8, device=dev)
     image = torch.empty((3, s.height, s.width), dtype=means.dtype, device=dev)
     alpha = torch.empty((1, s.height, s.width), dtype=means.dtype, device=dev)
-    if want_depth:
-        depth = torch.empty((1, s.height, s.width), dtype=means.dtype, device=dev)
-        check(lib.lfs_fastgs_render_depth(C.c_uint32(N), C.c_uint32(s.width), C.c_uint32(s.height), C.c_int64(n_instances), ptr(pws), C.c_size_t(pws.numel()),
-                                          ptr(iws), C.c_size_t(iws.numel()), ptr(image), ptr(alpha), ptr(depth), stream()), "fastgs_render_depth")
-        return image, alpha, depth, pws, iws, n_instances
-    check(lib.lfs_fastgs_render(C.c_uint32(N), C.c_uint32(s.width), C.c_uint32(s.height), C.c_int64(n_instances), ptr(pws), C.c_size_t(pws.numel()),
-                                ptr(iws), C.c_size_t(iws.numel()), ptr(image), ptr(alpha), stream()), "fastgs_render")
-    return image, alpha, pws, iws, n_instances
+    depth = torch.empty((1, s.height, s.width), dtype=means.dtype, device=dev) if want_depth else None
+    check(lib.lfs_fastgs_view_render(C.byref(view), C.c_int64(n_instances), ptr(iws), C.c_size_t(iws.numel()), ptr(image), ptr(alpha), ptr(depth), stream()), "fastgs_view_render")
+    return (image, alpha, depth, pws, iws, n_instances) if want_depth else (image, alpha, pws, iws, n_instances)
 
 
 def backward_wrapper(densification_info: Optional[torch.Tensor], grad_image, grad_alpha, image, alpha, means, scales_raw, rotations_raw,
@@ -111,11 +103,11 @@ def backward_wrapper(densification_info: Optional[torch.Tensor], grad_image, gra
     """-> (grad_means, grad_scales_raw, grad_rotations_raw, grad_opacities_raw [N,1], grad_sh_coefficients_0, grad_sh_coefficients_rest);
     densification_info [2,N] (when given and non-empty) is accumulated into in place (kernels_backward.cuh:229-232).
     Extension `adam_sh_rest` (FusedAdam.prepare_inline of sh_coefficients_rest; single-view steps): the rest-coefficient gradient is not
-    written, the coefficients and their moments are updated in place by the SH backward (lfs_fastgs_backward_adam).
+    written, the coefficients and their moments are updated in place by the SH backward (lfs_fastgs_view_backward_args.adam).
     `grad_w2c` (pose optimisation; a contiguous float32 out buffer of 16 elements, e.g. zeros_like(w2c)): the camera gradient the reference's backward returns
     when w2c requires grad (rasterization_api.cu:133-136) is WRITTEN into it - rows 0-2 = sum over the visible primitives of dL/d(mean in camera space) (x) (mean, 1),
-    row 3 = 0 (lfs_fastgs_backward_w2c). None: today's entry points. Not combined with adam_sh_rest.
-    `grad_depth` ([1,H,W] or [H,W]; the workspace of a forward with s.depth on): the gradient of forward_wrapper_depth's depth plane (lfs_fastgs_backward_depth) - depth
+    row 3 = 0 (lfs_fastgs_view_backward_args.grad_w2c). None: no camera gradient. Not combined with adam_sh_rest.
+    `grad_depth` ([1,H,W] or [H,W]; the workspace of a forward with s.depth on): the gradient of forward_wrapper_depth's depth plane (lfs_fastgs_view_backward_args.grad_depth) - depth
     is blended as a fourth channel, and dL/dz reaches grad_means and, with grad_w2c, row 2 of the camera gradient. Not combined with adam_sh_rest."""
     w2c = w2c.reshape(-1, 4, 4)[0].contiguous()
     cam_position = s.cam_position.reshape(-1)[:3].contiguous()
@@ -149,40 +141,22 @@ def backward_wrapper(densification_info: Optional[torch.Tensor], grad_image, gra
         require_gpu(grad_depth)
         if grad_depth.numel() != s.width * s.height or grad_depth.dtype != torch.float32:
             raise LfsError("grad_depth must be a float32 [1,H,W] tensor")
-        lib = load_library()
-        ws = workspace(lib.lfs_fastgs_w2c_workspace_bytes(C.c_uint32(N)), means.device, "fastgs_w2c") if grad_w2c is not None else None
-        check(lib.lfs_fastgs_backward_depth(
-            C.c_uint32(N), ptr(means), ptr(scales_raw), ptr(rotations_raw), ptr(sh0), ptr(shr), C.c_uint32(total_rest), ptr(w2c), ptr(cam_position), *_frame_args(s),
-            C.c_int64(n_instances), ptr(primitive_workspace), C.c_size_t(primitive_workspace.numel()), ptr(instance_workspace), C.c_size_t(instance_workspace.numel()),
-            ptr(grad_image), ptr(grad_alpha), ptr(alpha), ptr(dens), ptr(g_means), ptr(g_scales), ptr(g_rot), ptr(g_opac), ptr(g_sh0), ptr(g_shr),
-            ptr(grad_depth), ptr(grad_w2c), ptr(ws), C.c_size_t(ws.numel() if ws is not None else 0), stream()),
-            "fastgs_backward_depth (LFS_E_INVALID here also means: this workspace is not known as a depth-mode workspace - its forward ran without FastGSSettings.depth, "
-            "or more than 256 depth-mode forwards were started since without their backward and it was forgotten)")
-        return g_means, g_scales, g_rot, g_opac, g_sh0, g_shr
-    if grad_w2c is not None:
-        lib = load_library()
-        ws = workspace(lib.lfs_fastgs_w2c_workspace_bytes(C.c_uint32(N)), means.device, "fastgs_w2c")
-        check(lib.lfs_fastgs_backward_w2c(
-            C.c_uint32(N), ptr(means), ptr(scales_raw), ptr(rotations_raw), ptr(sh0), ptr(shr), C.c_uint32(total_rest), ptr(w2c), ptr(cam_position), *_frame_args(s),
-            C.c_int64(n_instances), ptr(primitive_workspace), C.c_size_t(primitive_workspace.numel()), ptr(instance_workspace), C.c_size_t(instance_workspace.numel()),
-            ptr(grad_image), ptr(grad_alpha), ptr(alpha), ptr(dens), ptr(g_means), ptr(g_scales), ptr(g_rot), ptr(g_opac), ptr(g_sh0), ptr(g_shr),
-            ptr(grad_w2c), ptr(ws), C.c_size_t(ws.numel()), stream()), "fastgs_backward_w2c")
-        return g_means, g_scales, g_rot, g_opac, g_sh0, g_shr
+    lib = load_library()
+    ws = workspace(lib.lfs_fastgs_w2c_workspace_bytes(C.c_uint32(N)), means.device, "fastgs_w2c") if grad_w2c is not None else None
+    adam = None
     if adam_sh_rest is not None and total_rest > 0:
         a = adam_sh_rest
         if not sh_coefficients_rest.is_contiguous():
             raise LfsError("adam_sh_rest needs the parameter tensor itself (contiguous), it is updated in place")
-        check(load_library().lfs_fastgs_backward_adam(
-            C.c_uint32(N), ptr(means), ptr(scales_raw), ptr(rotations_raw), ptr(sh0), ptr(sh_coefficients_rest), C.c_uint32(total_rest), ptr(w2c), ptr(cam_position),
-            *_frame_args(s), C.c_int64(n_instances), ptr(primitive_workspace), C.c_size_t(primitive_workspace.numel()), ptr(instance_workspace),
-            C.c_size_t(instance_workspace.numel()), ptr(grad_image), ptr(grad_alpha), ptr(alpha), ptr(dens), ptr(g_means), ptr(g_scales), ptr(g_rot), ptr(g_opac),
-            ptr(g_sh0), ptr(a["exp_avg"]), ptr(a["exp_avg_sq"]), C.c_float(a["lr"]), C.c_float(a["beta1"]), C.c_float(a["beta2"]), C.c_float(a["eps"]),
-            C.c_float(a["bc1_rcp"]), C.c_float(a["bc2_sqrt_rcp"]), stream()), "fastgs_backward_adam")
-        return g_means, g_scales, g_rot, g_opac, g_sh0, g_shr
-    check(load_library().lfs_fastgs_backward(
-        C.c_uint32(N), ptr(means), ptr(scales_raw), ptr(rotations_raw), ptr(sh0), ptr(shr), C.c_uint32(total_rest), ptr(w2c), ptr(cam_position), *_frame_args(s),
-        C.c_int64(n_instances), ptr(primitive_workspace), C.c_size_t(primitive_workspace.numel()), ptr(instance_workspace), C.c_size_t(instance_workspace.numel()),
-        ptr(grad_image), ptr(grad_alpha), ptr(alpha), ptr(dens), ptr(g_means), ptr(g_scales), ptr(g_rot), ptr(g_opac), ptr(g_sh0), ptr(g_shr), stream()), "fastgs_backward")
+        adam = FastgsShRestAdam(ptr(sh_coefficients_rest), ptr(a["exp_avg"]), ptr(a["exp_avg_sq"]), a["lr"], a["beta1"], a["beta2"], a["eps"], a["bc1_rcp"], a["bc2_sqrt_rcp"])
+    view = view_struct(s, means, scales_raw, rotations_raw, None, sh0, shr, w2c, cam_position, primitive_workspace)
+    args = FastgsBackwardArgs(n_instances, ptr(instance_workspace), instance_workspace.numel(), ptr(grad_image), ptr(grad_alpha), ptr(alpha), ptr(grad_depth), ptr(dens),
+                              ptr(g_means), ptr(g_scales), ptr(g_rot), ptr(g_opac), ptr(g_sh0), ptr(g_shr), ptr(grad_w2c), ptr(ws), ws.numel() if ws is not None else 0,
+                              C.pointer(adam) if adam is not None else None)
+    check(lib.lfs_fastgs_view_backward(C.byref(view), C.byref(args), stream()),
+          "fastgs_view_backward" if grad_depth is None else
+          "fastgs_view_backward with grad_depth (LFS_E_INVALID here also means: this workspace is not known as a depth-mode workspace - its forward ran without "
+          "FastGSSettings.depth, or more than 256 depth-mode forwards were started since without their backward and it was forgotten)")
     return g_means, g_scales, g_rot, g_opac, g_sh0, g_shr
 
 

@@ -360,9 +360,9 @@ class GutTrainer:
             dens = self.densification_info
         if len(views) > 1 and (not hasattr(self, "_fg_tmp") or self._fg_tmp[0].shape[0] != N):
             self._fg_tmp = [torch.empty_like(v) for v in self.bucket.views]
-        inline = None   # one view on one rank, Adam reading shN: the SH backward inside lfs_fastgs_backward_adam updates shN itself
+        inline = None   # one view on one rank, Adam reading shN: the SH backward inside lfs_fastgs_view_backward (args.adam) updates shN itself
         if (self.inline_shN_adam and self.world == 1 and len(views) == 1 and self.strategy is None and self.iteration > 1000 and self.model.shN.shape[1] > 0
-                and getattr(self.optimizer, "fused", False) and self.pose_module is None   # (lfs_fastgs_backward_adam has no camera gradient)
+                and getattr(self.optimizer, "fused", False) and self.pose_module is None   # (the optimizer-fused backward has no camera gradient)
                 and self._depths is None):                                                   # (... and no depth gradient)
             inline = self.optimizer.prepare_inline(self.model.shN)
         for k, v in enumerate(views):

@@ -145,3 +145,30 @@ def test_step_driver_host_functions(lfs):
     n, lg = ctypes.c_int64(0), ctypes.c_int64(0)
     assert lib.lfs_gut_step_wait(counts, ctypes.c_int64(7), ctypes.c_double(0.1), ctypes.byref(n), ctypes.byref(lg)) == 0 and (n.value, lg.value) == (123, 45)
     assert lib.lfs_gut_step_wait(counts, ctypes.c_int64(8), ctypes.c_double(0.05), ctypes.byref(n), ctypes.byref(lg)) != 0     # a stamp that never arrives: time-out, not a hang
+
+
+def test_fastgs_struct_surface(lfs):
+    """csrc/fastgs_{prep,blend}.hip, host side only: the three fastgs entry points take structs whose ctypes mirrors are laid out by hand (the sizes are the literals
+    the static_asserts next to the entry points pin), and refuse NULL structs, all-zero structs and a view without extent with LFS_E_INVALID - before any launch: a
+    launch on this machine would come back as a HIP error code, not as -1, and the pointers below are host memory no kernel could read."""
+    from lichtfeld_studio_amd.capi import FastgsBackwardArgs, FastgsShRestAdam, FastgsView
+    lib = lfs.load_library()
+    assert (ctypes.sizeof(FastgsView), ctypes.sizeof(FastgsShRestAdam), ctypes.sizeof(FastgsBackwardArgs)) == (136, 48, 144)
+    assert lib.lfs_version().decode().split()[2] == "abi-4"
+    n = ctypes.c_int64(-7)
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+
+    def three(view, args):
+        return (lib.lfs_fastgs_view_preprocess(view, ctypes.c_uint32(0), ctypes.byref(n), None),
+                lib.lfs_fastgs_view_render(view, ctypes.c_int64(0), p, ctypes.c_size_t(256), p, p, None, None),
+                lib.lfs_fastgs_view_backward(view, args, None))
+
+    full_args = FastgsBackwardArgs(0, p, 256, p, p, p, None, None, p, p, p, p, p, p, None, None, 0, None)
+    assert three(None, ctypes.byref(full_args)) == (-1, -1, -1)                                  # NULL view
+    assert three(ctypes.byref(FastgsView()), ctypes.byref(FastgsBackwardArgs())) == (-1, -1, -1)  # all-zero structs
+    full_view = FastgsView(1, p, p, p, p, p, None, 0, p, p, 1, 16, 16, 10.0, 10.0, 8.0, 8.0, 0.01, 1e10, p, 1 << 20)
+    assert lib.lfs_fastgs_view_backward(ctypes.byref(full_view), None, None) == -1                # NULL args
+    no_extent = FastgsView(1, p, p, p, p, p, None, 0, p, p, 1, 0, 16, 10.0, 10.0, 8.0, 8.0, 0.01, 1e10, p, 1 << 20)
+    assert three(ctypes.byref(no_extent), ctypes.byref(full_args)) == (-1, -1, -1)
+    assert n.value == -7 and not any(buf)

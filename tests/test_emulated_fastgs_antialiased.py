@@ -1,7 +1,7 @@
 """Cases 1-5 of tests/test_gpu_fastgs_antialiased.py on the CPU: the product library compiled as host code on the wavefront emulator, "cuda:0" served by CPU
 tensors (the fixture pattern of tests/test_emulated_masked_loss.py). Same scenes, same float64 host model, same oracle calls, same bounds. What this holds without
 a GPU is the kernels' logic: the compensation and the order of the cuts in the forward, the rho term of the per-primitive backward in both W2C forms, the mode word
-of the workspace and the two backward instantiations picking by it, and the argument checks of lfs_fastgs_preprocess_ex. (The deterministic accumulation mode the
+of the workspace and the two backward instantiations picking by it, and the argument checks of lfs_fastgs_view_preprocess. (The deterministic accumulation mode the
 tests ask for is dropped by the emulated library: its wavefronts run one after the other, the float sums are reproducible as they are.)"""
 import os
 import sys

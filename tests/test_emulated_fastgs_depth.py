@@ -41,6 +41,7 @@ def test_emulated__depth_backward_is_linear_in_its_three_gradients(lfs, idx, kin
 test_emulated__depth_camera_gradient = gpu_tests.test_depth_camera_gradient
 test_emulated__default_mode_is_untouched_by_the_depth_modes = gpu_tests.test_default_mode_is_untouched_by_the_depth_modes
 test_emulated__fast_rasterize_render_modes_and_autograd = gpu_tests.test_fast_rasterize_render_modes_and_autograd
+test_emulated__adam_is_refused_with_grad_w2c_and_with_grad_depth = gpu_tests.test_adam_is_refused_with_grad_w2c_and_with_grad_depth
 
 
 def test_the_emulated_library_served_these_tests():

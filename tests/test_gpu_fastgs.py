@@ -172,8 +172,8 @@ def test_fastgs_trainer_reference_default_configuration(lfs):
 
 
 def test_fastgs_inline_shN_adam_matches_separate_optimizer(lfs):
-    """lfs_fastgs_backward_adam (single-view steps: the SH backward inside the fastgs backward applies shN's Adam update, no rest-coefficient gradient
-    tensor) against lfs_fastgs_backward + the optimizer launch. The blend backward sums with float atomics, so two runs are compared to tolerance;
+    """lfs_fastgs_view_backward with args.adam (single-view steps: the SH backward inside the fastgs backward applies shN's Adam update, no rest-coefficient gradient
+    tensor) against the plain backward + the optimizer launch. The blend backward sums with float atomics, so two runs are compared to tolerance;
     the SH/Adam arithmetic itself is the kernel pinned bit for bit in tests/test_gpu_fused.py."""
     from lichtfeld_studio_amd import scenes
     from lichtfeld_studio_amd.trainer import GutTrainer

@@ -1,4 +1,4 @@
-"""GPU: the antialiased mode of the fastgs (EWA) rasterizer (lfs_fastgs_preprocess_ex, LFS_FASTGS_ANTIALIASED).
+"""GPU: the antialiased mode of the fastgs (EWA) rasterizer (lfs_fastgs_view_preprocess, LFS_FASTGS_ANTIALIASED).
 
 The mode multiplies a primitive's opacity by rho = sqrt(max(0, det(Sigma2d) / det(Sigma2d + 0.3 I))) before anything looks at it, so an antialiased render of
 (..., raw) IS the ordinary render of (..., raw' = logit(sigmoid(raw) * rho)). Every value test here rests on that identity, with rho from the float64 host model
@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from fastgs_aa_reference import rho64, rho_vjp
+from fastgs_raw import preprocess_raw as _preprocess_raw, render_and_backward_raw as _render_and_backward_raw
 from gpu_util import n, noise_check, rel_l2, rows_check, t
 from test_oracle_fastgs import _scene
 
@@ -234,37 +235,6 @@ def test_antialiased_cuts(lfs):
 
 
 # ---- 4. the default mode is untouched ---------------------------------------------------------------------------------------------------------------------------
-def _preprocess_raw(lib, a, s, flags, pws=None, n_dev=None):
-    """lfs_fastgs_preprocess (flags None) or lfs_fastgs_preprocess_ex through ctypes -> (return code, primitive workspace, device n_instances)"""
-    from lichtfeld_studio_amd import fastgs
-    from lichtfeld_studio_amd.capi import ptr, stream
-    N = a[0].shape[0]
-    if pws is None:
-        pws = torch.zeros(max(256, lib.lfs_fastgs_primitive_workspace_bytes(C.c_uint32(N), C.c_uint32(s.width), C.c_uint32(s.height))), dtype=torch.uint8, device=DEV)
-    if n_dev is None:
-        n_dev = torch.zeros(1, dtype=torch.int64, device=DEV)
-    cam, w2c = s.cam_position.reshape(-1)[:3].contiguous(), a[6].reshape(-1, 4, 4)[0].contiguous()
-    args = [C.c_uint32(N), ptr(a[0]), ptr(a[1]), ptr(a[2]), ptr(a[3].reshape(-1)), ptr(a[4]), ptr(a[5]), C.c_uint32(a[5].shape[1]), ptr(w2c), ptr(cam), *fastgs._frame_args(s),
-            ptr(n_dev), ptr(pws), C.c_size_t(pws.numel())]
-    rc = lib.lfs_fastgs_preprocess(*args, stream()) if flags is None else lib.lfs_fastgs_preprocess_ex(*args, C.c_uint32(flags), stream())
-    return rc, pws, n_dev
-
-
-def _render_and_backward_raw(lib, a, s, pws, n_dev, gi, ga):
-    """the rest of the forward and the backward on a preprocessed workspace -> (image, alpha, n_instances, gradients, densification_info)"""
-    from lichtfeld_studio_amd import fastgs
-    from lichtfeld_studio_amd.capi import check, ptr, stream
-    N = a[0].shape[0]
-    n_inst = int(n_dev.item())
-    iws = torch.empty(max(256, lib.lfs_fastgs_instance_workspace_bytes(C.c_uint32(s.width), C.c_uint32(s.height), C.c_int64(n_inst))), dtype=torch.uint8, device=DEV)
-    image, alpha = torch.empty((3, s.height, s.width), device=DEV), torch.empty((1, s.height, s.width), device=DEV)
-    check(lib.lfs_fastgs_render(C.c_uint32(N), C.c_uint32(s.width), C.c_uint32(s.height), C.c_int64(n_inst), ptr(pws), C.c_size_t(pws.numel()), ptr(iws), C.c_size_t(iws.numel()),
-                                ptr(image), ptr(alpha), stream()), "render")
-    dens = torch.zeros(2, N, device=DEV)
-    g = fastgs.backward_wrapper(dens, gi, ga, image, alpha, a[0], a[1], a[2], a[4], a[5], pws, iws, a[6], s, n_inst)
-    return image, alpha, n_inst, g, dens
-
-
 def _same_bits(x, y):
     assert x[2] == y[2] and torch.equal(x[0], y[0]) and torch.equal(x[1], y[1])
     for p, q in zip(x[3], y[3]):
@@ -278,7 +248,7 @@ def test_default_mode_is_untouched(lfs):
     with _deterministic(lfs) as lib:
         a, s = _dev(sc), _settings(sc)
         gi, ga = [t(x) for x in _upstream(sc)]
-        rc0, pws0, n0 = _preprocess_raw(lib, a, s, None)
+        rc0, pws0, n0 = _preprocess_raw(lib, a, s, 0)      # (two independent calls: the flag-less entry point this compared against is flags = 0 of the one entry)
         rc1, pws1, n1 = _preprocess_raw(lib, a, s, 0)
         assert rc0 == 0 and rc1 == 0
         base, ex = _render_and_backward_raw(lib, a, s, pws0, n0, gi, ga), _render_and_backward_raw(lib, a, s, pws1, n1, gi, ga)
@@ -288,7 +258,7 @@ def test_default_mode_is_untouched(lfs):
         rc2, pws2, n2 = _preprocess_raw(lib, a, s, 1)
         aa = _render_and_backward_raw(lib, a, s, pws2, n2, gi, ga)
         assert rc2 == 0 and not torch.equal(aa[3][1], base[3][1]) and not torch.equal(aa[0], base[0])
-        rc3, _, n3 = _preprocess_raw(lib, a, s, None, pws=pws2)
+        rc3, _, n3 = _preprocess_raw(lib, a, s, 0, pws=pws2)
         assert rc3 == 0
         _same_bits(base, _render_and_backward_raw(lib, a, s, pws2, n3, gi, ga))
     lib = lfs.load_library()
@@ -357,8 +327,8 @@ def test_libtorch_route_matches_the_ctypes_route_bit_for_bit(lfs):
 
 
 def test_antialiased_inline_shN_adam_matches_separate_optimizer(lfs):
-    """tests/test_gpu_fastgs.py::test_fastgs_inline_shN_adam_matches_separate_optimizer with antialiasing=True: lfs_fastgs_backward_adam reads the mode from the
-    workspace like the other backward entry points."""
+    """tests/test_gpu_fastgs.py::test_fastgs_inline_shN_adam_matches_separate_optimizer with antialiasing=True: the optimizer-fused backward reads the mode from the
+    workspace like every other form of lfs_fastgs_view_backward."""
     from gpu_util import noise_allclose
     from lichtfeld_studio_amd import scenes
     from lichtfeld_studio_amd.trainer import GutTrainer

@@ -1,8 +1,8 @@
-"""GPU: the depth modes of the fastgs (EWA) rasterizer (LFS_FASTGS_DEPTH / LFS_FASTGS_INVDEPTH, lfs_fastgs_render_depth, lfs_fastgs_backward_depth).
+"""GPU: the depth modes of the fastgs (EWA) rasterizer (LFS_FASTGS_DEPTH / LFS_FASTGS_INVDEPTH, the depth plane of lfs_fastgs_view_render, grad_depth of lfs_fastgs_view_backward).
 
 A depth render is a colour render whose colour is d_i (= z_i or 1 / z_i in camera space). Every value test here rests on that identity, with z_i from the float64
 host model tests/fastgs_depth_reference.py (independent of the code under test): with s = max d_i, the degree-0 "twin" scene has red = d_i / s, and
-  - the depth map / s is the twin's red channel from the existing lfs_fastgs_render, and the float32 oracle's;
+  - the depth map / s is the twin's red channel from a render without a depth plane, and the float32 oracle's;
   - the depth-only backward (g_image = 0, g_alpha = 0, g_depth = G) is the twin's default backward with g_image = (G s, 0, 0), plus dL/dz_i = dL/dd_i dd/dz along
     w2c[2,:3] in grad_means and in row 2 of grad_w2c, with dL/dd_i = grad_sh0'[:,0,0] / C0 / s read off the twin.
 Tolerances are the ones tests/test_gpu_fastgs.py, tests/test_gpu_fastgs_antialiased.py and tests/test_gpu_fastgs_w2c.py hold this rasterizer to.
@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from fastgs_depth_reference import C0, d64, twin
+from fastgs_raw import backward_raw, instance_workspace, render_raw
 from gpu_util import n, rel_l2, rows_check, t
 from test_gpu_fastgs_antialiased import (GRADS, KEYS, _compensated, _deterministic, _image_bounds, _oracle_fwd, _preprocess_raw, _render_and_backward_raw, _rows,
                                          _same_bits, _upstream)
@@ -93,7 +94,7 @@ def test_depth_forward_is_the_colour_forward_of_the_twin(lfs, oracle_mod, idx, k
     assert tuple(depth.shape) == (1, sc["H"], sc["W"]) and bool(torch.isfinite(depth).all())
     got = n(depth)[0].astype(np.float64) / s
     tw_img = _forward_default(tw, aa)[0]
-    _image_bounds(f"{kind} map / s vs the twin's red channel (lfs_fastgs_render)", got, n(tw_img)[0])
+    _image_bounds(f"{kind} map / s vs the twin's red channel (render without a depth plane)", got, n(tw_img)[0])
     f32 = _oracle_fwd(oracle_mod, _compensated(tw)[1] if aa else tw, np.float32)           # (the oracle has no antialiased mode: the twin at the compensated opacity)
     _image_bounds(f"{kind} map / s vs the float32 oracle on the twin", got, f32["image"][0])
     # the scene exercises it: the expected depth (map / alpha) varies by more than 20 % over the covered pixels - a pixel some instance contributed to has alpha >=
@@ -171,13 +172,13 @@ def test_depth_backward_is_linear_in_its_three_gradients(lfs, idx, kind):
         full = _backward(st, gi, ga, gd)[0]
         colour = _backward(st, gi, ga, torch.zeros_like(gd))[0]
         depth_only = _backward(st, zi, za, gd)[0]
-        plain = _backward(st, gi, ga)[0]                                                    # lfs_fastgs_backward on the same (depth-mode) workspace
+        plain = _backward(st, gi, ga)[0]                                                    # the backward without grad_depth on the same (depth-mode) workspace
     for name, a, b, c, p in zip(GRADS, full, colour, depth_only, plain):
         if a.numel() == 0:
             continue
         e = rel_l2(n(a), n(b).astype(np.float64) + n(c).astype(np.float64))
         e0 = rel_l2(n(b), n(p))
-        print(f"{name}: backward(gi, ga, gd) vs backward(gi, ga, 0) + backward(0, 0, gd) rel-L2 {e:.2e}; backward(gi, ga, 0) vs lfs_fastgs_backward {e0:.2e} (both <= 1e-6)")
+        print(f"{name}: backward(gi, ga, gd) vs backward(gi, ga, 0) + backward(0, 0, gd) rel-L2 {e:.2e}; backward(gi, ga, 0) vs backward(gi, ga) {e0:.2e} (both <= 1e-6)")
         assert e <= 1e-6 and e0 <= 1e-6, (name, e, e0)
     assert float(depth_only[0].abs().max()) > 0 and float((full[0] - colour[0]).abs().max()) > 0
 
@@ -216,13 +217,11 @@ def test_depth_camera_gradient(lfs, idx, kind):
 
 # ---- 5. the default mode is untouched; flag errors ----------------------------------------------------------------------------------------------------------------------
 def test_default_mode_is_untouched_by_the_depth_modes(lfs):
-    from lichtfeld_studio_amd import fastgs
-    from lichtfeld_studio_amd.capi import ptr, stream
     sc = _case(0, "depth")[0]
     with _deterministic(lfs) as lib:
         a, s = _dev(sc), _settings(sc)
         gi, ga = [t(x) for x in _upstream(sc)]
-        rc0, pws0, n0 = _preprocess_raw(lib, a, s, None)
+        rc0, pws0, n0 = _preprocess_raw(lib, a, s, 0)
         rc1, pws1, n1 = _preprocess_raw(lib, a, s, 0)
         assert rc0 == 0 and rc1 == 0
         base = _render_and_backward_raw(lib, a, s, pws0, n0, gi, ga)
@@ -233,8 +232,8 @@ def test_default_mode_is_untouched_by_the_depth_modes(lfs):
             rc2, pws2, n2 = _preprocess_raw(lib, a, s, flag)
             assert rc2 == 0
             _same_bits(base, _render_and_backward_raw(lib, a, s, pws2, n2, gi, ga))
-            # ... and the next default preprocess into it gives today's render and backward, and takes the depth entry points away again
-            rc3, _, n3 = _preprocess_raw(lib, a, s, None, pws=pws2)
+            # ... and the next default preprocess into it gives today's render and backward, and takes the depth plane away again
+            rc3, _, n3 = _preprocess_raw(lib, a, s, 0, pws=pws2)
             assert rc3 == 0
             _same_bits(base, _render_and_backward_raw(lib, a, s, pws2, n3, gi, ga))
             assert _render_depth_rc(lib, sc, pws2, int(n3.item())) == INVALID
@@ -248,23 +247,19 @@ def test_default_mode_is_untouched_by_the_depth_modes(lfs):
         rc, _, _ = _preprocess_raw(lib, a, s, flags, pws=pws, n_dev=n_dev)
         torch.cuda.synchronize()
         assert rc == INVALID and int(n_dev.item()) == -7 and bool((pws == 0xA5).all()), flags
-    # the depth entry points on a workspace whose preprocess carried no depth flag, and without their depth operand: LFS_E_INVALID, no launch
+    # the depth plane and the depth gradient on a workspace whose preprocess carried no depth flag: LFS_E_INVALID, no launch
     st = _forward_default(sc)
     image, alpha, _, pws, iws, n_inst, a, s = st
     assert _render_depth_rc(lib, sc, pws, n_inst) == INVALID
     gd = t(_g_depth(sc))
     grads = [torch.full_like(x, 7.0) for x in (a[0], a[1], a[2], a[3].reshape(-1, 1), a[4], a[5])]
     def bwd_depth(pws_, iws_, gd_):
-        cam, w2c = s.cam_position.reshape(-1)[:3].contiguous(), a[6].reshape(-1, 4, 4)[0].contiguous()
-        return lib.lfs_fastgs_backward_depth(
-            C.c_uint32(a[0].shape[0]), ptr(a[0]), ptr(a[1]), ptr(a[2]), ptr(a[4]), ptr(a[5]), C.c_uint32(a[5].shape[1]), ptr(w2c), ptr(cam), *fastgs._frame_args(s),
-            C.c_int64(n_inst), ptr(pws_), C.c_size_t(pws_.numel()), ptr(iws_), C.c_size_t(iws_.numel()), ptr(gi), ptr(ga), ptr(alpha), None, *[ptr(g) for g in grads],
-            ptr(gd_), None, None, C.c_size_t(0), stream())
+        return backward_raw(lib, a, s, pws_, iws_, n_inst, gi, ga, alpha, None, grads, gd=gd_)
     assert bwd_depth(pws, iws, gd) == INVALID
-    std = _forward_depth(sc, "depth")
-    assert std[5] == n_inst and bwd_depth(std[3], std[4], None) == INVALID
     torch.cuda.synchronize()
     assert all(bool((g == 7.0).all()) for g in grads)
+    std = _forward_depth(sc, "depth")
+    assert std[5] == n_inst and bwd_depth(std[3], std[4], None) == 0                      # no grad_depth: the plain backward, which takes a depth workspace
     assert bwd_depth(std[3], std[4], gd) == 0 and not bool((grads[0] == 7.0).all())
     # forwards without a depth flag between a depth forward and its backward do not cost it its place in the host's table (20 > any small table; evaluation renders
     # and other views do exactly this), a default forward into a depth workspace's own address does
@@ -287,13 +282,42 @@ def test_default_mode_is_untouched_by_the_depth_modes(lfs):
                 assert x.shape[0] == N and bool(torch.isfinite(x).all())
 
 
+# ---- 5b. the optimizer-fused backward has no camera gradient and no depth gradient ----------------------------------------------------------------------------------------
+def test_adam_is_refused_with_grad_w2c_and_with_grad_depth(lfs):
+    """args.adam together with grad_w2c or with grad_depth: LFS_E_INVALID before any launch (the rule fastgs.backward_wrapper states as an LfsError, held by the library
+    itself). The forward ran in a depth mode and the w2c workspace is valid, so each call is accepted once adam is taken away: the combination is what is refused.
+    Every output buffer, the parameter the fused form would update and its moments are pre-filled and found untouched."""
+    from lichtfeld_studio_amd.capi import ptr
+    lib = lfs.load_library()
+    sc = _scene(N=300, W=80, H=64, deg=1)
+    N = len(sc["means"])
+    image, alpha, depth, pws, iws, n_inst, a, s = _forward_depth(sc, "depth")
+    assert n_inst > 0 and a[5].shape[1] > 0
+    gi, ga = [t(x) for x in _upstream(sc)]
+    gd = t(_g_depth(sc))
+    shr = a[5].clone()
+    a_fused = a[:5] + [shr] + a[6:]
+    grads = [torch.full_like(x, 7.0) for x in (a[0], a[1], a[2], a[3].reshape(-1, 1), a[4], a[5])]
+    gw, dens = torch.full((4, 4), 7.0, device=DEV), torch.full((2, N), 7.0, device=DEV)
+    m1, m2 = torch.full_like(shr, 3.0), torch.full_like(shr, 5.0)
+    ws = torch.full((lib.lfs_fastgs_w2c_workspace_bytes(C.c_uint32(N)),), 0xA5, dtype=torch.uint8, device=DEV)
+    tail = (ptr(gw), ptr(ws), ws.numel())
+    call = lambda **kw: backward_raw(lib, a_fused, s, pws, iws, n_inst, gi, ga, alpha, dens, grads, **kw)
+    assert call(adam=(shr, m1, m2), w2c_tail=tail) == INVALID
+    assert call(adam=(shr, m1, m2), gd=gd) == INVALID
+    assert call(adam=(shr, m1, m2), gd=gd, w2c_tail=tail) == INVALID
+    torch.cuda.synchronize()
+    assert all(bool((g == 7.0).all()) for g in grads) and bool((gw == 7.0).all()) and bool((dens == 7.0).all()) and bool((ws == 0xA5).all())
+    assert torch.equal(shr, a[5]) and bool((m1 == 3.0).all()) and bool((m2 == 5.0).all())
+    dens.zero_()
+    assert call(gd=gd, w2c_tail=tail) == 0 and not bool((grads[0] == 7.0).all()) and bool(torch.isfinite(gw).all())     # without adam: accepted
+
+
 def _render_depth_rc(lib, sc, pws, n_inst):
-    from lichtfeld_studio_amd.capi import ptr, stream
     W, H = sc["W"], sc["H"]
-    iws = torch.empty(max(256, lib.lfs_fastgs_instance_workspace_bytes(C.c_uint32(W), C.c_uint32(H), C.c_int64(n_inst))), dtype=torch.uint8, device=DEV)
+    s = _settings(sc)
     image, alpha, depth = torch.full((3, H, W), 5.0, device=DEV), torch.full((1, H, W), 5.0, device=DEV), torch.full((1, H, W), 5.0, device=DEV)
-    rc = lib.lfs_fastgs_render_depth(C.c_uint32(len(sc["means"])), C.c_uint32(W), C.c_uint32(H), C.c_int64(n_inst), ptr(pws), C.c_size_t(pws.numel()), ptr(iws),
-                                     C.c_size_t(iws.numel()), ptr(image), ptr(alpha), ptr(depth), stream())
+    rc = render_raw(lib, _dev(sc), s, pws, n_inst, instance_workspace(lib, s, n_inst), image, alpha, depth)
     if rc != 0:
         torch.cuda.synchronize()
         assert bool((image == 5.0).all()) and bool((depth == 5.0).all())                   # refused before any launch

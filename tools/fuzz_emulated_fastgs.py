@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Differential shape fuzzer for the fastgs (EWA) rasterizer - SURVEY.md §8f row 1 - on the EMULATED product library (tests/emul_util.py; no GPU): random small
 problems (1 .. 400 primitives, images 1 x 1 .. 120 x 120, SH degree 0 - 3, near / far / lateral spreads that put part or all of the model outside the frustum,
-tiny to image-filling scales) through lfs_fastgs_preprocess -> render -> backward, each case against the CPU oracle (oracle/oracle_fastgs.hpp) at the bars of
+tiny to image-filling scales) through lfs_fastgs_view_preprocess -> render -> backward, each case against the CPU oracle (oracle/oracle_fastgs.hpp) at the bars of
 tests/test_gpu_fastgs.py: instance count identical, image / alpha mean |diff| <= 2e-6 with <= 0.1 % of the pixels (at least one allowed) beyond 1/255 + 1e-4, gradients
 against the fp64 oracle <= 5e-4 relative L2 after setting aside at most 3 threshold-flip rows, visibility counts of the densification statistics identical, and the
 forward with cell culling on == off bit for bit.

@@ -3,12 +3,12 @@
 tools/time_masked_loss.py: after a warm-up of each form, `--rounds` rounds alternate between the modes. Per mode, the median over the rounds and the round-to-round
 spread (max - min) of
 
-  preprocess_us   one lfs_fastgs_preprocess[_ex] call (memset, the per-primitive kernel, the tile scan, the count read-back, the SH colours), between device events
+  preprocess_us   one lfs_fastgs_view_preprocess call (memset, the per-primitive kernel, the tile scan, the count read-back, the SH colours), between device events
   prep_bwd_us     the per-primitive stage of the backward: the "fastgs_preprocess_bwd" scope of the library's event profiler (both instantiations of
                   fg_preprocess_bwd_kernel are queued, the one that does not match the workspace's mode word returns at once), blend backward held out (debug bit 1)
   step_ms         one GutTrainer(rasterizer="fastgs") train_step, between device events
 
-The tool runs on a tree without lfs_fastgs_preprocess_ex too and then times the default mode only: that run is the baseline the default mode's step is held to
+On a library without lfs_fastgs_view_preprocess the antialiased mode is left out and the default mode alone is timed: such a run is the baseline the default mode's step is held to
 (not slower than the baseline by more than the baseline's own round-to-round spread; --baseline FILE puts both numbers and the verdict into the output).
 The antialiased mode's cost is reported, not gated. VGPRs / scratch / occupancy of the instantiations come from tools/kernel_resources.py.
 
@@ -44,7 +44,7 @@ def main():
         raise SystemExit("time_fastgs_aa.py measures on the GPU: no device found")
     dev = torch.device("cuda:0")
     lib = lfs.load_library()
-    modes = ["default"] + (["antialiased"] if hasattr(lib, "lfs_fastgs_preprocess_ex") else [])
+    modes = ["default"] + (["antialiased"] if hasattr(lib, "lfs_fastgs_view_preprocess") else [])
     sc = scenes.syn_b(n=args.n, n_views=4).to(dev)
     target = scenes.target_image(sc.height, sc.width).to(dev)
     trainers = {m: GutTrainer(sc, dev, iterations=30000, rasterizer="fastgs", **({"antialiasing": True} if m == "antialiased" else {})) for m in modes}
@@ -57,14 +57,10 @@ def main():
     N = means.shape[0]
     pws = torch.empty(lib.lfs_fastgs_primitive_workspace_bytes(C.c_uint32(N), C.c_uint32(s.width), C.c_uint32(s.height)), dtype=torch.uint8, device=dev)
     n_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-    pre = [C.c_uint32(N), ptr(means), ptr(raw_scales), ptr(raw_quats), ptr(raw_opac.reshape(-1)), ptr(sh0), ptr(shN), C.c_uint32(shN.shape[1]), ptr(w2c), ptr(cam),
-           *fastgs._frame_args(s), ptr(n_dev), ptr(pws), C.c_size_t(pws.numel())]
+    view = fastgs.view_struct(s, means, raw_scales, raw_quats, raw_opac.reshape(-1), sh0, shN, w2c, cam, pws)
 
     def preprocess(mode):
-        if mode == "antialiased":
-            capi.check(lib.lfs_fastgs_preprocess_ex(*pre, C.c_uint32(1), stream()), "preprocess_ex")
-        else:
-            capi.check(lib.lfs_fastgs_preprocess(*pre, stream()), "preprocess")
+        capi.check(lib.lfs_fastgs_view_preprocess(C.byref(view), C.c_uint32(1 if mode == "antialiased" else 0), ptr(n_dev), stream()), "view_preprocess")
 
     # one forward + backward per mode; the later backward calls keep its accumulator rows (debug bit 1) and run the per-primitive stage only
     state = {}

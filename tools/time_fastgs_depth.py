@@ -3,8 +3,8 @@
 method of tools/time_fastgs_aa.py: after a warm-up of each form, `--rounds` rounds alternate between the modes. Per mode, the median over the rounds and the
 round-to-round spread (max - min) of
 
-  blend_fwd_us    the blending forward: the "fastgs_blend_fwd" scope of the library's event profiler inside lfs_fastgs_render / lfs_fastgs_render_depth
-  blend_bwd_us    the blending backward: the "fastgs_blend_bwd" scope inside lfs_fastgs_backward / lfs_fastgs_backward_depth (nine / ten reduced values per instance)
+  blend_fwd_us    the blending forward: the "fastgs_blend_fwd" scope of the library's event profiler inside lfs_fastgs_view_render without / with a depth plane
+  blend_bwd_us    the blending backward: the "fastgs_blend_bwd" scope inside lfs_fastgs_view_backward without / with grad_depth (nine / ten reduced values per instance)
   step_ms         one GutTrainer(rasterizer="fastgs") train_step, between device events; the depth mode's step carries a depth target for its view
                   (depth_loss="invdepth": the depth forward and backward and the fused depth loss)
 
@@ -42,7 +42,7 @@ def main():
         raise SystemExit("time_fastgs_depth.py measures on the GPU: no device found")
     dev = torch.device("cuda:0")
     lib = lfs.load_library()
-    has_depth = hasattr(lib, "lfs_fastgs_render_depth")
+    has_depth = hasattr(lib, "lfs_fastgs_view_render")
     modes = ["default"] + (["invdepth"] if has_depth else [])
     sc = scenes.syn_b(n=args.n, n_views=4).to(dev)
     target = scenes.target_image(sc.height, sc.width).to(dev)
