@@ -345,6 +345,39 @@ typedef struct lfs_fastgs_view_backward_args {
 } lfs_fastgs_view_backward_args;
 LFS_API size_t lfs_fastgs_w2c_workspace_bytes(uint32_t N);
 LFS_API int lfs_fastgs_view_backward(const lfs_fastgs_view* view, const lfs_fastgs_view_backward_args* args, lfs_stream_t stream);
+/* ---- The 3D smoothing filter of Mip-Splatting (the other half of LFS_FASTGS_ANTIALIASED, which is its 2D Mip filter). Nothing in the reference provides it.
+ *      With v_i >= 0 the filter variance of Gaussian i (lfs_filter3d_compute below), R S^2 R^T + v I = R (S^2 + v I) R^T: the filtered modes of the per-primitive
+ *      kernels use s'_ik = sqrt(s_ik^2 + v_i) wherever the default mode uses exp(raw_scale), and o'_i = sigmoid(raw_i) * kappa_i, kappa_i = prod_k s_ik / s'_ik,
+ *      wherever it uses sigmoid(raw_i): the 1/255 cut, the EWA projection, rho of the antialiased mode (o_eff = o' rho(s')), the power threshold, the extents, the
+ *      tile tests, the records. A filtered render of (raw_scales, raw, v) is the default render of (log s', logit(o')).
+ *      Backward, with g'_k the gradient w.r.t. log s'_k, S = o_eff dL/do_eff and u_k = v / (s_k^2 + v):
+ *        grad_scales_raw_k = g'_k (1 - u_k) + S u_k,  grad_opacities_raw = S (1 - sigmoid(raw));  everything else is the gradient at the effective parameters.
+ *      v itself takes no gradient (it is a statistic of the training cameras, recomputed by the trainer).
+ *      The operand arrives through an extension struct on two entries; further per-view operands go into this struct. ext == NULL, or ext->filter3d_var == NULL,
+ *      IS the entry without _ex. The public flags are those of lfs_fastgs_view_preprocess. The filtered mode is recorded in the workspace's mode word (an internal
+ *      bit) and in the library's by-address memory of workspaces (as the depth modes): lfs_fastgs_view_backward_ex returns LFS_E_INVALID before any launch, nothing
+ *      written, when its ext disagrees - in either direction - with what is remembered for the workspace. lfs_fastgs_view_render is the same call in every mode.
+ *      args->adam works with the filter. The workspace sizes do not change. */
+typedef struct lfs_fastgs_view_ext {
+    const float* filter3d_var;              /* [N] (device) or NULL */
+} lfs_fastgs_view_ext;
+LFS_API int lfs_fastgs_view_preprocess_ex(const lfs_fastgs_view* view, uint32_t flags, const lfs_fastgs_view_ext* ext, int64_t* n_instances /* device */,
+                                          lfs_stream_t stream);
+LFS_API int lfs_fastgs_view_backward_ex(const lfs_fastgs_view* view, const lfs_fastgs_view_backward_args* args, const lfs_fastgs_view_ext* ext, lfs_stream_t stream);
+/* The filter variance. One packed camera: rows 0-2 of the row-major world-to-camera matrix, the pinhole intrinsics in pixels, the image size.
+ *   camera c SEES Gaussian i  iff  z_ic > 0.2 and -0.15 W_c <= x <= 1.15 W_c and -0.15 H_c <= y <= 1.15 H_c   ((x, y) the pinhole projection in pixels)
+ *   nu_i = max over the cameras that see i of max(fx_c, fy_c) / z_ic;  a Gaussian no camera sees takes the smallest nu among the seen ones;
+ *   filter_var[i] = variance_scale / nu_i^2 (Mip-Splatting's variance_scale: 0.2);  no Gaussian seen, or C == 0: every filter_var[i] = 0.
+ * cameras: device array of C records. workspace: 4-byte aligned, lfs_filter3d_workspace_bytes() bytes. No host read, no allocation, no float atomics: the same
+ * bits on every run. N == 0: LFS_OK, nothing launched. LFS_E_INVALID: NULL means / filter_var, NULL cameras with C > 0, a negative or NaN variance_scale. */
+typedef struct lfs_filter3d_camera {
+    float w2c[12];
+    float fx, fy, cx, cy;
+    uint32_t width, height;
+} lfs_filter3d_camera;
+LFS_API size_t lfs_filter3d_workspace_bytes(void);
+LFS_API int lfs_filter3d_compute(uint32_t N, const float* means, uint32_t C, const lfs_filter3d_camera* cameras /* device */, float variance_scale,
+                                 float* filter_var, void* workspace, size_t workspace_bytes, lfs_stream_t stream);
 LFS_API void lfs_fastgs_set_debug_flags(uint32_t flags); /* bit 0: no per-cell culling (bit-identity test); bit 1: the backward skips the blending
                                                            * backward and reuses the accumulator rows the previous backward left in the primitive workspace (its float
                                                            * atomics round differently from run to run: bit-identity tests of the per-primitive stage hold them fixed).

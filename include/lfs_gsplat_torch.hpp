@@ -130,6 +130,20 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Te
     const torch::Tensor& per_primitive_buffers, const torch::Tensor& per_instance_buffers, const torch::Tensor& w2c, const torch::Tensor& cam_position,
     const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
     const float center_y, const float near_plane, const float far_plane, const int n_instances);
+// Extension: the 3D smoothing filter of Mip-Splatting (lfs_fastgs_view_preprocess_ex / lfs_fastgs_view_backward_ex; include/lfs_gsplat.h). filter3d_var: the [N] filter
+// variances (lfs_filter3d_compute). The forward returns what fastgs_forward_wrapper_ex returns; the backward MUST be this one, with the same tensor (a backward
+// without it on such a workspace is refused), and returns what fast_gs::rasterization::backward_wrapper returns (7th element: grad_w2c when w2c requires grad).
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int> fastgs_forward_wrapper_filter3d(
+    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
+    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
+    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
+    const float center_y, const float near_plane, const float far_plane, const bool antialiased, const torch::Tensor& filter3d_var);
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> fastgs_backward_wrapper_filter3d(
+    torch::Tensor& densification_info, const torch::Tensor& grad_image, const torch::Tensor& grad_alpha, const torch::Tensor& alpha,
+    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& sh_coefficients_rest,
+    const torch::Tensor& per_primitive_buffers, const torch::Tensor& per_instance_buffers, const torch::Tensor& w2c, const torch::Tensor& cam_position,
+    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
+    const float center_y, const float near_plane, const float far_plane, const int n_instances, const torch::Tensor& filter3d_var);
 } // namespace lfs
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> fusedssim(float C1, float C2, torch::Tensor& img1, torch::Tensor& img2, bool train);

@@ -38,6 +38,7 @@ SOURCES = {
     "bilateral_grid.hip": ["-ffp-contract=off"],
     "dataprep.hip": ["-ffp-contract=off"],
     "fastgs_prep.hip": ["-ffp-contract=off"],
+    "filter3d.hip": ["-ffp-contract=off"],   # the 3D smoothing filter's variance from all training cameras (its per-primitive use is in fastgs_prep.hip)
     "sog.hip": ["-ffp-contract=off"],   # SOG export: Morton codes, k-means (the MFMA assignment is an fmaf chain by construction; the flag holds the rest)
     "sparsity.hip": ["-ffp-contract=off"],   # ADMM sparsity: radix select, state update, loss + gradient (the sigmoid of l2_fused.hip, same flags: same bits)
     "fastgs_blend.hip": ["-fno-slp-vectorize"],

@@ -95,6 +95,14 @@ class FastgsBackwardArgs(C.Structure):  # lfs_fastgs_view_backward_args
                 ("adam", C.POINTER(FastgsShRestAdam))]
 
 
+class FastgsViewExt(C.Structure):  # lfs_fastgs_view_ext
+    _fields_ = [("filter3d_var", C.c_void_p)]
+
+
+class Filter3dCamera(C.Structure):  # lfs_filter3d_camera (72 bytes: 18 dwords, the row layout of filter3d.pack_cameras)
+    _fields_ = [("w2c", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
 ADAM_MAX_TENSORS = 8
 
 # every symbol include/lfs_gsplat.h declares
@@ -114,6 +122,7 @@ EXPORTS = [
     "lfs_admm_prune_mask_workspace_bytes", "lfs_admm_prune_mask",
     "lfs_mask_prepare", "lfs_photometric_loss_masked_fwd_bwd", "lfs_mse_loss_masked_fwd_bwd",
     "lfs_depth_prepare", "lfs_depth_l1_loss_fwd_bwd",
+    "lfs_fastgs_view_preprocess_ex", "lfs_fastgs_view_backward_ex", "lfs_filter3d_workspace_bytes", "lfs_filter3d_compute",
 ]
 
 
@@ -146,10 +155,12 @@ def load_library():
         lib.lfs_rasterize_workspace_acc_offset.restype = C.c_size_t
         lib.lfs_morton_workspace_bytes.restype = C.c_size_t
         lib.lfs_kmeans_assign_workspace_bytes.restype = C.c_size_t
+        lib.lfs_filter3d_workspace_bytes.restype = C.c_size_t
         for name in ("lfs_select_kth_workspace_bytes", "lfs_admm_update_workspace_bytes", "lfs_admm_loss_grad_workspace_bytes", "lfs_admm_prune_mask_workspace_bytes"):
             getattr(lib, name).restype = C.c_size_t
         lib.lfs_version.restype = C.c_char_p
-        for name in ("lfs_fastgs_view_preprocess", "lfs_fastgs_view_render", "lfs_fastgs_view_backward"):
+        for name in ("lfs_fastgs_view_preprocess", "lfs_fastgs_view_render", "lfs_fastgs_view_backward", "lfs_fastgs_view_preprocess_ex", "lfs_fastgs_view_backward_ex",
+                     "lfs_filter3d_compute"):
             getattr(lib, name).restype = C.c_int
         if os.environ.get("LFS_DEBUG_FLAGS"):   # measurement / debugging only (tools/*.sh): e.g. 64 = the reference's tile lists + pack + cull kernels inside the step
             lib.lfs_set_debug_flags(C.c_uint32(int(os.environ["LFS_DEBUG_FLAGS"], 0)))

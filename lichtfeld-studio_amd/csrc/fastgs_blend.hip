@@ -17,7 +17,7 @@ namespace fgs {
 int launch_scatter(uint32_t N, const Frame& f, const PrimWs& w, int64_t* keys, hipStream_t s);
 Frame make_frame(const lfs_fastgs_view& v);
 int launch_preprocess_bwd(const lfs_fastgs_view& v, const Frame& f, const PrimWs& w, const lfs_fastgs_view_backward_args& a, const float* sh_rest, const ShAdamArgs* adam,
-                          int depth, hipStream_t s);
+                          int depth, const float* filter_var, hipStream_t s);
 uint32_t remembered_flags(const void* primitive_workspace);
 size_t w2c_workspace_bytes(uint32_t N);
 int launch_w2c_reduce(uint32_t N, const float* w2c_partials, float* grad_w2c, hipStream_t s);
@@ -306,11 +306,21 @@ extern "C" int lfs_fastgs_view_render(const lfs_fastgs_view* view, int64_t n_ins
 
 extern "C" size_t lfs_fastgs_w2c_workspace_bytes(uint32_t N) { return fgs::w2c_workspace_bytes(N); }
 
+// filter_var (lfs_fastgs_view_ext::filter3d_var) must agree with what the library remembers for the workspace - filled with the 3D filter or not - in both directions:
+// LFS_E_INVALID before any launch otherwise (a backward of the wrong form would differentiate a function the forward did not render).
+static int view_backward(const lfs_fastgs_view* view, const lfs_fastgs_view_backward_args* args, const float* filter_var, lfs_stream_t stream);
 extern "C" int lfs_fastgs_view_backward(const lfs_fastgs_view* view, const lfs_fastgs_view_backward_args* args, lfs_stream_t stream) {
+    return view_backward(view, args, nullptr, stream);
+}
+extern "C" int lfs_fastgs_view_backward_ex(const lfs_fastgs_view* view, const lfs_fastgs_view_backward_args* args, const lfs_fastgs_view_ext* ext, lfs_stream_t stream) {
+    return view_backward(view, args, ext ? ext->filter3d_var : nullptr, stream);
+}
+static int view_backward(const lfs_fastgs_view* view, const lfs_fastgs_view_backward_args* args, const float* filter_var, lfs_stream_t stream) {
     if (!view || !args) return LFS_E_INVALID;
     const lfs_fastgs_view& v = *view;
     const lfs_fastgs_view_backward_args& a = *args;
     const uint32_t N = v.N;
+    if (v.primitive_workspace && ((fgs::remembered_flags(v.primitive_workspace) & fgs::MODE_FILTER3D) != 0u) != (filter_var != nullptr)) return LFS_E_INVALID;
     // the optimizer-fused form: the parameter it updates replaces the view's sh_coefficients_rest; it has no camera gradient and no depth gradient
     const float* sh_rest = v.sh_coefficients_rest;
     lfs::ShAdamArgs adam_args{};
@@ -374,5 +384,5 @@ extern "C" int lfs_fastgs_view_backward(const lfs_fastgs_view* view, const lfs_f
 #undef LFS_FG_BWD
 #undef LFS_FG_BWD_D
     }
-    return fgs::launch_preprocess_bwd(v, f, w, a, sh_rest, adam, depth, s);
+    return fgs::launch_preprocess_bwd(v, f, w, a, sh_rest, adam, depth, filter_var, s);
 }

@@ -37,12 +37,15 @@ struct Cov { // what forward and backward both need of a primitive's geometry
     float tx, ty, j11, j13, j22, j23, jw1[3], jw2[3], jc1[3], jc2[3], a, b, c;
     float a0, c0; // (a, c) before the dilation: the antialiased mode's compensation needs both determinants
 };
-LFS_DI void ewa(const Frame& f, const float* __restrict__ m, const float* __restrict__ rs, const float4 q, Cov& o) {
+// FILTER3D: var3 = the activated variances s_k^2 + v the caller formed (the 3D smoothing filter); the raw scales are not read
+template <bool FILTER3D = false>
+LFS_DI void ewa(const Frame& f, const float* __restrict__ m, const float* __restrict__ rs, const float4 q, Cov& o, const float* var3 = nullptr) {
     const float* r1 = f.w2c; const float* r2 = f.w2c + 4; const float* r3 = f.w2c + 8;
     o.depth = r3[0] * m[0] + r3[1] * m[1] + r3[2] * m[2] + r3[3];
     o.x = (r1[0] * m[0] + r1[1] * m[1] + r1[2] * m[2] + r1[3]) / o.depth;
     o.y = (r2[0] * m[0] + r2[1] * m[1] + r2[2] * m[2] + r2[3]) / o.depth;
-    o.var[0] = expf(2.f * rs[0]); o.var[1] = expf(2.f * rs[1]); o.var[2] = expf(2.f * rs[2]);
+    if constexpr (FILTER3D) { o.var[0] = var3[0]; o.var[1] = var3[1]; o.var[2] = var3[2]; }
+    else { o.var[0] = expf(2.f * rs[0]); o.var[1] = expf(2.f * rs[1]); o.var[2] = expf(2.f * rs[2]); }
     o.qr = q.x; o.qx = q.y; o.qy = q.z; o.qz = q.w;
     o.qn = o.qr * o.qr + o.qx * o.qx + o.qy * o.qy + o.qz * o.qz;
     o.qxx = 2.f * o.qx * o.qx / o.qn; o.qyy = 2.f * o.qy * o.qy / o.qn; o.qzz = 2.f * o.qz * o.qz / o.qn;
@@ -86,14 +89,20 @@ LFS_DI void ewa(const Frame& f, const float* __restrict__ m, const float* __rest
 // DEPTH (1: LFS_FASTGS_DEPTH, 2: LFS_FASTGS_INVDEPTH): d = z or 1 / z of the camera-space z the cuts and the sort key already use goes into the record's free r2.w
 // (one dword store; the SH kernel that fills r2.xyz afterwards writes three dwords and leaves it alone). Nothing else changes: the default forms store nothing there.
 // ---------------------------------------------------------------------------
-template <bool LDS_HIST, bool AA, int DEPTH>
-__global__ void __launch_bounds__(1024) fg_preprocess_kernel(
+// FILTER3D (lfs_fastgs_view_ext::filter3d_var, the 3D smoothing filter of Mip-Splatting): v = filter_var[i] is loaded after the depth cut; with s2_k = exp(2 raw_scale_k),
+// u_k = v / (s2_k + v) (0 for v = 0) the variances are s2_k + v and the opacity is sigmoid(raw) * kappa, kappa = sqrt(prod (1 - u_k)) = prod s_k / s'_k, before the 1/255
+// cut and everything after it (rho of the AA form is that of the filtered covariance). sigmoid(raw) goes to r1.w as in the AA form. The body is shared; the kernels
+// below it are its FILTER3D = false / true wrappers under separate names, so the default forms keep theirs. (Both shared bodies take the Frame by value and their
+// pointers __restrict__, exactly as the kernels do: with either changed, the default forms no longer compile to the registers they had as kernels of their own.)
+template <bool LDS_HIST, bool AA, int DEPTH, bool FILTER3D>
+LFS_DI void preprocess_body(
     const uint32_t N, const uint32_t per_block, const float* __restrict__ means, const float* __restrict__ scales_raw, const float* __restrict__ rot_raw,
     const float* __restrict__ opac_raw, const Frame f,
     GaussRec* __restrict__ rec, float2* __restrict__ mean2d_o, float4* __restrict__ conic_opacity_o, ushort4* __restrict__ bounds_o,
-    uint32_t* __restrict__ n_touched_o, uint32_t* __restrict__ depth_bits_o, uint32_t* __restrict__ totals, uint32_t* __restrict__ mode_o) {
+    uint32_t* __restrict__ n_touched_o, uint32_t* __restrict__ depth_bits_o, uint32_t* __restrict__ totals, uint32_t* __restrict__ mode_o,
+    const float* __restrict__ filter_var) {
     extern __shared__ __attribute__((aligned(16))) uint32_t hist[];
-    if (blockIdx.x == 0 && threadIdx.x == 0) *mode_o = (AA ? MODE_ANTIALIASED : 0u) | depth_mode_bits(DEPTH);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *mode_o = (AA ? MODE_ANTIALIASED : 0u) | depth_mode_bits(DEPTH) | (FILTER3D ? MODE_FILTER3D : 0u);
     const uint32_t T = f.gw * f.gh;
     if (LDS_HIST) {
         for (uint32_t t = threadIdx.x; t < T; t += blockDim.x) hist[t] = 0u;
@@ -108,16 +117,29 @@ __global__ void __launch_bounds__(1024) fg_preprocess_kernel(
             const float depth = r3[0] * m[0] + r3[1] * m[1] + r3[2] * m[2] + r3[3];
             if (depth < f.near_ || depth > f.far_) break;
             const float sig = 1.0f / (1.0f + expf(-opac_raw[i]));
-            if (sig < MIN_ALPHA) break;
+            float base = sig;   // the opacity before rho: sigmoid(raw), or sigmoid(raw) * kappa
+            float var3[3];
+            if constexpr (FILTER3D) {
+                const float v = filter_var[i];
+                float keep = 1.f;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const float s2 = expf(2.f * scales_raw[3 * size_t(i) + k]);
+                    var3[k] = s2 + v;
+                    keep *= 1.f - (v > 0.f ? v / var3[k] : 0.f);
+                }
+                base = sig * sqrtf(keep);
+            }
+            if (base < MIN_ALPHA) break;
             const float4 q = reinterpret_cast<const float4*>(rot_raw)[i];
             if (q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w < 1e-8f) break;
             Cov cv;
-            ewa(f, m, scales_raw + 3 * size_t(i), q, cv);
+            ewa<FILTER3D>(f, m, scales_raw + 3 * size_t(i), q, cv, var3);
             const float det = cv.a * cv.c - cv.b * cv.b;
             if (det < 1e-8f) break;
-            float opacity = sig;
+            float opacity = base;
             if constexpr (AA) {
-                opacity = sig * sqrtf(fmaxf(0.f, (cv.a0 * cv.c0 - cv.b * cv.b) / det));
+                opacity = base * sqrtf(fmaxf(0.f, (cv.a0 * cv.c0 - cv.b * cv.b) / det));
                 if (opacity < MIN_ALPHA) break;
             }
             const float ca = cv.c / det, cb = -cv.b / det, cc = cv.a / det;
@@ -140,7 +162,7 @@ __global__ void __launch_bounds__(1024) fg_preprocess_kernel(
             // (r2 = max(SH colour + 0.5, 0) is filled in by the SH kernel of sh.hip right after this one)
             float4* r = reinterpret_cast<float4*>(rec + i);
             r[0] = make_float4(mx, my, 0.5f * LOG2E * ca, LOG2E * cb);
-            r[1] = make_float4(0.5f * LOG2E * cc, LOG2E * power_threshold, opacity, AA ? sig : 0.f);
+            r[1] = make_float4(0.5f * LOG2E * cc, LOG2E * power_threshold, opacity, (AA || FILTER3D) ? sig : 0.f);
             if constexpr (DEPTH != 0) reinterpret_cast<float*>(rec + i)[11] = DEPTH == 1 ? depth : 1.0f / depth;   // r2.w (depth >= near_plane > 0 here)
             mean2d_o[i] = make_float2(mx, my);
             conic_opacity_o[i] = make_float4(ca, cb, cc, opacity);
@@ -157,6 +179,30 @@ __global__ void __launch_bounds__(1024) fg_preprocess_kernel(
         }
     }
 }
+
+#define LFS_FG_PREP_PARAMS \
+    const uint32_t N, const uint32_t per_block, const float* __restrict__ means, const float* __restrict__ scales_raw, const float* __restrict__ rot_raw, \
+    const float* __restrict__ opac_raw, const Frame f, \
+    GaussRec* __restrict__ rec, float2* __restrict__ mean2d_o, float4* __restrict__ conic_opacity_o, ushort4* __restrict__ bounds_o, \
+    uint32_t* __restrict__ n_touched_o, uint32_t* __restrict__ depth_bits_o, uint32_t* __restrict__ totals, uint32_t* __restrict__ mode_o
+#define LFS_FG_PREP_ARGS N, per_block, means, scales_raw, rot_raw, opac_raw, f, rec, mean2d_o, conic_opacity_o, bounds_o, n_touched_o, depth_bits_o, totals, mode_o
+template <bool LDS_HIST, bool AA, int DEPTH>
+__global__ void __launch_bounds__(1024) fg_preprocess_kernel(LFS_FG_PREP_PARAMS) {
+    preprocess_body<LDS_HIST, AA, DEPTH, false>(LFS_FG_PREP_ARGS, nullptr);
+}
+// (96 SGPRs: the filter operand's pointer would otherwise take the forms without the LDS histogram two registers past the allocation step their default forms stay
+// under; the compiler finds them without spilling to memory - tests/test_kernel_resources_fastgs_filter3d.py)
+#ifdef LFS_EMULATE
+#define LFS_FG_F3D_SGPRS
+#else
+#define LFS_FG_F3D_SGPRS __attribute__((amdgpu_num_sgpr(96)))
+#endif
+template <bool LDS_HIST, bool AA, int DEPTH>
+__global__ void __launch_bounds__(1024) LFS_FG_F3D_SGPRS fg_preprocess_f3d_kernel(LFS_FG_PREP_PARAMS, const float* __restrict__ filter_var) {
+    preprocess_body<LDS_HIST, AA, DEPTH, true>(LFS_FG_PREP_ARGS, filter_var);
+}
+#undef LFS_FG_PREP_PARAMS
+#undef LFS_FG_PREP_ARGS
 
 // ---------------------------------------------------------------------------
 // scatter: (depth bits << 32 | primitive) of every instance into its tile bucket (unordered inside the bucket; the
@@ -218,12 +264,15 @@ LFS_DI void preprocess_bwd_zero_rows(const uint32_t i, float* __restrict__ g_mea
 // a0/det0 - a/det1) - no division by rho (a visible primitive has rho >= 1/255, hence det0 > 0). Everything below dcv is the code both modes share.
 // DEPTH (1 / 2, a backward with grad_depth): slot 9 of the row is dL/dd, d = z or 1 / z, and z is the third camera-space coordinate: dL/dz = acc[9] (1 | -1 / z^2) is
 // added to dcam[2] before grad_means and the camera gradient are made of it. densification_info keeps its definition (dL/dmean2d only).
-template <bool AA, int DEPTH>
+// FILTER3D: the geometry is that of the filtered variances s2_k + v, so everything below is the gradient at the effective parameters, g'_k w.r.t. log s'_k included;
+// d log s'_k / d raw_k = 1 - u_k and d log kappa / d raw_k = u_k, u_k = v / (s2_k + v): grad_scales_raw_k = g'_k (1 - u_k) + S u_k with S = a2.x. u_k is formed from v and
+// s2_k + v (0 for v = 0; 0 again for an overflowed s2_k), never as a quotient of two overflowed values. sigmoid(raw) comes from r1.w as in the AA form.
+template <bool AA, int DEPTH, bool FILTER3D>
 LFS_DI void preprocess_bwd_one(
     const uint32_t i, const uint32_t N, const float* __restrict__ means, const float* __restrict__ scales_raw, const float* __restrict__ rot_raw,
     const Frame& f, const GaussRec* __restrict__ rec, const float4* __restrict__ conic_opacity, const float* __restrict__ acc,
     float* __restrict__ g_means, float* __restrict__ g_scales_raw, float* __restrict__ g_rot_raw, float* __restrict__ g_opac_raw,
-    float* __restrict__ densification_info, float (&dcam)[3]) {
+    float* __restrict__ densification_info, float (&dcam)[3], const float* __restrict__ filter_var = nullptr) {
     const float4* a4 = reinterpret_cast<const float4*>(acc + size_t(i) * ACC_STRIDE);
     const float4 a0 = a4[0], a1 = a4[1], a2 = a4[2];
     const GaussRec r = rec[i];
@@ -232,14 +281,23 @@ LFS_DI void preprocess_bwd_one(
     const float4 co = conic_opacity[i];
     const float dm2[2] = {co.x * a0.x + co.y * a0.y, co.y * a0.x + co.z * a0.y};
     const float dcon[3] = {0.5f * a0.z, 0.5f * a0.w, 0.5f * a1.x};
-    const float opacity = AA ? r.r1.w : r.r1.z;   // sigmoid(raw)
+    const float opacity = (AA || FILTER3D) ? r.r1.w : r.r1.z;   // sigmoid(raw)
     g_opac_raw[i] = a2.x * (1.0f - opacity);
     const float* m = means + 3 * size_t(i);
     const float dpos[3] = {0.f, 0.f, 0.f}; // (the colour -> position term is added by the SH backward kernel of sh.hip, which runs after this one)
     // ---- EWA backward
     const float4 q = reinterpret_cast<const float4*>(rot_raw)[i];
     Cov cv;
-    ewa(f, m, scales_raw + 3 * size_t(i), q, cv);
+    float var3[3], u3[3];
+    if constexpr (FILTER3D) {
+        const float v = filter_var[i];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            var3[k] = expf(2.f * scales_raw[3 * size_t(i) + k]) + v;
+            u3[k] = v > 0.f ? v / var3[k] : 0.f;
+        }
+    }
+    ewa<FILTER3D>(f, m, scales_raw + 3 * size_t(i), q, cv, var3);
     const float* r1 = f.w2c; const float* r2 = f.w2c + 4; const float* r3 = f.w2c + 8;
     const float A = cv.a, B = cv.b, C = cv.c;
     const float det = A * C - B * B, dr = 1.0f / det, dr2 = dr * dr;
@@ -274,7 +332,8 @@ LFS_DI void preprocess_bwd_one(
     for (int v = 0; v < 3; ++v) {
         const float dvar = cv.R[0][v] * cv.R[0][v] * G[0][0] + cv.R[1][v] * cv.R[1][v] * G[1][1] + cv.R[2][v] * cv.R[2][v] * G[2][2] +
                            2.0f * (cv.R[0][v] * cv.R[1][v] * G[0][1] + cv.R[0][v] * cv.R[2][v] * G[0][2] + cv.R[1][v] * cv.R[2][v] * G[1][2]);
-        g_scales_raw[3 * size_t(i) + v] = 2.0f * cv.var[v] * dvar;
+        if constexpr (FILTER3D) g_scales_raw[3 * size_t(i) + v] = (2.0f * cv.var[v] * dvar) * (1.f - u3[v]) + a2.x * u3[v];
+        else g_scales_raw[3 * size_t(i) + v] = 2.0f * cv.var[v] * dvar;
     }
     float dR[3][3];
 #pragma unroll
@@ -321,27 +380,31 @@ LFS_DI float block_sum12(float (&v)[W2C_VALS], float (*s_part)[W2C_VALS]) {
 // AA: the instantiation for the antialiased mode. The launcher queues both; the one that does not match the mode word the forward left in the workspace returns at once.
 // DEPTH: 0 = the forms of a backward without a depth gradient, which look at the antialiased bit only (a depth-mode workspace is an ordinary workspace to
 // them: slot 9 of the rows is zero and not read); 1 / 2 = the forms of a backward with grad_depth, which also require their depth bit in the mode word.
-template <bool W2C, bool AA, int DEPTH>
-__global__ void __launch_bounds__(256) fg_preprocess_bwd_kernel(
+// FILTER3D: the forms of a backward with lfs_fastgs_view_ext::filter3d_var (chosen on the host, from its memory of the workspace); they require their bit in the mode
+// word as the depth forms do. The kernels below the body are its FILTER3D = false / true wrappers under separate names.
+template <bool W2C, bool AA, int DEPTH, bool FILTER3D>
+LFS_DI void preprocess_bwd_body(
     const uint32_t N, const float* __restrict__ means, const float* __restrict__ scales_raw, const float* __restrict__ rot_raw,
     const Frame f, const GaussRec* __restrict__ rec, const float4* __restrict__ conic_opacity,
     const uint32_t* __restrict__ n_touched, const float* __restrict__ acc, float* __restrict__ g_means, float* __restrict__ g_scales_raw, float* __restrict__ g_rot_raw,
-    float* __restrict__ g_opac_raw, float* __restrict__ densification_info, float* __restrict__ w2c_partials, const uint32_t* __restrict__ mode) {
+    float* __restrict__ g_opac_raw, float* __restrict__ densification_info, float* __restrict__ w2c_partials, const uint32_t* __restrict__ mode,
+    const float* __restrict__ filter_var) {
     if (((*mode & MODE_ANTIALIASED) != 0u) != AA) return;   // (uniform: before any barrier)
     if constexpr (DEPTH != 0) { if ((*mode & depth_mode_bits(DEPTH)) == 0u) return; }
+    if constexpr (FILTER3D) { if ((*mode & MODE_FILTER3D) == 0u) return; }
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if constexpr (!W2C) {   // the kernel as it was: the same early returns, no operand of the sum below exists
         if (i >= N) return;
         if (n_touched[i] == 0) { preprocess_bwd_zero_rows(i, g_means, g_scales_raw, g_rot_raw, g_opac_raw); return; }
         float dcam[3];
-        preprocess_bwd_one<AA, DEPTH>(i, N, means, scales_raw, rot_raw, f, rec, conic_opacity, acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, dcam);
+        preprocess_bwd_one<AA, DEPTH, FILTER3D>(i, N, means, scales_raw, rot_raw, f, rec, conic_opacity, acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, dcam, filter_var);
     } else {
         __shared__ float s_part[4][W2C_VALS];
         float dcam[3] = {0.f, 0.f, 0.f}, m[3] = {0.f, 0.f, 0.f};
         bool visible = i < N;
         if (visible && n_touched[i] == 0) { preprocess_bwd_zero_rows(i, g_means, g_scales_raw, g_rot_raw, g_opac_raw); visible = false; }
         if (visible) {
-            preprocess_bwd_one<AA, DEPTH>(i, N, means, scales_raw, rot_raw, f, rec, conic_opacity, acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, dcam);
+            preprocess_bwd_one<AA, DEPTH, FILTER3D>(i, N, means, scales_raw, rot_raw, f, rec, conic_opacity, acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, dcam, filter_var);
             m[0] = means[3 * size_t(i)]; m[1] = means[3 * size_t(i) + 1]; m[2] = means[3 * size_t(i) + 2];
         }
         float v[W2C_VALS];
@@ -351,6 +414,23 @@ __global__ void __launch_bounds__(256) fg_preprocess_bwd_kernel(
         if (threadIdx.x < W2C_VALS) w2c_partials[size_t(blockIdx.x) * W2C_VALS + threadIdx.x] = sum;
     }
 }
+
+#define LFS_FG_PREP_BWD_PARAMS \
+    const uint32_t N, const float* __restrict__ means, const float* __restrict__ scales_raw, const float* __restrict__ rot_raw, \
+    const Frame f, const GaussRec* __restrict__ rec, const float4* __restrict__ conic_opacity, \
+    const uint32_t* __restrict__ n_touched, const float* __restrict__ acc, float* __restrict__ g_means, float* __restrict__ g_scales_raw, float* __restrict__ g_rot_raw, \
+    float* __restrict__ g_opac_raw, float* __restrict__ densification_info, float* __restrict__ w2c_partials, const uint32_t* __restrict__ mode
+#define LFS_FG_PREP_BWD_ARGS N, means, scales_raw, rot_raw, f, rec, conic_opacity, n_touched, acc, g_means, g_scales_raw, g_rot_raw, g_opac_raw, densification_info, w2c_partials, mode
+template <bool W2C, bool AA, int DEPTH>
+__global__ void __launch_bounds__(256) fg_preprocess_bwd_kernel(LFS_FG_PREP_BWD_PARAMS) {
+    preprocess_bwd_body<W2C, AA, DEPTH, false>(LFS_FG_PREP_BWD_ARGS, nullptr);
+}
+template <bool W2C, bool AA, int DEPTH>
+__global__ void __launch_bounds__(256) fg_preprocess_bwd_f3d_kernel(LFS_FG_PREP_BWD_PARAMS, const float* __restrict__ filter_var) {
+    preprocess_bwd_body<W2C, AA, DEPTH, true>(LFS_FG_PREP_BWD_ARGS, filter_var);
+}
+#undef LFS_FG_PREP_BWD_PARAMS
+#undef LFS_FG_PREP_BWD_ARGS
 
 // one workgroup: the n_rows partial rows of fg_preprocess_bwd_kernel<true> -> grad_w2c [4,4], all 16 floats written (row 3 = 0; n_rows == 0 -> all zeros).
 // Thread t adds rows t, t + 256, ... in that order, then the same workgroup sum as above.
@@ -400,7 +480,7 @@ Frame make_frame(const lfs_fastgs_view& v) {
 // sh_rest / adam: the view's coefficients and no optimizer, or the optimizer-fused form's parameter; depth: with grad_depth 1 / 2, the kind the host remembers for
 // this workspace, 0 otherwise
 int launch_preprocess_bwd(const lfs_fastgs_view& v, const Frame& f, const PrimWs& w, const lfs_fastgs_view_backward_args& a, const float* sh_rest, const ShAdamArgs* adam,
-                          int depth, hipStream_t s) {
+                          int depth, const float* filter_var, hipStream_t s) {
     const uint32_t N = v.N;
     float* const w2c_partials = a.grad_w2c ? static_cast<float*>(a.w2c_workspace) : nullptr;
     {
@@ -412,9 +492,20 @@ int launch_preprocess_bwd(const lfs_fastgs_view& v, const Frame& f, const PrimWs
             {LFS_FG_PREP_BWD_PAIR(true, 0), LFS_FG_PREP_BWD_PAIR(false, 0)}, {LFS_FG_PREP_BWD_PAIR(true, 1), LFS_FG_PREP_BWD_PAIR(false, 1)},
             {LFS_FG_PREP_BWD_PAIR(true, 2), LFS_FG_PREP_BWD_PAIR(false, 2)}};
 #undef LFS_FG_PREP_BWD_PAIR
-        for (const auto kernel : kernels[depth][a.grad_w2c == nullptr])
-            hipLaunchKernelGGL(kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, v.means, v.scales_raw, v.rotations_raw, f, w.rec, w.conic_opacity, w.n_touched, w.acc,
-                               a.grad_means, a.grad_scales_raw, a.grad_rotations_raw, a.grad_opacities_raw, a.densification_info, w2c_partials, w.mode);
+#define LFS_FG_PREP_BWD_F3D_PAIR(W2C, DEPTH) {&fg_preprocess_bwd_f3d_kernel<W2C, false, DEPTH>, &fg_preprocess_bwd_f3d_kernel<W2C, true, DEPTH>}
+        static constexpr decltype(&fg_preprocess_bwd_f3d_kernel<false, false, 0>) kernels_f3d[3][2][2] = {   // the filtered forms, in the same order
+            {LFS_FG_PREP_BWD_F3D_PAIR(true, 0), LFS_FG_PREP_BWD_F3D_PAIR(false, 0)}, {LFS_FG_PREP_BWD_F3D_PAIR(true, 1), LFS_FG_PREP_BWD_F3D_PAIR(false, 1)},
+            {LFS_FG_PREP_BWD_F3D_PAIR(true, 2), LFS_FG_PREP_BWD_F3D_PAIR(false, 2)}};
+#undef LFS_FG_PREP_BWD_F3D_PAIR
+        if (filter_var != nullptr) {
+            for (const auto kernel : kernels_f3d[depth][a.grad_w2c == nullptr])
+                hipLaunchKernelGGL(kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, v.means, v.scales_raw, v.rotations_raw, f, w.rec, w.conic_opacity, w.n_touched, w.acc,
+                                   a.grad_means, a.grad_scales_raw, a.grad_rotations_raw, a.grad_opacities_raw, a.densification_info, w2c_partials, w.mode, filter_var);
+        } else {
+            for (const auto kernel : kernels[depth][a.grad_w2c == nullptr])
+                hipLaunchKernelGGL(kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, v.means, v.scales_raw, v.rotations_raw, f, w.rec, w.conic_opacity, w.n_touched, w.acc,
+                                   a.grad_means, a.grad_scales_raw, a.grad_rotations_raw, a.grad_opacities_raw, a.densification_info, w2c_partials, w.mode);
+        }
     }
     if (a.grad_w2c != nullptr) {
         const int rc = launch_w2c_reduce(N, w2c_partials, a.grad_w2c, s);
@@ -457,7 +548,7 @@ static DepthSlot g_depth_slots[DEPTH_SLOTS];
 static uint64_t g_depth_stamp = 0;
 static std::mutex g_depth_mutex;
 static void remember_flags(const void* ws, uint32_t flags) {
-    const bool depth = (flags & (MODE_DEPTH | MODE_INVDEPTH)) != 0;
+    const bool depth = (flags & (MODE_DEPTH | MODE_INVDEPTH | MODE_FILTER3D)) != 0;   // what takes an entry: a depth mode or the 3D filter
     std::lock_guard<std::mutex> lock(g_depth_mutex);
     DepthSlot* pick = &g_depth_slots[0];
     for (DepthSlot& m : g_depth_slots) {
@@ -502,7 +593,16 @@ extern "C" size_t lfs_fastgs_instance_workspace_bytes(uint32_t width, uint32_t h
 // bits 2 / 3 (LFS_FASTGS_DEPTH / LFS_FASTGS_INVDEPTH, exclusive): the depth forms of the kernel; the host remembers the flags by the workspace's address for the
 // render's depth plane and the backward's grad_depth (remember_flags).
 static_assert(sizeof(lfs_fastgs_view) == 136, "the ctypes mirror (capi.py) is laid out by hand");
+// filter_var (lfs_fastgs_view_ext::filter3d_var): the filtered forms (fg_preprocess_f3d_kernel); the workspace is remembered with the internal MODE_FILTER3D bit next to
+// its public flags.
+static int view_preprocess(const lfs_fastgs_view* view, uint32_t flags, const float* filter_var, int64_t* n_instances, lfs_stream_t stream);
 extern "C" int lfs_fastgs_view_preprocess(const lfs_fastgs_view* view, uint32_t flags, int64_t* n_instances, lfs_stream_t stream) {
+    return view_preprocess(view, flags, nullptr, n_instances, stream);
+}
+extern "C" int lfs_fastgs_view_preprocess_ex(const lfs_fastgs_view* view, uint32_t flags, const lfs_fastgs_view_ext* ext, int64_t* n_instances, lfs_stream_t stream) {
+    return view_preprocess(view, flags, ext ? ext->filter3d_var : nullptr, n_instances, stream);
+}
+static int view_preprocess(const lfs_fastgs_view* view, uint32_t flags, const float* filter_var, int64_t* n_instances, lfs_stream_t stream) {
     if (!view) return LFS_E_INVALID;
     const lfs_fastgs_view& v = *view;
     if (flags & ~uint32_t(LFS_FASTGS_ANTIALIASED | LFS_FASTGS_DEPTH | LFS_FASTGS_INVDEPTH)) return LFS_E_INVALID;
@@ -532,8 +632,16 @@ extern "C" int lfs_fastgs_view_preprocess(const lfs_fastgs_view* view, uint32_t 
             static constexpr decltype(&fgs::fg_preprocess_kernel<false, false, 0>) kernels[2][2][3] = {   // [no LDS][default mode][depth]: the code object's order
                 {LFS_FG_PREP_ROW(true, true), LFS_FG_PREP_ROW(true, false)}, {LFS_FG_PREP_ROW(false, true), LFS_FG_PREP_ROW(false, false)}};
 #undef LFS_FG_PREP_ROW
-            hipLaunchKernelGGL(kernels[!lds][!aa][depth], dim3(blocks), dim3(1024), lds ? size_t(T) * 4 : size_t(0), s, N, pb, v.means, v.scales_raw, v.rotations_raw,
-                               v.opacities_raw, f, w.rec, w.mean2d, w.conic_opacity, w.bounds, w.n_touched, w.depth_bits, w.totals, w.mode);
+#define LFS_FG_PREP_F3D_ROW(LDS, AA) {&fgs::fg_preprocess_f3d_kernel<LDS, AA, 0>, &fgs::fg_preprocess_f3d_kernel<LDS, AA, 1>, &fgs::fg_preprocess_f3d_kernel<LDS, AA, 2>}
+            static constexpr decltype(&fgs::fg_preprocess_f3d_kernel<false, false, 0>) kernels_f3d[2][2][3] = {   // the filtered forms, in the same order
+                {LFS_FG_PREP_F3D_ROW(true, true), LFS_FG_PREP_F3D_ROW(true, false)}, {LFS_FG_PREP_F3D_ROW(false, true), LFS_FG_PREP_F3D_ROW(false, false)}};
+#undef LFS_FG_PREP_F3D_ROW
+            if (filter_var != nullptr)
+                hipLaunchKernelGGL(kernels_f3d[!lds][!aa][depth], dim3(blocks), dim3(1024), lds ? size_t(T) * 4 : size_t(0), s, N, pb, v.means, v.scales_raw, v.rotations_raw,
+                                   v.opacities_raw, f, w.rec, w.mean2d, w.conic_opacity, w.bounds, w.n_touched, w.depth_bits, w.totals, w.mode, filter_var);
+            else
+                hipLaunchKernelGGL(kernels[!lds][!aa][depth], dim3(blocks), dim3(1024), lds ? size_t(T) * 4 : size_t(0), s, N, pb, v.means, v.scales_raw, v.rotations_raw,
+                                   v.opacities_raw, f, w.rec, w.mean2d, w.conic_opacity, w.bounds, w.n_touched, w.depth_bits, w.totals, w.mode);
         }
         hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, s, T, w.totals, w.offsets, n_instances);
     }
@@ -553,6 +661,6 @@ extern "C" int lfs_fastgs_view_preprocess(const lfs_fastgs_view* view, uint32_t 
         if (rc) return rc;
     }
     const int rc = (int)hipGetLastError();
-    if (rc == 0) fgs::remember_flags(v.primitive_workspace, flags);
+    if (rc == 0) fgs::remember_flags(v.primitive_workspace, flags | (filter_var != nullptr ? fgs::MODE_FILTER3D : 0u));
     return rc;
 }

@@ -25,6 +25,8 @@ constexpr float LOG2E = 1.4426950408889634f;
 constexpr uint32_t MODE_ANTIALIASED = 1u; // PrimWs::mode bit 0 (= LFS_FASTGS_ANTIALIASED of lfs_fastgs_view_preprocess)
 constexpr uint32_t MODE_DEPTH = 4u;       // bit 2 (= LFS_FASTGS_DEPTH): r2.w of every visible record = camera-space z
 constexpr uint32_t MODE_INVDEPTH = 8u;    // bit 3 (= LFS_FASTGS_INVDEPTH): r2.w = 1 / z
+constexpr uint32_t MODE_FILTER3D = 1u << 16; // internal (no public flag): filled by a preprocess with the 3D smoothing filter (lfs_fastgs_view_ext::filter3d_var);
+                                              // the opacity of the records is sigmoid(raw) * kappa [* rho] and r1.w = sigmoid(raw), as in the antialiased mode
 // the DEPTH template parameter of the per-primitive kernels: 0 none, 1 z, 2 1 / z
 constexpr uint32_t depth_mode_bits(int depth) { return depth == 1 ? MODE_DEPTH : depth == 2 ? MODE_INVDEPTH : 0u; }
 

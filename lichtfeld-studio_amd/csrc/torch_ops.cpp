@@ -547,7 +547,7 @@ FastgsForward fastgs_forward_impl(
     const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
     const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
     const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane, const uint32_t flags, const bool want_depth) {
+    const float center_y, const float near_plane, const float far_plane, const uint32_t flags, const bool want_depth, const torch::Tensor& filter3d_var = torch::Tensor()) {
     LFS_DEVICE_GUARD(means);
     LFS_CHECK_INPUT(means); LFS_CHECK_INPUT(scales_raw); LFS_CHECK_INPUT(rotations_raw); LFS_CHECK_INPUT(opacities_raw);
     LFS_CHECK_INPUT(sh_coefficients_0); LFS_CHECK_INPUT(sh_coefficients_rest);
@@ -559,6 +559,12 @@ FastgsForward fastgs_forward_impl(
     at::Tensor n_inst_dev = at::zeros({1}, means.options().dtype(at::kLong));
     const lfs_fastgs_view view = fastgs_view(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c_c, cam_c, active_sh_bases, width,
                                              height, focal_x, focal_y, center_x, center_y, near_plane, far_plane, prim);
+    if (filter3d_var.defined()) {   // the 3D smoothing filter: the _ex entry with the [N] variances (undefined: the entry every other mode has always called)
+        LFS_CHECK_INPUT(filter3d_var);
+        TORCH_CHECK(filter3d_var.numel() == (int64_t)N && filter3d_var.scalar_type() == at::kFloat, "filter3d_var must hold N floats");
+        const lfs_fastgs_view_ext ext{filter3d_var.data_ptr<float>()};
+        check_rc(lfs_fastgs_view_preprocess_ex(&view, flags, &ext, n_inst_dev.data_ptr<int64_t>(), cur_stream()), "lfs::fastgs_forward_wrapper_filter3d (preprocess)");
+    } else
     check_rc(lfs_fastgs_view_preprocess(&view, flags, n_inst_dev.data_ptr<int64_t>(), cur_stream()), "fast_gs::rasterization::forward (preprocess)");
     const int64_t n_instances = n_inst_dev.item<int64_t>(); // the host sync of forward.cu:114-117
     at::Tensor inst = at::empty({(int64_t)std::max<size_t>(256, lfs_fastgs_instance_workspace_bytes((uint32_t)width, (uint32_t)height, n_instances))}, bopt);
@@ -577,7 +583,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Te
     const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& sh_coefficients_rest,
     const torch::Tensor& per_primitive_buffers, const torch::Tensor& per_instance_buffers, const torch::Tensor& w2c, const torch::Tensor& cam_position,
     const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane, const int n_instances, const char* what) {
+    const float center_y, const float near_plane, const float far_plane, const int n_instances, const char* what, const torch::Tensor& filter3d_var = torch::Tensor()) {
     LFS_DEVICE_GUARD(means);
     const uint32_t N = (uint32_t)means.size(0), total_rest = (uint32_t)sh_coefficients_rest.size(1);
     const auto fopt = means.options().dtype(at::kFloat);
@@ -609,6 +615,12 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Te
     args.grad_opacities_raw = g_opac.data_ptr<float>(); args.grad_sh_coefficients_0 = g_sh0.data_ptr<float>();
     args.grad_sh_coefficients_rest = total_rest ? g_shr.data_ptr<float>() : nullptr;
     if (g_w2c.defined()) { args.grad_w2c = g_w2c.data_ptr<float>(); args.w2c_workspace = ws.data_ptr(); args.w2c_workspace_bytes = (size_t)ws.numel(); }
+    if (filter3d_var.defined()) {
+        LFS_CHECK_INPUT(filter3d_var);
+        TORCH_CHECK(filter3d_var.numel() == (int64_t)N && filter3d_var.scalar_type() == at::kFloat, "filter3d_var must hold N floats");
+        const lfs_fastgs_view_ext ext{filter3d_var.data_ptr<float>()};
+        check_rc(lfs_fastgs_view_backward_ex(&view, &args, &ext, cur_stream()), what);
+    } else
     check_rc(lfs_fastgs_view_backward(&view, &args, cur_stream()), what);
     return {g_means, g_scales, g_rot, g_opac, g_sh0, g_shr, g_w2c};
 }
@@ -624,6 +636,32 @@ lfs::fastgs_forward_wrapper_ex(
                                                 width, height, focal_x, focal_y, center_x, center_y, near_plane, far_plane, antialiased ? LFS_FASTGS_ANTIALIASED : 0u, false);
     at::Tensor none = at::empty({0}, means.options().dtype(at::kByte));
     return {f.image, f.alpha, f.prim, none, f.inst, none.clone(), 0, (int)f.n_instances, 0, 0, 0};
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int>
+lfs::fastgs_forward_wrapper_filter3d(
+    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
+    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
+    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
+    const float center_y, const float near_plane, const float far_plane, const bool antialiased, const torch::Tensor& filter3d_var) {
+    TORCH_CHECK(filter3d_var.defined(), "filter3d_var must hold N floats");
+    const FastgsForward f = fastgs_forward_impl(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c, cam_position, active_sh_bases,
+                                                width, height, focal_x, focal_y, center_x, center_y, near_plane, far_plane, antialiased ? LFS_FASTGS_ANTIALIASED : 0u, false,
+                                                filter3d_var);
+    at::Tensor none = at::empty({0}, means.options().dtype(at::kByte));
+    return {f.image, f.alpha, f.prim, none, f.inst, none.clone(), 0, (int)f.n_instances, 0, 0, 0};
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> lfs::fastgs_backward_wrapper_filter3d(
+    torch::Tensor& densification_info, const torch::Tensor& grad_image, const torch::Tensor& grad_alpha, const torch::Tensor& alpha,
+    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& sh_coefficients_rest,
+    const torch::Tensor& per_primitive_buffers, const torch::Tensor& per_instance_buffers, const torch::Tensor& w2c, const torch::Tensor& cam_position,
+    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
+    const float center_y, const float near_plane, const float far_plane, const int n_instances, const torch::Tensor& filter3d_var) {
+    TORCH_CHECK(filter3d_var.defined(), "filter3d_var must hold N floats");
+    return fastgs_backward_impl(densification_info, grad_image, grad_alpha, torch::Tensor(), alpha, means, scales_raw, rotations_raw, sh_coefficients_rest, per_primitive_buffers,
+                                per_instance_buffers, w2c, cam_position, active_sh_bases, width, height, focal_x, focal_y, center_x, center_y, near_plane, far_plane,
+                                n_instances, "lfs::fastgs_backward_wrapper_filter3d", filter3d_var);
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int> lfs::fastgs_forward_wrapper_depth(

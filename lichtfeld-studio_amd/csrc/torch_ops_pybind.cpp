@@ -78,6 +78,22 @@ PYBIND11_MODULE(_lfs_torch_ops, m) {
               return lfs::fastgs_backward_wrapper_depth(densification_info, grad_image, grad_alpha, grad_depth, alpha, means, scales_raw, rotations_raw, sh_rest, prim,
                                                         inst, w2c, cam_position, active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane, n_instances);
           });
+    m.def("fastgs_forward_wrapper_filter3d",
+          [](at::Tensor means, at::Tensor scales_raw, at::Tensor rotations_raw, at::Tensor opacities_raw, at::Tensor sh0, at::Tensor sh_rest, at::Tensor w2c,
+             at::Tensor cam_position, int active_sh_bases, int width, int height, float fx, float fy, float cx, float cy, float near_plane, float far_plane,
+             bool antialiased, at::Tensor filter3d_var) {
+              return lfs::fastgs_forward_wrapper_filter3d(means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest, w2c, cam_position,
+                                                          active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane, antialiased, filter3d_var);
+          });
+    m.def("fastgs_backward_wrapper_filter3d",
+          [](at::Tensor densification_info, at::Tensor grad_image, at::Tensor grad_alpha, at::Tensor alpha, at::Tensor means,
+             at::Tensor scales_raw, at::Tensor rotations_raw, at::Tensor sh_rest, at::Tensor prim, at::Tensor inst, at::Tensor w2c, at::Tensor cam_position,
+             int active_sh_bases, int width, int height, float fx, float fy, float cx, float cy, float near_plane, float far_plane, int n_instances,
+             at::Tensor filter3d_var) {
+              return lfs::fastgs_backward_wrapper_filter3d(densification_info, grad_image, grad_alpha, alpha, means, scales_raw, rotations_raw, sh_rest, prim,
+                                                           inst, w2c, cam_position, active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane, n_instances,
+                                                           filter3d_var);
+          });
     m.def("fastgs_backward_wrapper",
           [](at::Tensor densification_info, at::Tensor grad_image, at::Tensor grad_alpha, at::Tensor image, at::Tensor alpha, at::Tensor means,
              at::Tensor scales_raw, at::Tensor rotations_raw, at::Tensor sh_rest, at::Tensor prim, at::Tensor tile, at::Tensor inst, at::Tensor bucket,

@@ -49,21 +49,26 @@ class EvalMetrics:
 
 @torch.no_grad()
 def evaluate(model, cameras: List, images: List[torch.Tensor], iteration: int = 0, background: Optional[torch.Tensor] = None,
-             rasterizer: str = "fastgs", masks: Optional[List] = None, antialiased: bool = False) -> EvalMetrics:
+             rasterizer: str = "fastgs", masks: Optional[List] = None, antialiased: bool = False,
+             filter3d: Optional[torch.Tensor] = None) -> EvalMetrics:
     """cameras: rasterizer.Camera per validation view; images: the ground truth [3,H,W] in [0,1]. rasterizer="fastgs" is the reference's protocol
     (metrics.cpp:430 renders with fast_rasterize whatever was trained with); "gut" renders with the 3DGUT rasterizer instead - what a model trained with
     --gut was optimised for: 3DGUT has no screen-space dilation, the EWA renderer adds its 0.3-pixel low-pass to Gaussians the training shrank below a
     pixel (profiles/r04/scale_train_*: up to 13 dB between the two numbers on an MCMC model with noise injection).
     masks (parallel to images; None entries = unmasked views): the PSNR is the masked one (psnr(mask=...)). SSIM stays UNMASKED: its 11x11 window has no
     per-pixel form that a mask could weight without printing the mask's edge into the statistics.
-    antialiased: the fastgs renders run in the antialiased mode (fastgs.FastGSSettings.antialiased) - for a model trained with GutTrainer(antialiasing=True)."""
+    antialiased: the fastgs renders run in the antialiased mode (fastgs.FastGSSettings.antialiased) - for a model trained with GutTrainer(antialiasing=True).
+    filter3d: the [N] variances of the 3D smoothing filter the model was trained with (GutTrainer.update_filter3d(); fastgs.FastGSSettings.filter3d): the renders are
+    the filtered ones. A model whose parameters were baked (filter3d.bake) is evaluated without it."""
     from .fastgs import fast_rasterize
     from .rasterizer import rasterize
     if rasterizer not in ("fastgs", "gut"):
         raise ValueError("rasterizer must be 'fastgs' or 'gut'")
     if antialiased and rasterizer != "fastgs":
         raise ValueError("antialiased evaluation is wired into the fastgs rasterizer only")
-    render = (lambda c, m, b: fast_rasterize(c, m, b, antialiased=antialiased)) if rasterizer == "fastgs" else rasterize
+    if filter3d is not None and rasterizer != "fastgs":
+        raise ValueError("filter3d evaluation is wired into the fastgs rasterizer only")
+    render = (lambda c, m, b: fast_rasterize(c, m, b, antialiased=antialiased, filter3d=filter3d)) if rasterizer == "fastgs" else rasterize
     dev = model.means.device
     bg = background if background is not None else torch.zeros(3, device=dev)
     ps, ss = [], []

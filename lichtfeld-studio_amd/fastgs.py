@@ -14,7 +14,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from .capi import FastgsBackwardArgs, FastgsShRestAdam, FastgsView, LfsError, check, load_library, ptr, require_gpu, stream, workspace
+from .capi import FastgsBackwardArgs, FastgsShRestAdam, FastgsView, FastgsViewExt, LfsError, check, load_library, ptr, require_gpu, stream, workspace
 from .rasterizer import Camera, RenderMode, RenderOutput, SplatModel
 
 
@@ -32,11 +32,25 @@ class FastGSSettings:  # rasterization_api.h:12-24
     far_plane: float
     antialiased: bool = False   # opacity * sqrt(det(Sigma2d) / det(Sigma2d + 0.3 I)) (LFS_FASTGS_ANTIALIASED; the reference's OptimizationParameters::antialiasing)
     depth: str = "none"         # "depth" | "invdepth": the records also carry z | 1 / z (LFS_FASTGS_DEPTH | LFS_FASTGS_INVDEPTH) for forward_wrapper_depth
+    filter3d: Optional[torch.Tensor] = None   # [N] filter variances of the 3D smoothing filter (filter3d.compute_filter3d; lfs_fastgs_view_ext.filter3d_var): scales
+                                              # sqrt(s^2 + v), opacity sigmoid(raw) * prod s / s'. Forward and backward of one view take the same tensor. No gradient.
 
 
 ANTIALIASED = 1         # LFS_FASTGS_ANTIALIASED
 DEPTH_FLAGS = {"none": 0, "depth": 4, "invdepth": 8}   # LFS_FASTGS_DEPTH, LFS_FASTGS_INVDEPTH
 ASYNC_READBACK = True   # False: n_instances via a stream synchronisation (A/B timing)
+
+
+def _filter3d_operand(s: FastGSSettings, N: int, device) -> Optional[torch.Tensor]:
+    """the contiguous float32 [N] device tensor behind FastGSSettings.filter3d (None: the unfiltered entries are called, the code path of a build without the filter)"""
+    v = s.filter3d
+    if v is None:
+        return None
+    v = v.detach().reshape(-1).contiguous()
+    if v.numel() != N or v.dtype != torch.float32 or v.device != device:
+        raise LfsError(f"FastGSSettings.filter3d must be a float32 tensor of N = {N} elements on {device} (got {tuple(v.shape)}, {v.dtype}, {v.device})")
+    require_gpu(v)
+    return v
 
 
 def view_struct(s: FastGSSettings, means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest, w2c, cam_position, primitive_workspace) -> FastgsView:
@@ -80,7 +94,12 @@ def _forward(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0,
         raise LfsError(f"FastGSSettings.depth must be 'none', 'depth' or 'invdepth' (got {s.depth!r})")
     flags = (ANTIALIASED if s.antialiased else 0) | DEPTH_FLAGS[s.depth]
     view = view_struct(s, means, scales_raw, rotations_raw, opac, sh0, shr, w2c, cam_position, pws)
-    check(lib.lfs_fastgs_view_preprocess(C.byref(view), C.c_uint32(flags), ptr(n_inst_dev), stream()), "fastgs_view_preprocess")
+    f3d = _filter3d_operand(s, N, dev)
+    if f3d is None:
+        check(lib.lfs_fastgs_view_preprocess(C.byref(view), C.c_uint32(flags), ptr(n_inst_dev), stream()), "fastgs_view_preprocess")
+    else:
+        ext = FastgsViewExt(ptr(f3d))
+        check(lib.lfs_fastgs_view_preprocess_ex(C.byref(view), C.c_uint32(flags), C.byref(ext), ptr(n_inst_dev), stream()), "fastgs_view_preprocess_ex")
     # the one host sync (forward.cu:114-117 reads n_visible_primitives and n_instances): waits for the read-back event the library queued before
     # its SH kernel, so the GPU keeps working through the host round trip
     if ASYNC_READBACK:
@@ -153,6 +172,13 @@ def backward_wrapper(densification_info: Optional[torch.Tensor], grad_image, gra
     args = FastgsBackwardArgs(n_instances, ptr(instance_workspace), instance_workspace.numel(), ptr(grad_image), ptr(grad_alpha), ptr(alpha), ptr(grad_depth), ptr(dens),
                               ptr(g_means), ptr(g_scales), ptr(g_rot), ptr(g_opac), ptr(g_sh0), ptr(g_shr), ptr(grad_w2c), ptr(ws), ws.numel() if ws is not None else 0,
                               C.pointer(adam) if adam is not None else None)
+    f3d = _filter3d_operand(s, N, means.device)
+    if f3d is not None:
+        ext = FastgsViewExt(ptr(f3d))
+        check(lib.lfs_fastgs_view_backward_ex(C.byref(view), C.byref(args), C.byref(ext), stream()),
+              "fastgs_view_backward_ex (LFS_E_INVALID here also means: the forward of this workspace ran without FastGSSettings.filter3d, or more than 256 filtered or "
+              "depth-mode forwards were started since without their backward and it was forgotten)")
+        return g_means, g_scales, g_rot, g_opac, g_sh0, g_shr
     check(lib.lfs_fastgs_view_backward(C.byref(view), C.byref(args), stream()),
           "fastgs_view_backward" if grad_depth is None else
           "fastgs_view_backward with grad_depth (LFS_E_INVALID here also means: this workspace is not known as a depth-mode workspace - its forward ran without "
@@ -185,11 +211,11 @@ class FastGSRasterize(torch.autograd.Function):
 
 
 def fast_rasterize(camera: Camera, model: SplatModel, bg_color: torch.Tensor, densification_info: Optional[torch.Tensor] = None, antialiased: bool = False,
-                   render_mode: RenderMode = RenderMode.RGB, depth_kind: str = "depth") -> RenderOutput:
+                   render_mode: RenderMode = RenderMode.RGB, depth_kind: str = "depth", filter3d: Optional[torch.Tensor] = None) -> RenderOutput:
     """fast_rasterizer.cpp:12-68; antialiased: FastGSSettings.antialiased (an extension: the reference's fast_rasterize has no such argument).
     render_mode (the reference's RenderMode, which its EWA path ignores): D / RGB_D fill RenderOutput.depth [1,H,W] with the accumulated sum w_i d_i, ED / RGB_ED with
     that over alpha.clamp_min(1e-10) (rasterizer.py's rule); D / ED return image None (the colour is still rendered inside). depth_kind "depth": d = z,
-    "invdepth": d = 1 / z. RGB: everything as before."""
+    "invdepth": d = 1 / z. RGB: everything as before. filter3d: FastGSSettings.filter3d, the [N] variances of the 3D smoothing filter (no gradient flows into it)."""
     render_mode = RenderMode(render_mode)
     if depth_kind not in ("depth", "invdepth"):
         raise ValueError(f"depth_kind must be 'depth' or 'invdepth' (got {depth_kind!r})")
@@ -200,7 +226,7 @@ def fast_rasterize(camera: Camera, model: SplatModel, bg_color: torch.Tensor, de
     deg = model.get_active_sh_degree()
     settings = FastGSSettings(cam_position=(-(R.T @ t)).contiguous(), active_sh_bases=(deg + 1) ** 2, width=W, height=H,
                               focal_x=float(K[0, 0]), focal_y=float(K[1, 1]), center_x=float(K[0, 2]), center_y=float(K[1, 2]), near_plane=0.01, far_plane=1e10, antialiased=bool(antialiased),
-                              depth="none" if render_mode == RenderMode.RGB else depth_kind)
+                              depth="none" if render_mode == RenderMode.RGB else depth_kind, filter3d=filter3d)
     out = FastGSRasterize.apply(model.means, model.raw_scales, model.raw_quats, model.raw_opacities, model.sh0, model.shN, w2c, densification_info, settings)
     image, alpha = out[0], out[1]
     depth = None

@@ -90,7 +90,8 @@ class GutTrainer:
                  use_bilateral_grid: bool = False, bilateral_grid_dims=(16, 16, 8), bilateral_grid_lr: float = 2e-3, tv_loss_weight: float = 10.0,
                  sh_sharded: Optional[bool] = None, factored_sh: bool = False, one_call: bool = False, pose_optimization: str = "none", pose_lr: float = 1e-5,
                  enable_sparsity: bool = False, sparsify_steps: int = 15000, init_rho: float = 0.0005, prune_ratio: float = 0.6, sparsity_update_every: int = 50,
-                 mask_mode: str = "none", mask_alpha_weight: float = 1.0, antialiasing: bool = False, depth_loss: str = "none", depth_weight=(1.0, 0.01)):
+                 mask_mode: str = "none", mask_alpha_weight: float = 1.0, antialiasing: bool = False, depth_loss: str = "none", depth_weight=(1.0, 0.01),
+                 filter3d: bool = False, filter3d_every: int = 100, filter3d_variance: float = 0.2):
         """strategy: None (fixed set of Gaussians: the benchmark), "mcmc" (strategies.MCMC: relocation + growth + SGLD noise, with
         the scale / opacity regularisers of trainer.cpp:132-158) or "default" (ADC; needs densification_info, see strategies.py).
         `seed` seeds the strategy's generator: the same on every rank, so replicas densify identically.
@@ -108,6 +109,12 @@ class GutTrainer:
         on the fastgs rasterizer, whose backward takes an alpha gradient; the autograd form of the 3DGUT rasterizer as well).
         antialiasing (OptimizationParameters::antialiasing; DESIGN.md 8f): every fastgs render of the trainer runs in the antialiased mode (FastGSSettings.antialiased).
         fastgs rasterizer only.
+        filter3d (filter3d.py): the 3D smoothing filter of Mip-Splatting - every fastgs render of the trainer takes the per-Gaussian filter variance
+        computed over ALL training views (filter3d_variance: the paper's 0.2). It is recomputed before the first step, after every iteration in which the strategy
+        changed the model (an ADC refinement, an MCMC relocation or growth, the sparsity prune), and otherwise every filter3d_every iterations (the means move).
+        Every rank computes the same filter from the replicated means: no collective. Combines with antialiasing (together: Mip-Splatting), masks, the depth loss,
+        pose optimisation (the filter uses the stored cameras) and sparsity. fastgs rasterizer only. export_model() returns the raw parameters: bake them
+        (filter3d.bake) before writing a file for a viewer.
         depth_loss: "none" | "invdepth" | "depth" (DESIGN.md 8g): what train_step(depths=...) supervises - the accumulated inverse depth (the Inria trainer's
         convention: monocular depth, scale and offset fitted per image) or the accumulated depth of the view against a losses.PreparedDepth, by a masked L1 whose weight
         decays exponentially from depth_weight[0] (first iteration) to depth_weight[1] (iteration `iterations`) - the log-linear interpolation of the Inria trainer's
@@ -128,6 +135,17 @@ class GutTrainer:
             raise ValueError("antialiasing is not wired into the 3DGUT route (rasterizer='gut'): its fused and autograd steps render without the opacity compensation. "
                              "Use rasterizer='fastgs'.")
         self.antialiasing = bool(antialiasing)
+        if filter3d and rasterizer == "gut":
+            raise ValueError("filter3d is not wired into the 3DGUT route (rasterizer='gut'): its step forms render the unfiltered scales and opacities. "
+                             "Use rasterizer='fastgs'.")
+        if filter3d and int(filter3d_every) < 1:
+            raise ValueError("filter3d_every must be >= 1")
+        from .filter3d import Filter3dSchedule
+        self.filter3d, self.filter3d_variance = bool(filter3d), float(filter3d_variance)
+        self.filter3d_schedule = Filter3dSchedule(int(filter3d_every)) if filter3d else None
+        self.filter3d_var = None        # [N] float32: the filter of the model as it stands (None: off)
+        self.filter3d_computes = 0      # how many times it was computed (tests, tools)
+        self._f3d_cameras = None        # the packed training cameras, built once
         if mask_mode not in ("none", "ignore", "segment"):
             raise ValueError(f"Invalid mask mode: {mask_mode}")
         if mask_mode == "segment":
@@ -334,7 +352,24 @@ class GutTrainer:
             self._fg_settings[view] = st
         st.active_sh_bases = (self.model.get_active_sh_degree() + 1) ** 2
         st.depth = "none"   # (_train_step_fastgs switches a view with a depth target to the trainer's depth kind)
+        st.filter3d = self.filter3d_var
         return st
+
+    def update_filter3d(self, force: bool = False):
+        """Recompute the 3D smoothing filter when the schedule says so (or force) -> the [N] variances, None with filter3d off. Called at the start of every fastgs
+        step; evaluation code calls it to get the filter of the current model."""
+        if not self.filter3d:
+            return None
+        N = self.model.means.shape[0]
+        if force or self.filter3d_var is None or self.filter3d_var.shape[0] != N or self.filter3d_schedule.due():
+            from .filter3d import compute_filter3d, pack_cameras
+            if self._f3d_cameras is None:
+                sc = self.scene
+                self._f3d_cameras = pack_cameras(viewmats=sc.viewmats, Ks=sc.Ks, width=int(sc.width), height=int(sc.height), device=self.device)
+            self.filter3d_var = compute_filter3d(self.model.means, self._f3d_cameras, self.filter3d_variance)
+            self.filter3d_schedule.computed()
+            self.filter3d_computes += 1
+        return self.filter3d_var
 
     def depth_weight_at(self, iteration: int) -> float:
         """the depth loss weight of (1-based) iteration `iteration`: depth_weight[0] at the first, depth_weight[1] at iteration `iterations` and after, log-linear between"""
@@ -348,6 +383,7 @@ class GutTrainer:
         gradients straight into the flat bucket) -> all-reduce -> strategy.post_backward (ADC fed by the rasterizer's
         densification_info, or MCMC) -> fused Adam. Black background."""
         from .fastgs import render_and_backward as fg_step
+        self.update_filter3d()
         if self.bucket is None:
             self.bucket = lfs_dist.GradBucket(self.model.parameters(), deferred=self._deferred())
         params = self.model.parameters()
@@ -418,6 +454,9 @@ class GutTrainer:
         if self.pose_optimizer is not None:   # trainer.cpp:763-765: after the model's optimizer step
             self.pose_optimizer.step()
             self.pose_optimizer.zero_grad(set_to_none=True)
+        if self.filter3d:
+            changed = self.strategy is not None and not self._past_base() and self.strategy.is_refining(self.iteration)
+            self.filter3d_schedule.step_done(model_changed=changed or self.model.means.shape[0] != N)
         return self.loss_acc
 
     def _mask_of(self, k: int):

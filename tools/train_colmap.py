@@ -50,6 +50,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--mask-threshold", type=int, default=-1, help="binarise: mask byte >= N counts fully, below it not at all (default: keep soft values)")
     ap.add_argument("--mask-alpha-weight", type=float, default=1.0, help="weight of the opacity penalty of --mask-mode segment")
     ap.add_argument("--antialiasing", action="store_true", help="antialiased mode of the EWA rasterizer for training and --eval renders (the reference's antialiasing parameter)")
+    ap.add_argument("--filter3d", action="store_true", help="the 3D smoothing filter of Mip-Splatting (fastgs rasterizer): a per-Gaussian low-pass sized by the highest rate at which any "
+                    "training camera samples the Gaussian; training and --eval renders use it, and the saved PLY / SOG hold the BAKED scales and opacities, so any viewer "
+                    "renders what was trained (a baked file is not a resume point: training on from it would apply the filter twice)")
+    ap.add_argument("--filter3d-every", type=int, default=100, help="recompute the filter every N iterations (and after every refinement)")
+    ap.add_argument("--mip-splatting", action="store_true", help="--filter3d and --antialiasing together: the 3D smoothing filter and the 2D Mip filter")
     ap.add_argument("--depth-loss", default="none", choices=["none", "invdepth", "depth"],
                     help="depth-regularised training (fastgs rasterizer): L1 between the accumulated inverse depth (invdepth: monocular depth, the Inria convention) or depth of a view "
                          "and <data>/<depths folder>/<image stem>.npy (float32 [H,W]) or .png (16-bit greyscale, value / 65536). With --eval, every held-out render is then saved as "
@@ -64,6 +69,10 @@ def build_parser() -> argparse.ArgumentParser:
 
 def check_args(args) -> None:
     """the combinations the tool refuses, before anything is loaded"""
+    if args.mip_splatting:
+        args.filter3d = args.antialiasing = True
+    if args.filter3d and args.gut:
+        raise SystemExit("--filter3d is not wired into the 3DGUT route. Please disable the 3D filter or disable gut.")
     if args.antialiasing and args.gut:
         raise SystemExit("--antialiasing is not wired into the 3DGUT route. Please disable antialiasing or disable gut.")
     if args.depth_loss != "none" and args.gut:
@@ -117,8 +126,20 @@ def main():
                     scene_scale=scene_scale, rasterizer=rast, use_bilateral_grid=args.bilateral_grid, pose_optimization=args.pose_optimization,
                     enable_sparsity=args.enable_sparsity, sparsify_steps=args.sparsify_steps, init_rho=args.init_rho, prune_ratio=args.prune_ratio,
                     mask_mode=args.mask_mode, mask_alpha_weight=args.mask_alpha_weight, antialiasing=args.antialiasing,
-                    depth_loss=args.depth_loss, depth_weight=(args.depth_weight_init, args.depth_weight_final))
+                    depth_loss=args.depth_loss, depth_weight=(args.depth_weight_init, args.depth_weight_final),
+                    filter3d=args.filter3d, filter3d_every=args.filter3d_every)
     total = tr.total_iterations                                             # --iterations, plus the sparsification phase
+
+    def export():
+        """the model a file is written from: with --filter3d the filter of the CURRENT model folded into scales and opacities (filter3d.bake), the model itself otherwise"""
+        if not args.filter3d:
+            return tr.model
+        from lichtfeld_studio_amd import filter3d
+        from lichtfeld_studio_amd.rasterizer import SplatModel
+        m = tr.model
+        with torch.no_grad():
+            scales, opac = filter3d.bake(m, tr.update_filter3d(force=True))
+        return SplatModel(m.means.detach(), m.sh0.detach(), m.shN.detach(), scales, m.raw_quats.detach(), opac, m.max_sh_degree, m.active_sh_degree)
     os.makedirs(args.output_path, exist_ok=True)
     g = torch.Generator().manual_seed(0)
     val_set = None
@@ -142,15 +163,17 @@ def main():
         v = order.pop()
         tr.train_step([targets[v]], views=[v], masks=None if masks is None else [masks[v]], depths=None if depths is None else [depths[v]])
         if args.enable_sparsity and it + 1 == args.iterations:              # the model of the base run, before sparsification touches it
-            loader.save_ply(tr.model, os.path.join(args.output_path, f"splat_{args.iterations}.ply"))
+            loader.save_ply(export(), os.path.join(args.output_path, f"splat_{args.iterations}.ply"))
         if val_set is not None and (it + 1) % args.eval_every == 0:
             torch.cuda.synchronize(); te = time.time()
-            m = evaluate.evaluate(tr.model, val_set[0], val_set[1], it + 1, rasterizer=rast if args.gut else "fastgs", antialiased=args.antialiasing)
+            m = evaluate.evaluate(tr.model, val_set[0], val_set[1], it + 1, rasterizer=rast if args.gut else "fastgs", antialiased=args.antialiasing,
+                                  filter3d=tr.update_filter3d(force=True))
             # the same metric on 12 TRAINING views: a held-out PSNR that falls while this one holds is a generalisation gap (Gaussians fitted to the rays the training views
             # sample), both falling is an unstable optimisation
             tsel = list(range(0, len(ds), max(1, len(ds) // 12)))[:12]
             tcams = [tr.camera(v) for v in tsel]
-            mt = evaluate.evaluate(tr.model, tcams, [targets[v] for v in tsel], it + 1, rasterizer=rast if args.gut else "fastgs", antialiased=args.antialiasing)
+            mt = evaluate.evaluate(tr.model, tcams, [targets[v] for v in tsel], it + 1, rasterizer=rast if args.gut else "fastgs", antialiased=args.antialiasing,
+                                  filter3d=tr.update_filter3d(force=True))
             s3 = tr.model.raw_scales.detach()
             asp = (s3.max(-1).values - s3.min(-1).values).exp()
             # projected size of the SMALLEST axis of every Gaussian in pixels at the first training camera (focal length x scale / depth): the share below half a pixel
@@ -167,7 +190,7 @@ def main():
     torch.cuda.synchronize()
     t_train = time.time() - t0 - t_eval
     out = {"data": args.data_path, "images": len(ds), "size": [scene.width, scene.height], "iterations": total, "rasterizer": rast,
-           "strategy": args.strategy, "antialiasing": bool(args.antialiasing), "pose_optimization": args.pose_optimization, "gaussians": int(tr.model.means.shape[0]), "load_s": round(t_load, 1), "train_s": round(t_train, 1),
+           "strategy": args.strategy, "antialiasing": bool(args.antialiasing), "filter3d": bool(args.filter3d), "pose_optimization": args.pose_optimization, "gaussians": int(tr.model.means.shape[0]), "load_s": round(t_load, 1), "train_s": round(t_train, 1),
            "iters_per_s": round(total / max(t_train, 1e-9), 1)}
     if masks is not None:
         out.update(mask_mode=args.mask_mode, masked_views=sum(m is not None for m in masks))
@@ -185,7 +208,7 @@ def main():
             h, w = img.shape[1:]
             cameras.append(Camera(torch.from_numpy(loader.world_to_view(cam))[None].to(dev), torch.from_numpy(loader.intrinsics(cam, w, h))[None].to(dev), w, h))
             images.append(img)
-        m = evaluate.evaluate(tr.model, cameras, images, total, masks=val_masks, antialiased=args.antialiasing)
+        m = evaluate.evaluate(tr.model, cameras, images, total, masks=val_masks, antialiased=args.antialiasing, filter3d=tr.update_filter3d(force=True))
         out.update(psnr=round(m.psnr, 4), ssim=round(m.ssim, 5), val_images=m.n_images)
         if args.depth_loss != "none":   # the held-out renders and, beside each, its expected depth map (D / alpha; grey, scaled to the view's own range)
             from lichtfeld_studio_amd import fastgs
@@ -194,7 +217,8 @@ def main():
             os.makedirs(rdir, exist_ok=True)
             for k, cam in enumerate(cameras):
                 with torch.no_grad():
-                    r = fastgs.fast_rasterize(cam, tr.model, torch.zeros(3, device=dev), antialiased=args.antialiasing, render_mode=RenderMode.RGB_ED, depth_kind=args.depth_loss)
+                    r = fastgs.fast_rasterize(cam, tr.model, torch.zeros(3, device=dev), antialiased=args.antialiasing, render_mode=RenderMode.RGB_ED, depth_kind=args.depth_loss,
+                                              filter3d=tr.filter3d_var)
                 rgb = (r.image.clamp(0, 1) * 255.0 + 0.5).to(torch.uint8).permute(1, 2, 0).contiguous().cpu().numpy()
                 d = r.depth[0]
                 lo, hi = float(d[r.alpha[0] > 0.5].min()) if bool((r.alpha[0] > 0.5).any()) else 0.0, float(d.max())
@@ -208,11 +232,15 @@ def main():
     if curve:
         out["psnr_curve"] = curve
     ply = os.path.join(args.output_path, f"splat_{total}.ply")
-    loader.save_ply(tr.model, ply)
+    loader.save_ply(export(), ply)
     out["ply"] = ply
+    if args.filter3d:   # the file above holds the baked parameters (what a viewer renders); the raw ones - the state training would go on from - beside it
+        raw_ply = os.path.join(args.output_path, f"splat_{total}_unfiltered.ply")
+        loader.save_ply(tr.model, raw_ply)
+        out["ply_unfiltered"] = raw_ply
     if args.save_sog:
         sog_path = os.path.join(args.output_path, f"splat_{total}.sog")
-        loader.save_sog(tr.model, sog_path, iterations=args.sog_iterations, palette_size=args.sog_palette_size)
+        loader.save_sog(export(), sog_path, iterations=args.sog_iterations, palette_size=args.sog_palette_size)
         out.update(sog=sog_path, sog_bytes=os.path.getsize(sog_path), ply_bytes=os.path.getsize(ply))
     print(json.dumps(out), flush=True)
 
