@@ -301,6 +301,15 @@ typedef struct lfs_fastgs_view {
  * counts as a default-mode workspace. */
 #define LFS_FASTGS_DEPTH 4u
 #define LFS_FASTGS_INVDEPTH 8u
+/* Absolute screen-space gradients for densification (AbsGS, Ye et al. 2024; gsplat's absgrad). Combines with every flag above and with the 3D filter operand, and
+ * changes nothing in the preprocess, the render, the records, the workspace sizes or any gradient. A backward on a workspace filled with it, with densification_info
+ * != NULL, adds for every primitive i with n_touched != 0
+ *     densification_info[0][i] += 1,   densification_info[1][i] += sqrt((0.5 W Gx_i)^2 + (0.5 H Gy_i)^2),
+ * Gx_i = sum_p |gx_p|, Gy_i = sum_p |gy_p| over the pixels p the backward blends i into, (gx_p, gy_p) = conic_i . (hx, hy) that pixel's share of dL/dmean2d_i -
+ * the default mode's expression with the per-pixel absolute values summed instead of the signed ones, which cancel on a large Gaussian over fine texture.
+ * With densification_info == NULL the backward launches what it launches on a default workspace. Remembered with the workspace like the depth flags (the same 256
+ * entries). (Bit 4, value 16, stays undefined.) */
+#define LFS_FASTGS_ABSGRAD 32u
 LFS_API int lfs_fastgs_view_preprocess(const lfs_fastgs_view* view, uint32_t flags, int64_t* n_instances /* device */, lfs_stream_t stream);
 /* n_instances of this process's last lfs_fastgs_view_preprocess call, read back asynchronously: blocks until the 8-byte copy (queued before the SH kernel)
  * has landed, not until the stream is idle. Alternative to reading the device value with a stream synchronisation. */

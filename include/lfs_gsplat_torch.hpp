@@ -116,6 +116,14 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Te
     const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
     const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
     const float center_y, const float near_plane, const float far_plane, const bool antialiased);
+// Extension: absolute screen-space gradients for densification (LFS_FASTGS_ABSGRAD; AbsGS / gsplat's absgrad). The forward returns what fastgs_forward_wrapper_ex returns, bit for
+// bit; the per_primitive_buffers remember the mode, and fast_gs::rasterization::backward_wrapper (or the depth backward) on them accumulates the absolute-gradient
+// norm into a defined densification_info. Every gradient is the default mode's.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int> fastgs_forward_wrapper_absgrad(
+    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
+    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
+    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
+    const float center_y, const float near_plane, const float far_plane, const bool antialiased, const bool absgrad);
 // Extension: the depth modes (the depth plane of lfs_fastgs_view_render / grad_depth of lfs_fastgs_view_backward; LFS_FASTGS_DEPTH, LFS_FASTGS_INVDEPTH). Forward: inverse_depth false blends the
 // camera-space z of every Gaussian, true its reciprocal; -> (image [3,H,W], alpha [1,H,W], depth [1,H,W] = the ACCUMULATED sum w_i d_i, per_primitive_buffers,
 // per_instance_buffers, n_instances). Backward: fast_gs::rasterization::backward_wrapper with grad_depth [1,H,W]; the 7th element is grad_w2c when w2c requires grad.

@@ -17,7 +17,7 @@ namespace fgs {
 int launch_scatter(uint32_t N, const Frame& f, const PrimWs& w, int64_t* keys, hipStream_t s);
 Frame make_frame(const lfs_fastgs_view& v);
 int launch_preprocess_bwd(const lfs_fastgs_view& v, const Frame& f, const PrimWs& w, const lfs_fastgs_view_backward_args& a, const float* sh_rest, const ShAdamArgs* adam,
-                          int depth, const float* filter_var, hipStream_t s);
+                          int depth, const float* filter_var, bool absgrad, hipStream_t s);
 uint32_t remembered_flags(const void* primitive_workspace);
 size_t w2c_workspace_bytes(uint32_t N);
 int launch_w2c_reduce(uint32_t N, const float* w2c_partials, float* grad_w2c, hipStream_t s);
@@ -158,14 +158,20 @@ __global__ void __launch_bounds__(64) fg_blend_fwd_kernel(
 // the deterministic mode (lfs_set_debug_flags bit 4, as the 3DGUT backward's: wave_sum16_atomic in lfs_raster_common.cuh), fg_det_resolve_kernel turns the sums back into floats.
 // DEPTH (lfs_fastgs_view_backward with grad_depth): depth is a fourth blended channel - cv = c . g_image + r2.w g_depth feeds dL/dalpha and the colour-behind recurrence - and slot 9
 // of the row takes sum w g_depth = dL/dd; the reduction carries ten values instead of nine (wave_sum9_atomic_lds<ACC, 10>), through the same block and atomic.
-template <int ACC, bool DEPTH>
-__global__ void __launch_bounds__(64) fg_blend_bwd_kernel(
-    const uint32_t gw, const uint32_t gh, const uint32_t width, const uint32_t height,
-    const GaussRec* __restrict__ recs, const int32_t* __restrict__ offsets, const int32_t* __restrict__ cell_count, const int2* __restrict__ cell_list,
-    const float* __restrict__ alpha_map, const int32_t* __restrict__ n_contrib, const float* __restrict__ g_image, const float* __restrict__ g_alpha,
-    float* __restrict__ acc, unsigned long long* __restrict__ det64, const float* __restrict__ g_depth) {
+// ABS (a backward with densification_info on a workspace filled with LFS_FASTGS_ABSGRAD; AbsGS, Ye et al. 2024): slots 10 / 11 of the row take sum |k gx_p|, sum |k gy_p| over the
+// same instances, (gx_p, gy_p) = conic . (hx, hy) this pixel's share of dL/dmean2d and k = 0.5 log2(e) the scale the record's conic carries (fg_densify_abs_kernel applies 1 / k):
+// twelve values through the same block and atomic (wave_sum9_atomic_lds<ACC, 12>); without DEPTH the value for slot 9 is a zero. Slots 0 .. 9 are computed exactly as in the
+// default form. The kernels below the body are its ABS = false / true wrappers under separate names: the default forms keep their names and registers.
+#define LFS_FG_BLEND_BWD_PARAMS \
+    const uint32_t gw, const uint32_t gh, const uint32_t width, const uint32_t height, \
+    const GaussRec* __restrict__ recs, const int32_t* __restrict__ offsets, const int32_t* __restrict__ cell_count, const int2* __restrict__ cell_list, \
+    const float* __restrict__ alpha_map, const int32_t* __restrict__ n_contrib, const float* __restrict__ g_image, const float* __restrict__ g_alpha, \
+    float* __restrict__ acc, unsigned long long* __restrict__ det64, const float* __restrict__ g_depth
+#define LFS_FG_BLEND_BWD_ARGS gw, gh, width, height, recs, offsets, cell_count, cell_list, alpha_map, n_contrib, g_image, g_alpha, acc, det64, g_depth
+template <int ACC, bool DEPTH, bool ABS>
+LFS_DI void blend_bwd_body(LFS_FG_BLEND_BWD_PARAMS) {
     const uint32_t total_tiles = gw * gh;
-    constexpr int NV = DEPTH ? 10 : 9;
+    constexpr int NV = ABS ? 12 : DEPTH ? 10 : 9;
     __shared__ __attribute__((aligned(16))) float s_red[red_n_scratch_floats(NV)]; // this wavefront's transpose block (wave_sum9_atomic_lds)
     float* const red_scratch = s_red;
     const CellCtx cc = cell_ctx(total_tiles, total_tiles, gw, TILE, WPT, 1);
@@ -214,7 +220,13 @@ __global__ void __launch_bounds__(64) fg_blend_bwd_kernel(
         // accumulator row: {sum hx, sum hy, sum hx dx, sum hx dy | sum hy dy, dc.r, dc.g, dc.b | sum alpha dL/dalpha}
         //   dL/dmean2d = conic . (sum hx, sum hy), dL/dconic = 0.5 (sum hx dx, sum hx dy, sum hy dy)   (fastgs_prep.hip); depth form: | sum w g_depth}
         float* row = acc + size_t(e.x) * ACC_STRIDE;
-        if constexpr (DEPTH) {
+        if constexpr (ABS) {
+            // |k gx_p| = |aD| |kA dx + kB dy|, |k gy_p| = |aD| |kB dx + kC dy| (kB = r0.w / 2): aD = 0 masks both like every other sum
+            const float hb = 0.5f * rec.r0.w;
+            const float mx = __builtin_fmaf(rec.r0.z, f.dx, hb * f.dy), my = __builtin_fmaf(rec.r1.x, f.dy, hb * f.dx);
+            const float v[12] = {hx, hy, hx * f.dx, hx * f.dy, hy * f.dy, w * gc0, w * gc1, w * gc2, aD, DEPTH ? w * gd : 0.f, fabsf(aD) * fabsf(mx), fabsf(aD) * fabsf(my)};
+            wave_sum9_atomic_lds<ACC, 12>(v, row, lane, red_scratch, ACC == 2 ? det64 + size_t(e.x) * ACC_STRIDE : nullptr);
+        } else if constexpr (DEPTH) {
             const float v[10] = {hx, hy, hx * f.dx, hx * f.dy, hy * f.dy, w * gc0, w * gc1, w * gc2, aD, w * gd};
             wave_sum9_atomic_lds<ACC, 10>(v, row, lane, red_scratch, ACC == 2 ? det64 + size_t(e.x) * ACC_STRIDE : nullptr);
         } else {
@@ -224,6 +236,12 @@ __global__ void __launch_bounds__(64) fg_blend_bwd_kernel(
     };
     walk_cell_list<-1>(cl, recs, lo - 1, lo, eval, []() { return true; });
 }
+template <int ACC, bool DEPTH>
+__global__ void __launch_bounds__(64) fg_blend_bwd_kernel(LFS_FG_BLEND_BWD_PARAMS) { blend_bwd_body<ACC, DEPTH, false>(LFS_FG_BLEND_BWD_ARGS); }
+template <int ACC, bool DEPTH>
+__global__ void __launch_bounds__(64) fg_blend_bwd_abs_kernel(LFS_FG_BLEND_BWD_PARAMS) { blend_bwd_body<ACC, DEPTH, true>(LFS_FG_BLEND_BWD_ARGS); }
+#undef LFS_FG_BLEND_BWD_PARAMS
+#undef LFS_FG_BLEND_BWD_ARGS
 
 // deterministic mode, after pass 2: acc[i] = fixed-point sum * 2^(e - 40), e from the pass-1 maximum that acc[i] still holds as bits (the slots no form writes hold 0 and stay 0)
 __global__ void __launch_bounds__(256) fg_det_resolve_kernel(const size_t n, float* __restrict__ acc, const unsigned long long* __restrict__ det64) {
@@ -333,6 +351,8 @@ static int view_backward(const lfs_fastgs_view* view, const lfs_fastgs_view_back
         adam = &adam_args;
         sh_rest = a.adam->sh_coefficients_rest;
     }
+    // the abs form (LFS_FASTGS_ABSGRAD): only where its two sums have a reader; without densification_info the call launches what a default workspace's does
+    const bool absgrad = a.densification_info != nullptr && v.primitive_workspace && (fgs::remembered_flags(v.primitive_workspace) & LFS_FASTGS_ABSGRAD) != 0u;
     int depth = 0;   // with grad_depth: the workspace's depth kind
     if (a.grad_depth) {
         if (!v.primitive_workspace) return LFS_E_INVALID;
@@ -371,8 +391,9 @@ static int view_backward(const lfs_fastgs_view* view, const lfs_fastgs_view_back
     if (a.n_instances > 0 && !keep_acc) {
         lfs::ProfScope prof("fastgs_blend_bwd", s);
         const uint32_t wgrid = cell_grid_blocks(uint64_t(T) * fgs::WPT, fgs::WPT);
-#define LFS_FG_BWD_D(ACC, DEPTH) hipLaunchKernelGGL((fgs::fg_blend_bwd_kernel<ACC, DEPTH>), dim3(wgrid), dim3(64), 0, s, f.gw, f.gh, v.width, v.height, w.rec, w.offsets, iw.cell_count, \
-                                                   iw.cell_list, a.alpha, w.n_contrib, a.grad_image, a.grad_alpha, w.acc, w.det64, a.grad_depth)
+#define LFS_FG_BWD_K(KERNEL, ACC, DEPTH) hipLaunchKernelGGL((fgs::KERNEL<ACC, DEPTH>), dim3(wgrid), dim3(64), 0, s, f.gw, f.gh, v.width, v.height, w.rec, w.offsets, iw.cell_count, \
+                                                           iw.cell_list, a.alpha, w.n_contrib, a.grad_image, a.grad_alpha, w.acc, w.det64, a.grad_depth)
+#define LFS_FG_BWD_D(ACC, DEPTH) do { if (absgrad) LFS_FG_BWD_K(fg_blend_bwd_abs_kernel, ACC, DEPTH); else LFS_FG_BWD_K(fg_blend_bwd_kernel, ACC, DEPTH); } while (0)
 #define LFS_FG_BWD(ACC) do { if (a.grad_depth) LFS_FG_BWD_D(ACC, true); else LFS_FG_BWD_D(ACC, false); } while (0)
         if (det) { // pass 1: per-slot maxima of |total| (integer atomicMax), pass 2: 64-bit fixed-point sums, then back to float
             const size_t n_acc = ACC_STRIDE * size_t(N);
@@ -383,6 +404,7 @@ static int view_backward(const lfs_fastgs_view* view, const lfs_fastgs_view_back
         } else LFS_FG_BWD(0);
 #undef LFS_FG_BWD
 #undef LFS_FG_BWD_D
+#undef LFS_FG_BWD_K
     }
-    return fgs::launch_preprocess_bwd(v, f, w, a, sh_rest, adam, depth, filter_var, s);
+    return fgs::launch_preprocess_bwd(v, f, w, a, sh_rest, adam, depth, filter_var, absgrad, s);
 }

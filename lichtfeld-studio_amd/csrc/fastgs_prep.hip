@@ -448,6 +448,23 @@ __global__ void __launch_bounds__(256) fg_w2c_reduce_kernel(const uint32_t n_row
     if (threadIdx.x < 16) grad_w2c[threadIdx.x] = threadIdx.x < W2C_VALS ? sum : 0.f;
 }
 
+// densification_info of an absgrad backward (LFS_FASTGS_ABSGRAD): the per-primitive backward above ran with densification_info = nullptr, this kernel makes the two entries from
+// slots 10 / 11 of the row (sum |k gx_p|, sum |k gy_p| of fg_blend_bwd_abs_kernel, k = 0.5 log2(e)) - the expression of preprocess_bwd_one with the |.|-sums in place of dm2.
+// One thread per Gaussian, whatever the antialiasing / depth / filter mode; the workspace's mode word must carry the bit (as the depth and filter forms check theirs).
+__global__ void __launch_bounds__(256) fg_densify_abs_kernel(const uint32_t N, const uint32_t width, const uint32_t height, const uint32_t* __restrict__ n_touched,
+                                                             const float* __restrict__ acc, float* __restrict__ densification_info, const uint32_t* __restrict__ mode) {
+    if ((*mode & MODE_ABSGRAD) == 0u) return;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N || n_touched[i] == 0) return;
+    const float2 G = *reinterpret_cast<const float2*>(acc + size_t(i) * ACC_STRIDE + 10);
+    constexpr float K_RCP = 2.0f / LOG2E;
+    const float gx = (G.x * K_RCP) * 0.5f * float(width), gy = (G.y * K_RCP) * 0.5f * float(height);
+    densification_info[i] += 1.0f;
+    densification_info[size_t(N) + i] += sqrtf(gx * gx + gy * gy);
+}
+// the absgrad bit of the mode word: the preprocess kernels write the word from their template parameters, which know nothing of it (it changes nothing in them)
+__global__ void fg_mode_or_kernel(uint32_t* __restrict__ mode, const uint32_t bits) { *mode |= bits; }
+
 static inline uint32_t per_block_for(uint32_t N) {
     size_t pb = (size_t(N) + 511) / 512;
     if (pb < 1024) pb = 1024;
@@ -480,9 +497,10 @@ Frame make_frame(const lfs_fastgs_view& v) {
 // sh_rest / adam: the view's coefficients and no optimizer, or the optimizer-fused form's parameter; depth: with grad_depth 1 / 2, the kind the host remembers for
 // this workspace, 0 otherwise
 int launch_preprocess_bwd(const lfs_fastgs_view& v, const Frame& f, const PrimWs& w, const lfs_fastgs_view_backward_args& a, const float* sh_rest, const ShAdamArgs* adam,
-                          int depth, const float* filter_var, hipStream_t s) {
+                          int depth, const float* filter_var, bool absgrad, hipStream_t s) {
     const uint32_t N = v.N;
     float* const w2c_partials = a.grad_w2c ? static_cast<float*>(a.w2c_workspace) : nullptr;
+    float* const densification_info = absgrad ? nullptr : a.densification_info;   // absgrad: fg_densify_abs_kernel below writes it
     {
         // the mode of the forward that filled this workspace is a word IN the workspace, which the host does not read: both AA instantiations are queued, one returns
         // at once. (depth, w2c) pick the pair on the host. (The table lists the kernels in the order the code object has always had them: with W2C first.)
@@ -500,12 +518,16 @@ int launch_preprocess_bwd(const lfs_fastgs_view& v, const Frame& f, const PrimWs
         if (filter_var != nullptr) {
             for (const auto kernel : kernels_f3d[depth][a.grad_w2c == nullptr])
                 hipLaunchKernelGGL(kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, v.means, v.scales_raw, v.rotations_raw, f, w.rec, w.conic_opacity, w.n_touched, w.acc,
-                                   a.grad_means, a.grad_scales_raw, a.grad_rotations_raw, a.grad_opacities_raw, a.densification_info, w2c_partials, w.mode, filter_var);
+                                   a.grad_means, a.grad_scales_raw, a.grad_rotations_raw, a.grad_opacities_raw, densification_info, w2c_partials, w.mode, filter_var);
         } else {
             for (const auto kernel : kernels[depth][a.grad_w2c == nullptr])
                 hipLaunchKernelGGL(kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, v.means, v.scales_raw, v.rotations_raw, f, w.rec, w.conic_opacity, w.n_touched, w.acc,
-                                   a.grad_means, a.grad_scales_raw, a.grad_rotations_raw, a.grad_opacities_raw, a.densification_info, w2c_partials, w.mode);
+                                   a.grad_means, a.grad_scales_raw, a.grad_rotations_raw, a.grad_opacities_raw, densification_info, w2c_partials, w.mode);
         }
+    }
+    if (absgrad) {
+        lfs::ProfScope prof("fastgs_densify_abs", s);
+        hipLaunchKernelGGL(fg_densify_abs_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, f.width, f.height, w.n_touched, w.acc, a.densification_info, w.mode);
     }
     if (a.grad_w2c != nullptr) {
         const int rc = launch_w2c_reduce(N, w2c_partials, a.grad_w2c, s);
@@ -548,7 +570,7 @@ static DepthSlot g_depth_slots[DEPTH_SLOTS];
 static uint64_t g_depth_stamp = 0;
 static std::mutex g_depth_mutex;
 static void remember_flags(const void* ws, uint32_t flags) {
-    const bool depth = (flags & (MODE_DEPTH | MODE_INVDEPTH | MODE_FILTER3D)) != 0;   // what takes an entry: a depth mode or the 3D filter
+    const bool depth = (flags & (MODE_DEPTH | MODE_INVDEPTH | MODE_FILTER3D | MODE_ABSGRAD)) != 0;   // what takes an entry: a depth mode, the 3D filter or absgrad
     std::lock_guard<std::mutex> lock(g_depth_mutex);
     DepthSlot* pick = &g_depth_slots[0];
     for (DepthSlot& m : g_depth_slots) {
@@ -593,6 +615,7 @@ extern "C" size_t lfs_fastgs_instance_workspace_bytes(uint32_t width, uint32_t h
 // bits 2 / 3 (LFS_FASTGS_DEPTH / LFS_FASTGS_INVDEPTH, exclusive): the depth forms of the kernel; the host remembers the flags by the workspace's address for the
 // render's depth plane and the backward's grad_depth (remember_flags).
 static_assert(sizeof(lfs_fastgs_view) == 136, "the ctypes mirror (capi.py) is laid out by hand");
+// bit 5 (LFS_FASTGS_ABSGRAD): nothing in this stage changes; the bit is OR-ed into the mode word and remembered on the host, where the backward picks its abs form by it.
 // filter_var (lfs_fastgs_view_ext::filter3d_var): the filtered forms (fg_preprocess_f3d_kernel); the workspace is remembered with the internal MODE_FILTER3D bit next to
 // its public flags.
 static int view_preprocess(const lfs_fastgs_view* view, uint32_t flags, const float* filter_var, int64_t* n_instances, lfs_stream_t stream);
@@ -605,9 +628,10 @@ extern "C" int lfs_fastgs_view_preprocess_ex(const lfs_fastgs_view* view, uint32
 static int view_preprocess(const lfs_fastgs_view* view, uint32_t flags, const float* filter_var, int64_t* n_instances, lfs_stream_t stream) {
     if (!view) return LFS_E_INVALID;
     const lfs_fastgs_view& v = *view;
-    if (flags & ~uint32_t(LFS_FASTGS_ANTIALIASED | LFS_FASTGS_DEPTH | LFS_FASTGS_INVDEPTH)) return LFS_E_INVALID;
+    if (flags & ~uint32_t(LFS_FASTGS_ANTIALIASED | LFS_FASTGS_DEPTH | LFS_FASTGS_INVDEPTH | LFS_FASTGS_ABSGRAD)) return LFS_E_INVALID;
     if ((flags & LFS_FASTGS_DEPTH) && (flags & LFS_FASTGS_INVDEPTH)) return LFS_E_INVALID;
-    static_assert(LFS_FASTGS_ANTIALIASED == fgs::MODE_ANTIALIASED && LFS_FASTGS_DEPTH == fgs::MODE_DEPTH && LFS_FASTGS_INVDEPTH == fgs::MODE_INVDEPTH, "the mode word holds the flags");
+    static_assert(LFS_FASTGS_ANTIALIASED == fgs::MODE_ANTIALIASED && LFS_FASTGS_DEPTH == fgs::MODE_DEPTH && LFS_FASTGS_INVDEPTH == fgs::MODE_INVDEPTH &&
+                  LFS_FASTGS_ABSGRAD == fgs::MODE_ABSGRAD, "the mode word holds the flags");
     const bool aa = (flags & LFS_FASTGS_ANTIALIASED) != 0;
     const int depth = (flags & LFS_FASTGS_DEPTH) ? 1 : (flags & LFS_FASTGS_INVDEPTH) ? 2 : 0;
     const uint32_t N = v.N;
@@ -643,6 +667,7 @@ static int view_preprocess(const lfs_fastgs_view* view, uint32_t flags, const fl
                 hipLaunchKernelGGL(kernels[!lds][!aa][depth], dim3(blocks), dim3(1024), lds ? size_t(T) * 4 : size_t(0), s, N, pb, v.means, v.scales_raw, v.rotations_raw,
                                    v.opacities_raw, f, w.rec, w.mean2d, w.conic_opacity, w.bounds, w.n_touched, w.depth_bits, w.totals, w.mode);
         }
+        if (N > 0 && (flags & LFS_FASTGS_ABSGRAD)) hipLaunchKernelGGL(fgs::fg_mode_or_kernel, dim3(1), dim3(1), 0, s, w.mode, fgs::MODE_ABSGRAD);
         hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, s, T, w.totals, w.offsets, n_instances);
     }
     // The host needs n_instances to size the instance workspace (the reference syncs here, forward.cu:114-117). Queue the read-back BEFORE the SH

@@ -25,6 +25,7 @@ constexpr float LOG2E = 1.4426950408889634f;
 constexpr uint32_t MODE_ANTIALIASED = 1u; // PrimWs::mode bit 0 (= LFS_FASTGS_ANTIALIASED of lfs_fastgs_view_preprocess)
 constexpr uint32_t MODE_DEPTH = 4u;       // bit 2 (= LFS_FASTGS_DEPTH): r2.w of every visible record = camera-space z
 constexpr uint32_t MODE_INVDEPTH = 8u;    // bit 3 (= LFS_FASTGS_INVDEPTH): r2.w = 1 / z
+constexpr uint32_t MODE_ABSGRAD = 32u;    // bit 5 (= LFS_FASTGS_ABSGRAD): a backward with densification_info runs the abs form of the blend backward + fg_densify_abs_kernel
 constexpr uint32_t MODE_FILTER3D = 1u << 16; // internal (no public flag): filled by a preprocess with the 3D smoothing filter (lfs_fastgs_view_ext::filter3d_var);
                                               // the opacity of the records is sigmoid(raw) * kappa [* rho] and r1.w = sigmoid(raw), as in the antialiased mode
 // the DEPTH template parameter of the per-primitive kernels: 0 none, 1 z, 2 1 / z
@@ -89,6 +90,6 @@ inline InstWs inst_ws(void* base, uint32_t width, uint32_t height, uint64_t n_in
 
 // accumulator row of the blend backward (16 floats per primitive, one 64-B line):
 //   0,1 sum h (dx, dy) | 2,3,4 sum h (dx dx, dx dy, dy dy), h = -alpha dL/dalpha | 5,6,7 dL/d(clamped colour) | 8 sum alpha dL/dalpha |
-//   9 dL/dd = sum w g_depth (depth form of the backward only; 0 otherwise) | 10..15 unused
+//   9 dL/dd = sum w g_depth (depth form of the backward only; 0 otherwise) | 10,11 sum |k gx_p|, sum |k gy_p| (abs form only; 0 otherwise) | 12..15 unused
 } // namespace fgs
 } // namespace lfs

@@ -453,6 +453,8 @@ LFS_DI void wave_sum16_atomic_quad(const v2f (&V)[8], float* __restrict__ dst /*
 // fastgs_blend_bwd 0.452 - 0.457 -> 0.391 - 0.395 ms (profiles/r03/fastgs_blend_bwd_lds_reduce_ab.txt).
 // NV = 10: the depth form of that backward (slot 9 = sum w g_depth) - one more store, one more live column, the same reads, swaps and atomic instruction;
 // its row-major block takes stride 11 (odd again). NV = 9 is the code it always was.
+// NV = 12: the abs form of that backward (slots 10 / 11 = sum |k gx|, sum |k gy|, fastgs_blend.hip) - three more stores (the caller's v[9] is the depth sum or a zero, so
+// every row a live lane reads was written), three more live columns; row-major stride 13.
 constexpr int red_n_stride(int nv) { return nv | 1; }
 constexpr int red_n_scratch_floats(int nv) { return LFS_RED_ADDTID ? 16 * RED_ROW : 64 * red_n_stride(nv); } // per wavefront (value-major form: rows NV..15 are read by the dropped lanes, never written)
 constexpr int RED9_SCRATCH_FLOATS = red_n_scratch_floats(9);
@@ -460,7 +462,7 @@ constexpr int RED9_SCRATCH_FLOATS = red_n_scratch_floats(9);
 template <int ACC = 0, int NV = 9>
 LFS_DI void wave_sum9_atomic_lds(const float (&v)[NV], float* __restrict__ dst, const uint32_t lane, float* __restrict__ scratch /* this wavefront's [red_n_scratch_floats(NV)] */,
                                  unsigned long long* __restrict__ det64 = nullptr) {
-    static_assert(NV == 9 || NV == 10, "nine sums, or ten in the depth form");
+    static_assert(NV == 9 || NV == 10 || NV == 12, "nine sums, ten in the depth form, twelve in the abs forms");
     float c[16];
 #if LFS_RED_ADDTID && !defined(LFS_EMULATE)
     {   // value-major block through ds_write_addtid_b32 / ds_read_b128 (LFS_RED_ADDTID above)
@@ -468,7 +470,7 @@ LFS_DI void wave_sum9_atomic_lds(const float (&v)[NV], float* __restrict__ dst, 
         // M0 is a register the compiler manages itself (LLVM does not promise to honour an "m0" clobber): the block saves it, sets it, and puts it back - it leaves no
         // trace in M0, so nothing depends on how the compiler places its own M0 initialisations around the asm. (s_nop: one wait state between the SALU write
         // of M0 and an add-TID LDS instruction; the stores have read M0 when they issue, so the restore needs none.)
-        // ONE text for both forms: the nine stores every form has, then TENTH - nothing for NV = 9, the store into row 9 for NV = 10 - between the same M0 frame.
+        // ONE text for all forms: the nine stores every form has, then TENTH - nothing for NV = 9, the store into row 9 for NV = 10, into rows 9 .. 11 for NV = 12 - between the same M0 frame.
 #define LFS_RED9_ASM(TENTH) "s_mov_b32 %[sv], m0\n\ts_mov_b32 m0, %[base]\n\ts_nop 0\n\t" \
                      "ds_write_addtid_b32 %[a0] offset:0\n\tds_write_addtid_b32 %[a1] offset:288\n\tds_write_addtid_b32 %[a2] offset:576\n\tds_write_addtid_b32 %[a3] offset:864\n\t" \
                      "ds_write_addtid_b32 %[a4] offset:1152\n\tds_write_addtid_b32 %[a5] offset:1440\n\tds_write_addtid_b32 %[a6] offset:1728\n\tds_write_addtid_b32 %[a7] offset:2016\n\t" \
@@ -478,8 +480,11 @@ LFS_DI void wave_sum9_atomic_lds(const float (&v)[NV], float* __restrict__ dst, 
         uint32_t m0_saved;
         if constexpr (NV == 9)
             asm volatile(LFS_RED9_ASM("") : [sv] "=&s"(m0_saved) : LFS_RED9_OPERANDS, [base] "s"(base) : "memory");
-        else
+        else if constexpr (NV == 10)
             asm volatile(LFS_RED9_ASM("ds_write_addtid_b32 %[a9] offset:2592\n\t") : [sv] "=&s"(m0_saved) : LFS_RED9_OPERANDS, [a9] "v"(v[NV - 1]), [base] "s"(base) : "memory");
+        else
+            asm volatile(LFS_RED9_ASM("ds_write_addtid_b32 %[a9] offset:2592\n\tds_write_addtid_b32 %[a10] offset:2880\n\tds_write_addtid_b32 %[a11] offset:3168\n\t")
+                         : [sv] "=&s"(m0_saved) : LFS_RED9_OPERANDS, [a9] "v"(v[NV - 3]), [a10] "v"(v[NV - 2]), [a11] "v"(v[NV - 1]), [base] "s"(base) : "memory");
 #undef LFS_RED9_ASM
 #undef LFS_RED9_OPERANDS
         __builtin_amdgcn_wave_barrier();

@@ -639,6 +639,19 @@ lfs::fastgs_forward_wrapper_ex(
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int>
+lfs::fastgs_forward_wrapper_absgrad(
+    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
+    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
+    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
+    const float center_y, const float near_plane, const float far_plane, const bool antialiased, const bool absgrad) {
+    const FastgsForward f = fastgs_forward_impl(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c, cam_position, active_sh_bases,
+                                                width, height, focal_x, focal_y, center_x, center_y, near_plane, far_plane,
+                                                (antialiased ? LFS_FASTGS_ANTIALIASED : 0u) | (absgrad ? LFS_FASTGS_ABSGRAD : 0u), false);
+    at::Tensor none = at::empty({0}, means.options().dtype(at::kByte));
+    return {f.image, f.alpha, f.prim, none, f.inst, none.clone(), 0, (int)f.n_instances, 0, 0, 0};
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int>
 lfs::fastgs_forward_wrapper_filter3d(
     const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
     const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,

@@ -64,6 +64,13 @@ PYBIND11_MODULE(_lfs_torch_ops, m) {
               return lfs::fastgs_forward_wrapper_ex(means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest, w2c, cam_position,
                                                     active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane, antialiased);
           });
+    m.def("fastgs_forward_wrapper_absgrad",
+          [](at::Tensor means, at::Tensor scales_raw, at::Tensor rotations_raw, at::Tensor opacities_raw, at::Tensor sh0, at::Tensor sh_rest, at::Tensor w2c,
+             at::Tensor cam_position, int active_sh_bases, int width, int height, float fx, float fy, float cx, float cy, float near_plane, float far_plane,
+             bool antialiased, bool absgrad) {
+              return lfs::fastgs_forward_wrapper_absgrad(means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest, w2c, cam_position,
+                                                         active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane, antialiased, absgrad);
+          });
     m.def("fastgs_forward_wrapper_depth",
           [](at::Tensor means, at::Tensor scales_raw, at::Tensor rotations_raw, at::Tensor opacities_raw, at::Tensor sh0, at::Tensor sh_rest, at::Tensor w2c,
              at::Tensor cam_position, int active_sh_bases, int width, int height, float fx, float fy, float cx, float cy, float near_plane, float far_plane,

@@ -34,9 +34,12 @@ class FastGSSettings:  # rasterization_api.h:12-24
     depth: str = "none"         # "depth" | "invdepth": the records also carry z | 1 / z (LFS_FASTGS_DEPTH | LFS_FASTGS_INVDEPTH) for forward_wrapper_depth
     filter3d: Optional[torch.Tensor] = None   # [N] filter variances of the 3D smoothing filter (filter3d.compute_filter3d; lfs_fastgs_view_ext.filter3d_var): scales
                                               # sqrt(s^2 + v), opacity sigmoid(raw) * prod s / s'. Forward and backward of one view take the same tensor. No gradient.
+    absgrad: bool = False       # LFS_FASTGS_ABSGRAD: densification_info takes the norm of the per-pixel ABSOLUTE screen-space gradients (AbsGS / gsplat's absgrad); the
+                                # workspace remembers it, the render and every gradient are the default mode's
 
 
 ANTIALIASED = 1         # LFS_FASTGS_ANTIALIASED
+ABSGRAD = 32            # LFS_FASTGS_ABSGRAD
 DEPTH_FLAGS = {"none": 0, "depth": 4, "invdepth": 8}   # LFS_FASTGS_DEPTH, LFS_FASTGS_INVDEPTH
 ASYNC_READBACK = True   # False: n_instances via a stream synchronisation (A/B timing)
 
@@ -92,7 +95,7 @@ def _forward(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0,
     n_inst_dev = torch.zeros(1, dtype=torch.int64, device=dev)
     if s.depth not in DEPTH_FLAGS:
         raise LfsError(f"FastGSSettings.depth must be 'none', 'depth' or 'invdepth' (got {s.depth!r})")
-    flags = (ANTIALIASED if s.antialiased else 0) | DEPTH_FLAGS[s.depth]
+    flags = (ANTIALIASED if s.antialiased else 0) | DEPTH_FLAGS[s.depth] | (ABSGRAD if s.absgrad else 0)
     view = view_struct(s, means, scales_raw, rotations_raw, opac, sh0, shr, w2c, cam_position, pws)
     f3d = _filter3d_operand(s, N, dev)
     if f3d is None:
@@ -211,11 +214,12 @@ class FastGSRasterize(torch.autograd.Function):
 
 
 def fast_rasterize(camera: Camera, model: SplatModel, bg_color: torch.Tensor, densification_info: Optional[torch.Tensor] = None, antialiased: bool = False,
-                   render_mode: RenderMode = RenderMode.RGB, depth_kind: str = "depth", filter3d: Optional[torch.Tensor] = None) -> RenderOutput:
+                   render_mode: RenderMode = RenderMode.RGB, depth_kind: str = "depth", filter3d: Optional[torch.Tensor] = None, absgrad: bool = False) -> RenderOutput:
     """fast_rasterizer.cpp:12-68; antialiased: FastGSSettings.antialiased (an extension: the reference's fast_rasterize has no such argument).
     render_mode (the reference's RenderMode, which its EWA path ignores): D / RGB_D fill RenderOutput.depth [1,H,W] with the accumulated sum w_i d_i, ED / RGB_ED with
     that over alpha.clamp_min(1e-10) (rasterizer.py's rule); D / ED return image None (the colour is still rendered inside). depth_kind "depth": d = z,
-    "invdepth": d = 1 / z. RGB: everything as before. filter3d: FastGSSettings.filter3d, the [N] variances of the 3D smoothing filter (no gradient flows into it)."""
+    "invdepth": d = 1 / z. RGB: everything as before. filter3d: FastGSSettings.filter3d, the [N] variances of the 3D smoothing filter (no gradient flows into it).
+    absgrad: FastGSSettings.absgrad - the backward accumulates the absolute-gradient norm into densification_info; nothing else changes."""
     render_mode = RenderMode(render_mode)
     if depth_kind not in ("depth", "invdepth"):
         raise ValueError(f"depth_kind must be 'depth' or 'invdepth' (got {depth_kind!r})")
@@ -226,7 +230,7 @@ def fast_rasterize(camera: Camera, model: SplatModel, bg_color: torch.Tensor, de
     deg = model.get_active_sh_degree()
     settings = FastGSSettings(cam_position=(-(R.T @ t)).contiguous(), active_sh_bases=(deg + 1) ** 2, width=W, height=H,
                               focal_x=float(K[0, 0]), focal_y=float(K[1, 1]), center_x=float(K[0, 2]), center_y=float(K[1, 2]), near_plane=0.01, far_plane=1e10, antialiased=bool(antialiased),
-                              depth="none" if render_mode == RenderMode.RGB else depth_kind, filter3d=filter3d)
+                              depth="none" if render_mode == RenderMode.RGB else depth_kind, filter3d=filter3d, absgrad=bool(absgrad))
     out = FastGSRasterize.apply(model.means, model.raw_scales, model.raw_quats, model.raw_opacities, model.sh0, model.shN, w2c, densification_info, settings)
     image, alpha = out[0], out[1]
     depth = None

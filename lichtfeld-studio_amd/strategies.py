@@ -55,11 +55,18 @@ class OptimizationParameters:
     @staticmethod
     def for_strategy(strategy: str, **kw) -> "OptimizationParameters":
         """The reference keeps one JSON per strategy; the class defaults are eval/mcmc_optimization_params.json, and ADC differs in
-        stop_refine (15000) and the regularisers (0) - eval/default_optimization_params.json."""
+        stop_refine (15000) and the regularisers (0) - eval/default_optimization_params.json.
+        absgrad=True (ADC only; GutTrainer(absgrad=True)): grad_threshold defaults to 8e-4, gsplat's documented value for absolute gradients, whose norms are larger
+        than the signed ones; an explicit grad_threshold wins."""
+        absgrad = bool(kw.pop("absgrad", False))
+        if absgrad and strategy != "default":
+            raise ValueError("absgrad is an option of strategy='default' (ADC)")
         if strategy == "default":
-            kw = dict(dict(stop_refine=15000, opacity_reg=0.0, scale_reg=0.0), **kw)
+            kw = dict(dict(stop_refine=15000, opacity_reg=0.0, scale_reg=0.0, **({"grad_threshold": ABSGRAD_GRAD_THRESHOLD} if absgrad else {})), **kw)
         return OptimizationParameters(**kw)
 
+
+ABSGRAD_GRAD_THRESHOLD = 8e-4   # gsplat DefaultStrategy: "grow_grad2d ... 0.0002; if absgrad, 0.0008"
 
 _PARAM_NAMES = ["means", "sh0", "shN", "raw_scales", "raw_quats", "raw_opacities"]  # param-group order, strategy_utils.cpp:35-40
 

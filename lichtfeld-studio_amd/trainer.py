@@ -91,7 +91,7 @@ class GutTrainer:
                  sh_sharded: Optional[bool] = None, factored_sh: bool = False, one_call: bool = False, pose_optimization: str = "none", pose_lr: float = 1e-5,
                  enable_sparsity: bool = False, sparsify_steps: int = 15000, init_rho: float = 0.0005, prune_ratio: float = 0.6, sparsity_update_every: int = 50,
                  mask_mode: str = "none", mask_alpha_weight: float = 1.0, antialiasing: bool = False, depth_loss: str = "none", depth_weight=(1.0, 0.01),
-                 filter3d: bool = False, filter3d_every: int = 100, filter3d_variance: float = 0.2):
+                 filter3d: bool = False, filter3d_every: int = 100, filter3d_variance: float = 0.2, absgrad: bool = False):
         """strategy: None (fixed set of Gaussians: the benchmark), "mcmc" (strategies.MCMC: relocation + growth + SGLD noise, with
         the scale / opacity regularisers of trainer.cpp:132-158) or "default" (ADC; needs densification_info, see strategies.py).
         `seed` seeds the strategy's generator: the same on every rank, so replicas densify identically.
@@ -115,6 +115,9 @@ class GutTrainer:
         Every rank computes the same filter from the replicated means: no collective. Combines with antialiasing (together: Mip-Splatting), masks, the depth loss,
         pose optimisation (the filter uses the stored cameras) and sparsity. fastgs rasterizer only. export_model() returns the raw parameters: bake them
         (filter3d.bake) before writing a file for a viewer.
+        absgrad (AbsGS, gsplat's absgrad): ADC's densification_info takes the norm of the per-pixel ABSOLUTE screen-space gradients, which do not cancel
+        on a large Gaussian over fine texture (FastGSSettings.absgrad on every view whose backward feeds densification_info). Renders and gradients are unchanged.
+        fastgs rasterizer with strategy="default" only; OptimizationParameters.for_strategy("default", absgrad=True) carries the matching grad_threshold.
         depth_loss: "none" | "invdepth" | "depth" (DESIGN.md 8g): what train_step(depths=...) supervises - the accumulated inverse depth (the Inria trainer's
         convention: monocular depth, scale and offset fitted per image) or the accumulated depth of the view against a losses.PreparedDepth, by a masked L1 whose weight
         decays exponentially from depth_weight[0] (first iteration) to depth_weight[1] (iteration `iterations`) - the log-linear interpolation of the Inria trainer's
@@ -138,6 +141,11 @@ class GutTrainer:
         if filter3d and rasterizer == "gut":
             raise ValueError("filter3d is not wired into the 3DGUT route (rasterizer='gut'): its step forms render the unfiltered scales and opacities. "
                              "Use rasterizer='fastgs'.")
+        if absgrad and rasterizer == "gut":
+            raise ValueError("absgrad is not wired into the 3DGUT route (rasterizer='gut'): its backward has no densification_info. Use rasterizer='fastgs'.")
+        if absgrad and strategy != "default":
+            raise ValueError("absgrad changes what ADC reads from densification_info: it needs strategy='default'")
+        self.absgrad = bool(absgrad)
         if filter3d and int(filter3d_every) < 1:
             raise ValueError("filter3d_every must be >= 1")
         from .filter3d import Filter3dSchedule
@@ -204,7 +212,7 @@ class GutTrainer:
             raise ValueError("strategy='default' (ADC) needs rasterizer='fastgs': the 3DGUT backward has no densification_info")
         if strategy is not None:
             from . import strategies
-            op = opt_params or strategies.OptimizationParameters.for_strategy(strategy, iterations=iterations)
+            op = opt_params or strategies.OptimizationParameters.for_strategy(strategy, iterations=iterations, **({"absgrad": True} if self.absgrad else {}))
             gen = torch.Generator(device=device).manual_seed(seed)
             cls = {"mcmc": strategies.MCMC, "default": strategies.DefaultStrategy}[strategy]
             self.strategy = cls(self.model, op, scene_scale=scene_scale, generator=gen, on_resize=self._on_resize)
@@ -353,6 +361,7 @@ class GutTrainer:
         st.active_sh_bases = (self.model.get_active_sh_degree() + 1) ** 2
         st.depth = "none"   # (_train_step_fastgs switches a view with a depth target to the trainer's depth kind)
         st.filter3d = self.filter3d_var
+        st.absgrad = False   # (_train_step_fastgs sets it on the views whose backward feeds densification_info)
         return st
 
     def update_filter3d(self, force: bool = False):
@@ -409,6 +418,7 @@ class GutTrainer:
                 w2c_adj = self.pose_module(w2c, [v])
                 w2c, g_w2c = w2c_adj.detach().contiguous(), torch.empty_like(w2c)
             st, depth_args = self._fastgs_settings(v), {}
+            st.absgrad = self.absgrad and dens is not None
             if self._depths is not None and self._depths[k % len(self._depths)] is not None:
                 st.depth = self.depth_loss
                 depth_args = {"depth_target": self._depths[k % len(self._depths)], "depth_weight": self.depth_weight_at(self.iteration)}

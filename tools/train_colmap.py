@@ -55,6 +55,9 @@ def build_parser() -> argparse.ArgumentParser:
                     "renders what was trained (a baked file is not a resume point: training on from it would apply the filter twice)")
     ap.add_argument("--filter3d-every", type=int, default=100, help="recompute the filter every N iterations (and after every refinement)")
     ap.add_argument("--mip-splatting", action="store_true", help="--filter3d and --antialiasing together: the 3D smoothing filter and the 2D Mip filter")
+    ap.add_argument("--absgrad", action="store_true", help="ADC densifies by the per-pixel ABSOLUTE screen-space gradients (AbsGS; fastgs rasterizer, --strategy default): large "
+                    "Gaussians over fine texture, whose signed gradients cancel, get split. Without --grad-threshold the threshold becomes 8e-4")
+    ap.add_argument("--grad-threshold", type=float, default=None, help="ADC's screen-space gradient threshold for splitting / cloning (default 2e-4; 8e-4 with --absgrad)")
     ap.add_argument("--depth-loss", default="none", choices=["none", "invdepth", "depth"],
                     help="depth-regularised training (fastgs rasterizer): L1 between the accumulated inverse depth (invdepth: monocular depth, the Inria convention) or depth of a view "
                          "and <data>/<depths folder>/<image stem>.npy (float32 [H,W]) or .png (16-bit greyscale, value / 65536). With --eval, every held-out render is then saved as "
@@ -75,6 +78,12 @@ def check_args(args) -> None:
         raise SystemExit("--filter3d is not wired into the 3DGUT route. Please disable the 3D filter or disable gut.")
     if args.antialiasing and args.gut:
         raise SystemExit("--antialiasing is not wired into the 3DGUT route. Please disable antialiasing or disable gut.")
+    if args.absgrad and args.gut:
+        raise SystemExit("--absgrad is not wired into the 3DGUT route. Please disable absgrad or disable gut.")
+    if args.absgrad and args.strategy != "default":
+        raise SystemExit("--absgrad changes what ADC densifies by: it needs --strategy default.")
+    if args.grad_threshold is not None and not args.grad_threshold > 0:
+        raise SystemExit("--grad-threshold must be > 0")
     if args.depth_loss != "none" and args.gut:
         raise SystemExit("--depth-loss is not wired into the 3DGUT route. Please disable the depth loss or disable gut.")
     if args.depth_loss != "none" and not (args.depth_weight_init > 0 and args.depth_weight_final > 0):
@@ -104,7 +113,12 @@ def main():
 
     dev = torch.device("cuda:0")
     mcmc = args.strategy == "mcmc"
-    op = strategies.OptimizationParameters.for_strategy(args.strategy, iterations=args.iterations)   # ADC: stop_refine 15000, no regularisers
+    op_kw = {"absgrad": True} if args.absgrad else {}
+    if args.grad_threshold is not None:
+        op_kw["grad_threshold"] = args.grad_threshold
+    op = strategies.OptimizationParameters.for_strategy(args.strategy, iterations=args.iterations, **op_kw)   # ADC: stop_refine 15000, no regularisers
+    if args.absgrad:
+        print(f"absgrad: ADC reads absolute screen-space gradients, grad_threshold {op.grad_threshold:g}" + ("" if args.grad_threshold is not None else " (the default of this mode)"))
     init_scaling, init_opacity = (0.1, 0.5) if mcmc else (1.0, 0.1)        # parameter/{mcmc,default}_optimization_params.json
     t0 = time.time()
     split = "train" if args.eval else "all"
@@ -127,7 +141,7 @@ def main():
                     enable_sparsity=args.enable_sparsity, sparsify_steps=args.sparsify_steps, init_rho=args.init_rho, prune_ratio=args.prune_ratio,
                     mask_mode=args.mask_mode, mask_alpha_weight=args.mask_alpha_weight, antialiasing=args.antialiasing,
                     depth_loss=args.depth_loss, depth_weight=(args.depth_weight_init, args.depth_weight_final),
-                    filter3d=args.filter3d, filter3d_every=args.filter3d_every)
+                    filter3d=args.filter3d, filter3d_every=args.filter3d_every, absgrad=args.absgrad)
     total = tr.total_iterations                                             # --iterations, plus the sparsification phase
 
     def export():
@@ -190,7 +204,7 @@ def main():
     torch.cuda.synchronize()
     t_train = time.time() - t0 - t_eval
     out = {"data": args.data_path, "images": len(ds), "size": [scene.width, scene.height], "iterations": total, "rasterizer": rast,
-           "strategy": args.strategy, "antialiasing": bool(args.antialiasing), "filter3d": bool(args.filter3d), "pose_optimization": args.pose_optimization, "gaussians": int(tr.model.means.shape[0]), "load_s": round(t_load, 1), "train_s": round(t_train, 1),
+           "strategy": args.strategy, "antialiasing": bool(args.antialiasing), "filter3d": bool(args.filter3d), "absgrad": bool(args.absgrad), "pose_optimization": args.pose_optimization, "gaussians": int(tr.model.means.shape[0]), "load_s": round(t_load, 1), "train_s": round(t_train, 1),
            "iters_per_s": round(total / max(t_train, 1e-9), 1)}
     if masks is not None:
         out.update(mask_mode=args.mask_mode, masked_views=sum(m is not None for m in masks))
