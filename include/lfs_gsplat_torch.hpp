@@ -109,49 +109,34 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Te
     const int n_buckets, const int primitive_primitive_indices_selector, const int instance_primitive_indices_selector);
 } // namespace fast_gs::rasterization
 namespace lfs {
-// Extension: fast_gs::rasterization::forward_wrapper with the antialiased mode (lfs_fastgs_view_preprocess, LFS_FASTGS_ANTIALIASED) - what a trainer that honours
-// OptimizationParameters::antialiasing calls in its place. The mode is kept in per_primitive_buffers: fast_gs::rasterization::backward_wrapper serves both modes.
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int> fastgs_forward_wrapper_ex(
-    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
-    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
-    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane, const bool antialiased);
-// Extension: absolute screen-space gradients for densification (LFS_FASTGS_ABSGRAD; AbsGS / gsplat's absgrad). The forward returns what fastgs_forward_wrapper_ex returns, bit for
-// bit; the per_primitive_buffers remember the mode, and fast_gs::rasterization::backward_wrapper (or the depth backward) on them accumulates the absolute-gradient
-// norm into a defined densification_info. Every gradient is the default mode's.
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int> fastgs_forward_wrapper_absgrad(
-    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
-    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
-    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane, const bool antialiased, const bool absgrad);
-// Extension: the depth modes (the depth plane of lfs_fastgs_view_render / grad_depth of lfs_fastgs_view_backward; LFS_FASTGS_DEPTH, LFS_FASTGS_INVDEPTH). Forward: inverse_depth false blends the
-// camera-space z of every Gaussian, true its reciprocal; -> (image [3,H,W], alpha [1,H,W], depth [1,H,W] = the ACCUMULATED sum w_i d_i, per_primitive_buffers,
-// per_instance_buffers, n_instances). Backward: fast_gs::rasterization::backward_wrapper with grad_depth [1,H,W]; the 7th element is grad_w2c when w2c requires grad.
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int> fastgs_forward_wrapper_depth(
-    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
-    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
-    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane, const bool antialiased, const bool inverse_depth);
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> fastgs_backward_wrapper_depth(
-    torch::Tensor& densification_info, const torch::Tensor& grad_image, const torch::Tensor& grad_alpha, const torch::Tensor& grad_depth, const torch::Tensor& alpha,
-    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& sh_coefficients_rest,
-    const torch::Tensor& per_primitive_buffers, const torch::Tensor& per_instance_buffers, const torch::Tensor& w2c, const torch::Tensor& cam_position,
-    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane, const int n_instances);
-// Extension: the 3D smoothing filter of Mip-Splatting (lfs_fastgs_view_preprocess_ex / lfs_fastgs_view_backward_ex; include/lfs_gsplat.h). filter3d_var: the [N] filter
-// variances (lfs_filter3d_compute). The forward returns what fastgs_forward_wrapper_ex returns; the backward MUST be this one, with the same tensor (a backward
-// without it on such a workspace is refused), and returns what fast_gs::rasterization::backward_wrapper returns (7th element: grad_w2c when w2c requires grad).
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int> fastgs_forward_wrapper_filter3d(
-    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
-    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
-    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane, const bool antialiased, const torch::Tensor& filter3d_var);
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> fastgs_backward_wrapper_filter3d(
-    torch::Tensor& densification_info, const torch::Tensor& grad_image, const torch::Tensor& grad_alpha, const torch::Tensor& alpha,
-    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& sh_coefficients_rest,
-    const torch::Tensor& per_primitive_buffers, const torch::Tensor& per_instance_buffers, const torch::Tensor& w2c, const torch::Tensor& cam_position,
-    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane, const int n_instances, const torch::Tensor& filter3d_var);
+// Extension: the fastgs rasterizer with every mode of the C ABI (lfs_fastgs_view_preprocess[_ex] / _render / _backward[_ex]; include/lfs_gsplat.h), in any combination.
+// fast_gs::rasterization::forward_wrapper / backward_wrapper above are these two with default options.
+struct FastgsCamera {
+    torch::Tensor w2c, cam_position;
+    int active_sh_bases, width, height;
+    float focal_x, focal_y, center_x, center_y, near_plane, far_plane;
+};
+enum class FastgsDepth { None = 0, Z = 1, InverseZ = 2 };   // what the depth plane blends: nothing, the camera-space z of every Gaussian, its reciprocal
+struct FastgsOptions {
+    bool antialiased = false;                 // LFS_FASTGS_ANTIALIASED (what a trainer that honours OptimizationParameters::antialiasing sets)
+    FastgsDepth depth = FastgsDepth::None;    // LFS_FASTGS_DEPTH / LFS_FASTGS_INVDEPTH
+    bool absgrad = false;                     // LFS_FASTGS_ABSGRAD (AbsGS / gsplat's absgrad): a backward with a defined densification_info accumulates the absolute-gradient
+                                              // norm into it; the forward's outputs and every gradient are the default mode's
+    torch::Tensor filter3d_var;               // the 3D smoothing filter of Mip-Splatting: the [N] filter variances (lfs_filter3d_compute); undefined: no 3D filter
+};
+// depth [1,H,W]: the ACCUMULATED sum w_i d_i, defined iff options.depth != None. The modes are kept with per_primitive_buffers.
+struct FastgsForwardOut { torch::Tensor image, alpha, depth, per_primitive_buffers, per_instance_buffers; int n_instances; };
+// caller: the name a failure of the C ABI is reported under (the reference's symbols pass their own)
+FastgsForwardOut fastgs_forward(const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
+                                const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const FastgsCamera& camera,
+                                const FastgsOptions& options = {}, const char* caller = "lfs::fastgs_forward");
+struct FastgsGrads { torch::Tensor means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest, w2c /* defined iff camera.w2c.requires_grad(); shaped like w2c */; };
+// options: those of the forward that filled the buffers. Only filter3d_var is read - it MUST be the forward's tensor (the library refuses a backward whose filter disagrees
+// with its forward's) - the other modes are remembered with per_primitive_buffers. grad_depth [1,H,W]: the gradient of the forward's depth plane; undefined: none.
+FastgsGrads fastgs_backward(torch::Tensor& densification_info, const torch::Tensor& grad_image, const torch::Tensor& grad_alpha, const torch::Tensor& grad_depth,
+                            const torch::Tensor& alpha, const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw,
+                            const torch::Tensor& sh_coefficients_rest, const torch::Tensor& per_primitive_buffers, const torch::Tensor& per_instance_buffers,
+                            int n_instances, const FastgsCamera& camera, const FastgsOptions& options, const char* caller = "lfs::fastgs_backward");
 } // namespace lfs
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> fusedssim(float C1, float C2, torch::Tensor& img1, torch::Tensor& img2, bool train);

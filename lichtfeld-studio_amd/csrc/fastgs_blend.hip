@@ -9,18 +9,9 @@
 #include "lfs_fastgs.cuh"
 #include "lfs_prof.h"
 #include "lfs_tilelists.cuh"
-#include "../../include/lfs_gsplat.h"
 
 namespace lfs {
 namespace fgs {
-
-int launch_scatter(uint32_t N, const Frame& f, const PrimWs& w, int64_t* keys, hipStream_t s);
-Frame make_frame(const lfs_fastgs_view& v);
-int launch_preprocess_bwd(const lfs_fastgs_view& v, const Frame& f, const PrimWs& w, const lfs_fastgs_view_backward_args& a, const float* sh_rest, const ShAdamArgs* adam,
-                          int depth, const float* filter_var, bool absgrad, hipStream_t s);
-uint32_t remembered_flags(const void* primitive_workspace);
-size_t w2c_workspace_bytes(uint32_t N);
-int launch_w2c_reduce(uint32_t N, const float* w2c_partials, float* grad_w2c, hipStream_t s);
 
 // cell-level version of kernel_utils.cuh:108-148 on the record's conic in bits (A, B, C) = log2(e) (a/2, b, c/2): the ratios that
 // locate the maximum are scale free; thr already carries the safety margin
@@ -267,12 +258,6 @@ extern "C" void lfs_fastgs_set_debug_flags(uint32_t flags) { fgs::g_fastgs_debug
 
 static_assert(sizeof(lfs_fastgs_sh_rest_adam) == 48 && sizeof(lfs_fastgs_view_backward_args) == 144, "the ctypes mirrors (capi.py) are laid out by hand");
 
-// the depth kind (1: z, 2: 1 / z) of the preprocess that last filled this workspace, 0 when it carried no depth flag (fastgs_prep.hip: remember_flags)
-static int workspace_depth_kind(const void* primitive_workspace) {
-    const uint32_t flags = fgs::remembered_flags(primitive_workspace);
-    return (flags & LFS_FASTGS_DEPTH) ? 1 : (flags & LFS_FASTGS_INVDEPTH) ? 2 : 0;
-}
-
 // Whether the workspace carries d in its records is validated on the HOST (the flags the library remembers by the workspace's address: no device read, no launch on
 // a refusal); the antialiased bit is picked on the device.
 extern "C" int lfs_fastgs_view_render(const lfs_fastgs_view* view, int64_t n_instances, void* instance_workspace, size_t instance_workspace_bytes,
@@ -280,7 +265,7 @@ extern "C" int lfs_fastgs_view_render(const lfs_fastgs_view* view, int64_t n_ins
     if (!view) return LFS_E_INVALID;
     const uint32_t N = view->N, width = view->width, height = view->height;
     void* const primitive_workspace = view->primitive_workspace;
-    if (depth && (!primitive_workspace || workspace_depth_kind(primitive_workspace) == 0)) return LFS_E_INVALID;
+    if (depth && (!primitive_workspace || fgs::ws_mode(fgs::remembered_flags(primitive_workspace)).depth == 0)) return LFS_E_INVALID;
     if (!primitive_workspace || !image || !alpha || width == 0 || height == 0 || n_instances < 0 || n_instances > 0x7FFFFFFFll) return LFS_E_INVALID;
     if (N >= (1u << 26) || uint64_t(n_instances) >= (1ull << 29)) return LFS_E_UNSUPPORTED; // 32-bit byte offsets of the record walker
     fgs::PrimWs w = fgs::prim_ws(primitive_workspace, N, width, height);
@@ -338,7 +323,9 @@ static int view_backward(const lfs_fastgs_view* view, const lfs_fastgs_view_back
     const lfs_fastgs_view& v = *view;
     const lfs_fastgs_view_backward_args& a = *args;
     const uint32_t N = v.N;
-    if (v.primitive_workspace && ((fgs::remembered_flags(v.primitive_workspace) & fgs::MODE_FILTER3D) != 0u) != (filter_var != nullptr)) return LFS_E_INVALID;
+    // what the workspace was filled with, looked up once; below it becomes what this call runs. (No workspace: all zero - such a view is refused further down.)
+    fgs::WsMode mode = fgs::ws_mode(v.primitive_workspace ? fgs::remembered_flags(v.primitive_workspace) : 0u);
+    if (v.primitive_workspace && mode.filter3d != (filter_var != nullptr)) return LFS_E_INVALID;
     // the optimizer-fused form: the parameter it updates replaces the view's sh_coefficients_rest; it has no camera gradient and no depth gradient
     const float* sh_rest = v.sh_coefficients_rest;
     lfs::ShAdamArgs adam_args{};
@@ -352,13 +339,9 @@ static int view_backward(const lfs_fastgs_view* view, const lfs_fastgs_view_back
         sh_rest = a.adam->sh_coefficients_rest;
     }
     // the abs form (LFS_FASTGS_ABSGRAD): only where its two sums have a reader; without densification_info the call launches what a default workspace's does
-    const bool absgrad = a.densification_info != nullptr && v.primitive_workspace && (fgs::remembered_flags(v.primitive_workspace) & LFS_FASTGS_ABSGRAD) != 0u;
-    int depth = 0;   // with grad_depth: the workspace's depth kind
-    if (a.grad_depth) {
-        if (!v.primitive_workspace) return LFS_E_INVALID;
-        depth = workspace_depth_kind(v.primitive_workspace);
-        if (depth == 0) return LFS_E_INVALID;
-    }
+    mode.absgrad = mode.absgrad && a.densification_info != nullptr;
+    if (!a.grad_depth) mode.depth = 0;   // with grad_depth: the workspace's depth kind, which it must have
+    else if (mode.depth == 0) return LFS_E_INVALID;
     if (a.grad_w2c) {
         if (!a.w2c_workspace || a.w2c_workspace_bytes < fgs::w2c_workspace_bytes(N)) return LFS_E_WORKSPACE;
         if (reinterpret_cast<uintptr_t>(a.w2c_workspace) % 16 != 0) return LFS_E_INVALID;   // fg_w2c_reduce_kernel reads the partial rows as float4
@@ -391,20 +374,21 @@ static int view_backward(const lfs_fastgs_view* view, const lfs_fastgs_view_back
     if (a.n_instances > 0 && !keep_acc) {
         lfs::ProfScope prof("fastgs_blend_bwd", s);
         const uint32_t wgrid = cell_grid_blocks(uint64_t(T) * fgs::WPT, fgs::WPT);
-#define LFS_FG_BWD_K(KERNEL, ACC, DEPTH) hipLaunchKernelGGL((fgs::KERNEL<ACC, DEPTH>), dim3(wgrid), dim3(64), 0, s, f.gw, f.gh, v.width, v.height, w.rec, w.offsets, iw.cell_count, \
-                                                           iw.cell_list, a.alpha, w.n_contrib, a.grad_image, a.grad_alpha, w.acc, w.det64, a.grad_depth)
-#define LFS_FG_BWD_D(ACC, DEPTH) do { if (absgrad) LFS_FG_BWD_K(fg_blend_bwd_abs_kernel, ACC, DEPTH); else LFS_FG_BWD_K(fg_blend_bwd_kernel, ACC, DEPTH); } while (0)
-#define LFS_FG_BWD(ACC) do { if (a.grad_depth) LFS_FG_BWD_D(ACC, true); else LFS_FG_BWD_D(ACC, false); } while (0)
+#define LFS_FG_BWD_PAIR(ACC, DEPTH) {&fgs::fg_blend_bwd_abs_kernel<ACC, DEPTH>, &fgs::fg_blend_bwd_kernel<ACC, DEPTH>}
+        static constexpr decltype(&fgs::fg_blend_bwd_kernel<0, false>) kernels[3][2][2] = {   // [ACC 1, 2, 0][without grad_depth][default form]: the code object's order
+            {LFS_FG_BWD_PAIR(1, true), LFS_FG_BWD_PAIR(1, false)}, {LFS_FG_BWD_PAIR(2, true), LFS_FG_BWD_PAIR(2, false)}, {LFS_FG_BWD_PAIR(0, true), LFS_FG_BWD_PAIR(0, false)}};
+#undef LFS_FG_BWD_PAIR
+        const auto blend_bwd = [&](int acc) {
+            hipLaunchKernelGGL(kernels[acc == 0 ? 2 : acc - 1][mode.depth == 0][!mode.absgrad], dim3(wgrid), dim3(64), 0, s, f.gw, f.gh, v.width, v.height, w.rec, w.offsets,
+                               iw.cell_count, iw.cell_list, a.alpha, w.n_contrib, a.grad_image, a.grad_alpha, w.acc, w.det64, a.grad_depth);
+        };
         if (det) { // pass 1: per-slot maxima of |total| (integer atomicMax), pass 2: 64-bit fixed-point sums, then back to float
             const size_t n_acc = ACC_STRIDE * size_t(N);
             hipError_t e = hipMemsetAsync(w.det64, 0, sizeof(unsigned long long) * n_acc, s);
             if (e != hipSuccess) return (int)e;
-            LFS_FG_BWD(1); LFS_FG_BWD(2);
+            blend_bwd(1); blend_bwd(2);
             hipLaunchKernelGGL(fgs::fg_det_resolve_kernel, dim3(uint32_t((n_acc + 255) / 256)), dim3(256), 0, s, n_acc, w.acc, w.det64);
-        } else LFS_FG_BWD(0);
-#undef LFS_FG_BWD
-#undef LFS_FG_BWD_D
-#undef LFS_FG_BWD_K
+        } else blend_bwd(0);
     }
-    return fgs::launch_preprocess_bwd(v, f, w, a, sh_rest, adam, depth, filter_var, absgrad, s);
+    return fgs::launch_preprocess_bwd(v, f, w, a, sh_rest, adam, mode, filter_var, s);
 }

@@ -494,13 +494,11 @@ Frame make_frame(const lfs_fastgs_view& v) {
     return Frame{v.w2c, v.cam_position, v.active_sh_bases, v.total_bases_sh_rest, v.width, v.height, (v.width + TILE - 1) / TILE, (v.height + TILE - 1) / TILE,
                  v.fx, v.fy, v.cx, v.cy, v.near_plane, v.far_plane};
 }
-// sh_rest / adam: the view's coefficients and no optimizer, or the optimizer-fused form's parameter; depth: with grad_depth 1 / 2, the kind the host remembers for
-// this workspace, 0 otherwise
 int launch_preprocess_bwd(const lfs_fastgs_view& v, const Frame& f, const PrimWs& w, const lfs_fastgs_view_backward_args& a, const float* sh_rest, const ShAdamArgs* adam,
-                          int depth, const float* filter_var, bool absgrad, hipStream_t s) {
+                          const WsMode& mode, const float* filter_var, hipStream_t s) {
     const uint32_t N = v.N;
     float* const w2c_partials = a.grad_w2c ? static_cast<float*>(a.w2c_workspace) : nullptr;
-    float* const densification_info = absgrad ? nullptr : a.densification_info;   // absgrad: fg_densify_abs_kernel below writes it
+    float* const densification_info = mode.absgrad ? nullptr : a.densification_info;   // absgrad: fg_densify_abs_kernel below writes it
     {
         // the mode of the forward that filled this workspace is a word IN the workspace, which the host does not read: both AA instantiations are queued, one returns
         // at once. (depth, w2c) pick the pair on the host. (The table lists the kernels in the order the code object has always had them: with W2C first.)
@@ -516,16 +514,16 @@ int launch_preprocess_bwd(const lfs_fastgs_view& v, const Frame& f, const PrimWs
             {LFS_FG_PREP_BWD_F3D_PAIR(true, 2), LFS_FG_PREP_BWD_F3D_PAIR(false, 2)}};
 #undef LFS_FG_PREP_BWD_F3D_PAIR
         if (filter_var != nullptr) {
-            for (const auto kernel : kernels_f3d[depth][a.grad_w2c == nullptr])
+            for (const auto kernel : kernels_f3d[mode.depth][a.grad_w2c == nullptr])
                 hipLaunchKernelGGL(kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, v.means, v.scales_raw, v.rotations_raw, f, w.rec, w.conic_opacity, w.n_touched, w.acc,
                                    a.grad_means, a.grad_scales_raw, a.grad_rotations_raw, a.grad_opacities_raw, densification_info, w2c_partials, w.mode, filter_var);
         } else {
-            for (const auto kernel : kernels[depth][a.grad_w2c == nullptr])
+            for (const auto kernel : kernels[mode.depth][a.grad_w2c == nullptr])
                 hipLaunchKernelGGL(kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, v.means, v.scales_raw, v.rotations_raw, f, w.rec, w.conic_opacity, w.n_touched, w.acc,
                                    a.grad_means, a.grad_scales_raw, a.grad_rotations_raw, a.grad_opacities_raw, densification_info, w2c_partials, w.mode);
         }
     }
-    if (absgrad) {
+    if (mode.absgrad) {
         lfs::ProfScope prof("fastgs_densify_abs", s);
         hipLaunchKernelGGL(fg_densify_abs_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, f.width, f.height, w.n_touched, w.acc, a.densification_info, w.mode);
     }
@@ -558,34 +556,36 @@ static Readback& readback() {
     return rb;
 }
 
-// The flags of the depth-mode preprocess that last filled a primitive workspace, by the workspace's address: what a render with a depth plane and a backward with
-// grad_depth validate against without reading the mode word back (that would be a host sync). Only workspaces filled WITH a depth flag take an entry; a preprocess without one
-// erases the entry of its address (the workspace stops counting as a depth workspace) and takes none, so ordinary forwards - evaluation renders, other views - never
-// push a depth workspace out. DEPTH_SLOTS depth forwards can be outstanding (filled, their backward still to come); one more evicts the least recently filled, whose
-// depth plane and grad_depth are then refused with LFS_E_INVALID (fastgs.py names that cause in its error). Device addresses are unique across the devices of a process (one unified
-// address space), so the address alone is the key. A mutex guards the table: the entry points may be called from several host threads.
-constexpr int DEPTH_SLOTS = 256;
-struct DepthSlot { const void* ws = nullptr; uint32_t flags = 0; uint64_t stamp = 0; };
-static DepthSlot g_depth_slots[DEPTH_SLOTS];
-static uint64_t g_depth_stamp = 0;
-static std::mutex g_depth_mutex;
+// The flags of the preprocess that last filled a primitive workspace, by the workspace's address: what the host picks and validates by - render's depth plane, the
+// backward's grad_depth, its filtered and its abs form - without reading the mode word back (that would be a host sync). Only workspaces filled with a mode the host must
+// know - a depth mode, the 3D filter or absgrad - take an entry; a preprocess without one erases the entry of its address (the workspace counts as a default one again)
+// and takes none, so ordinary forwards - evaluation renders, other views - never push such a workspace out. MODE_SLOTS such forwards can be outstanding (filled, their
+// backward still to come); one more evicts the least recently filled, which then counts as a default workspace: its depth plane, its grad_depth and a backward with the
+// filter's variances are refused with LFS_E_INVALID (fastgs.py names that cause in its error), and a backward on it runs the default form in place of the abs form. Device
+// addresses are unique across the devices of a process (one unified address space), so the address alone is the key. A mutex guards the table: the entry points may
+// be called from several host threads.
+constexpr int MODE_SLOTS = 256;
+struct ModeSlot { const void* ws = nullptr; uint32_t flags = 0; uint64_t stamp = 0; };
+static ModeSlot g_mode_slots[MODE_SLOTS];
+static uint64_t g_mode_stamp = 0;
+static std::mutex g_mode_mutex;
 static void remember_flags(const void* ws, uint32_t flags) {
-    const bool depth = (flags & (MODE_DEPTH | MODE_INVDEPTH | MODE_FILTER3D | MODE_ABSGRAD)) != 0;   // what takes an entry: a depth mode, the 3D filter or absgrad
-    std::lock_guard<std::mutex> lock(g_depth_mutex);
-    DepthSlot* pick = &g_depth_slots[0];
-    for (DepthSlot& m : g_depth_slots) {
+    const bool takes_entry = (flags & (MODE_DEPTH | MODE_INVDEPTH | MODE_FILTER3D | MODE_ABSGRAD)) != 0;   // a depth mode, the 3D filter or absgrad
+    std::lock_guard<std::mutex> lock(g_mode_mutex);
+    ModeSlot* pick = &g_mode_slots[0];
+    for (ModeSlot& m : g_mode_slots) {
         if (m.ws == ws) { pick = &m; break; }
         if (m.stamp < pick->stamp) pick = &m;
     }
-    if (!depth) {
-        if (pick->ws == ws) *pick = DepthSlot{};
+    if (!takes_entry) {
+        if (pick->ws == ws) *pick = ModeSlot{};
         return;
     }
-    pick->ws = ws; pick->flags = flags; pick->stamp = ++g_depth_stamp;
+    pick->ws = ws; pick->flags = flags; pick->stamp = ++g_mode_stamp;
 }
-uint32_t remembered_flags(const void* ws) {   // 0: a workspace that was not (or not recently enough) filled by a depth-mode preprocess
-    std::lock_guard<std::mutex> lock(g_depth_mutex);
-    for (const DepthSlot& m : g_depth_slots)
+uint32_t remembered_flags(const void* ws) {   // 0: a workspace that was not (or not recently enough) filled by a preprocess with a depth mode, the 3D filter or absgrad
+    std::lock_guard<std::mutex> lock(g_mode_mutex);
+    for (const ModeSlot& m : g_mode_slots)
         if (m.ws == ws && m.stamp != 0) return m.flags;
     return 0u;
 }

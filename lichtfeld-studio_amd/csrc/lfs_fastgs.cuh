@@ -2,6 +2,7 @@
 // SURVEY.md §8f row 1; reference: fastgs/rasterization/*).
 #pragma once
 #include "lfs_raster_common.cuh"
+#include "../../include/lfs_gsplat.h"
 
 namespace lfs {
 // sh.hip: the SH kernels with strided colour operands (colours live inside the 64-B blend records / accumulator rows)
@@ -46,9 +47,10 @@ inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 //            Antialiased mode: opacity = sigmoid(raw) * rho everywhere, and r1.w = sigmoid(raw) for the backward.
 //            Depth modes: r2.w = d = z or 1 / z (camera space), blended by the depth forms of the blend kernels like a fourth colour channel.
 //   mode     one word of the (otherwise spare) 256-byte n_instances slot: the flags of the preprocess that filled the workspace. The per-primitive backward
-//            picks its antialiased or default instantiation by it on the device, so render and backward carry no flag. The depth bits are ALSO remembered on the
-//            host, by the workspace's address (fastgs_prep.hip: remember_flags): a depth plane or a depth gradient on a workspace without them is refused
-//            before any launch, and the depth forms of the kernels are chosen on the host from that table; they check their bit in this word again.
+//            picks its antialiased or default instantiation by it on the device, so render and backward carry no flag. The depth, 3D filter and absgrad bits are ALSO
+//            remembered on the host, by the workspace's address (fastgs_prep.hip: remember_flags; WsMode below): a depth plane or a depth gradient on a workspace
+//            without the depth bits is refused before any launch, and the depth, filtered and abs forms of the kernels are chosen on the host from that table; they
+//            check their bit in this word again.
 struct PrimWs {
     GaussRec* rec; float2* mean2d; float4* conic_opacity; ushort4* bounds; uint32_t* n_touched; uint32_t* depth_bits;
     uint32_t* totals; uint32_t* cursor; int32_t* offsets; int64_t* n_instances; uint32_t* mode; int32_t* n_contrib; float* acc; unsigned long long* det64; size_t bytes;
@@ -91,5 +93,23 @@ inline InstWs inst_ws(void* base, uint32_t width, uint32_t height, uint64_t n_in
 // accumulator row of the blend backward (16 floats per primitive, one 64-B line):
 //   0,1 sum h (dx, dy) | 2,3,4 sum h (dx dx, dx dy, dy dy), h = -alpha dL/dalpha | 5,6,7 dL/d(clamped colour) | 8 sum alpha dL/dalpha |
 //   9 dL/dd = sum w g_depth (depth form of the backward only; 0 otherwise) | 10,11 sum |k gx_p|, sum |k gy_p| (abs form only; 0 otherwise) | 12..15 unused
+
+// What the host remembers of the preprocess that last filled a primitive workspace (fastgs_prep.hip: remember_flags), as render and the backward use it: ONE lookup per
+// call, so every form a call picks comes from the same state of the table. All zero: a default (or antialiased-only) workspace, or one the table no longer holds.
+uint32_t remembered_flags(const void* primitive_workspace);
+struct WsMode { int depth; bool filter3d, absgrad; };   // depth: 0 none, 1 z, 2 1 / z (the DEPTH template parameter of the per-primitive kernels)
+inline WsMode ws_mode(uint32_t remembered) {
+    return WsMode{(remembered & MODE_DEPTH) ? 1 : (remembered & MODE_INVDEPTH) ? 2 : 0, (remembered & MODE_FILTER3D) != 0u, (remembered & MODE_ABSGRAD) != 0u};
+}
+
+// host-side launchers of fastgs_prep.hip that fastgs_blend.hip uses as well
+int launch_scatter(uint32_t N, const Frame& f, const PrimWs& w, int64_t* keys, hipStream_t s);
+Frame make_frame(const lfs_fastgs_view& v);
+// sh_rest / adam: the view's coefficients and no optimizer, or the optimizer-fused form's parameter. mode: the forms this backward runs - depth with grad_depth only,
+// absgrad with densification_info only, filter3d with filter_var (the [N] variances) only
+int launch_preprocess_bwd(const lfs_fastgs_view& v, const Frame& f, const PrimWs& w, const lfs_fastgs_view_backward_args& a, const float* sh_rest, const ShAdamArgs* adam,
+                          const WsMode& mode, const float* filter_var, hipStream_t s);
+size_t w2c_workspace_bytes(uint32_t N);
+int launch_w2c_reduce(uint32_t N, const float* w2c_partials, float* grad_w2c, hipStream_t s);
 } // namespace fgs
 } // namespace lfs

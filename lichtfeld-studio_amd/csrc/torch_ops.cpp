@@ -24,8 +24,8 @@
 
 namespace {
 lfs_stream_t cur_stream() { return (lfs_stream_t)c10::hip::getCurrentHIPStream().stream(); }
-void check_rc(int rc, const char* what) {
-    TORCH_CHECK(rc == 0, what, " failed (", rc == LFS_E_INVALID ? "invalid argument" : rc == LFS_E_UNSUPPORTED ? "unsupported configuration"
+void check_rc(int rc, const char* what, const char* stage = "") {
+    TORCH_CHECK(rc == 0, what, stage, " failed (", rc == LFS_E_INVALID ? "invalid argument" : rc == LFS_E_UNSUPPORTED ? "unsupported configuration"
                                              : rc == LFS_E_WORKSPACE ? "workspace too small" : "HIP error", ", code ", rc, ")");
 }
 // optional tensor -> pointer; an empty {0} tensor counts as absent (rasterizer.cpp:300-303 passes one for "no background")
@@ -528,72 +528,74 @@ torch::Tensor GutTrainStep::radii() const {
 // fast_gs::rasterization (rasterization_api.h:27-75, src/rasterization_api.cu) and fusedssim (ssim.cuh:11-30)
 // ---------------------------------------------------------------------------------------------------------
 namespace {
-// lfs_fastgs_view of (contiguous) tensors, which the caller holds for the duration of the call; opacities_raw / sh_coefficients_0 / prim: undefined -> NULL
+// lfs_fastgs_view of (contiguous) tensors, which the caller holds for the duration of the call; opacities_raw / sh_coefficients_0: undefined -> NULL
 lfs_fastgs_view fastgs_view(const at::Tensor& means, const at::Tensor& scales_raw, const at::Tensor& rotations_raw, const at::Tensor& opacities_raw,
                             const at::Tensor& sh_coefficients_0, const at::Tensor& sh_coefficients_rest, const at::Tensor& w2c_c, const at::Tensor& cam_c,
-                            int active_sh_bases, int width, int height, float focal_x, float focal_y, float center_x, float center_y, float near_plane, float far_plane,
-                            const at::Tensor& prim) {
+                            const lfs::FastgsCamera& c, const at::Tensor& prim) {
     const uint32_t total_rest = (uint32_t)sh_coefficients_rest.size(1);
     return lfs_fastgs_view{(uint32_t)means.size(0), means.data_ptr<float>(), scales_raw.data_ptr<float>(), rotations_raw.data_ptr<float>(),
                            opacities_raw.defined() ? opacities_raw.data_ptr<float>() : nullptr, sh_coefficients_0.defined() ? sh_coefficients_0.data_ptr<float>() : nullptr,
                            total_rest ? sh_coefficients_rest.data_ptr<float>() : nullptr, total_rest, w2c_c.data_ptr<float>(), cam_c.data_ptr<float>(),
-                           (uint32_t)active_sh_bases, (uint32_t)width, (uint32_t)height, focal_x, focal_y, center_x, center_y, near_plane, far_plane,
+                           (uint32_t)c.active_sh_bases, (uint32_t)c.width, (uint32_t)c.height, c.focal_x, c.focal_y, c.center_x, c.center_y, c.near_plane, c.far_plane,
                            prim.data_ptr(), (size_t)prim.numel()};
 }
+// the [N] variances of the 3D smoothing filter as the _ex entries take them
+lfs_fastgs_view_ext fastgs_ext(const at::Tensor& filter3d_var, uint32_t N) {
+    LFS_CHECK_INPUT(filter3d_var);
+    TORCH_CHECK(filter3d_var.numel() == (int64_t)N && filter3d_var.scalar_type() == at::kFloat, "filter3d_var must hold N floats");
+    return lfs_fastgs_view_ext{filter3d_var.data_ptr<float>()};
+}
+} // namespace
 
-// the forward of every mode (flags of lfs_fastgs_view_preprocess; depth: also the accumulated depth plane); the mode lives in per_primitive_buffers from here on
-struct FastgsForward { at::Tensor image, alpha, depth, prim, inst; int64_t n_instances; };
-FastgsForward fastgs_forward_impl(
+// the forward of every mode; the modes live with per_primitive_buffers from here on
+lfs::FastgsForwardOut lfs::fastgs_forward(
     const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
-    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
-    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane, const uint32_t flags, const bool want_depth, const torch::Tensor& filter3d_var = torch::Tensor()) {
+    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const FastgsCamera& camera, const FastgsOptions& options, const char* caller) {
     LFS_DEVICE_GUARD(means);
     LFS_CHECK_INPUT(means); LFS_CHECK_INPUT(scales_raw); LFS_CHECK_INPUT(rotations_raw); LFS_CHECK_INPUT(opacities_raw);
     LFS_CHECK_INPUT(sh_coefficients_0); LFS_CHECK_INPUT(sh_coefficients_rest);
     const uint32_t N = (uint32_t)means.size(0);
-    const at::Tensor w2c_c = w2c.contiguous(), cam_c = cam_position.contiguous();
+    const int width = camera.width, height = camera.height;
+    const bool want_depth = options.depth != FastgsDepth::None;
+    const uint32_t flags = (options.antialiased ? LFS_FASTGS_ANTIALIASED : 0u) | (options.absgrad ? LFS_FASTGS_ABSGRAD : 0u) |
+                           (options.depth == FastgsDepth::Z ? LFS_FASTGS_DEPTH : options.depth == FastgsDepth::InverseZ ? LFS_FASTGS_INVDEPTH : 0u);
+    const at::Tensor w2c_c = camera.w2c.contiguous(), cam_c = camera.cam_position.contiguous();
     const auto fopt = means.options().dtype(at::kFloat), bopt = means.options().dtype(at::kByte);
     at::Tensor image = at::empty({3, height, width}, fopt), alpha = at::empty({1, height, width}, fopt);
     at::Tensor prim = at::empty({(int64_t)lfs_fastgs_primitive_workspace_bytes(N, (uint32_t)width, (uint32_t)height)}, bopt);
     at::Tensor n_inst_dev = at::zeros({1}, means.options().dtype(at::kLong));
-    const lfs_fastgs_view view = fastgs_view(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c_c, cam_c, active_sh_bases, width,
-                                             height, focal_x, focal_y, center_x, center_y, near_plane, far_plane, prim);
-    if (filter3d_var.defined()) {   // the 3D smoothing filter: the _ex entry with the [N] variances (undefined: the entry every other mode has always called)
-        LFS_CHECK_INPUT(filter3d_var);
-        TORCH_CHECK(filter3d_var.numel() == (int64_t)N && filter3d_var.scalar_type() == at::kFloat, "filter3d_var must hold N floats");
-        const lfs_fastgs_view_ext ext{filter3d_var.data_ptr<float>()};
-        check_rc(lfs_fastgs_view_preprocess_ex(&view, flags, &ext, n_inst_dev.data_ptr<int64_t>(), cur_stream()), "lfs::fastgs_forward_wrapper_filter3d (preprocess)");
+    const lfs_fastgs_view view = fastgs_view(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c_c, cam_c, camera, prim);
+    if (options.filter3d_var.defined()) {   // the _ex entry with the variances (undefined: the entry every other mode has always called)
+        const lfs_fastgs_view_ext ext = fastgs_ext(options.filter3d_var, N);
+        check_rc(lfs_fastgs_view_preprocess_ex(&view, flags, &ext, n_inst_dev.data_ptr<int64_t>(), cur_stream()), caller, " (preprocess)");
     } else
-    check_rc(lfs_fastgs_view_preprocess(&view, flags, n_inst_dev.data_ptr<int64_t>(), cur_stream()), "fast_gs::rasterization::forward (preprocess)");
+    check_rc(lfs_fastgs_view_preprocess(&view, flags, n_inst_dev.data_ptr<int64_t>(), cur_stream()), caller, " (preprocess)");
     const int64_t n_instances = n_inst_dev.item<int64_t>(); // the host sync of forward.cu:114-117
     at::Tensor inst = at::empty({(int64_t)std::max<size_t>(256, lfs_fastgs_instance_workspace_bytes((uint32_t)width, (uint32_t)height, n_instances))}, bopt);
     at::Tensor depth;
     if (want_depth) depth = at::empty({1, height, width}, fopt);
     check_rc(lfs_fastgs_view_render(&view, n_instances, inst.data_ptr(), (size_t)inst.numel(), image.data_ptr<float>(), alpha.data_ptr<float>(),
-                                    want_depth ? depth.data_ptr<float>() : nullptr, cur_stream()),
-             want_depth ? "lfs::fastgs_forward_wrapper_depth (render)" : "fast_gs::rasterization::forward (render)");
-    return {image, alpha, depth, prim, inst, n_instances};
+                                    want_depth ? depth.data_ptr<float>() : nullptr, cur_stream()), caller, " (render)");
+    return {image, alpha, depth, prim, inst, (int)n_instances};
 }
 
-// the backward of every mode: grad_depth undefined -> no depth gradient; grad_w2c is asked for when w2c requires grad (pose optimisation,
-// rasterization_api.cu:133-136) and returned as the 7th element, shaped like w2c, otherwise that element stays an undefined tensor
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> fastgs_backward_impl(
+// the backward of every mode: grad_w2c is asked for when w2c requires grad (pose optimisation, rasterization_api.cu:133-136)
+lfs::FastgsGrads lfs::fastgs_backward(
     torch::Tensor& densification_info, const torch::Tensor& grad_image, const torch::Tensor& grad_alpha, const torch::Tensor& grad_depth, const torch::Tensor& alpha,
     const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& sh_coefficients_rest,
-    const torch::Tensor& per_primitive_buffers, const torch::Tensor& per_instance_buffers, const torch::Tensor& w2c, const torch::Tensor& cam_position,
-    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane, const int n_instances, const char* what, const torch::Tensor& filter3d_var = torch::Tensor()) {
+    const torch::Tensor& per_primitive_buffers, const torch::Tensor& per_instance_buffers, const int n_instances, const FastgsCamera& camera,
+    const FastgsOptions& options, const char* caller) {
     LFS_DEVICE_GUARD(means);
     const uint32_t N = (uint32_t)means.size(0), total_rest = (uint32_t)sh_coefficients_rest.size(1);
+    const torch::Tensor& w2c = camera.w2c;
     const auto fopt = means.options().dtype(at::kFloat);
     at::Tensor g_means = at::empty({N, 3}, fopt), g_scales = at::empty({N, 3}, fopt), g_rot = at::empty({N, 4}, fopt), g_opac = at::empty({N, 1}, fopt);
     at::Tensor g_sh0 = at::empty({N, 1, 3}, fopt), g_shr = at::empty({N, (int64_t)total_rest, 3}, fopt);
-    const at::Tensor gi = grad_image.contiguous(), ga = grad_alpha.contiguous(), al = alpha.contiguous(), w2c_c = w2c.contiguous(), cam_c = cam_position.contiguous();
+    const at::Tensor gi = grad_image.contiguous(), ga = grad_alpha.contiguous(), al = alpha.contiguous(), w2c_c = w2c.contiguous(), cam_c = camera.cam_position.contiguous();
     at::Tensor gd;
     if (grad_depth.defined()) {
         gd = grad_depth.contiguous();
-        TORCH_CHECK(gd.numel() == (int64_t)width * height, "grad_depth must hold one [1,H,W] plane");
+        TORCH_CHECK(gd.numel() == (int64_t)camera.width * camera.height, "grad_depth must hold one [1,H,W] plane");
     }
     const bool dens = densification_info.defined() && densification_info.dim() > 0 && densification_info.size(0) > 0;
     at::Tensor g_w2c, ws;
@@ -602,8 +604,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Te
         g_w2c = at::empty_like(w2c_c);
         ws = at::empty({(int64_t)lfs_fastgs_w2c_workspace_bytes(N)}, means.options().dtype(at::kByte));
     }
-    const lfs_fastgs_view view = fastgs_view(means, scales_raw, rotations_raw, at::Tensor(), at::Tensor(), sh_coefficients_rest, w2c_c, cam_c, active_sh_bases, width, height,
-                                             focal_x, focal_y, center_x, center_y, near_plane, far_plane, per_primitive_buffers);
+    const lfs_fastgs_view view = fastgs_view(means, scales_raw, rotations_raw, at::Tensor(), at::Tensor(), sh_coefficients_rest, w2c_c, cam_c, camera, per_primitive_buffers);
     lfs_fastgs_view_backward_args args{};
     args.n_instances = n_instances;
     args.instance_workspace = per_instance_buffers.data_ptr();
@@ -615,99 +616,27 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Te
     args.grad_opacities_raw = g_opac.data_ptr<float>(); args.grad_sh_coefficients_0 = g_sh0.data_ptr<float>();
     args.grad_sh_coefficients_rest = total_rest ? g_shr.data_ptr<float>() : nullptr;
     if (g_w2c.defined()) { args.grad_w2c = g_w2c.data_ptr<float>(); args.w2c_workspace = ws.data_ptr(); args.w2c_workspace_bytes = (size_t)ws.numel(); }
-    if (filter3d_var.defined()) {
-        LFS_CHECK_INPUT(filter3d_var);
-        TORCH_CHECK(filter3d_var.numel() == (int64_t)N && filter3d_var.scalar_type() == at::kFloat, "filter3d_var must hold N floats");
-        const lfs_fastgs_view_ext ext{filter3d_var.data_ptr<float>()};
-        check_rc(lfs_fastgs_view_backward_ex(&view, &args, &ext, cur_stream()), what);
+    const char* const stage = g_w2c.defined() ? " (grad_w2c)" : "";
+    if (options.filter3d_var.defined()) {
+        const lfs_fastgs_view_ext ext = fastgs_ext(options.filter3d_var, N);
+        check_rc(lfs_fastgs_view_backward_ex(&view, &args, &ext, cur_stream()), caller, stage);
     } else
-    check_rc(lfs_fastgs_view_backward(&view, &args, cur_stream()), what);
+    check_rc(lfs_fastgs_view_backward(&view, &args, cur_stream()), caller, stage);
     return {g_means, g_scales, g_rot, g_opac, g_sh0, g_shr, g_w2c};
 }
-} // namespace
 
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int>
-lfs::fastgs_forward_wrapper_ex(
-    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
-    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
-    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane, const bool antialiased) {
-    const FastgsForward f = fastgs_forward_impl(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c, cam_position, active_sh_bases,
-                                                width, height, focal_x, focal_y, center_x, center_y, near_plane, far_plane, antialiased ? LFS_FASTGS_ANTIALIASED : 0u, false);
-    at::Tensor none = at::empty({0}, means.options().dtype(at::kByte));
-    return {f.image, f.alpha, f.prim, none, f.inst, none.clone(), 0, (int)f.n_instances, 0, 0, 0};
-}
-
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int>
-lfs::fastgs_forward_wrapper_absgrad(
-    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
-    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
-    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane, const bool antialiased, const bool absgrad) {
-    const FastgsForward f = fastgs_forward_impl(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c, cam_position, active_sh_bases,
-                                                width, height, focal_x, focal_y, center_x, center_y, near_plane, far_plane,
-                                                (antialiased ? LFS_FASTGS_ANTIALIASED : 0u) | (absgrad ? LFS_FASTGS_ABSGRAD : 0u), false);
-    at::Tensor none = at::empty({0}, means.options().dtype(at::kByte));
-    return {f.image, f.alpha, f.prim, none, f.inst, none.clone(), 0, (int)f.n_instances, 0, 0, 0};
-}
-
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int>
-lfs::fastgs_forward_wrapper_filter3d(
-    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
-    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
-    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane, const bool antialiased, const torch::Tensor& filter3d_var) {
-    TORCH_CHECK(filter3d_var.defined(), "filter3d_var must hold N floats");
-    const FastgsForward f = fastgs_forward_impl(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c, cam_position, active_sh_bases,
-                                                width, height, focal_x, focal_y, center_x, center_y, near_plane, far_plane, antialiased ? LFS_FASTGS_ANTIALIASED : 0u, false,
-                                                filter3d_var);
-    at::Tensor none = at::empty({0}, means.options().dtype(at::kByte));
-    return {f.image, f.alpha, f.prim, none, f.inst, none.clone(), 0, (int)f.n_instances, 0, 0, 0};
-}
-
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> lfs::fastgs_backward_wrapper_filter3d(
-    torch::Tensor& densification_info, const torch::Tensor& grad_image, const torch::Tensor& grad_alpha, const torch::Tensor& alpha,
-    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& sh_coefficients_rest,
-    const torch::Tensor& per_primitive_buffers, const torch::Tensor& per_instance_buffers, const torch::Tensor& w2c, const torch::Tensor& cam_position,
-    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane, const int n_instances, const torch::Tensor& filter3d_var) {
-    TORCH_CHECK(filter3d_var.defined(), "filter3d_var must hold N floats");
-    return fastgs_backward_impl(densification_info, grad_image, grad_alpha, torch::Tensor(), alpha, means, scales_raw, rotations_raw, sh_coefficients_rest, per_primitive_buffers,
-                                per_instance_buffers, w2c, cam_position, active_sh_bases, width, height, focal_x, focal_y, center_x, center_y, near_plane, far_plane,
-                                n_instances, "lfs::fastgs_backward_wrapper_filter3d", filter3d_var);
-}
-
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int> lfs::fastgs_forward_wrapper_depth(
-    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
-    const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
-    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane, const bool antialiased, const bool inverse_depth) {
-    const uint32_t flags = (antialiased ? LFS_FASTGS_ANTIALIASED : 0u) | (inverse_depth ? LFS_FASTGS_INVDEPTH : LFS_FASTGS_DEPTH);
-    const FastgsForward f = fastgs_forward_impl(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c, cam_position, active_sh_bases,
-                                                width, height, focal_x, focal_y, center_x, center_y, near_plane, far_plane, flags, true);
-    return {f.image, f.alpha, f.depth, f.prim, f.inst, (int)f.n_instances};
-}
-
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> lfs::fastgs_backward_wrapper_depth(
-    torch::Tensor& densification_info, const torch::Tensor& grad_image, const torch::Tensor& grad_alpha, const torch::Tensor& grad_depth, const torch::Tensor& alpha,
-    const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& sh_coefficients_rest,
-    const torch::Tensor& per_primitive_buffers, const torch::Tensor& per_instance_buffers, const torch::Tensor& w2c, const torch::Tensor& cam_position,
-    const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
-    const float center_y, const float near_plane, const float far_plane, const int n_instances) {
-    TORCH_CHECK(grad_depth.defined(), "grad_depth must hold one [1,H,W] plane");
-    return fastgs_backward_impl(densification_info, grad_image, grad_alpha, grad_depth, alpha, means, scales_raw, rotations_raw, sh_coefficients_rest, per_primitive_buffers,
-                                per_instance_buffers, w2c, cam_position, active_sh_bases, width, height, focal_x, focal_y, center_x, center_y, near_plane, far_plane,
-                                n_instances, "lfs::fastgs_backward_wrapper_depth");
-}
-
+// the reference's two symbols: the pair above with default options
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int, int, int, int, int>
 fast_gs::rasterization::forward_wrapper(
     const torch::Tensor& means, const torch::Tensor& scales_raw, const torch::Tensor& rotations_raw, const torch::Tensor& opacities_raw,
     const torch::Tensor& sh_coefficients_0, const torch::Tensor& sh_coefficients_rest, const torch::Tensor& w2c, const torch::Tensor& cam_position,
     const int active_sh_bases, const int width, const int height, const float focal_x, const float focal_y, const float center_x,
     const float center_y, const float near_plane, const float far_plane) {
-    return lfs::fastgs_forward_wrapper_ex(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest, w2c, cam_position, active_sh_bases,
-                                          width, height, focal_x, focal_y, center_x, center_y, near_plane, far_plane, false);
+    const lfs::FastgsForwardOut f = lfs::fastgs_forward(means, scales_raw, rotations_raw, opacities_raw, sh_coefficients_0, sh_coefficients_rest,
+                                                        {w2c, cam_position, active_sh_bases, width, height, focal_x, focal_y, center_x, center_y, near_plane, far_plane}, {},
+                                                        "fast_gs::rasterization::forward");
+    at::Tensor none = at::empty({0}, means.options().dtype(at::kByte));
+    return {f.image, f.alpha, f.per_primitive_buffers, none, f.per_instance_buffers, none.clone(), 0, f.n_instances, 0, 0, 0};
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
@@ -721,9 +650,11 @@ fast_gs::rasterization::backward_wrapper(
     const int n_buckets, const int primitive_primitive_indices_selector, const int instance_primitive_indices_selector) {
     (void)image; (void)per_tile_buffers; (void)per_bucket_buffers; (void)n_visible_primitives; (void)n_buckets;
     (void)primitive_primitive_indices_selector; (void)instance_primitive_indices_selector;
-    return fastgs_backward_impl(densification_info, grad_image, grad_alpha, torch::Tensor(), alpha, means, scales_raw, rotations_raw, sh_coefficients_rest,
-                                per_primitive_buffers, per_instance_buffers, w2c, cam_position, active_sh_bases, width, height, focal_x, focal_y, center_x, center_y,
-                                near_plane, far_plane, n_instances, w2c.requires_grad() ? "fast_gs::rasterization::backward (grad_w2c)" : "fast_gs::rasterization::backward");
+    const lfs::FastgsGrads g = lfs::fastgs_backward(densification_info, grad_image, grad_alpha, torch::Tensor(), alpha, means, scales_raw, rotations_raw, sh_coefficients_rest,
+                                                    per_primitive_buffers, per_instance_buffers, n_instances,
+                                                    {w2c, cam_position, active_sh_bases, width, height, focal_x, focal_y, center_x, center_y, near_plane, far_plane}, {},
+                                                    "fast_gs::rasterization::backward");
+    return {g.means, g.scales_raw, g.rotations_raw, g.opacities_raw, g.sh0, g.sh_rest, g.w2c};
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> fusedssim(float C1, float C2, torch::Tensor& img1, torch::Tensor& img2, bool train) {

@@ -57,50 +57,35 @@ PYBIND11_MODULE(_lfs_torch_ops, m) {
               return fast_gs::rasterization::forward_wrapper(means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest, w2c, cam_position,
                                                              active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane);
           });
-    m.def("fastgs_forward_wrapper_ex",
+    // lfs::fastgs_forward / lfs::fastgs_backward: FastgsCamera and FastgsOptions travel flat, the options as keywords (depth: 0 none, 1 z, 2 1 / z); an undefined tensor
+    // (no depth plane, no grad_w2c) arrives as None
+    m.def("fastgs_forward",
           [](at::Tensor means, at::Tensor scales_raw, at::Tensor rotations_raw, at::Tensor opacities_raw, at::Tensor sh0, at::Tensor sh_rest, at::Tensor w2c,
              at::Tensor cam_position, int active_sh_bases, int width, int height, float fx, float fy, float cx, float cy, float near_plane, float far_plane,
-             bool antialiased) {
-              return lfs::fastgs_forward_wrapper_ex(means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest, w2c, cam_position,
-                                                    active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane, antialiased);
-          });
-    m.def("fastgs_forward_wrapper_absgrad",
-          [](at::Tensor means, at::Tensor scales_raw, at::Tensor rotations_raw, at::Tensor opacities_raw, at::Tensor sh0, at::Tensor sh_rest, at::Tensor w2c,
-             at::Tensor cam_position, int active_sh_bases, int width, int height, float fx, float fy, float cx, float cy, float near_plane, float far_plane,
-             bool antialiased, bool absgrad) {
-              return lfs::fastgs_forward_wrapper_absgrad(means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest, w2c, cam_position,
-                                                         active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane, antialiased, absgrad);
-          });
-    m.def("fastgs_forward_wrapper_depth",
-          [](at::Tensor means, at::Tensor scales_raw, at::Tensor rotations_raw, at::Tensor opacities_raw, at::Tensor sh0, at::Tensor sh_rest, at::Tensor w2c,
-             at::Tensor cam_position, int active_sh_bases, int width, int height, float fx, float fy, float cx, float cy, float near_plane, float far_plane,
-             bool antialiased, bool inverse_depth) {
-              return lfs::fastgs_forward_wrapper_depth(means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest, w2c, cam_position,
-                                                       active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane, antialiased, inverse_depth);
-          });
-    m.def("fastgs_backward_wrapper_depth",
-          [](at::Tensor densification_info, at::Tensor grad_image, at::Tensor grad_alpha, at::Tensor grad_depth, at::Tensor alpha, at::Tensor means,
-             at::Tensor scales_raw, at::Tensor rotations_raw, at::Tensor sh_rest, at::Tensor prim, at::Tensor inst, at::Tensor w2c, at::Tensor cam_position,
-             int active_sh_bases, int width, int height, float fx, float fy, float cx, float cy, float near_plane, float far_plane, int n_instances) {
-              return lfs::fastgs_backward_wrapper_depth(densification_info, grad_image, grad_alpha, grad_depth, alpha, means, scales_raw, rotations_raw, sh_rest, prim,
-                                                        inst, w2c, cam_position, active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane, n_instances);
-          });
-    m.def("fastgs_forward_wrapper_filter3d",
-          [](at::Tensor means, at::Tensor scales_raw, at::Tensor rotations_raw, at::Tensor opacities_raw, at::Tensor sh0, at::Tensor sh_rest, at::Tensor w2c,
-             at::Tensor cam_position, int active_sh_bases, int width, int height, float fx, float fy, float cx, float cy, float near_plane, float far_plane,
-             bool antialiased, at::Tensor filter3d_var) {
-              return lfs::fastgs_forward_wrapper_filter3d(means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest, w2c, cam_position,
-                                                          active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane, antialiased, filter3d_var);
-          });
-    m.def("fastgs_backward_wrapper_filter3d",
-          [](at::Tensor densification_info, at::Tensor grad_image, at::Tensor grad_alpha, at::Tensor alpha, at::Tensor means,
+             bool antialiased, int depth, bool absgrad, OptT filter3d_var) {
+              const auto f = lfs::fastgs_forward(means, scales_raw, rotations_raw, opacities_raw, sh0, sh_rest,
+                                                 {w2c, cam_position, active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane},
+                                                 {antialiased, (lfs::FastgsDepth)depth, absgrad, filter3d_var.value_or(at::Tensor())});
+              return std::make_tuple(f.image, f.alpha, f.depth, f.per_primitive_buffers, f.per_instance_buffers, f.n_instances);
+          }, py::arg("means"), py::arg("scales_raw"), py::arg("rotations_raw"), py::arg("opacities_raw"), py::arg("sh0"), py::arg("sh_rest"), py::arg("w2c"),
+             py::arg("cam_position"), py::arg("active_sh_bases"), py::arg("width"), py::arg("height"), py::arg("fx"), py::arg("fy"), py::arg("cx"), py::arg("cy"),
+             py::arg("near_plane"), py::arg("far_plane"), py::arg("antialiased") = false, py::arg("depth") = 0, py::arg("absgrad") = false,
+             py::arg("filter3d_var") = py::none());
+    m.def("fastgs_backward",
+          [](at::Tensor densification_info, at::Tensor grad_image, at::Tensor grad_alpha, OptT grad_depth, at::Tensor alpha, at::Tensor means,
              at::Tensor scales_raw, at::Tensor rotations_raw, at::Tensor sh_rest, at::Tensor prim, at::Tensor inst, at::Tensor w2c, at::Tensor cam_position,
              int active_sh_bases, int width, int height, float fx, float fy, float cx, float cy, float near_plane, float far_plane, int n_instances,
-             at::Tensor filter3d_var) {
-              return lfs::fastgs_backward_wrapper_filter3d(densification_info, grad_image, grad_alpha, alpha, means, scales_raw, rotations_raw, sh_rest, prim,
-                                                           inst, w2c, cam_position, active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane, n_instances,
-                                                           filter3d_var);
-          });
+             OptT filter3d_var) {
+              lfs::FastgsOptions options;
+              options.filter3d_var = filter3d_var.value_or(at::Tensor());
+              const auto g = lfs::fastgs_backward(densification_info, grad_image, grad_alpha, grad_depth.value_or(at::Tensor()), alpha, means, scales_raw, rotations_raw,
+                                                  sh_rest, prim, inst, n_instances,
+                                                  {w2c, cam_position, active_sh_bases, width, height, fx, fy, cx, cy, near_plane, far_plane}, options);
+              return std::make_tuple(g.means, g.scales_raw, g.rotations_raw, g.opacities_raw, g.sh0, g.sh_rest, g.w2c);
+          }, py::arg("densification_info"), py::arg("grad_image"), py::arg("grad_alpha"), py::arg("grad_depth"), py::arg("alpha"), py::arg("means"),
+             py::arg("scales_raw"), py::arg("rotations_raw"), py::arg("sh_rest"), py::arg("prim"), py::arg("inst"), py::arg("w2c"), py::arg("cam_position"),
+             py::arg("active_sh_bases"), py::arg("width"), py::arg("height"), py::arg("fx"), py::arg("fy"), py::arg("cx"), py::arg("cy"), py::arg("near_plane"),
+             py::arg("far_plane"), py::arg("n_instances"), py::arg("filter3d_var") = py::none());
     m.def("fastgs_backward_wrapper",
           [](at::Tensor densification_info, at::Tensor grad_image, at::Tensor grad_alpha, at::Tensor image, at::Tensor alpha, at::Tensor means,
              at::Tensor scales_raw, at::Tensor rotations_raw, at::Tensor sh_rest, at::Tensor prim, at::Tensor tile, at::Tensor inst, at::Tensor bucket,

@@ -252,15 +252,15 @@ def test_libtorch_route_matches_the_ctypes_route_bit_for_bit(lfs):
     none = torch.empty(0, device=DEV)
     with _deterministic(lfs):
         for aa in (False, True):
-            image, alpha, prim, tile, inst, bucket, n_vis, n_inst, n_buckets, s0, s1 = m.fastgs_forward_wrapper_absgrad(*a, cam, *fr, aa, True)
+            image, alpha, _, prim, inst, n_inst = m.fastgs_forward(*a, cam, *fr, antialiased=aa, absgrad=True)
             d1 = torch.zeros(2, N, device=DEV)
-            g1 = m.fastgs_backward_wrapper(d1, t(gi), t(ga), image, alpha, a[0], a[1], a[2], a[5], prim, tile, inst, bucket, a[6], cam, *fr, n_vis, n_inst, n_buckets, s0, s1)
+            g1 = m.fastgs_backward_wrapper(d1, t(gi), t(ga), image, alpha, a[0], a[1], a[2], a[5], prim, none, inst, none, a[6], cam, *fr, 0, n_inst, 0, 0, 0)
             out = _run(sc, gi, ga, True, aa=aa)
             assert n_inst == out["n_inst"] and torch.equal(image, out["image"]) and torch.equal(alpha, out["alpha"])
             assert torch.equal(d1, out["dens"]) and float(d1[1].sum()) > 0
             for p, q in zip(g1[:6], out["grads"]):
                 assert torch.equal(p.reshape(q.shape), q)
-            off = m.fastgs_forward_wrapper_absgrad(*a, cam, *fr, aa, False)    # absgrad = false: fastgs_forward_wrapper_ex
+            off = m.fastgs_forward(*a, cam, *fr, antialiased=aa, absgrad=False)    # absgrad = false: the default densification_info
             d0 = torch.zeros(2, N, device=DEV)
-            m.fastgs_backward_wrapper(d0, t(gi), t(ga), off[0], off[1], a[0], a[1], a[2], a[5], off[2], off[3], off[4], off[5], a[6], cam, *fr, off[6], off[7], off[8], off[9], off[10])
+            m.fastgs_backward_wrapper(d0, t(gi), t(ga), off[0], off[1], a[0], a[1], a[2], a[5], off[3], none, off[4], none, a[6], cam, *fr, 0, off[5], 0, 0, 0)
             assert torch.equal(d0, _run(sc, gi, ga, False, aa=aa)["dens"]) and not torch.equal(d0, d1)

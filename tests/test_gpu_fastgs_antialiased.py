@@ -313,12 +313,12 @@ def test_libtorch_route_matches_the_ctypes_route_bit_for_bit(lfs):
     gi, ga = [t(x) for x in _upstream(sc)]
     none = torch.empty(0, device=DEV)
     with _deterministic(lfs):
-        image, alpha, prim, tile, inst, bucket, n_vis, n_inst, n_buckets, s0, s1 = m.fastgs_forward_wrapper_ex(*a, cam, *fr, True)
-        g1 = m.fastgs_backward_wrapper(none, gi, ga, image, alpha, a[0], a[1], a[2], a[5], prim, tile, inst, bucket, a[6], cam, *fr, n_vis, n_inst, n_buckets, s0, s1)
+        image, alpha, _, prim, inst, n_inst = m.fastgs_forward(*a, cam, *fr, antialiased=True)
+        g1 = m.fastgs_backward_wrapper(none, gi, ga, image, alpha, a[0], a[1], a[2], a[5], prim, none, inst, none, a[6], cam, *fr, 0, n_inst, 0, 0, 0)
         s = fastgs.FastGSSettings(cam, *fr, True)
         img2, al2, pws, iws, n2 = fastgs.forward_wrapper(*a, s)
         g2 = fastgs.backward_wrapper(None, gi, ga, img2, al2, a[0], a[1], a[2], a[4], a[5], pws, iws, a[6], s, n2)
-        img0 = m.fastgs_forward_wrapper_ex(*a, cam, *fr, False)[0]
+        img0 = m.fastgs_forward(*a, cam, *fr, antialiased=False)[0]
         img_ref = m.fastgs_forward_wrapper(*a, cam, *fr)[0]
     assert n_inst == n2 and torch.equal(image, img2) and torch.equal(alpha, al2)
     for p, q in zip(g1[:6], g2):

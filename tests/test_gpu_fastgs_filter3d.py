@@ -450,12 +450,12 @@ def test_libtorch_route_matches_the_ctypes_route_bit_for_bit(lfs):
     gi, ga = [t(x) for x in aa._upstream(sc)]
     none = torch.empty(0, device=DEV)
     with aa._deterministic(lfs):
-        image, alpha, prim, _, inst, _, _, n_inst, _, _, _ = m.fastgs_forward_wrapper_filter3d(*a, cam, *fr, True, v)
-        g1 = m.fastgs_backward_wrapper_filter3d(none, gi, ga, alpha, a[0], a[1], a[2], a[5], prim, inst, a[6], cam, *fr, n_inst, v)
+        image, alpha, _, prim, inst, n_inst = m.fastgs_forward(*a, cam, *fr, antialiased=True, filter3d_var=v)
+        g1 = m.fastgs_backward(none, gi, ga, None, alpha, a[0], a[1], a[2], a[5], prim, inst, a[6], cam, *fr, n_inst, filter3d_var=v)
         s = fastgs.FastGSSettings(cam, *fr, True, "none", v)
         img2, al2, pws, iws, n2 = fastgs.forward_wrapper(*a, s)
         g2 = fastgs.backward_wrapper(None, gi, ga, img2, al2, a[0], a[1], a[2], a[4], a[5], pws, iws, a[6], s, n2)
-        img_aa = m.fastgs_forward_wrapper_ex(*a, cam, *fr, True)[0]
+        img_aa = m.fastgs_forward(*a, cam, *fr, antialiased=True)[0]
     assert n_inst == n2 and torch.equal(image, img2) and torch.equal(alpha, al2)
     for p, q in zip(g1[:6], g2):
         assert torch.equal(p.reshape(q.shape), q)
