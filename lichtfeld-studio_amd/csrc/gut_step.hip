@@ -71,16 +71,24 @@ bool step_ws(void* base, uint32_t N, uint32_t W, uint32_t H, uint32_t tile, int6
     return true;
 }
 
-struct Front { lfs_cameras cams; const int32_t* offsets; };
+struct Front { lfs_cameras cams; RasterScene scene; RasterLists lists; RasterWorkspace ws; };   // (scene.cams points at cams: filled in place, not copied)
 
-// the camera block and the tile offsets every guarded rasterizer call of a view takes
-void front_of(const lfs_gut_step_args* a, const StepWs& w, Front& f) {
+// what every guarded rasterizer call of a view takes: the camera block, the scene, the lists (count on the device, sized for `capacity`) and the workspace
+void front_of(const lfs_gut_step_args* a, const StepWs& w, int64_t capacity, Front& f) {
     const uint32_t tile = a->tile_size, tw = (a->image_width + tile - 1) / tile, th = (a->image_height + tile - 1) / tile;
     f.cams = lfs_cameras{};
     f.cams.C = 1; f.cams.image_width = a->image_width; f.cams.image_height = a->image_height; f.cams.camera_model = LFS_CAMERA_PINHOLE; f.cams.rs_type = LFS_SHUTTER_GLOBAL;
     f.cams.viewmats0 = a->viewmat; f.cams.Ks = a->Kmat;
-    f.offsets = isect_workspace_offsets(w.isect_ws, 1, a->N, tw, th);
+    f.scene = RasterScene{};
+    f.scene.N = a->N; f.scene.channels = 3; f.scene.means = a->means; f.scene.quats = w.quats; f.scene.scales = w.scales; f.scene.colors = w.colors;
+    f.scene.opacities = w.opacities; f.scene.backgrounds = a->background; f.scene.cams = &f.cams; f.scene.tile_size = tile;
+    f.lists = RasterLists{isect_workspace_offsets(w.isect_ws, 1, a->N, tw, th), w.flatten_ids, -1, capacity};
+    f.ws = RasterWorkspace{w.raster_ws, w.raster_ws_bytes};
 }
+// the groups of the finish and tail launchers, out of the argument block and the workspace
+GutParams params_of(const lfs_gut_step_args* a) { return GutParams{a->N, a->K, a->sh_degree, a->means, a->sh0, a->shN, a->raw_scales, a->raw_quats, a->raw_opacities}; }
+GutActivated activated_of(const StepWs& w) { return GutActivated{w.quats, w.scales, w.opacities}; }
+GutAdam adam_of(const lfs_gut_step_args* a, const StepWs& w) { return GutAdam{a->exp_avg, a->exp_avg_sq, a->adam, w.abort_flag}; }
 
 // what a call needs of its argument block: the forward's tensors only; all six Adam states; or all six with shN's optional (FusedAdam skips the frozen group)
 enum class Need { Forward, Adam, AdamFrozenShN };
@@ -117,7 +125,7 @@ int enqueue_forward(const lfs_gut_step_args* a, const StepWs& w, int64_t capacit
                     bool colors_ready = false) {   // colors_ready: w.colors holds this view's SH colours already (the previous step's fused tail wrote them)
     const uint32_t N = a->N, W = a->image_width, H = a->image_height, tile = a->tile_size;
     const uint32_t tw = (W + tile - 1) / tile, th = (H + tile - 1) / tile;
-    front_of(a, w, f);
+    front_of(a, w, capacity, f);
     const lfs_ut_params ut{0.1f, 2.f, 0.f, 0.1f, 1};   // Cameras.h:27-61 defaults, as the trainer passes them (rasterizer_autograd.cpp:223-234)
     // trainer constants of rasterizer.cpp:176-181: eps2d 0.3, near 0.01, far 1e4, radius_clip 0
     // the projection kernel also clears the intersection stage's per-tile totals and writes the rasterizer's camera state (first block of the raster workspace):
@@ -127,7 +135,7 @@ int enqueue_forward(const lfs_gut_step_args* a, const StepWs& w, int64_t capacit
     // visible Gaussian itself: raster_pack_kernel's second pass over the Gaussians (0.040 ms, 152 MB re-read) is gone. Debug bit 6: the round-3 order (A/B, tests).
     const bool pack_here = !(lfs_get_debug_flags() & 64u);
     void *recs = nullptr, *cull = nullptr;
-    raster_workspace_parts(w.raster_ws, N, nullptr, &recs, &cull);
+    raster_workspace_parts(w.raster_ws, N, &recs, &cull);
     int rc = LFS_OK;
     if (pack_here && !colors_ready) {
         rc = sh_model_fwd_impl(N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, nullptr, w.colors, s);
@@ -149,52 +157,37 @@ int enqueue_forward(const lfs_gut_step_args* a, const StepWs& w, int64_t capacit
     rc = isect_emit_impl(1, N, w.means2d, w.radii, w.depths, tile, tw, th, 1, -1, w.tiles_per_gauss, w.isect_ids, w.flatten_ids, nullptr, w.binned, -1, w.isect_ws,
                          w.isect_ws_bytes, s, &guard);
     if (rc) return rc;
-    return raster_fwd_guarded(N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &f.cams, tile, f.offsets, w.flatten_ids, capacity, w.render, w.alpha,
-                              w.last_ids, w.raster_ws, w.raster_ws_bytes, s, /*cams_ready=*/true, /*records_ready=*/pack_here);
+    return raster_forward(f.scene, f.lists, f.ws, RasterFwdOut{w.render, w.alpha, w.last_ids, /*cams_ready=*/true, /*records_ready=*/pack_here}, s);
 }
 
 // accumulator-rows rasterizer backward of the view in the workspace. v_render NULL: args->target_chw is the loss target, the clamped MSE is folded in; otherwise
 // v_render [H,W,3] is dL/d(render)
-int enqueue_backward(const lfs_gut_step_args* a, const StepWs& w, const Front& f, int64_t capacity, const float* v_render, hipStream_t s) {
-    if (v_render == nullptr)
-        return raster_bwd_mse_acc_guarded(a->N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &f.cams, a->tile_size, f.offsets, w.flatten_ids, capacity,
-                                          w.render, w.alpha, w.last_ids, a->target_chw, a->loss_weight, w.raster_ws, w.raster_ws_bytes, s);
-    return raster_bwd_acc_guarded(a->N, a->means, w.quats, w.scales, w.colors, w.opacities, a->background, &f.cams, a->tile_size, f.offsets, w.flatten_ids, capacity, w.alpha,
-                                  w.last_ids, v_render, w.raster_ws, w.raster_ws_bytes, s);
+int enqueue_backward(const lfs_gut_step_args* a, const StepWs& w, const Front& f, const float* v_render, hipStream_t s) {
+    const RasterMse mse{w.render, a->target_chw, a->loss_weight, nullptr};
+    RasterBwd b{};
+    b.render_alphas = w.alpha; b.last_ids = w.last_ids; b.v_render_colors = v_render; b.mse = v_render ? nullptr : &mse; b.prepared = true; b.rows_only = true;
+    return raster_backward(f.scene, f.lists, f.ws, b, s);
 }
 
 const float* acc_rows_of(const lfs_gut_step_args* a, const StepWs& w) {
     return reinterpret_cast<const float*>(static_cast<const char*>(w.raster_ws) + lfs_rasterize_workspace_acc_offset(1, a->N));
 }
 
-// finish + activation backward + Adam on means, raw_scales, raw_quats, raw_opacities = FusedAdam groups 0, 3, 4, 5 (lfs_gut_finish_adam's order). loss (nullable):
-// receives the fused MSE of the backward.
-int finish_adam(const lfs_gut_step_args* a, const StepWs& w, float* loss, hipStream_t s) {
-    const int grp[4] = {0, 3, 4, 5};
-    float *m[4], *v[4], sc[24];
-    for (int k = 0; k < 4; ++k) {
-        m[k] = a->exp_avg[grp[k]]; v[k] = a->exp_avg_sq[grp[k]];
-        for (int j = 0; j < 6; ++j) sc[6 * k + j] = a->adam[grp[k]][j];
-    }
-    return gut_finish_adam_impl(a->N, a->means, a->raw_scales, a->raw_quats, a->raw_opacities, w.quats, w.scales, w.opacities, w.v_dirs, m, v, sc, a->scale_reg,
-                                a->opacity_reg, loss, w.raster_ws, w.raster_ws_bytes, s, w.abort_flag);
-}
-
-// The tail as three per-Gaussian passes (SH backward + Adam on sh0 / shN, then finish + Adam on the other four tensors): the three-pass form, and what the fused-tail
-// form runs for K > 16 (no colours for the next step).
+// The tail as three per-Gaussian passes (SH backward + Adam on sh0 / shN, then finish + activation backward + Adam on means, raw_scales, raw_quats, raw_opacities): the
+// three-pass form, and what the fused-tail form runs for K > 16 (no colours for the next step). loss (nullable): receives the fused MSE of the backward.
 int three_pass_tail(const lfs_gut_step_args* a, const StepWs& w, float* loss, hipStream_t s) {
     const int rc = sh_model_bwd_adam_all_impl(a->N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, w.radii, w.colors, acc_rows_of(a, w), w.v_dirs, a->exp_avg[1],
                                               a->exp_avg_sq[1], a->adam[1], a->exp_avg[2], a->exp_avg_sq[2], a->adam[2], s, w.abort_flag);
-    return rc ? rc : finish_adam(a, w, loss, s);
+    if (rc) return rc;
+    return gut_finish_adam_impl(params_of(a), activated_of(w), adam_of(a, w), GutRegs{a->scale_reg, a->opacity_reg}, w.v_dirs, loss, RasterWorkspace{w.raster_ws, w.raster_ws_bytes}, s);
 }
 
 // The fused-tail form's tail: the three passes as ONE launch (raster.hip: gut_tail_kernel), with shN frozen and the MCMC noise on request. K > 16 (SH degree 4) has no
 // such kernel: the three passes run (the caller's next call must pass colors_ready = 0 - GutStep checks K); freeze and noise were refused by open_step.
 int enqueue_tail(const lfs_gut_step_args* a, const StepWs& w, const lfs_gut_step_options& o, const float* next_viewmat, float* loss, hipStream_t s) {
     if (a->K > 16) return three_pass_tail(a, w, loss, s);
-    return gut_tail_impl(a->N, a->K, a->sh_degree, a->means, a->sh0, a->shN, a->raw_scales, a->raw_quats, a->raw_opacities, w.quats, w.scales, w.opacities, a->viewmat,
-                         next_viewmat, w.radii, w.colors, a->exp_avg, a->exp_avg_sq, a->adam, a->scale_reg, a->opacity_reg, loss, w.raster_ws, w.raster_ws_bytes, s,
-                         w.abort_flag, o.freeze_shN != 0, o.noise, o.noise_lr);
+    const GutTailView view{a->viewmat, next_viewmat, w.radii, w.colors, o.freeze_shN != 0, o.noise, o.noise_lr};
+    return gut_tail_impl(params_of(a), activated_of(w), adam_of(a, w), GutRegs{a->scale_reg, a->opacity_reg}, view, loss, RasterWorkspace{w.raster_ws, w.raster_ws_bytes}, s);
 }
 
 // ---- the training step: ONE sequence (open -> forward -> [loss kernels] -> backward -> tail) in two forms ----------------------------------------------------
@@ -241,7 +234,7 @@ int train_step_impl(Form form, const lfs_gut_step_args* a, const lfs_gut_step_op
                                           maps_bytes, stream);
         if (rc) return rc;
     }
-    rc = enqueue_backward(a, w, f, capacity, v_render, s);
+    rc = enqueue_backward(a, w, f, v_render, s);
     if (rc) return rc;
     float* const tail_loss = ssim ? nullptr : a->loss;
     if (form == Form::FusedTail) return enqueue_tail(a, w, o, next_viewmat, tail_loss, s);
@@ -312,8 +305,8 @@ extern "C" int lfs_gut_view_backward_sh(const lfs_gut_step_args* a, int64_t capa
     if (inline_shN && (accumulate || !a->exp_avg_sq[2])) return LFS_E_INVALID;
     if (!grads || !grads[1] || (a->K > 1 && !grads[2] && !inline_shN) || (!a->target_chw && !v_render)) return LFS_E_INVALID;
     Front f;
-    front_of(a, w, f);
-    rc = enqueue_backward(a, w, f, capacity, a->target_chw ? nullptr : v_render, s);
+    front_of(a, w, capacity, f);
+    rc = enqueue_backward(a, w, f, a->target_chw ? nullptr : v_render, s);
     if (rc) return rc;
     return sh_model_bwd_rows_impl(a->N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, w.radii, w.colors, acc_rows_of(a, w), accumulate, grads[1], grads[2], w.v_dirs,
                                   s, inline_shN ? a->exp_avg[2] : nullptr, inline_shN ? a->exp_avg_sq[2] : nullptr, inline_shN ? a->adam[2] : nullptr);
@@ -325,8 +318,8 @@ extern "C" int lfs_gut_view_backward_finish(const lfs_gut_step_args* a, int64_t 
     const int rc = open_step(a, Need::Forward, nullptr, capacity, workspace, workspace_bytes, w);
     if (rc) return rc;
     if (!grads || !grads[0] || !grads[3] || !grads[4] || !grads[5] || (a->target_chw && !a->loss)) return LFS_E_INVALID;
-    return gut_finish_grads_impl(a->N, a->means, a->raw_quats, w.quats, w.scales, w.opacities, a->scale_reg, a->opacity_reg, accumulate, grads[0], grads[3], grads[4],
-                                 grads[5], nullptr, w.v_dirs, a->target_chw ? a->loss : nullptr, w.raster_ws, w.raster_ws_bytes, (hipStream_t)stream);
+    return gut_finish_grads_impl(params_of(a), activated_of(w), GutRegs{a->scale_reg, a->opacity_reg}, GutGrads{grads[0], grads[3], grads[4], grads[5], nullptr, accumulate},
+                                 w.v_dirs, a->target_chw ? a->loss : nullptr, RasterWorkspace{w.raster_ws, w.raster_ws_bytes}, (hipStream_t)stream);
 }
 
 // The view's backward for the FACTORED gradient exchange of the replicated data-parallel layout (dist.ColorGradExchange): rasterizer backward, then the finish pass -
@@ -341,11 +334,11 @@ extern "C" int lfs_gut_view_backward_rows(const lfs_gut_step_args* a, int64_t ca
     if (rc) return rc;
     if (!grads || !grads[0] || !grads[3] || !grads[4] || !grads[5] || !v_colors_out || (!a->target_chw && !v_render) || (a->target_chw && !a->loss)) return LFS_E_INVALID;
     Front f;
-    front_of(a, w, f);
-    rc = enqueue_backward(a, w, f, capacity, a->target_chw ? nullptr : v_render, s);
+    front_of(a, w, capacity, f);
+    rc = enqueue_backward(a, w, f, a->target_chw ? nullptr : v_render, s);
     if (rc) return rc;
-    return gut_finish_grads_impl(a->N, a->means, a->raw_quats, w.quats, w.scales, w.opacities, a->scale_reg, a->opacity_reg, accumulate, grads[0], grads[3], grads[4],
-                                 grads[5], v_colors_out, nullptr, a->target_chw ? a->loss : nullptr, w.raster_ws, w.raster_ws_bytes, s);
+    return gut_finish_grads_impl(params_of(a), activated_of(w), GutRegs{a->scale_reg, a->opacity_reg}, GutGrads{grads[0], grads[3], grads[4], grads[5], v_colors_out, accumulate},
+                                 nullptr, a->target_chw ? a->loss : nullptr, RasterWorkspace{w.raster_ws, w.raster_ws_bytes}, s);
 }
 
 extern "C" int lfs_gut_view_backward(const lfs_gut_step_args* a, int64_t capacity, const float* v_render, float* const* grads /* [6] host */, int accumulate,

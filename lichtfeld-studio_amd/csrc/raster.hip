@@ -78,18 +78,30 @@ static inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 constexpr uint32_t LOSS_SLOTS = 256; // fused MSE: the wavefronts' partial sums are spread over this many addresses (one hot address costs ~0.08 ms)
 struct RasterWs { CamDev* cams; GaussRec* recs; float* acc; CullRec* cull; int32_t* cell_count; int2* cell_list; unsigned long long* det64; size_t bytes; };
 // cells = C * tiles * (tile_size/8)^2 ; the compacted per-cell lists hold at most (tile_size/8)^2 * n_isects entries
-static RasterWs raster_ws(void* base, uint32_t C, uint32_t N, uint64_t cells, uint64_t cell_entries, bool det = false) {
-    RasterWs w; char* p = (char*)base; size_t o = 0;
-    w.cams = (CamDev*)(p + o); o += align256(sizeof(CamDev) * C);
-    w.recs = (GaussRec*)(p + o); o += align256(sizeof(GaussRec) * size_t(C) * N);
-    w.acc = (float*)(p + o); o += align256(sizeof(float) * (ACC_STRIDE * size_t(C) * N + LOSS_SLOTS)); // + the fused-loss partial sums
-    w.cull = (CullRec*)(p + o); o += align256(sizeof(CullRec) * size_t(C) * N);
-    w.cell_count = (int32_t*)(p + o); o += align256(sizeof(int32_t) * cells);
-    w.cell_list = (int2*)(p + o); o += align256(sizeof(int2) * cell_entries);
-    w.det64 = nullptr;
-    if (det) { w.det64 = (unsigned long long*)(p + o); o += align256(sizeof(unsigned long long) * ACC_STRIDE * size_t(C) * N); } // deterministic backward (debug bit 4)
-    w.bytes = o;
-    return w;
+struct RasterWsOffsets { size_t cams, recs, acc, cull, cell_count, cell_list, det64, bytes; };   // byte offsets of the parts above (det64: only in the deterministic mode)
+static RasterWsOffsets raster_ws_offsets(uint32_t C, uint32_t N, uint64_t cells, uint64_t cell_entries, bool det) {
+    RasterWsOffsets at; size_t o = 0;
+    at.cams = o; o += align256(sizeof(CamDev) * C);
+    at.recs = o; o += align256(sizeof(GaussRec) * size_t(C) * N);
+    at.acc = o; o += align256(sizeof(float) * (ACC_STRIDE * size_t(C) * N + LOSS_SLOTS)); // + the fused-loss partial sums
+    at.cull = o; o += align256(sizeof(CullRec) * size_t(C) * N);
+    at.cell_count = o; o += align256(sizeof(int32_t) * cells);
+    at.cell_list = o; o += align256(sizeof(int2) * cell_entries);
+    at.det64 = o;
+    if (det) o += align256(sizeof(unsigned long long) * ACC_STRIDE * size_t(C) * N); // deterministic backward (debug bit 4)
+    at.bytes = o;
+    return at;
+}
+static RasterWs raster_ws(void* base, const RasterWsOffsets& at, bool det) {
+    char* p = (char*)base;
+    return RasterWs{(CamDev*)(p + at.cams), (GaussRec*)(p + at.recs), (float*)(p + at.acc), (CullRec*)(p + at.cull), (int32_t*)(p + at.cell_count), (int2*)(p + at.cell_list),
+                    det ? (unsigned long long*)(p + at.det64) : nullptr, at.bytes};
+}
+// a one-camera workspace up to its culling records (camera state, records, accumulator rows): all the finish and tail passes touch. false: `ws` ends before them
+static bool rows_ws(const RasterWorkspace& ws, uint32_t N, RasterWs& w) {
+    const RasterWsOffsets at = raster_ws_offsets(1, N, 0, 0, false);
+    w = raster_ws(ws.base, at, false);
+    return ws.bytes >= at.cull;
 }
 
 __global__ void cam_prep_kernel(const lfs_cameras cams, CamDev* __restrict__ out) {
@@ -1385,91 +1397,75 @@ extern "C" size_t lfs_rasterize_workspace_bytes(uint32_t C, uint32_t N, uint32_t
     cams.C = C; cams.image_width = image_width; cams.image_height = image_height;
     RasterGeom g;
     if (!raster_geom(&cams, tile_size, g) || n_isects < 0) return 0;
-    return raster_ws(nullptr, C, N, g.cells, uint64_t(g.wpt) * uint64_t(n_isects), (g_debug_flags & 16u) != 0).bytes;
+    return raster_ws_offsets(C, N, g.cells, uint64_t(g.wpt) * uint64_t(n_isects), (g_debug_flags & 16u) != 0).bytes;
 }
 size_t lfs::raster_workspace_bytes_for(uint32_t N, uint32_t image_width, uint32_t image_height, uint32_t tile_size, int64_t capacity) {
     return lfs_rasterize_workspace_bytes(1, N, 3, image_width, image_height, tile_size, capacity);
 }
 
-static int raster_mode(const lfs_cameras* cams) {
-    if (cams->rs_type != LFS_SHUTTER_GLOBAL) return lfs::RAY_ROLLING;
-    return lfs::RAY_GLOBAL;
-}
+static int raster_mode(const lfs_cameras* cams) { return cams->rs_type != LFS_SHUTTER_GLOBAL ? lfs::RAY_ROLLING : lfs::RAY_GLOBAL; }
 
-static int raster_check(uint32_t N, uint32_t channels, const lfs_cameras* cams, uint32_t tile_size, RasterGeom& g) {
+// What both directions check before anything is launched or cleared: the scene's shape, the direction's own operands (`own_ok`, evaluated by the caller), the
+// list sizes and the workspace, which is laid out here.
+static int raster_check(const RasterScene& sc, const RasterLists& l, const RasterWorkspace& ws, bool own_ok, RasterGeom& g, RasterWs& w) {
+    const lfs_cameras* cams = sc.cams;
     if (!cams || !cams->viewmats0 || !cams->Ks || cams->C == 0) return LFS_E_INVALID;
     if (cams->camera_model != LFS_CAMERA_PINHOLE && cams->camera_model != LFS_CAMERA_FISHEYE) return LFS_E_UNSUPPORTED;
-    if (channels < 1 || channels > 4) return LFS_E_UNSUPPORTED; // Rasterization.cpp:65 asserts 3; depth modes need 1 and 4
-    if (!raster_geom(cams, tile_size, g)) return LFS_E_UNSUPPORTED;
-    if (uint64_t(cams->C) * N >= (1ull << 26)) return LFS_E_UNSUPPORTED; // 32-bit byte offsets of the record walker (4 GB of 64-B records)
-    if (uint64_t(cams->C) * N >= RED_MAX_ROWS) return LFS_E_UNSUPPORTED; // accumulator rows stay below the dead-lane offset of the backward's buffer atomic (lfs_raster_common.cuh)
-    return LFS_OK;
+    if (sc.channels < 1 || sc.channels > 4) return LFS_E_UNSUPPORTED; // Rasterization.cpp:65 asserts 3; depth modes need 1 and 4
+    if (!raster_geom(cams, sc.tile_size, g)) return LFS_E_UNSUPPORTED;
+    if (uint64_t(cams->C) * sc.N >= (1ull << 26)) return LFS_E_UNSUPPORTED; // 32-bit byte offsets of the record walker (4 GB of 64-B records)
+    if (uint64_t(cams->C) * sc.N >= RED_MAX_ROWS) return LFS_E_UNSUPPORTED; // accumulator rows stay below the dead-lane offset of the backward's buffer atomic (lfs_raster_common.cuh)
+    if (!own_ok || !l.tile_offsets || !ws.base) return LFS_E_INVALID;
+    const int64_t n_sized = l.sized();
+    if (n_sized < 0 || n_sized > 0x7FFFFFFFll) return LFS_E_INVALID;
+    if (uint64_t(n_sized) >= (1ull << 29)) return LFS_E_UNSUPPORTED; // 32-bit byte offsets inside one cell list
+    const bool det = (g_debug_flags & 16u) != 0;
+    w = raster_ws(ws.base, raster_ws_offsets(cams->C, sc.N, g.cells, uint64_t(g.wpt) * uint64_t(n_sized), det), det);
+    return ws.bytes < w.bytes ? LFS_E_WORKSPACE : LFS_OK;
 }
 
-// n_isects >= 0: the host knows the count (operator calls); the workspace holds lists for exactly that many intersections.
-// n_isects < 0 (guarded training step, lfs_step_internal.h): the count is on the device - tile_offsets has T + 1 entries, the kernels read the last one -
-// and the lists are sized for `capacity`.
-struct IsectCount { int64_t n_isects, capacity; int32_t arg() const { return n_isects >= 0 ? int32_t(n_isects) : -1; } int64_t sized() const { return n_isects >= 0 ? n_isects : capacity; } };
-
 // camera state, 64-byte records + culling records, compacted per-cell lists: everything fwd and bwd walk
-static void raster_prepare(const RasterWs& w, const RasterGeom& g, uint32_t N, uint32_t channels, const float* means, const float* quats,
-                           const float* scales, const float* colors, const float* opacities, const uint8_t* masks,
-                           const lfs_cameras* cams, uint32_t tile_size, const int32_t* tile_offsets, const int32_t* flatten_ids,
-                           const IsectCount ic, hipStream_t s, bool cams_ready = false, bool records_ready = false) {
+static void raster_prepare(const RasterWs& w, const RasterGeom& g, const RasterScene& sc, const RasterLists& l, hipStream_t s, bool cams_ready, bool records_ready) {
+    const lfs_cameras* cams = sc.cams;
     const uint32_t C = cams->C;
     const bool uniform = cams->rs_type == LFS_SHUTTER_GLOBAL;
     if (!cams_ready) hipLaunchKernelGGL(cam_prep_kernel, dim3(1), dim3(64), 0, s, *cams, w.cams); // (training step: written by the projection kernel already)
-    const size_t CN = size_t(C) * N;
+    const size_t CN = size_t(C) * sc.N;
     if (CN > 0 && !records_ready) { // (training step, round 4: records + culling records written by the projection kernel - projection_ut.hip, PACK)
         lfs::ProfScope prof_pack("raster_pack", s);
         const dim3 pg(uint32_t((CN + 255) / 256));
-        if (uniform) hipLaunchKernelGGL(raster_pack_kernel<true>, pg, dim3(256), 0, s, C, N, channels, means, quats, scales, colors, opacities, w.cams, w.recs, w.cull);
-        else hipLaunchKernelGGL(raster_pack_kernel<false>, pg, dim3(256), 0, s, C, N, channels, means, quats, scales, colors, opacities, w.cams, w.recs, w.cull);
+        if (uniform) hipLaunchKernelGGL(raster_pack_kernel<true>, pg, dim3(256), 0, s, C, sc.N, sc.channels, sc.means, sc.quats, sc.scales, sc.colors, sc.opacities, w.cams, w.recs, w.cull);
+        else hipLaunchKernelGGL(raster_pack_kernel<false>, pg, dim3(256), 0, s, C, sc.N, sc.channels, sc.means, sc.quats, sc.scales, sc.colors, sc.opacities, w.cams, w.recs, w.cull);
     }
     lfs::ProfScope prof_cull("raster_cull", s);
     const uint32_t cull_on = (g_debug_flags & 1u) ? 0u : 1u;
 #define LFS_CULL(U)                                                                                                                     \
     hipLaunchKernelGGL((raster_cull_kernel<U>), dim3(g.grid), dim3(g.threads), 0, s, C, g.tw, g.th, cams->image_width, cams->image_height, \
-                       tile_size, g.blocks_per_tile, g.waves_per_block, cull_on, w.cams, w.cull, masks, tile_offsets, flatten_ids,        \
-                       ic.arg(), w.cell_count, w.cell_list)
+                       sc.tile_size, g.blocks_per_tile, g.waves_per_block, cull_on, w.cams, w.cull, sc.masks, l.tile_offsets, l.flatten_ids,  \
+                       l.arg(), w.cell_count, w.cell_list)
     if (uniform) LFS_CULL(true); else LFS_CULL(false);
 #undef LFS_CULL
 }
 
-static int raster_fwd_impl(
-    uint32_t N, uint32_t channels, const float* means, const float* quats, const float* scales,
-    const float* colors, const float* opacities, const float* backgrounds, const uint8_t* masks,
-    const lfs_cameras* cams, uint32_t tile_size,
-    const int32_t* tile_offsets, const int32_t* flatten_ids, const IsectCount ic,
-    float* render_colors, float* render_alphas, int32_t* last_ids,
-    void* workspace, size_t workspace_bytes, hipStream_t s, bool cams_ready = false, bool records_ready = false) {
+int lfs::raster_forward(const RasterScene& sc, const RasterLists& l, const RasterWorkspace& ws, const RasterFwdOut& out, hipStream_t s) {
     RasterGeom g;
-    int rc = raster_check(N, channels, cams, tile_size, g);
+    RasterWs w;
+    const int rc = raster_check(sc, l, ws, out.render_colors && out.render_alphas && out.last_ids, g, w);
     if (rc) return rc;
-    if (!render_colors || !render_alphas || !last_ids || !tile_offsets || !workspace) return LFS_E_INVALID;
-    const int64_t n_sized = ic.sized();
-    if (n_sized < 0 || n_sized > 0x7FFFFFFFll) return LFS_E_INVALID;
-    if (uint64_t(n_sized) >= (1ull << 29)) return LFS_E_UNSUPPORTED; // 32-bit byte offsets inside one cell list
-    const uint32_t C = cams->C;
-    RasterWs w = raster_ws(workspace, C, N, g.cells, uint64_t(g.wpt) * uint64_t(n_sized), (g_debug_flags & 16u) != 0);
-    if (workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
-    if (N > 0 && (!means || !quats || !scales || !colors || !opacities)) return LFS_E_INVALID;
-    if (n_sized > 0 && !flatten_ids) return LFS_E_INVALID;
-    raster_prepare(w, g, N, channels, means, quats, scales, colors, opacities, masks, cams, tile_size, tile_offsets, flatten_ids, ic, s, cams_ready, records_ready);
+    if (sc.N > 0 && (!sc.means || !sc.quats || !sc.scales || !sc.colors || !sc.opacities)) return LFS_E_INVALID;
+    if (l.sized() > 0 && !l.flatten_ids) return LFS_E_INVALID;
+    const lfs_cameras* cams = sc.cams;
+    raster_prepare(w, g, sc, l, s, out.cams_ready, out.records_ready);
     lfs::ProfScope prof("raster_fwd", s);
     const RasterGeom gw = wave_geom(cams, g);
-#define LFS_FWD(CD, MODE)                                                                                        \
-    hipLaunchKernelGGL((raster_fwd_kernel<CD, MODE>), dim3(gw.grid), dim3(gw.threads), 0, s, C, N, g.tw, g.th,     \
-                       cams->image_width, cams->image_height, tile_size, gw.blocks_per_tile, gw.waves_per_block, \
-                       w.cams, w.recs, colors, backgrounds, masks, tile_offsets, w.cell_count, w.cell_list, ic.arg(), \
-                       render_colors, render_alphas, last_ids, (int32_t*)nullptr)
-    switch (channels * 2 + raster_mode(cams)) {
-    case 2: LFS_FWD(1, 0); break; case 3: LFS_FWD(1, 1); break;
-    case 4: LFS_FWD(2, 0); break; case 5: LFS_FWD(2, 1); break;
-    case 6: LFS_FWD(3, 0); break; case 7: LFS_FWD(3, 1); break;
-    case 8: LFS_FWD(4, 0); break; default: LFS_FWD(4, 1); break;
-    }
-#undef LFS_FWD
+    using FwdKernel = decltype(&raster_fwd_kernel<3, 0>);
+    static constexpr FwdKernel table[4][2] = {   // [channels - 1][shutter mode]
+        {raster_fwd_kernel<1, 0>, raster_fwd_kernel<1, 1>}, {raster_fwd_kernel<2, 0>, raster_fwd_kernel<2, 1>},
+        {raster_fwd_kernel<3, 0>, raster_fwd_kernel<3, 1>}, {raster_fwd_kernel<4, 0>, raster_fwd_kernel<4, 1>}};
+    hipLaunchKernelGGL(table[sc.channels - 1][raster_mode(cams)], dim3(gw.grid), dim3(gw.threads), 0, s, cams->C, sc.N, g.tw, g.th,
+                       cams->image_width, cams->image_height, sc.tile_size, gw.blocks_per_tile, gw.waves_per_block,
+                       w.cams, w.recs, sc.colors, sc.backgrounds, sc.masks, l.tile_offsets, w.cell_count, w.cell_list, l.arg(),
+                       out.render_colors, out.render_alphas, out.last_ids, (int32_t*)nullptr);
     return (int)hipGetLastError();
 }
 
@@ -1482,64 +1478,49 @@ extern "C" int lfs_rasterize_to_pixels_from_world_3dgs_fwd(
     void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
     (void)ut_params; // carried by the reference signature, unused by its rasterizer as well
     if (n_isects < 0) return LFS_E_INVALID;
-    return raster_fwd_impl(N, channels, means, quats, scales, colors, opacities, backgrounds, masks, cams, tile_size, tile_offsets, flatten_ids, IsectCount{n_isects, 0},
-                           render_colors, render_alphas, last_ids, workspace, workspace_bytes, (hipStream_t)stream);
+    RasterScene sc{}; RasterFwdOut out{};
+    sc.N = N; sc.channels = channels; sc.means = means; sc.quats = quats; sc.scales = scales; sc.colors = colors; sc.opacities = opacities;
+    sc.backgrounds = backgrounds; sc.masks = masks; sc.cams = cams; sc.tile_size = tile_size;
+    out.render_colors = render_colors; out.render_alphas = render_alphas; out.last_ids = last_ids;
+    return raster_forward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, RasterWorkspace{workspace, workspace_bytes}, out, (hipStream_t)stream);
 }
 
-int lfs::raster_fwd_guarded(uint32_t N, const float* means, const float* quats, const float* scales, const float* colors, const float* opacities,
-                            const float* backgrounds, const lfs_cameras* cams, uint32_t tile_size, const int32_t* tile_offsets, const int32_t* flatten_ids,
-                            int64_t capacity, float* render_colors, float* render_alphas, int32_t* last_ids, void* workspace, size_t workspace_bytes, hipStream_t s,
-                            bool cams_ready, bool records_ready) {
-    if (capacity < 0) return LFS_E_INVALID;
-    return raster_fwd_impl(N, 3, means, quats, scales, colors, opacities, backgrounds, nullptr, cams, tile_size, tile_offsets, flatten_ids, IsectCount{-1, capacity},
-                           render_colors, render_alphas, last_ids, workspace, workspace_bytes, s, cams_ready, records_ready);
+// where the records / culling records of a (one-camera) rasterizer workspace live: the training step's projection kernel writes them there (the camera state is its first block)
+void lfs::raster_workspace_parts(void* workspace, uint32_t N, void** recs, void** cull) {
+    const RasterWsOffsets at = raster_ws_offsets(1, N, 0, 0, false);
+    *recs = static_cast<char*>(workspace) + at.recs;
+    *cull = static_cast<char*>(workspace) + at.cull;
 }
 
-// where the camera state / records / culling records of a (one-camera) rasterizer workspace live: the training step's projection kernel writes them there
-void lfs::raster_workspace_parts(void* workspace, uint32_t N, void** cams_dev, void** recs, void** cull) {
-    const RasterWs w = raster_ws(workspace, 1, N, 0, 0);
-    if (cams_dev) *cams_dev = w.cams;
-    if (recs) *recs = w.recs;
-    if (cull) *cull = w.cull;
+// the fused MSE takes one camera, RGB, no masks and no dL/d(alpha); its loss pointer is needed only where a finish pass writes through it
+static bool mse_form_ok(const RasterScene& sc, const RasterBwd& b) {
+    const RasterMse* m = b.mse;
+    return !m || (sc.channels == 3 && sc.cams && sc.cams->C == 1 && !sc.masks && !b.v_render_alphas && m->render && m->target_chw && (b.rows_only || m->loss));
 }
 
-static int raster_bwd_impl(
-    uint32_t N, uint32_t channels, const float* means, const float* quats, const float* scales,
-    const float* colors, const float* opacities, const float* backgrounds, const uint8_t* masks,
-    const lfs_cameras* cams, uint32_t tile_size,
-    const int32_t* tile_offsets, const int32_t* flatten_ids, const IsectCount ic,
-    const float* render_alphas, const int32_t* last_ids,
-    const float* v_render_colors, const float* v_render_alphas,
-    float* v_means, float* v_quats, float* v_scales, float* v_colors, float* v_opacities,
-    void* workspace, size_t workspace_bytes, hipStream_t s, bool prepared, const MseFuse* mse = nullptr, bool finish = true) {
+int lfs::raster_backward(const RasterScene& sc, const RasterLists& l, const RasterWorkspace& ws, const RasterBwd& b, hipStream_t s) {
     RasterGeom g;
-    int rc = raster_check(N, channels, cams, tile_size, g);
+    RasterWs w;
+    const int rc = raster_check(sc, l, ws, mse_form_ok(sc, b), g, w);
     if (rc) return rc;
-    if (!workspace || !tile_offsets) return LFS_E_INVALID;
-    if (mse && (channels != 3 || cams->C != 1 || masks || v_render_alphas || !mse->render || !mse->target || !mse->loss)) return LFS_E_INVALID;
-    const int64_t n_sized = ic.sized();
-    if (n_sized < 0 || n_sized > 0x7FFFFFFFll) return LFS_E_INVALID;
-    if (uint64_t(n_sized) >= (1ull << 29)) return LFS_E_UNSUPPORTED; // 32-bit byte offsets inside one cell list
-    const uint32_t C = cams->C;
+    const lfs_cameras* cams = sc.cams;
+    const uint32_t C = cams->C, N = sc.N, channels = sc.channels;
+    const int64_t n_sized = l.sized();
     const bool det = (g_debug_flags & 16u) != 0 && channels == 3;
-    RasterWs w = raster_ws(workspace, C, N, g.cells, uint64_t(g.wpt) * uint64_t(n_sized), (g_debug_flags & 16u) != 0);
-    if (workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
     if (N == 0) return LFS_OK;
-    if (!means || !quats || !scales || !colors || !opacities) return LFS_E_INVALID;
-    if (finish && (!v_means || !v_quats || !v_scales || !v_colors || !v_opacities)) return LFS_E_INVALID;
-    if (!finish && (channels != 3 || C != 1)) return LFS_E_INVALID; // the accumulator-only forms feed lfs_gut_finish_adam / lfs_gut_finish_grads (one camera, RGB)
-    if (n_sized > 0 && (!flatten_ids || !render_alphas || !last_ids || (!v_render_colors && !mse))) return LFS_E_INVALID; // v_render_alphas == NULL: zeros
+    if (!sc.means || !sc.quats || !sc.scales || !sc.colors || !sc.opacities) return LFS_E_INVALID;
+    if (!b.rows_only && (!b.v_means || !b.v_quats || !b.v_scales || !b.v_colors || !b.v_opacities)) return LFS_E_INVALID;
+    if (b.rows_only && (channels != 3 || C != 1)) return LFS_E_INVALID; // the accumulator-only forms feed lfs_gut_finish_adam / lfs_gut_finish_grads (one camera, RGB)
+    if (n_sized > 0 && (!l.flatten_ids || !b.render_alphas || !b.last_ids || (!b.v_render_colors && !b.mse))) return LFS_E_INVALID; // v_render_alphas == NULL: zeros
     const bool uniform = cams->rs_type == LFS_SHUTTER_GLOBAL;
     const size_t CN = size_t(C) * N;
-    hipError_t e = hipMemsetAsync(w.acc, 0, sizeof(float) * (ACC_STRIDE * CN + (mse ? LOSS_SLOTS : 0)), s);
-    MseFuse mse_dev{};
-    if (mse) { mse_dev = *mse; mse_dev.loss = w.acc + ACC_STRIDE * CN; } // the kernel adds into the slots, raster_finish folds them into *loss
+    hipError_t e = hipMemsetAsync(w.acc, 0, sizeof(float) * (ACC_STRIDE * CN + (b.mse ? LOSS_SLOTS : 0)), s);
+    MseFuse mse_dev{};   // the kernel adds its partial sums into the slots behind the rows; raster_finish (or the step's finish / tail pass) folds them into *loss
+    if (b.mse) mse_dev = MseFuse{b.mse->render, b.mse->target_chw, b.mse->weight / float(3u * cams->image_width * cams->image_height), w.acc + ACC_STRIDE * CN, nullptr};
     if (e != hipSuccess) return (int)e;
     if (det) { e = hipMemsetAsync(w.det64, 0, sizeof(unsigned long long) * ACC_STRIDE * CN, s); if (e != hipSuccess) return (int)e; mse_dev.det64 = w.det64; }
-    if (channels > 3) { e = hipMemsetAsync(v_colors, 0, sizeof(float) * channels * CN, s); if (e != hipSuccess) return (int)e; }
-    // self-contained call: camera state, records and cell lists are rebuilt; "prepared" = the caller guarantees
-    // the workspace still holds what the forward call with the same inputs left there
-    if (!prepared) raster_prepare(w, g, N, channels, means, quats, scales, colors, opacities, masks, cams, tile_size, tile_offsets, flatten_ids, ic, s);
+    if (channels > 3) { e = hipMemsetAsync(b.v_colors, 0, sizeof(float) * channels * CN, s); if (e != hipSuccess) return (int)e; }
+    if (!b.prepared) raster_prepare(w, g, sc, l, s, false, false);
     if (n_sized > 0) {
         // One launch (every mode but the deterministic one): timed, when asked for, through the dispatch packet's own signal (lfs_prof.h, prof_kernel_events) - no
         // event-record packets around the dominant kernel inside bench.py's timed region (profiles/r06/lease33_ext_launch_timing_ab.txt). The deterministic mode's two passes + resolve keep the event scope.
@@ -1551,60 +1532,40 @@ static int raster_bwd_impl(
 #endif
         lfs::ProfScope prof(ext_timed ? "" : "raster_bwd", s);
         const RasterGeom gw = wave_geom(cams, g);
-#ifndef LFS_EMULATE
-#define LFS_BWD_LAUNCH(KERNEL, ...) do { if (ext_timed) hipExtLaunchKernelGGL(KERNEL, dim3(gw.grid), dim3(gw.threads), 0, s, pe0, pe1, 0, __VA_ARGS__); \
-                                         else hipLaunchKernelGGL(KERNEL, dim3(gw.grid), dim3(gw.threads), 0, s, __VA_ARGS__); } while (0)
-#else
-#define LFS_BWD_LAUNCH(KERNEL, ...) hipLaunchKernelGGL(KERNEL, dim3(gw.grid), dim3(gw.threads), 0, s, __VA_ARGS__)
-#endif
-#define LFS_BWD_K(CD, MODE, ...)                                                                                 \
-    LFS_BWD_LAUNCH((raster_bwd_kernel<CD, MODE, ##__VA_ARGS__>), C, N, g.tw, g.th, \
-                       cams->image_width, cams->image_height, tile_size, gw.blocks_per_tile, gw.waves_per_block, \
-                       w.cams, w.recs, colors, backgrounds, masks, tile_offsets, w.cell_count, w.cell_list, ic.arg(), \
-                       render_alphas, last_ids, v_render_colors, v_render_alphas, w.acc, v_colors, mse_dev)
-        if (det) { // pass 1: per-slot maxima of |total| (integer atomicMax), pass 2: 64-bit fixed-point sums, then back to float
-#define LFS_BWD_DET(MODE, LOSSV) do { LFS_BWD_K(3, MODE, LOSSV, 1); LFS_BWD_K(3, MODE, LOSSV, 2); } while (0)
-            if (mse) { if (raster_mode(cams) == 0) LFS_BWD_DET(0, true); else LFS_BWD_DET(1, true); }
-            else { if (raster_mode(cams) == 0) LFS_BWD_DET(0, false); else LFS_BWD_DET(1, false); }
+        using BwdKernel = decltype(&raster_bwd_kernel<3, 0>);
+#define LFS_BWD_DET(LOSSV) {{raster_bwd_kernel<3, 0, LOSSV, 1>, raster_bwd_kernel<3, 0, LOSSV, 2>}, {raster_bwd_kernel<3, 1, LOSSV, 1>, raster_bwd_kernel<3, 1, LOSSV, 2>}}
+        // the deterministic mode's passes (1: per-slot maxima of |total|, integer atomicMax; 2: 64-bit fixed-point sums, then back to float): [no fused loss][shutter mode][pass - 1]
+        // (the tables name the kernels in the order the code object has always defined them: its layout follows the order of first use)
+        static constexpr BwdKernel det_passes[2][2][2] = {LFS_BWD_DET(true), LFS_BWD_DET(false)};
 #undef LFS_BWD_DET
+        static constexpr BwdKernel fused_mse[2] = {raster_bwd_kernel<3, 0, true>, raster_bwd_kernel<3, 1, true>};   // [shutter mode]
+        static constexpr BwdKernel plain[4][2] = {   // [channels - 1][shutter mode]
+            {raster_bwd_kernel<1, 0>, raster_bwd_kernel<1, 1>}, {raster_bwd_kernel<2, 0>, raster_bwd_kernel<2, 1>},
+            {raster_bwd_kernel<3, 0>, raster_bwd_kernel<3, 1>}, {raster_bwd_kernel<4, 0>, raster_bwd_kernel<4, 1>}};
+        const int mode = raster_mode(cams);
+#define LFS_BWD_ARGS C, N, g.tw, g.th, cams->image_width, cams->image_height, sc.tile_size, gw.blocks_per_tile, gw.waves_per_block, w.cams, w.recs, sc.colors, sc.backgrounds, \
+                     sc.masks, l.tile_offsets, w.cell_count, w.cell_list, l.arg(), b.render_alphas, b.last_ids, b.v_render_colors, b.v_render_alphas, w.acc, b.v_colors, mse_dev
+        auto launch = [&](BwdKernel k) {
+#ifndef LFS_EMULATE
+            if (ext_timed) { hipExtLaunchKernelGGL(k, dim3(gw.grid), dim3(gw.threads), 0, s, pe0, pe1, 0, LFS_BWD_ARGS); return; }
+#endif
+            hipLaunchKernelGGL(k, dim3(gw.grid), dim3(gw.threads), 0, s, LFS_BWD_ARGS);
+        };
+#undef LFS_BWD_ARGS
+        if (det) {
+            launch(det_passes[b.mse ? 0 : 1][mode][0]); launch(det_passes[b.mse ? 0 : 1][mode][1]);
             const size_t n_acc = ACC_STRIDE * CN;
             hipLaunchKernelGGL(raster_det_resolve_kernel, dim3(uint32_t((n_acc + 255) / 256)), dim3(256), 0, s, n_acc, w.acc, w.det64);
-        } else if (mse) {
-            if (raster_mode(cams) == 0) LFS_BWD_K(3, 0, true); else LFS_BWD_K(3, 1, true);
-        } else
-        switch (channels * 2 + raster_mode(cams)) {
-        case 2: LFS_BWD_K(1, 0); break; case 3: LFS_BWD_K(1, 1); break;
-        case 4: LFS_BWD_K(2, 0); break; case 5: LFS_BWD_K(2, 1); break;
-        case 6: LFS_BWD_K(3, 0); break; case 7: LFS_BWD_K(3, 1); break;
-        case 8: LFS_BWD_K(4, 0); break; default: LFS_BWD_K(4, 1); break;
-        }
-#undef LFS_BWD_K
-#undef LFS_BWD_LAUNCH
+        } else launch(b.mse ? fused_mse[mode] : plain[channels - 1][mode]);
     }
-    if (!finish) return (int)hipGetLastError();
+    if (b.rows_only) return (int)hipGetLastError();
     const dim3 fg((N + 255) / 256);
     lfs::ProfScope prof_fin("raster_finish", s);
-    const float* slots = mse ? w.acc + ACC_STRIDE * CN : nullptr;
-    float* loss_out = mse ? mse->loss : nullptr;
-    if (uniform) hipLaunchKernelGGL(raster_finish_kernel<true>, fg, dim3(256), 0, s, C, N, channels, means, quats, scales, w.cams, w.acc, v_means, v_quats, v_scales, v_colors, v_opacities, slots, loss_out, opacities);
-    else hipLaunchKernelGGL(raster_finish_kernel<false>, fg, dim3(256), 0, s, C, N, channels, means, quats, scales, w.cams, w.acc, v_means, v_quats, v_scales, v_colors, v_opacities, slots, loss_out, opacities);
+    const float* slots = b.mse ? w.acc + ACC_STRIDE * CN : nullptr;
+    float* loss_out = b.mse ? b.mse->loss : nullptr;
+    if (uniform) hipLaunchKernelGGL(raster_finish_kernel<true>, fg, dim3(256), 0, s, C, N, channels, sc.means, sc.quats, sc.scales, w.cams, w.acc, b.v_means, b.v_quats, b.v_scales, b.v_colors, b.v_opacities, slots, loss_out, sc.opacities);
+    else hipLaunchKernelGGL(raster_finish_kernel<false>, fg, dim3(256), 0, s, C, N, channels, sc.means, sc.quats, sc.scales, w.cams, w.acc, b.v_means, b.v_quats, b.v_scales, b.v_colors, b.v_opacities, slots, loss_out, sc.opacities);
     return (int)hipGetLastError();
-}
-
-extern "C" int lfs_rasterize_to_pixels_from_world_3dgs_bwd(
-    uint32_t N, uint32_t channels, const float* means, const float* quats, const float* scales,
-    const float* colors, const float* opacities, const float* backgrounds, const uint8_t* masks,
-    const lfs_cameras* cams, uint32_t tile_size, const lfs_ut_params* ut_params,
-    const int32_t* tile_offsets, const int32_t* flatten_ids, int64_t n_isects,
-    const float* render_alphas, const int32_t* last_ids,
-    const float* v_render_colors, const float* v_render_alphas,
-    float* v_means, float* v_quats, float* v_scales, float* v_colors, float* v_opacities,
-    void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
-    (void)ut_params;
-    if (n_isects < 0) return LFS_E_INVALID;
-    return raster_bwd_impl(N, channels, means, quats, scales, colors, opacities, backgrounds, masks, cams, tile_size, tile_offsets, flatten_ids,
-                           IsectCount{n_isects, 0}, render_alphas, last_ids, v_render_colors, v_render_alphas, v_means, v_quats, v_scales, v_colors,
-                           v_opacities, workspace, workspace_bytes, (hipStream_t)stream, false);
 }
 
 extern "C" int lfs_rasterize_to_pixels_from_world_3dgs_bwd_prepared(
@@ -1618,9 +1579,32 @@ extern "C" int lfs_rasterize_to_pixels_from_world_3dgs_bwd_prepared(
     void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
     (void)ut_params;
     if (n_isects < 0) return LFS_E_INVALID;
-    return raster_bwd_impl(N, channels, means, quats, scales, colors, opacities, backgrounds, masks, cams, tile_size, tile_offsets, flatten_ids,
-                           IsectCount{n_isects, 0}, render_alphas, last_ids, v_render_colors, v_render_alphas, v_means, v_quats, v_scales, v_colors,
-                           v_opacities, workspace, workspace_bytes, (hipStream_t)stream, true);
+    RasterScene sc{}; RasterBwd b{};
+    sc.N = N; sc.channels = channels; sc.means = means; sc.quats = quats; sc.scales = scales; sc.colors = colors; sc.opacities = opacities;
+    sc.backgrounds = backgrounds; sc.masks = masks; sc.cams = cams; sc.tile_size = tile_size;
+    b.render_alphas = render_alphas; b.last_ids = last_ids; b.v_render_colors = v_render_colors; b.v_render_alphas = v_render_alphas;
+    b.v_means = v_means; b.v_quats = v_quats; b.v_scales = v_scales; b.v_colors = v_colors; b.v_opacities = v_opacities; b.prepared = true;
+    return raster_backward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, RasterWorkspace{workspace, workspace_bytes}, b, (hipStream_t)stream);
+}
+
+// the self-contained form: camera state, records and cell lists are rebuilt in front of the backward
+extern "C" int lfs_rasterize_to_pixels_from_world_3dgs_bwd(
+    uint32_t N, uint32_t channels, const float* means, const float* quats, const float* scales,
+    const float* colors, const float* opacities, const float* backgrounds, const uint8_t* masks,
+    const lfs_cameras* cams, uint32_t tile_size, const lfs_ut_params* ut_params,
+    const int32_t* tile_offsets, const int32_t* flatten_ids, int64_t n_isects,
+    const float* render_alphas, const int32_t* last_ids,
+    const float* v_render_colors, const float* v_render_alphas,
+    float* v_means, float* v_quats, float* v_scales, float* v_colors, float* v_opacities,
+    void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
+    (void)ut_params;
+    if (n_isects < 0) return LFS_E_INVALID;
+    RasterScene sc{}; RasterBwd b{};
+    sc.N = N; sc.channels = channels; sc.means = means; sc.quats = quats; sc.scales = scales; sc.colors = colors; sc.opacities = opacities;
+    sc.backgrounds = backgrounds; sc.masks = masks; sc.cams = cams; sc.tile_size = tile_size;
+    b.render_alphas = render_alphas; b.last_ids = last_ids; b.v_render_colors = v_render_colors; b.v_render_alphas = v_render_alphas;
+    b.v_means = v_means; b.v_quats = v_quats; b.v_scales = v_scales; b.v_colors = v_colors; b.v_opacities = v_opacities;
+    return raster_backward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, RasterWorkspace{workspace, workspace_bytes}, b, (hipStream_t)stream);
 }
 
 // "prepared" backward with the clamped MSE loss of lfs_mse_loss_fwd_bwd folded in (extension): render_colors [H,W,3] = the forward
@@ -1632,11 +1616,14 @@ extern "C" int lfs_rasterize_to_pixels_from_world_3dgs_bwd_prepared_mse(
     float* loss, float* v_means, float* v_quats, float* v_scales, float* v_colors, float* v_opacities, void* workspace, size_t workspace_bytes,
     lfs_stream_t stream) {
     if (!cams || !render_colors || !target_chw || !loss || n_isects < 0) return LFS_E_INVALID;
-    const MseFuse mse{render_colors, target_chw, weight / float(3u * cams->image_width * cams->image_height), loss, nullptr};
     if (n_isects == 0) return LFS_E_UNSUPPORTED; // nothing rendered: use lfs_mse_loss_fwd_bwd (the loss of the background image)
-    return raster_bwd_impl(N, 3, means, quats, scales, colors, opacities, backgrounds, nullptr, cams, tile_size, tile_offsets, flatten_ids, IsectCount{n_isects, 0},
-                           render_alphas, last_ids, nullptr, nullptr, v_means, v_quats, v_scales, v_colors, v_opacities, workspace, workspace_bytes,
-                           (hipStream_t)stream, true, &mse);
+    const RasterMse mse{render_colors, target_chw, weight, loss};
+    RasterScene sc{}; RasterBwd b{};   // (RGB, no masks)
+    b.render_alphas = render_alphas; b.last_ids = last_ids; b.mse = &mse;
+    b.v_means = v_means; b.v_quats = v_quats; b.v_scales = v_scales; b.v_colors = v_colors; b.v_opacities = v_opacities; b.prepared = true;
+    sc.N = N; sc.channels = 3; sc.means = means; sc.quats = quats; sc.scales = scales; sc.colors = colors; sc.opacities = opacities;
+    sc.backgrounds = backgrounds; sc.cams = cams; sc.tile_size = tile_size;
+    return raster_backward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, RasterWorkspace{workspace, workspace_bytes}, b, (hipStream_t)stream);
 }
 
 
@@ -1644,21 +1631,7 @@ extern "C" int lfs_rasterize_to_pixels_from_world_3dgs_bwd_prepared_mse(
 // lfs_rasterize_..._bwd_prepared_mse without its last kernel: the per-Gaussian sums stay in the workspace (rows of 16 floats at
 // lfs_rasterize_workspace_acc_offset) together with the loss partial sums; lfs_sh_model_bwd_adam_all reads dL/dcolour from the rows and writes
 // dL/d(dirs) into them, lfs_gut_finish_adam turns them into the parameter updates.
-extern "C" size_t lfs_rasterize_workspace_acc_offset(uint32_t C, uint32_t N) {
-    const RasterWs w = raster_ws(nullptr, C, N, 0, 0);
-    return size_t(reinterpret_cast<const char*>(w.acc) - static_cast<const char*>(nullptr));
-}
-
-static int raster_bwd_mse_acc(uint32_t N, const float* means, const float* quats, const float* scales, const float* colors, const float* opacities,
-                              const float* backgrounds, const lfs_cameras* cams, uint32_t tile_size, const int32_t* tile_offsets, const int32_t* flatten_ids,
-                              const IsectCount ic, const float* render_colors, const float* render_alphas, const int32_t* last_ids, const float* target_chw,
-                              float weight, void* workspace, size_t workspace_bytes, hipStream_t s) {
-    if (!cams || !render_colors || !target_chw) return LFS_E_INVALID;
-    float dummy_loss;
-    const MseFuse mse{render_colors, target_chw, weight / float(3u * cams->image_width * cams->image_height), &dummy_loss, nullptr}; // (.loss is redirected to the slots)
-    return raster_bwd_impl(N, 3, means, quats, scales, colors, opacities, backgrounds, nullptr, cams, tile_size, tile_offsets, flatten_ids, ic,
-                           render_alphas, last_ids, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, s, true, &mse, false);
-}
+extern "C" size_t lfs_rasterize_workspace_acc_offset(uint32_t C, uint32_t N) { return raster_ws_offsets(C, N, 0, 0, false).acc; }
 
 extern "C" int lfs_rasterize_to_pixels_from_world_3dgs_bwd_prepared_mse_acc(
     uint32_t N, const float* means, const float* quats, const float* scales, const float* colors, const float* opacities,
@@ -1667,17 +1640,13 @@ extern "C" int lfs_rasterize_to_pixels_from_world_3dgs_bwd_prepared_mse_acc(
     void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
     if (n_isects < 0) return LFS_E_INVALID;
     if (n_isects == 0) return LFS_E_UNSUPPORTED;
-    return raster_bwd_mse_acc(N, means, quats, scales, colors, opacities, backgrounds, cams, tile_size, tile_offsets, flatten_ids, IsectCount{n_isects, 0}, render_colors,
-                              render_alphas, last_ids, target_chw, weight, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-int lfs::raster_bwd_mse_acc_guarded(uint32_t N, const float* means, const float* quats, const float* scales, const float* colors, const float* opacities,
-                                    const float* backgrounds, const lfs_cameras* cams, uint32_t tile_size, const int32_t* tile_offsets, const int32_t* flatten_ids,
-                                    int64_t capacity, const float* render_colors, const float* render_alphas, const int32_t* last_ids, const float* target_chw,
-                                    float weight, void* workspace, size_t workspace_bytes, hipStream_t s) {
-    if (capacity <= 0) return LFS_E_INVALID;
-    return raster_bwd_mse_acc(N, means, quats, scales, colors, opacities, backgrounds, cams, tile_size, tile_offsets, flatten_ids, IsectCount{-1, capacity}, render_colors,
-                              render_alphas, last_ids, target_chw, weight, workspace, workspace_bytes, s);
+    if (!cams || !render_colors || !target_chw) return LFS_E_INVALID;
+    const RasterMse mse{render_colors, target_chw, weight, nullptr};
+    RasterScene sc{}; RasterBwd b{};   // (RGB, no masks)
+    b.render_alphas = render_alphas; b.last_ids = last_ids; b.mse = &mse; b.prepared = true; b.rows_only = true;
+    sc.N = N; sc.channels = 3; sc.means = means; sc.quats = quats; sc.scales = scales; sc.colors = colors; sc.opacities = opacities;
+    sc.backgrounds = backgrounds; sc.cams = cams; sc.tile_size = tile_size;
+    return raster_backward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, RasterWorkspace{workspace, workspace_bytes}, b, (hipStream_t)stream);
 }
 
 // the same for a caller-provided dL/d(render) (any loss): lfs_..._bwd_prepared without its last kernel
@@ -1687,38 +1656,47 @@ extern "C" int lfs_rasterize_to_pixels_from_world_3dgs_bwd_prepared_acc(
     int64_t n_isects, const float* render_alphas, const int32_t* last_ids, const float* v_render_colors, const float* v_render_alphas,
     void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
     if (!cams || !v_render_colors || n_isects < 0) return LFS_E_INVALID;
-    return raster_bwd_impl(N, 3, means, quats, scales, colors, opacities, backgrounds, nullptr, cams, tile_size, tile_offsets, flatten_ids, IsectCount{n_isects, 0},
-                           render_alphas, last_ids, v_render_colors, v_render_alphas, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes,
-                           (hipStream_t)stream, true, nullptr, false);
+    RasterScene sc{}; RasterBwd b{};   // (RGB, no masks)
+    b.render_alphas = render_alphas; b.last_ids = last_ids; b.v_render_colors = v_render_colors; b.v_render_alphas = v_render_alphas; b.prepared = true; b.rows_only = true;
+    sc.N = N; sc.channels = 3; sc.means = means; sc.quats = quats; sc.scales = scales; sc.colors = colors; sc.opacities = opacities;
+    sc.backgrounds = backgrounds; sc.cams = cams; sc.tile_size = tile_size;
+    return raster_backward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, RasterWorkspace{workspace, workspace_bytes}, b, (hipStream_t)stream);
 }
 
-int lfs::raster_bwd_acc_guarded(uint32_t N, const float* means, const float* quats, const float* scales, const float* colors, const float* opacities,
-                                const float* backgrounds, const lfs_cameras* cams, uint32_t tile_size, const int32_t* tile_offsets, const int32_t* flatten_ids,
-                                int64_t capacity, const float* render_alphas, const int32_t* last_ids, const float* v_render_colors, void* workspace,
-                                size_t workspace_bytes, hipStream_t s) {
-    if (!cams || !v_render_colors || capacity <= 0) return LFS_E_INVALID;
-    return raster_bwd_impl(N, 3, means, quats, scales, colors, opacities, backgrounds, nullptr, cams, tile_size, tile_offsets, flatten_ids, IsectCount{-1, capacity},
-                           render_alphas, last_ids, v_render_colors, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, s, true, nullptr, false);
+// ---- the finish and tail passes over the accumulator rows ----
+constexpr int FINISH_GROUP[4] = {0, 3, 4, 5};   // FusedAdam's groups in raster_finish_adam_kernel's order: means, raw_scales, raw_quats, raw_opacities
+static AdamScalars adam_scalars(const float (&v)[6]) { return AdamScalars{v[0], v[1], v[2], v[3], v[4], v[5]}; }
+
+// FinishAdam of a pass over N Gaussians: the regularisers of trainer.cpp:132-158 (as lfs_activations_bwd): scale_reg * mean(scales) over 3N values, opacity_reg *
+// mean(opacities) - and, with `adam`, the moments and scalars of its four groups (false: one of them is missing)
+static bool fill_finish_adam(FinishAdam& ad, uint32_t N, const GutRegs& regs, const GutAdam* adam) {
+    ad = FinishAdam{};
+    ad.scale_reg = regs.scale_reg / (3.f * float(N)); ad.opacity_reg = regs.opacity_reg / float(N);
+    for (int j = 0; adam && j < 4; ++j) {
+        const int k = FINISH_GROUP[j];
+        if (!adam->exp_avg[k] || !adam->exp_avg_sq[k]) return false;
+        ad.m[j] = adam->exp_avg[k]; ad.v[j] = adam->exp_avg_sq[k]; ad.s[j] = adam_scalars(adam->scalars[k]);
+    }
+    return true;
 }
+static const float* loss_slots_of(const RasterWs& w, uint32_t N, const float* loss) { return loss ? w.acc + ACC_STRIDE * size_t(N) : nullptr; }
 
 // The accumulator rows -> gradient TENSORS of the raw parameters in one pass (raster_finish + lfs_activations_bwd + the copy of dL/dmeans): for steps
-// that need the gradients themselves (multi-GPU all-reduce, several views per step, non-MSE losses). g_* are written or, accumulate != 0, added to;
-// v_colors [N,3] is written (the SH backward consumes it and adds dL/d(dirs) onto g_means). loss (nullable): += the fused MSE partial sums.
-int lfs::gut_finish_grads_impl(
-    uint32_t N, const float* means, const float* raw_quats, const float* quats, const float* scales, const float* opacities, float scale_reg, float opacity_reg,
-    int accumulate, float* g_means, float* g_raw_scales, float* g_raw_quats, float* g_raw_opacities, float* v_colors, const float* v_dirs, float* loss,
-    void* workspace, size_t workspace_bytes, hipStream_t s) {
+// that need the gradients themselves (multi-GPU all-reduce, several views per step, non-MSE losses). g.* are written or, accumulate != 0, added to;
+// v_colors [N,3] is written (the SH backward consumes it and adds dL/d(dirs) onto g.means). loss (nullable): += the fused MSE partial sums.
+int lfs::gut_finish_grads_impl(const GutParams& p, const GutActivated& act, const GutRegs& regs, const GutGrads& g, const float* v_dirs, float* loss,
+                               const RasterWorkspace& ws, hipStream_t s) {
+    const uint32_t N = p.N;
     if (N == 0) return LFS_OK;
-    if (!means || !raw_quats || !quats || !scales || !opacities || !g_means || !g_raw_scales || !g_raw_quats || !g_raw_opacities || (!v_colors && !v_dirs) || !workspace) return LFS_E_INVALID;
-    const RasterWs w = raster_ws(workspace, 1, N, 0, 0);
-    if (workspace_bytes < size_t(reinterpret_cast<const char*>(w.cull) - static_cast<const char*>(workspace))) return LFS_E_WORKSPACE;
-    FinishAdam ad{};
-    // regularisers of trainer.cpp:132-158 (as lfs_activations_bwd): scale_reg * mean(scales) over 3N values, opacity_reg * mean(opacities)
-    ad.scale_reg = scale_reg / (3.f * float(N)); ad.opacity_reg = opacity_reg / float(N);
-    const FinishGrads gr{g_means, g_raw_scales, g_raw_quats, g_raw_opacities, v_colors, accumulate};
+    if (!p.means || !p.raw_quats || !act.quats || !act.scales || !act.opacities || !g.means || !g.raw_scales || !g.raw_quats || !g.raw_opacities || (!g.v_colors && !v_dirs) || !ws.base) return LFS_E_INVALID;
+    RasterWs w;
+    if (!rows_ws(ws, N, w)) return LFS_E_WORKSPACE;
+    FinishAdam ad;
+    fill_finish_adam(ad, N, regs, nullptr);
+    const FinishGrads gr{g.means, g.raw_scales, g.raw_quats, g.raw_opacities, g.v_colors, g.accumulate};
     lfs::ProfScope prof("finish_grads", s);
-    hipLaunchKernelGGL(raster_finish_adam_kernel<false>, dim3((N + FINISH_BLOCK - 1) / FINISH_BLOCK), dim3(FINISH_BLOCK), 0, s, N, const_cast<float*>(means), (float*)nullptr, const_cast<float*>(raw_quats),
-                       (float*)nullptr, quats, scales, opacities, w.cams, w.acc, v_dirs, ad, gr, loss ? w.acc + ACC_STRIDE * size_t(N) : nullptr, loss, (const int32_t*)nullptr);
+    hipLaunchKernelGGL(raster_finish_adam_kernel<false>, dim3((N + FINISH_BLOCK - 1) / FINISH_BLOCK), dim3(FINISH_BLOCK), 0, s, N, p.means, (float*)nullptr, p.raw_quats,
+                       (float*)nullptr, act.quats, act.scales, act.opacities, w.cams, w.acc, v_dirs, ad, gr, loss_slots_of(w, N, loss), loss, (const int32_t*)nullptr);
     return (int)hipGetLastError();
 }
 
@@ -1727,77 +1705,75 @@ extern "C" int lfs_gut_finish_grads(
     int accumulate, float* g_means, float* g_raw_scales, float* g_raw_quats, float* g_raw_opacities, float* v_colors, float* loss,
     void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
     if (N != 0 && !v_colors) return LFS_E_INVALID;
-    return lfs::gut_finish_grads_impl(N, means, raw_quats, quats, scales, opacities, scale_reg, opacity_reg, accumulate, g_means, g_raw_scales, g_raw_quats, g_raw_opacities,
-                                      v_colors, nullptr, loss, workspace, workspace_bytes, (hipStream_t)stream);
+    GutParams p{};   // (read only: the kernel's <false> form stores no parameter)
+    p.N = N; p.means = const_cast<float*>(means); p.raw_quats = const_cast<float*>(raw_quats);
+    return lfs::gut_finish_grads_impl(p, GutActivated{quats, scales, opacities}, GutRegs{scale_reg, opacity_reg},
+                                      GutGrads{g_means, g_raw_scales, g_raw_quats, g_raw_opacities, v_colors, accumulate}, nullptr, loss,
+                                      RasterWorkspace{workspace, workspace_bytes}, (hipStream_t)stream);
 }
 
-// scalars[k] = {lr, beta1, beta2, eps, bc1_rcp, bc2_sqrt_rcp} for k = means, raw_scales, raw_quats, raw_opacities; *loss = the fused MSE of the backward (stored, not added)
-int lfs::gut_finish_adam_impl(
-    uint32_t N, float* means, float* raw_scales, float* raw_quats, float* raw_opacities, const float* quats, const float* scales, const float* opacities,
-    const float* v_dirs, float* const* exp_avg /* [4] host */, float* const* exp_avg_sq /* [4] host */, const float* scalars /* [4][6] host */, float scale_reg,
-    float opacity_reg, float* loss, void* workspace, size_t workspace_bytes, hipStream_t s, const int32_t* abort_flag) {
+int lfs::gut_finish_adam_impl(const GutParams& p, const GutActivated& act, const GutAdam& adam, const GutRegs& regs, const float* v_dirs, float* loss,
+                              const RasterWorkspace& ws, hipStream_t s) {
+    const uint32_t N = p.N;
     if (N == 0) return LFS_OK;
     if (!v_dirs) return LFS_E_INVALID;
-    if (!means || !raw_scales || !raw_quats || !raw_opacities || !quats || !scales || !opacities || !exp_avg || !exp_avg_sq || !scalars || !workspace) return LFS_E_INVALID;
-    const RasterWs w = raster_ws(workspace, 1, N, 0, 0);
-    if (workspace_bytes < size_t(reinterpret_cast<const char*>(w.cull) - static_cast<const char*>(workspace))) return LFS_E_WORKSPACE;
+    if (!p.means || !p.raw_scales || !p.raw_quats || !p.raw_opacities || !act.quats || !act.scales || !act.opacities || !adam.exp_avg || !adam.exp_avg_sq || !adam.scalars || !ws.base) return LFS_E_INVALID;
+    RasterWs w;
+    if (!rows_ws(ws, N, w)) return LFS_E_WORKSPACE;
     FinishAdam ad;
-    for (int k = 0; k < 4; ++k) {
-        if (!exp_avg[k] || !exp_avg_sq[k]) return LFS_E_INVALID;
-        ad.m[k] = exp_avg[k]; ad.v[k] = exp_avg_sq[k];
-        ad.s[k] = AdamScalars{scalars[6 * k], scalars[6 * k + 1], scalars[6 * k + 2], scalars[6 * k + 3], scalars[6 * k + 4], scalars[6 * k + 5]};
-    }
-    // regularisers of trainer.cpp:132-158 (as lfs_activations_bwd): scale_reg * mean(scales) over 3N values, opacity_reg * mean(opacities)
-    ad.scale_reg = scale_reg / (3.f * float(N)); ad.opacity_reg = opacity_reg / float(N);
+    if (!fill_finish_adam(ad, N, regs, &adam)) return LFS_E_INVALID;
     lfs::ProfScope prof("finish_adam", s);
-    hipLaunchKernelGGL(raster_finish_adam_kernel<true>, dim3((N + FINISH_BLOCK - 1) / FINISH_BLOCK), dim3(FINISH_BLOCK), 0, s, N, means, raw_scales, raw_quats, raw_opacities, quats, scales, opacities,
-                       w.cams, w.acc, v_dirs, ad, FinishGrads{}, loss ? w.acc + ACC_STRIDE * size_t(N) : nullptr, loss, abort_flag);
+    hipLaunchKernelGGL(raster_finish_adam_kernel<true>, dim3((N + FINISH_BLOCK - 1) / FINISH_BLOCK), dim3(FINISH_BLOCK), 0, s, N, p.means, p.raw_scales, p.raw_quats, p.raw_opacities,
+                       act.quats, act.scales, act.opacities, w.cams, w.acc, v_dirs, ad, FinishGrads{}, loss_slots_of(w, N, loss), loss, adam.abort_flag);
     return (int)hipGetLastError();
 }
 
 // The fused tail of the all-inline step (gut_tail_kernel): SH backward + all six Adam updates (+ the next view's SH colours -> colors [N,3] when next_viewmat is given).
 // LFS_E_UNSUPPORTED for K > 16 (degree 4): the caller enqueues lfs_sh_model_bwd_adam_all + lfs_gut_finish_adam instead.
-int lfs::gut_tail_impl(
-    uint32_t N, uint32_t K, uint32_t degrees_to_use, float* means, float* sh0, float* shN, float* raw_scales, float* raw_quats, float* raw_opacities,
-    const float* quats, const float* scales, const float* opacities, const float* viewmat, const float* next_viewmat, const int32_t* radii, float* colors,
-    float* const* exp_avg /* [6] host, FusedAdam group order */, float* const* exp_avg_sq, const float (*scalars)[6], float scale_reg, float opacity_reg, float* loss,
-    void* workspace, size_t workspace_bytes, hipStream_t s, const int32_t* abort_flag, bool freeze_shN, const float* noise, float noise_lr) {
+int lfs::gut_tail_impl(const GutParams& p, const GutActivated& act, const GutAdam& adam, const GutRegs& regs, const GutTailView& view, float* loss,
+                       const RasterWorkspace& ws, hipStream_t s) {
+    const uint32_t N = p.N, K = p.K;
     if (N == 0) return LFS_OK;
-    const uint32_t Kd = (degrees_to_use + 1) * (degrees_to_use + 1);
-    if (degrees_to_use > 3 || Kd > K || K < 2) return LFS_E_INVALID;
+    const uint32_t Kd = (p.sh_degree + 1) * (p.sh_degree + 1);
+    if (p.sh_degree > 3 || Kd > K || K < 2) return LFS_E_INVALID;
     if (K > 16) return LFS_E_UNSUPPORTED;
-    if (!means || !sh0 || !shN || !raw_scales || !raw_quats || !raw_opacities || !quats || !scales || !opacities || !viewmat || !radii || !colors || !exp_avg || !exp_avg_sq ||
-        !scalars || !workspace) return LFS_E_INVALID;
-    for (int k = 0; k < 6; ++k) if ((!exp_avg[k] || !exp_avg_sq[k]) && !(freeze_shN && k == 2)) return LFS_E_INVALID;
-    const RasterWs w = raster_ws(workspace, 1, N, 0, 0);
-    if (workspace_bytes < size_t(reinterpret_cast<const char*>(w.cull) - static_cast<const char*>(workspace))) return LFS_E_WORKSPACE;
+    if (!p.means || !p.sh0 || !p.shN || !p.raw_scales || !p.raw_quats || !p.raw_opacities || !act.quats || !act.scales || !act.opacities || !view.viewmat || !view.radii ||
+        !view.colors || !adam.exp_avg || !adam.exp_avg_sq || !adam.scalars || !ws.base) return LFS_E_INVALID;
+    for (int k = 0; k < 6; ++k) if ((!adam.exp_avg[k] || !adam.exp_avg_sq[k]) && !(view.freeze_shN && k == 2)) return LFS_E_INVALID;
+    RasterWs w;
+    if (!rows_ws(ws, N, w)) return LFS_E_WORKSPACE;
     GutTail t{};
-    t.N = N; t.K = K; t.degree = int(degrees_to_use);
-    t.means = means; t.sh0 = sh0; t.shN = shN; t.raw_scales = raw_scales; t.raw_quats = raw_quats; t.raw_opacities = raw_opacities;
-    t.quats = quats; t.scales = scales; t.opacities = opacities; t.viewmat = viewmat; t.next_viewmat = next_viewmat; t.radii = radii; t.colors = colors; t.acc = w.acc;
-    auto sc = [&](int k) { return AdamScalars{scalars[k][0], scalars[k][1], scalars[k][2], scalars[k][3], scalars[k][4], scalars[k][5]}; };
-    t.m0 = exp_avg[1]; t.v0 = exp_avg_sq[1]; t.s0 = sc(1);
-    t.mN = exp_avg[2]; t.vN = exp_avg_sq[2]; t.sN = sc(2);
-    const int grp[4] = {0, 3, 4, 5};   // raster_finish_adam_kernel's order: means, raw_scales, raw_quats, raw_opacities
-    for (int j = 0; j < 4; ++j) { t.fin.m[j] = exp_avg[grp[j]]; t.fin.v[j] = exp_avg_sq[grp[j]]; t.fin.s[j] = sc(grp[j]); }
-    t.fin.scale_reg = scale_reg / (3.f * float(N)); t.fin.opacity_reg = opacity_reg / float(N);   // (as gut_finish_adam_impl)
-    t.loss_slots = loss ? w.acc + ACC_STRIDE * size_t(N) : nullptr; t.loss = loss; t.abort_flag = abort_flag;
-    t.noise = noise; t.noise_lr = noise_lr;
+    t.N = N; t.K = K; t.degree = int(p.sh_degree);
+    t.means = p.means; t.sh0 = p.sh0; t.shN = p.shN; t.raw_scales = p.raw_scales; t.raw_quats = p.raw_quats; t.raw_opacities = p.raw_opacities;
+    t.quats = act.quats; t.scales = act.scales; t.opacities = act.opacities;
+    t.viewmat = view.viewmat; t.next_viewmat = view.next_viewmat; t.radii = view.radii; t.colors = view.colors; t.acc = w.acc;
+    t.m0 = adam.exp_avg[1]; t.v0 = adam.exp_avg_sq[1]; t.s0 = adam_scalars(adam.scalars[1]);
+    t.mN = adam.exp_avg[2]; t.vN = adam.exp_avg_sq[2]; t.sN = adam_scalars(adam.scalars[2]);
+    fill_finish_adam(t.fin, N, regs, &adam);
+    t.loss_slots = loss_slots_of(w, N, loss); t.loss = loss; t.abort_flag = adam.abort_flag;
+    t.noise = view.noise; t.noise_lr = view.noise_lr;
     const dim3 grid((N + 63) / 64), block(64);
     lfs::ProfScope prof("tail_sh_finish_adam", s);
-    const bool next = next_viewmat != nullptr;
     using TailKernel = void (*)(const GutTail, const CamDev*);
 #define LFS_TAIL_ROW(LPG, NEXT) {gut_tail_kernel<LPG, NEXT, false, false>, gut_tail_kernel<LPG, NEXT, false, true>, gut_tail_kernel<LPG, NEXT, true, false>, gut_tail_kernel<LPG, NEXT, true, true>}
     static const TailKernel table[2][2][4] = {{LFS_TAIL_ROW(4, false), LFS_TAIL_ROW(4, true)}, {LFS_TAIL_ROW(16, false), LFS_TAIL_ROW(16, true)}};   // [LPG][NEXT][2 FREEZE + NOISE]
 #undef LFS_TAIL_ROW
-    hipLaunchKernelGGL(table[K <= 4 ? 0 : 1][next ? 1 : 0][(freeze_shN ? 2 : 0) + (noise != nullptr ? 1 : 0)], grid, block, 0, s, t, w.cams);
+    hipLaunchKernelGGL(table[K <= 4 ? 0 : 1][view.next_viewmat ? 1 : 0][(view.freeze_shN ? 2 : 0) + (view.noise ? 1 : 0)], grid, block, 0, s, t, w.cams);
     return (int)hipGetLastError();
 }
 
+// the public form takes its four groups in the kernel's order: scalars[k] = {lr, beta1, beta2, eps, bc1_rcp, bc2_sqrt_rcp} for k = means, raw_scales, raw_quats,
+// raw_opacities; *loss = the fused MSE of the backward (stored, not added)
 extern "C" int lfs_gut_finish_adam(
     uint32_t N, float* means, float* raw_scales, float* raw_quats, float* raw_opacities, const float* quats, const float* scales, const float* opacities,
     const float* v_dirs, float* const* exp_avg /* [4] host */, float* const* exp_avg_sq /* [4] host */, const float* scalars /* [4][6] host */, float scale_reg,
     float opacity_reg, float* loss, void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
-    return lfs::gut_finish_adam_impl(N, means, raw_scales, raw_quats, raw_opacities, quats, scales, opacities, v_dirs, exp_avg, exp_avg_sq, scalars, scale_reg, opacity_reg,
-                                     loss, workspace, workspace_bytes, (hipStream_t)stream, nullptr);
+    if (N == 0) return LFS_OK;
+    if (!exp_avg || !exp_avg_sq || !scalars) return LFS_E_INVALID;
+    float *m[6] = {}, *v[6] = {}, sc[6][6] = {};
+    for (int j = 0; j < 4; ++j) { const int k = FINISH_GROUP[j]; m[k] = exp_avg[j]; v[k] = exp_avg_sq[j]; for (int i = 0; i < 6; ++i) sc[k][i] = scalars[6 * j + i]; }
+    GutParams p{};
+    p.N = N; p.means = means; p.raw_scales = raw_scales; p.raw_quats = raw_quats; p.raw_opacities = raw_opacities;
+    return lfs::gut_finish_adam_impl(p, GutActivated{quats, scales, opacities}, GutAdam{m, v, sc, nullptr}, GutRegs{scale_reg, opacity_reg}, v_dirs, loss,
+                                     RasterWorkspace{workspace, workspace_bytes}, (hipStream_t)stream);
 }

@@ -425,3 +425,10 @@ def test_lds_reduction_asm_block_agrees_with_the_compiler_generated_stores(lfs, 
             assert np.abs(y0).max() == 0
             continue
         noise_check(f"EWA LDS reduction asm vs ds_write2 {name}", rel_l2(y0, x0), atomic_noise_bar(x0, x1, b[f"fastgs1_{name}"]))
+
+
+def test_every_refused_rasterizer_call_returns_its_code_and_writes_nothing(lfs):
+    """tests/raster_refusals.py on the real library: each single-fault call of the forward, the five backwards, lfs_gut_finish_grads and lfs_gut_finish_adam
+    returns the code of its row and leaves its outputs and its workspace untouched (the emulated runner: tests/test_emulated_raster_refusals.py)."""
+    import raster_refusals
+    assert raster_refusals.run_all() == sum(len(entries) for entries, _, _, _ in raster_refusals.ROWS)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Are the gfx950 code objects of two builds of the product library the same machine code?   python tools/code_object_identity.py <old.so> <new.so>
 Extracts every gfx950 code object (tools/kernel_resources.py: the clang offload bundles inside the .so), and compares, per kernel symbol, the bytes of the function in
-.text and of its kernel descriptor in .rodata (llvm-objdump / llvm-readelf symbol tables). Used when a source edit that is compiled OUT by default changes the library's
+.text and of its kernel descriptor in .rodata (llvm-objdump / llvm-readelf symbol tables), and the order of the symbols. Used when a source edit that is compiled OUT by default changes the library's
 source hash: counters measured on the old build (profiles/traffic.json) describe the new one exactly when every kernel is byte-identical."""
 import hashlib
 import subprocess
@@ -44,7 +44,9 @@ def main():
           f"only in the first: {len(only_a)}; only in the second: {len(only_b)}")
     for k in diff + only_a + only_b:
         print("  differs:", subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip()[:160])
-    sys.exit(1 if diff or only_a or only_b else 0)
+    same_order = list(a) == list(b)   # (symbol-table order: the order in which the code objects define their kernels)
+    print("symbol order:", "the same" if same_order else "DIFFERENT")
+    sys.exit(1 if diff or only_a or only_b or not same_order else 0)
 
 
 if __name__ == "__main__":
