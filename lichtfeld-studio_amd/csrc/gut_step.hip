@@ -36,54 +36,59 @@ struct StepWs {
     float *quats, *scales, *opacities, *means2d, *depths, *colors, *v_dirs, *render, *alpha;
     int32_t *radii, *tiles_per_gauss, *flatten_ids, *last_ids, *abort_flag;
     int64_t *isect_ids, *binned, *dev_counts;
-    void *isect_ws, *raster_ws;
-    size_t isect_ws_bytes, raster_ws_bytes, bytes;
+    uint32_t* isect_totals; const int32_t* isect_offsets;   // inside the intersection workspace: the per-tile totals [T], the offsets [T + 1]
+    IsectGrid grid;                                          // one camera; computed once (step_layout)
+    Workspace isect, raster;
+    size_t bytes;
 };
+// the step workspace as byte offsets: what a caller may look at (lfs_gut_step_layout) and the driver's own blocks
+struct StepLayout { lfs_gut_step_layout pub; size_t tiles_per_gauss, v_dirs, isect, binned, raster, raster_bytes; IsectGrid grid; IsectLayout il; };
 
-bool step_ws(void* base, uint32_t N, uint32_t W, uint32_t H, uint32_t tile, int64_t capacity, StepWs& w, lfs_gut_step_layout* lay) {
+bool step_layout(uint32_t N, uint32_t W, uint32_t H, uint32_t tile, int64_t capacity, StepLayout& l) {
     if (tile == 0 || W == 0 || H == 0 || capacity <= 0) return false;
-    const uint32_t tw = (W + tile - 1) / tile, th = (H + tile - 1) / tile;
-    char* p = static_cast<char*>(base);
+    l.grid = isect_grid_of_image(N, W, H, tile);
+    l.il = isect_layout(l.grid);
+    l.raster_bytes = raster_workspace_bytes_for(N, W, H, tile, capacity);
+    if (l.raster_bytes == 0) return false;
     size_t o = 0;
     auto take = [&](size_t nbytes) { const size_t at = o; o += a256(nbytes); return at; };
     const size_t n = N, P = size_t(W) * H, cap = size_t(capacity);
-    const size_t o_quats = take(16 * n), o_scales = take(12 * n), o_opac = take(4 * n), o_radii = take(8 * n), o_m2d = take(8 * n), o_depths = take(4 * n);
-    const size_t o_tpg = take(4 * n), o_colors = take(12 * n), o_vdirs = take(12 * n);
-    w.isect_ws_bytes = lfs_intersect_tile_workspace_bytes(1, N, tw, th);
-    const size_t o_iws = take(w.isect_ws_bytes);
-    const size_t o_ids = take(8 * cap), o_flat = take(4 * cap), o_binned = take(8 * cap);
-    w.raster_ws_bytes = raster_workspace_bytes_for(N, W, H, tile, capacity);
-    if (w.raster_ws_bytes == 0) return false;
-    const size_t o_rws = take(w.raster_ws_bytes);
-    const size_t o_render = take(12 * P), o_alpha = take(4 * P), o_last = take(4 * P), o_flag = take(4), o_counts = take(32);
-    w.bytes = o;
-    w.quats = (float*)(p + o_quats); w.scales = (float*)(p + o_scales); w.opacities = (float*)(p + o_opac); w.radii = (int32_t*)(p + o_radii);
-    w.means2d = (float*)(p + o_m2d); w.depths = (float*)(p + o_depths); w.tiles_per_gauss = (int32_t*)(p + o_tpg); w.colors = (float*)(p + o_colors);
-    w.v_dirs = (float*)(p + o_vdirs); w.isect_ws = p + o_iws; w.isect_ids = (int64_t*)(p + o_ids); w.flatten_ids = (int32_t*)(p + o_flat);
-    w.binned = (int64_t*)(p + o_binned); w.raster_ws = p + o_rws; w.render = (float*)(p + o_render); w.alpha = (float*)(p + o_alpha);
-    w.last_ids = (int32_t*)(p + o_last); w.abort_flag = (int32_t*)(p + o_flag); w.dev_counts = (int64_t*)(p + o_counts);
-    if (lay) {
-        lay->bytes = o; lay->quats = o_quats; lay->scales = o_scales; lay->opacities = o_opac; lay->radii = o_radii; lay->means2d = o_m2d; lay->depths = o_depths;
-        lay->colors = o_colors; lay->isect_ids = o_ids; lay->flatten_ids = o_flat; lay->render = o_render; lay->alpha = o_alpha; lay->last_ids = o_last;
-        lay->abort_flag = o_flag; lay->counts = o_counts;
-        lay->tile_offsets = o_iws + size_t(reinterpret_cast<const char*>(isect_workspace_offsets(nullptr, 1, N, tw, th)) - static_cast<const char*>(nullptr));
-    }
+    lfs_gut_step_layout& p = l.pub;
+    p.quats = take(16 * n); p.scales = take(12 * n); p.opacities = take(4 * n); p.radii = take(8 * n); p.means2d = take(8 * n); p.depths = take(4 * n);
+    l.tiles_per_gauss = take(4 * n); p.colors = take(12 * n); l.v_dirs = take(12 * n);
+    l.isect = take(l.il.bytes); p.tile_offsets = l.isect + l.il.offsets;
+    p.isect_ids = take(8 * cap); p.flatten_ids = take(4 * cap); l.binned = take(8 * cap);
+    l.raster = take(l.raster_bytes);
+    p.render = take(12 * P); p.alpha = take(4 * P); p.last_ids = take(4 * P); p.abort_flag = take(4); p.counts = take(32);
+    p.bytes = o;
     return true;
 }
 
-struct Front { lfs_cameras cams; RasterScene scene; RasterLists lists; RasterWorkspace ws; };   // (scene.cams points at cams: filled in place, not copied)
+void step_ws(void* base, const StepLayout& l, StepWs& w) {
+    const lfs_gut_step_layout& p = l.pub;
+    w.bytes = p.bytes; w.grid = l.grid;
+    w.quats = at_offset<float>(base, p.quats); w.scales = at_offset<float>(base, p.scales); w.opacities = at_offset<float>(base, p.opacities);
+    w.radii = at_offset<int32_t>(base, p.radii); w.means2d = at_offset<float>(base, p.means2d); w.depths = at_offset<float>(base, p.depths);
+    w.tiles_per_gauss = at_offset<int32_t>(base, l.tiles_per_gauss); w.colors = at_offset<float>(base, p.colors); w.v_dirs = at_offset<float>(base, l.v_dirs);
+    w.isect = Workspace{at_offset<char>(base, l.isect), l.il.bytes}; w.raster = Workspace{at_offset<char>(base, l.raster), l.raster_bytes};
+    w.isect_totals = at_offset<uint32_t>(w.isect.base, l.il.totals); w.isect_offsets = at_offset<const int32_t>(w.isect.base, l.il.offsets);
+    w.isect_ids = at_offset<int64_t>(base, p.isect_ids); w.flatten_ids = at_offset<int32_t>(base, p.flatten_ids); w.binned = at_offset<int64_t>(base, l.binned);
+    w.render = at_offset<float>(base, p.render); w.alpha = at_offset<float>(base, p.alpha); w.last_ids = at_offset<int32_t>(base, p.last_ids);
+    w.abort_flag = at_offset<int32_t>(base, p.abort_flag); w.dev_counts = at_offset<int64_t>(base, p.counts);
+}
+
+struct Front { lfs_cameras cams; RasterScene scene; RasterLists lists; Workspace ws; };   // (scene.cams points at cams: filled in place, not copied)
 
 // what every guarded rasterizer call of a view takes: the camera block, the scene, the lists (count on the device, sized for `capacity`) and the workspace
 void front_of(const lfs_gut_step_args* a, const StepWs& w, int64_t capacity, Front& f) {
-    const uint32_t tile = a->tile_size, tw = (a->image_width + tile - 1) / tile, th = (a->image_height + tile - 1) / tile;
     f.cams = lfs_cameras{};
     f.cams.C = 1; f.cams.image_width = a->image_width; f.cams.image_height = a->image_height; f.cams.camera_model = LFS_CAMERA_PINHOLE; f.cams.rs_type = LFS_SHUTTER_GLOBAL;
     f.cams.viewmats0 = a->viewmat; f.cams.Ks = a->Kmat;
     f.scene = RasterScene{};
     f.scene.N = a->N; f.scene.channels = 3; f.scene.means = a->means; f.scene.quats = w.quats; f.scene.scales = w.scales; f.scene.colors = w.colors;
-    f.scene.opacities = w.opacities; f.scene.backgrounds = a->background; f.scene.cams = &f.cams; f.scene.tile_size = tile;
-    f.lists = RasterLists{isect_workspace_offsets(w.isect_ws, 1, a->N, tw, th), w.flatten_ids, -1, capacity};
-    f.ws = RasterWorkspace{w.raster_ws, w.raster_ws_bytes};
+    f.scene.opacities = w.opacities; f.scene.backgrounds = a->background; f.scene.cams = &f.cams; f.scene.tile_size = w.grid.tile_size;
+    f.lists = RasterLists{w.isect_offsets, w.flatten_ids, -1, capacity};
+    f.ws = w.raster;
 }
 // the groups of the finish and tail launchers, out of the argument block and the workspace
 GutParams params_of(const lfs_gut_step_args* a) { return GutParams{a->N, a->K, a->sh_degree, a->means, a->sh0, a->shN, a->raw_scales, a->raw_quats, a->raw_opacities}; }
@@ -109,9 +114,10 @@ int open_step(const lfs_gut_step_args* a, Need need, const lfs_gut_step_options*
     const int rc = check_args(a, need);
     if (rc) return rc;
     if (o && a->K > 16 && (o->freeze_shN || o->noise)) return LFS_E_UNSUPPORTED;   // the three-pass tail of degree 4 has neither (enqueue_tail)
-    if (!workspace) return LFS_E_INVALID;
-    if (!step_ws(workspace, a->N, a->image_width, a->image_height, a->tile_size, capacity, w, nullptr)) return LFS_E_INVALID;
-    if (workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
+    StepLayout l;
+    if (!workspace || !step_layout(a->N, a->image_width, a->image_height, a->tile_size, capacity, l)) return LFS_E_INVALID;
+    if (workspace_bytes < l.pub.bytes) return LFS_E_WORKSPACE;
+    step_ws(workspace, l, w);
     if (o && o->loss_kind == 1) {
         if (!have_loss_kernels()) return LFS_E_UNSUPPORTED;
         if (!o->loss_workspace) return LFS_E_INVALID;
@@ -123,8 +129,6 @@ int open_step(const lfs_gut_step_args* a, Need need, const lfs_gut_step_options*
 // everything up to and including the rasterizer forward; shared by the Adam-inline step and the gradient-tensor step
 int enqueue_forward(const lfs_gut_step_args* a, const StepWs& w, int64_t capacity, int64_t assumed_longest, int64_t* host_counts, int64_t stamp, hipStream_t s, Front& f,
                     bool colors_ready = false) {   // colors_ready: w.colors holds this view's SH colours already (the previous step's fused tail wrote them)
-    const uint32_t N = a->N, W = a->image_width, H = a->image_height, tile = a->tile_size;
-    const uint32_t tw = (W + tile - 1) / tile, th = (H + tile - 1) / tile;
     front_of(a, w, capacity, f);
     const lfs_ut_params ut{0.1f, 2.f, 0.f, 0.1f, 1};   // Cameras.h:27-61 defaults, as the trainer passes them (rasterizer_autograd.cpp:223-234)
     // trainer constants of rasterizer.cpp:176-181: eps2d 0.3, near 0.01, far 1e4, radius_clip 0
@@ -135,27 +139,31 @@ int enqueue_forward(const lfs_gut_step_args* a, const StepWs& w, int64_t capacit
     // visible Gaussian itself: raster_pack_kernel's second pass over the Gaussians (0.040 ms, 152 MB re-read) is gone. Debug bit 6: the round-3 order (A/B, tests).
     const bool pack_here = !(lfs_get_debug_flags() & 64u);
     void *recs = nullptr, *cull = nullptr;
-    raster_workspace_parts(w.raster_ws, N, &recs, &cull);
+    raster_workspace_parts(w.raster.base, a->N, &recs, &cull);
     int rc = LFS_OK;
     if (pack_here && !colors_ready) {
-        rc = sh_model_fwd_impl(N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, nullptr, w.colors, s);
+        rc = sh_model_fwd_impl(params_of(a), ShView{a->viewmat, /*radii=*/nullptr, w.colors}, s);
         if (rc) return rc;
     }
-    rc = activations_project_ut_impl(N, a->means, a->raw_quats, a->raw_scales, a->raw_opacities, &f.cams, 0.3f, 0.01f, 10000.f, 0.f, &ut, w.quats, w.scales,
-                                     w.opacities, w.radii, w.means2d, w.depths, isect_workspace_totals(w.isect_ws, 1, N, tw, th), tw * th, w.raster_ws, s,
-                                     pack_here ? recs : nullptr, pack_here ? cull : nullptr, pack_here ? w.colors : nullptr);
+    const ProjCamera cam{&f.cams, /*eps2d=*/0.3f, /*near_plane=*/0.01f, /*far_plane=*/10000.f, /*radius_clip=*/0.f, &ut};
+    const ProjRiders riders{w.isect_totals, w.grid.tiles(), /*cams_out=*/w.raster.base, pack_here ? recs : nullptr, pack_here ? cull : nullptr, pack_here ? w.colors : nullptr};
+    rc = activations_project_ut_impl(ProjModel{a->N, a->means, a->raw_quats, a->raw_scales, a->raw_opacities}, cam, ProjOut{w.quats, w.scales, w.opacities, w.radii, w.means2d, w.depths},
+                                     &riders, s);
     if (rc) return rc;
     const IsectGuard guard{capacity, assumed_longest, w.abort_flag};
+    const IsectInputs in{w.means2d, w.radii, w.depths};
     int64_t* counts = host_counts ? host_counts : w.dev_counts;   // [n_isects, longest tile list, stamp]
-    rc = isect_count_impl(1, N, w.means2d, w.radii, tile, tw, th, w.tiles_per_gauss, counts, counts + 1, nullptr, LFS_ISECT_COUNTERS_ZERO, counts + 2, stamp, w.isect_ws,
-                          w.isect_ws_bytes, s, &guard);
+    IsectCounts cnt{};   // (no tile_offsets copy: the rasterizer reads the workspace's own; the projection kernel has cleared the totals)
+    cnt.tiles_per_gauss = w.tiles_per_gauss; cnt.n_isects = counts; cnt.max_tile_isects = counts + 1; cnt.stamp_out = counts + 2; cnt.stamp = stamp; cnt.flags = LFS_ISECT_COUNTERS_ZERO;
+    rc = isect_count(w.grid, in, cnt, w.isect, s, &guard);
     if (rc) return rc;
     if (!pack_here && !colors_ready) { // the SH colours need the projection's radii only: enqueued between the count and the binning passes, as the Python step did with its `overlap` hook
-        rc = lfs_sh_model_fwd(N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, w.radii, w.colors, s);
+        rc = lfs_sh_model_fwd(a->N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, w.radii, w.colors, s);
         if (rc) return rc;
     }
-    rc = isect_emit_impl(1, N, w.means2d, w.radii, w.depths, tile, tw, th, 1, -1, w.tiles_per_gauss, w.isect_ids, w.flatten_ids, nullptr, w.binned, -1, w.isect_ws,
-                         w.isect_ws_bytes, s, &guard);
+    IsectLists lists{};   // (guarded: the count and the longest list are the guard's)
+    lists.sort = 1; lists.n_isects = -1; lists.max_tile_isects = -1; lists.tiles_per_gauss = w.tiles_per_gauss; lists.isect_ids = w.isect_ids; lists.flatten_ids = w.flatten_ids; lists.scratch = w.binned;
+    rc = isect_emit(w.grid, in, lists, w.isect, s, &guard);
     if (rc) return rc;
     return raster_forward(f.scene, f.lists, f.ws, RasterFwdOut{w.render, w.alpha, w.last_ids, /*cams_ready=*/true, /*records_ready=*/pack_here}, s);
 }
@@ -170,16 +178,15 @@ int enqueue_backward(const lfs_gut_step_args* a, const StepWs& w, const Front& f
 }
 
 const float* acc_rows_of(const lfs_gut_step_args* a, const StepWs& w) {
-    return reinterpret_cast<const float*>(static_cast<const char*>(w.raster_ws) + lfs_rasterize_workspace_acc_offset(1, a->N));
+    return reinterpret_cast<const float*>(static_cast<const char*>(w.raster.base) + lfs_rasterize_workspace_acc_offset(1, a->N));
 }
 
 // The tail as three per-Gaussian passes (SH backward + Adam on sh0 / shN, then finish + activation backward + Adam on means, raw_scales, raw_quats, raw_opacities): the
 // three-pass form, and what the fused-tail form runs for K > 16 (no colours for the next step). loss (nullable): receives the fused MSE of the backward.
 int three_pass_tail(const lfs_gut_step_args* a, const StepWs& w, float* loss, hipStream_t s) {
-    const int rc = sh_model_bwd_adam_all_impl(a->N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, w.radii, w.colors, acc_rows_of(a, w), w.v_dirs, a->exp_avg[1],
-                                              a->exp_avg_sq[1], a->adam[1], a->exp_avg[2], a->exp_avg_sq[2], a->adam[2], s, w.abort_flag);
+    const int rc = sh_model_bwd_adam_all_impl(params_of(a), ShView{a->viewmat, w.radii, w.colors}, adam_of(a, w), acc_rows_of(a, w), w.v_dirs, s);
     if (rc) return rc;
-    return gut_finish_adam_impl(params_of(a), activated_of(w), adam_of(a, w), GutRegs{a->scale_reg, a->opacity_reg}, w.v_dirs, loss, RasterWorkspace{w.raster_ws, w.raster_ws_bytes}, s);
+    return gut_finish_adam_impl(params_of(a), activated_of(w), adam_of(a, w), GutRegs{a->scale_reg, a->opacity_reg}, w.v_dirs, loss, w.raster, s);
 }
 
 // The fused-tail form's tail: the three passes as ONE launch (raster.hip: gut_tail_kernel), with shN frozen and the MCMC noise on request. K > 16 (SH degree 4) has no
@@ -187,7 +194,7 @@ int three_pass_tail(const lfs_gut_step_args* a, const StepWs& w, float* loss, hi
 int enqueue_tail(const lfs_gut_step_args* a, const StepWs& w, const lfs_gut_step_options& o, const float* next_viewmat, float* loss, hipStream_t s) {
     if (a->K > 16) return three_pass_tail(a, w, loss, s);
     const GutTailView view{a->viewmat, next_viewmat, w.radii, w.colors, o.freeze_shN != 0, o.noise, o.noise_lr};
-    return gut_tail_impl(params_of(a), activated_of(w), adam_of(a, w), GutRegs{a->scale_reg, a->opacity_reg}, view, loss, RasterWorkspace{w.raster_ws, w.raster_ws_bytes}, s);
+    return gut_tail_impl(params_of(a), activated_of(w), adam_of(a, w), GutRegs{a->scale_reg, a->opacity_reg}, view, loss, w.raster, s);
 }
 
 // ---- the training step: ONE sequence (open -> forward -> [loss kernels] -> backward -> tail) in two forms ----------------------------------------------------
@@ -247,9 +254,9 @@ int train_step_impl(Form form, const lfs_gut_step_args* a, const lfs_gut_step_op
 using namespace lfs;
 
 extern "C" int lfs_gut_step_layout_for(uint32_t N, uint32_t image_width, uint32_t image_height, uint32_t tile_size, int64_t capacity, lfs_gut_step_layout* out) {
-    if (!out) return LFS_E_INVALID;
-    StepWs w;
-    if (!step_ws(nullptr, N, image_width, image_height, tile_size, capacity, w, out)) return LFS_E_INVALID;
+    StepLayout l{};
+    if (!out || !step_layout(N, image_width, image_height, tile_size, capacity, l)) return LFS_E_INVALID;
+    *out = l.pub;
     return LFS_OK;
 }
 
@@ -257,8 +264,7 @@ extern "C" int lfs_gut_step_layout_for(uint32_t N, uint32_t image_width, uint32_
 // bit 5 off; tile sizes the rasterizer has cell kernels for). 0: lfs_gut_* would return LFS_E_UNSUPPORTED - the caller enqueues the operators one by one instead.
 extern "C" int lfs_gut_step_supported(uint32_t N, uint32_t image_width, uint32_t image_height, uint32_t tile_size) {
     if (N == 0 || tile_size < 8 || tile_size > 64 || (tile_size & 7) || image_width == 0 || image_height == 0) return 0;
-    const uint32_t tw = (image_width + tile_size - 1) / tile_size, th = (image_height + tile_size - 1) / tile_size;
-    return isect_two_pass_supported(1, N, tw, th) ? 1 : 0;
+    return isect_two_pass_supported(isect_grid_of_image(N, image_width, image_height, tile_size)) ? 1 : 0;
 }
 
 extern "C" int lfs_gut_step_fits(int64_t n_isects, int64_t longest, int64_t capacity, int64_t assumed_longest) {
@@ -308,8 +314,9 @@ extern "C" int lfs_gut_view_backward_sh(const lfs_gut_step_args* a, int64_t capa
     front_of(a, w, capacity, f);
     rc = enqueue_backward(a, w, f, a->target_chw ? nullptr : v_render, s);
     if (rc) return rc;
-    return sh_model_bwd_rows_impl(a->N, a->K, a->sh_degree, a->means, a->viewmat, a->sh0, a->shN, w.radii, w.colors, acc_rows_of(a, w), accumulate, grads[1], grads[2], w.v_dirs,
-                                  s, inline_shN ? a->exp_avg[2] : nullptr, inline_shN ? a->exp_avg_sq[2] : nullptr, inline_shN ? a->adam[2] : nullptr);
+    const GutAdam adam = adam_of(a, w);
+    return sh_model_bwd_rows_impl(params_of(a), ShView{a->viewmat, w.radii, w.colors}, acc_rows_of(a, w), ShGrads{grads[1], grads[2], w.v_dirs, accumulate},
+                                  inline_shN ? &adam : nullptr, s);
 }
 
 extern "C" int lfs_gut_view_backward_finish(const lfs_gut_step_args* a, int64_t capacity, float* const* grads /* [6] host */, int accumulate,
@@ -319,7 +326,7 @@ extern "C" int lfs_gut_view_backward_finish(const lfs_gut_step_args* a, int64_t 
     if (rc) return rc;
     if (!grads || !grads[0] || !grads[3] || !grads[4] || !grads[5] || (a->target_chw && !a->loss)) return LFS_E_INVALID;
     return gut_finish_grads_impl(params_of(a), activated_of(w), GutRegs{a->scale_reg, a->opacity_reg}, GutGrads{grads[0], grads[3], grads[4], grads[5], nullptr, accumulate},
-                                 w.v_dirs, a->target_chw ? a->loss : nullptr, RasterWorkspace{w.raster_ws, w.raster_ws_bytes}, (hipStream_t)stream);
+                                 w.v_dirs, a->target_chw ? a->loss : nullptr, w.raster, (hipStream_t)stream);
 }
 
 // The view's backward for the FACTORED gradient exchange of the replicated data-parallel layout (dist.ColorGradExchange): rasterizer backward, then the finish pass -
@@ -338,7 +345,7 @@ extern "C" int lfs_gut_view_backward_rows(const lfs_gut_step_args* a, int64_t ca
     rc = enqueue_backward(a, w, f, a->target_chw ? nullptr : v_render, s);
     if (rc) return rc;
     return gut_finish_grads_impl(params_of(a), activated_of(w), GutRegs{a->scale_reg, a->opacity_reg}, GutGrads{grads[0], grads[3], grads[4], grads[5], v_colors_out, accumulate},
-                                 nullptr, a->target_chw ? a->loss : nullptr, RasterWorkspace{w.raster_ws, w.raster_ws_bytes}, s);
+                                 nullptr, a->target_chw ? a->loss : nullptr, w.raster, s);
 }
 
 extern "C" int lfs_gut_view_backward(const lfs_gut_step_args* a, int64_t capacity, const float* v_render, float* const* grads /* [6] host */, int accumulate,

@@ -305,7 +305,7 @@ __global__ void __launch_bounds__(1024) isect_tiles_kernel(
 // sort == false path: reference emission order (Gaussian-major), needs the
 // inclusive scan of tiles_per_gauss.
 // ---------------------------------------------------------------------------
-constexpr int SCAN_ITEMS = 2048; // per workgroup of 256 threads (8 per thread)
+constexpr int SCAN_ITEMS = int(ISECT_SCAN_ITEMS); // 2048 per workgroup of 256 threads (8 per thread); the workspace layout counts the workgroups
 
 __global__ void __launch_bounds__(256) scan_block_sums_kernel(const size_t n, const int32_t* __restrict__ in, int64_t* __restrict__ block_sums) {
     __shared__ int64_t ws[4];
@@ -398,229 +398,219 @@ __global__ void __launch_bounds__(256) isect_offset_kernel(
     if (i == n_isects - 1) for (int64_t t = cur + 1; t < T; ++t) offsets[t] = int32_t(n_isects);
 }
 
-// ---- workspace layout ------------------------------------------------------
-struct IsectWs {
-    uint32_t* totals;   // [T]
-    uint32_t* cursor;   // [T]
-    uint32_t* row_cursor; // [C * tile_h]   (two-pass scatter)
-    int32_t* offsets;   // [T+1]
-    int64_t* block_sums; // [ceil(CN / SCAN_ITEMS) + 1]
-    size_t bytes;
-};
-static inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
-static IsectWs isect_ws(void* base, uint32_t C, uint32_t N, uint32_t tw, uint32_t th) {
-    const size_t T = size_t(C) * tw * th;
-    const size_t nb = (size_t(C) * N + SCAN_ITEMS - 1) / SCAN_ITEMS + 1;
-    IsectWs w; char* p = (char*)base; size_t o = 0;
-    w.totals = (uint32_t*)(p + o); o += align256(T * 4);
-    w.cursor = (uint32_t*)(p + o); o += align256(T * 4);
-    w.row_cursor = (uint32_t*)(p + o); o += align256(size_t(C) * th * 4);
-    w.offsets = (int32_t*)(p + o); o += align256((T + 1) * 4);
-    w.block_sums = (int64_t*)(p + o); o += align256(nb * 8);
-    w.bytes = o;
-    return w;
+// ---- host layer: one described call per direction (lfs_step_internal.h), every check in front of the first enqueue ----
+struct IsectWs { uint32_t *totals, *cursor, *row_cursor; int32_t* offsets; int64_t* block_sums; };   // the workspace's arrays: base + IsectLayout offset
+static IsectWs isect_ws(const Workspace& ws, const IsectLayout& l) {
+    return IsectWs{at_offset<uint32_t>(ws.base, l.totals), at_offset<uint32_t>(ws.base, l.cursor), at_offset<uint32_t>(ws.base, l.row_cursor),
+                   at_offset<int32_t>(ws.base, l.offsets), at_offset<int64_t>(ws.base, l.block_sums)};
 }
-static inline uint32_t isect_per_block(size_t total) {
-    // ~512 workgroups of 1024 threads on a big problem, never fewer than 1024 Gaussians each
+static inline uint32_t isect_per_block(size_t total) {   // ~512 workgroups of 1024 threads on a big problem, never fewer than 1024 Gaussians each
     size_t pb = (total + 511) / 512;
     if (pb < 1024) pb = 1024;
     return uint32_t((pb + 1023) / 1024 * 1024);
 }
 constexpr size_t LDS_HIST_LIMIT = 64 * 1024; // bytes for the scatter kernel's two [T] arrays
+static bool grid_ok(const IsectGrid& g) { return g.tile_size != 0 && g.tile_width != 0 && g.tile_height != 0 && g.C != 0; }
+static bool guard_ok(const IsectGuard* guard) { return guard == nullptr || (guard->capacity >= 0 && guard->abort_flag != nullptr); }
 
 } // namespace lfs
 
 using namespace lfs;
 
 extern "C" size_t lfs_intersect_tile_workspace_bytes(uint32_t C, uint32_t N, uint32_t tile_width, uint32_t tile_height) {
-    return isect_ws(nullptr, C, N, tile_width, tile_height).bytes;
+    return isect_layout(IsectGrid{C, N, 0, tile_width, tile_height}).bytes;
 }
 
-int lfs::isect_count_impl(
-    uint32_t C, uint32_t N, const float* means2d, const int32_t* radii,
-    uint32_t tile_size, uint32_t tile_width, uint32_t tile_height,
-    int32_t* tiles_per_gauss, int64_t* n_isects, int64_t* max_tile_isects, int32_t* tile_offsets, uint32_t flags, int64_t* stamp_out, int64_t stamp,
-    void* workspace, size_t workspace_bytes, hipStream_t s, const IsectGuard* guard) {
-    if (!n_isects || !workspace || tile_size == 0 || tile_width == 0 || tile_height == 0 || C == 0) return LFS_E_INVALID;
-    if (bit_width_u32(tile_width * tile_height) + bit_width_u32(C) > 32) return LFS_E_UNSUPPORTED; // IntersectTile.cu:154
-    IsectWs w = isect_ws(workspace, C, N, tile_width, tile_height);
-    if (workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
-    const uint32_t T = C * tile_width * tile_height;
+static int count_check(const IsectGrid& g, const IsectInputs& in, const IsectCounts& c, const Workspace& ws, const IsectGuard* guard) {
+    if (!c.n_isects || !ws.base || !grid_ok(g)) return LFS_E_INVALID;
+    if (bit_width_u32(g.tile_width * g.tile_height) + bit_width_u32(g.C) > 32) return LFS_E_UNSUPPORTED; // IntersectTile.cu:154
+    if (ws.bytes < isect_layout(g).bytes) return LFS_E_WORKSPACE;
+    if (size_t(g.C) * g.N > 0 && (!in.means2d || !in.radii || !c.tiles_per_gauss)) return LFS_E_INVALID;
+    return guard_ok(guard) ? LFS_OK : LFS_E_INVALID;
+}
+
+int lfs::isect_count(const IsectGrid& g, const IsectInputs& in, const IsectCounts& c, const Workspace& ws, hipStream_t s, const IsectGuard* guard) {
+    const int rc = count_check(g, in, c, ws, guard);
+    if (rc) return rc;
+    const IsectWs w = isect_ws(ws, isect_layout(g));
+    const uint32_t T = g.tiles();
     // the scan kernel leaves totals[] zero again and zeroes both cursors itself: a caller that OWNS the workspace and passes the one of its previous call
-    // (same C, N, tile grid) may set LFS_ISECT_COUNTERS_ZERO and save the memset (nothing in this repository does any more: 32 KB, ~2 us)
-    if (!(flags & LFS_ISECT_COUNTERS_ZERO)) {
+    // (same C, N, tile grid) may set LFS_ISECT_COUNTERS_ZERO and save the memset (32 KB, ~2 us). The training step does, on every call: its projection
+    // kernel clears the totals (ProjRiders::zero_words)
+    if (!(c.flags & LFS_ISECT_COUNTERS_ZERO)) {
         hipError_t e = hipMemsetAsync(w.totals, 0, size_t(T) * 4, s);
         if (e != hipSuccess) return (int)e;
     }
-    const size_t total = size_t(C) * N;
+    const size_t total = size_t(g.C) * g.N;
     // Round 6, measured and removed (profiles/r06/lease16_count_scan_tail_ab.txt): the scan as the tail of the count kernel's LAST workgroup (ticket counter behind a
     // device-scope fence, totals read with device-scope atomic loads) - count + scan 0.031 -> 0.140 ms. A device-scope release on this part writes the L2 of the XCD
     // back (the eight L2s are not coherent with each other), and every one of the 512 workgroups paid for it behind the projection kernel's 200 MB of dirty lines:
     // "last workgroup finishes the job" is not a pattern for an eight-XCD device; the second launch (8 us + gap) stays.
     lfs::ProfScope prof("isect_count_scan", s);
     if (total > 0) {
-        if (!means2d || !radii || !tiles_per_gauss) return LFS_E_INVALID;
-        const uint32_t pb = isect_per_block(total);
-        const uint32_t blocks = uint32_t((total + pb - 1) / pb);
+        const uint32_t pb = isect_per_block(total), blocks = uint32_t((total + pb - 1) / pb);
         if (size_t(T) * 8 <= LDS_HIST_LIMIT)
-            hipLaunchKernelGGL(isect_count_kernel<true>, dim3(blocks), dim3(1024), T * 4, s, C, N, pb, means2d, radii,
-                               float(tile_size), tile_width, tile_height, tiles_per_gauss, w.totals);
+            hipLaunchKernelGGL(isect_count_kernel<true>, dim3(blocks), dim3(1024), T * 4, s, g.C, g.N, pb, in.means2d, in.radii,
+                               float(g.tile_size), g.tile_width, g.tile_height, c.tiles_per_gauss, w.totals);
         else
-            hipLaunchKernelGGL(isect_count_kernel<false>, dim3(blocks), dim3(1024), 0, s, C, N, pb, means2d, radii,
-                               float(tile_size), tile_width, tile_height, tiles_per_gauss, w.totals);
+            hipLaunchKernelGGL(isect_count_kernel<false>, dim3(blocks), dim3(1024), 0, s, g.C, g.N, pb, in.means2d, in.radii,
+                               float(g.tile_size), g.tile_width, g.tile_height, c.tiles_per_gauss, w.totals);
     }
-    if (guard != nullptr) {
-        if (guard->capacity < 0 || !guard->abort_flag) return LFS_E_INVALID;
-        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, s, T, w.totals, w.offsets, n_isects, true, w.cursor, w.row_cursor, C * tile_height, tile_offsets,
-                           max_tile_isects, stamp_out, stamp, guard->capacity, sort_class_limit(guard->assumed_longest), guard->abort_flag);
-    } else
-        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, s, T, w.totals, w.offsets, n_isects, true, w.cursor, w.row_cursor, C * tile_height, tile_offsets,
-                           max_tile_isects, stamp_out, stamp);
+    // unguarded: the kernel's own defaults (no capacity, no list limit, no flag)
+    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, s, T, w.totals, w.offsets, c.n_isects, true, w.cursor, w.row_cursor, g.rows(), c.tile_offsets,
+                       c.max_tile_isects, c.stamp_out, c.stamp, guard ? guard->capacity : int64_t(-1), guard ? sort_class_limit(guard->assumed_longest) : 0xFFFFFFFFu,
+                       guard ? guard->abort_flag : nullptr);
     return (int)hipGetLastError();
 }
 
+// ---- the per-tile sort classes: lists of up to `limit` entries are ordered by `kernel` in workgroups of `block` threads with `lds_bytes` of dynamic LDS (sized to
+// the class so that small tiles do not cap the occupancy). <= 1024 entries: the counting kernel on 256 bins (256 threads, keys staged in LDS); <= 4096: 512 bins with
+// 512 threads and only the binned copy in LDS (32 KiB; measured against the staged 256-thread form: 0.277 -> 0.127 ms per view at 12 M intersections, 0.058 -> 0.042
+// at 4.4 M; 1024 threads or the same change for the first class: no further gain) - this class has no kernel of its own, tile_sort_bins_2class_kernel runs it
+// TOGETHER with the first one; <= 16384: 1024 bins (1024 threads, 128 KiB LDS; a bin of more than 64 keys falls back to the bitonic network inside the kernel).
+// Longer lists: tile_sort_global_kernel, bitonic on global memory. The launch ladder, the LDS opt-in and sort_class_limit read this table.
+// (what else takes the LDS opt-in below. In front of the table: a code object lays its kernels out in the order they are first named, and tile_sort_lds_kernel<1024> is its first sort kernel)
+struct BigLds { const void* kernel; uint32_t lds_bytes; };
+static const BigLds OTHER_BIG_LDS[3] = {{reinterpret_cast<const void*>(&tile_sort_lds_kernel<1024>), 16384 * 8},
+                                        {reinterpret_cast<const void*>(&isect_rows_kernel), ROWS_STAGE * 8},
+                                        {reinterpret_cast<const void*>(&isect_tiles_kernel), TILES_CHUNK * 8}};
+using TileSortKernel = decltype(&tile_sort_bins_kernel<256>);
+struct SortClass { uint32_t limit; TileSortKernel kernel; uint32_t block, lds_bytes; };
+constexpr SortClass SORT_CLASSES[3] = {
+    {1024, tile_sort_bins_kernel<256>, 256, 2 * 1024 * 8},
+    {4096, nullptr, 512, 4096 * 8},
+    {16384, tile_sort_bins_kernel<1024, 1024, false, 64>, 1024, 16384 * 8},
+};
+
+uint32_t lfs::sort_class_limit(int64_t assumed_longest) {
+    for (const SortClass& c : SORT_CLASSES) if (assumed_longest <= int64_t(c.limit)) return c.limit;
+    return 0xFFFFFFFFu;
+}
+
+// > 64 KiB of dynamic LDS has to be opted into once per process
+static hipError_t opt_in_big_lds() {
+    static bool done = false;
+    if (done) return hipSuccess;
+    auto opt_in = [](const void* kernel, size_t bytes) { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)); };
+    hipError_t e = hipSuccess;
+    for (const SortClass& c : SORT_CLASSES) if (e == hipSuccess && c.kernel != nullptr) e = opt_in(reinterpret_cast<const void*>(c.kernel), c.lds_bytes);
+    for (const BigLds& k : OTHER_BIG_LDS) if (e == hipSuccess) e = opt_in(k.kernel, k.lds_bytes);
+    done = e == hipSuccess;
+    return e;
+}
+
 // what the guarded (speculative) emit needs: the two-pass binned scatter (the one-pass kernels do not watch the abort flag)
-bool lfs::isect_two_pass_supported(uint32_t C, uint32_t N, uint32_t tile_width, uint32_t tile_height) {
-    const size_t total = size_t(C) * N;
-    if (total == 0 || tile_width == 0 || tile_height == 0) return false;
+bool lfs::isect_two_pass_supported(const IsectGrid& g) {
+    const size_t total = size_t(g.C) * g.N;
+    if (total == 0 || g.tile_width == 0 || g.tile_height == 0) return false;
     const uint32_t idx_bits = bit_width_u32(uint32_t(total - 1)) ? bit_width_u32(uint32_t(total - 1)) : 1u;
-    return C * tile_height <= ROWS_MAX && total <= 0xFFFFFFFFull && idx_bits + bit_width_u32(tile_width - 1) <= 32 && !(lfs_get_debug_flags() & 32u);
+    return g.rows() <= ROWS_MAX && total <= 0xFFFFFFFFull && idx_bits + bit_width_u32(g.tile_width - 1) <= 32 && !(lfs_get_debug_flags() & 32u);
 }
 
-uint32_t* lfs::isect_workspace_totals(void* workspace, uint32_t C, uint32_t N, uint32_t tile_width, uint32_t tile_height) {
-    return isect_ws(workspace, C, N, tile_width, tile_height).totals;
-}
-const int32_t* lfs::isect_workspace_offsets(void* workspace, uint32_t C, uint32_t N, uint32_t tile_width, uint32_t tile_height) {
-    return isect_ws(workspace, C, N, tile_width, tile_height).offsets;
+static int emit_check(const IsectGrid& g, const IsectInputs& in, const IsectLists& l, const Workspace& ws, const IsectGuard* guard) {
+    if (!ws.base || !grid_ok(g)) return LFS_E_INVALID;
+    if (ws.bytes < isect_layout(g).bytes) return LFS_E_WORKSPACE;
+    if (guard && (!l.sort || !l.scratch || !guard_ok(guard))) return LFS_E_INVALID;
+    const int64_t n_isects = guard ? guard->capacity : l.n_isects;
+    if (n_isects <= 0) return LFS_OK;   // (nothing to emit: only tile_offsets is written)
+    if (n_isects > 0x7FFFFFFFll) return LFS_E_UNSUPPORTED; // offsets / last_ids are int32 in the reference API
+    if (!in.means2d || !in.radii || !in.depths || !l.isect_ids || !l.flatten_ids) return LFS_E_INVALID;
+    if (!l.sort) return l.tiles_per_gauss ? LFS_OK : LFS_E_INVALID;
+    return (guard && !isect_two_pass_supported(g)) ? LFS_E_UNSUPPORTED : LFS_OK; // (the one-pass scatter does not watch the abort flag)
 }
 
+int lfs::isect_emit(const IsectGrid& g, const IsectInputs& in, const IsectLists& l, const Workspace& ws, hipStream_t s, const IsectGuard* guard) {
+    const int rc = emit_check(g, in, l, ws, guard);
+    if (rc) return rc;
+    const IsectWs w = isect_ws(ws, isect_layout(g));
+    const uint32_t T = g.tiles(), tile_width = g.tile_width, tile_height = g.tile_height;
+    // guarded (speculative) call: the count is on the device. Grids cover the caller's capacity, the kernels read offsets[T]; the sort classes are the ones
+    // tile_scan_kernel was told about (anything longer raised the abort flag and emptied the lists)
+    const int64_t n_grid = guard ? guard->capacity : l.n_isects;   // what the launch geometry covers
+    const int64_t n_arg = guard ? int64_t(-1) : l.n_isects;        // what the kernels receive
+    if (l.tile_offsets) {
+        hipError_t e = hipMemcpyAsync(l.tile_offsets, w.offsets, size_t(T) * 4, hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) return (int)e;
+    }
+    if (n_grid <= 0) return LFS_OK;
+    const uint32_t tile_n_bits = bit_width_u32(tile_width * tile_height);
+    const size_t total = size_t(g.C) * g.N;
+    if (l.sort) {
+        if (const hipError_t ae = opt_in_big_lds()) return (int)ae;
+        const uint32_t pb = isect_per_block(total), blocks = uint32_t((total + pb - 1) / pb);
+        int tok = lfs::prof_begin("isect_scatter", s);
+        const uint32_t idx_bits = bit_width_u32(uint32_t(total - 1)) ? bit_width_u32(uint32_t(total - 1)) : 1u;
+        if (l.scratch != nullptr && isect_two_pass_supported(g)) {
+            hipLaunchKernelGGL(isect_rows_kernel, dim3(uint32_t((total + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)), dim3(1024), ROWS_STAGE * 8, s, g.C, g.N, in.means2d, in.radii,
+                               in.depths, float(g.tile_size), tile_width, tile_height, idx_bits, w.offsets, w.row_cursor, reinterpret_cast<uint64_t*>(l.scratch),
+                               guard ? guard->abort_flag : nullptr);
+            hipLaunchKernelGGL(isect_tiles_kernel, dim3(uint32_t((n_grid + TILES_CHUNK - 1) / TILES_CHUNK)), dim3(1024), TILES_CHUNK * 8, s, g.rows(), tile_width, idx_bits,
+                               n_arg, w.offsets, w.cursor, reinterpret_cast<const uint64_t*>(l.scratch), l.isect_ids);
+        } else if (size_t(T) * 8 <= LDS_HIST_LIMIT)
+            hipLaunchKernelGGL(isect_scatter_kernel<true>, dim3(blocks), dim3(1024), size_t(T) * 8, s, g.C, g.N, pb, in.means2d, in.radii, in.depths,
+                               float(g.tile_size), tile_width, tile_height, tile_n_bits, w.offsets, w.cursor, l.isect_ids, l.flatten_ids);
+        else
+            hipLaunchKernelGGL(isect_scatter_kernel<false>, dim3(blocks), dim3(1024), 0, s, g.C, g.N, pb, in.means2d, in.radii, in.depths,
+                               float(g.tile_size), tile_width, tile_height, tile_n_bits, w.offsets, w.cursor, l.isect_ids, l.flatten_ids);
+        lfs::prof_end(tok, s);
+        lfs::ProfScope prof_sort("isect_tile_sort", s);
+        const uint32_t n_tiles_ = tile_width * tile_height;
+        // the longest tile list (lfs_intersect_tile_count_ex; guarded: the limit of the classes the guard assumed) - classes no tile falls into are not launched:
+        // ~9 us each at T = 8160. Unknown (< 0): every class
+        const int64_t known = guard ? int64_t(sort_class_limit(guard->assumed_longest)) : l.max_tile_isects;
+        const int64_t longest = known >= 0 ? known : INT64_MAX;
+        const SortClass &c0 = SORT_CLASSES[0], &c1 = SORT_CLASSES[1], &c2 = SORT_CLASSES[2];
+        // (round 5) both first classes in one launch whenever the second one is needed at all: its few long lists then run beside the many short ones instead of after them
+        if (longest > c0.limit)
+            hipLaunchKernelGGL(tile_sort_bins_2class_kernel, dim3(T), dim3(c1.block), c1.lds_bytes, s, n_tiles_, tile_n_bits, w.offsets, l.isect_ids, l.flatten_ids);
+        else
+            hipLaunchKernelGGL(c0.kernel, dim3(T), dim3(c0.block), c0.lds_bytes, s, 1u, c0.limit, n_tiles_, tile_n_bits, w.offsets, l.isect_ids, l.flatten_ids);
+        if (longest > c1.limit)
+            hipLaunchKernelGGL(c2.kernel, dim3(T), dim3(c2.block), c2.lds_bytes, s, c1.limit + 1, c2.limit, n_tiles_, tile_n_bits, w.offsets, l.isect_ids, l.flatten_ids);
+        if (longest > c2.limit)
+            hipLaunchKernelGGL(tile_sort_global_kernel, dim3(T), dim3(1024), 0, s, c2.limit + 1, n_tiles_, tile_n_bits, w.offsets, l.isect_ids, l.flatten_ids);
+    } else {
+        const uint32_t nb = uint32_t((total + SCAN_ITEMS - 1) / SCAN_ITEMS);
+        hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nb), dim3(256), 0, s, total, l.tiles_per_gauss, w.block_sums);
+        hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(1024), 0, s, nb, w.block_sums);
+        hipLaunchKernelGGL(isect_emit_unsorted_kernel, dim3(nb), dim3(256), 0, s, g.C, g.N, in.means2d, in.radii, in.depths, l.tiles_per_gauss,
+                           w.block_sums, float(g.tile_size), tile_width, tile_height, tile_n_bits, l.isect_ids, l.flatten_ids);
+    }
+    return (int)hipGetLastError();
+}
+
+// the four C entries: their positional arguments, field by field
 extern "C" int lfs_intersect_tile_count_ex(
-    uint32_t C, uint32_t N, const float* means2d, const int32_t* radii,
-    uint32_t tile_size, uint32_t tile_width, uint32_t tile_height,
-    int32_t* tiles_per_gauss, int64_t* n_isects, int64_t* max_tile_isects, int32_t* tile_offsets, uint32_t flags, int64_t* stamp_out, int64_t stamp,
-    void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
-    return lfs::isect_count_impl(C, N, means2d, radii, tile_size, tile_width, tile_height, tiles_per_gauss, n_isects, max_tile_isects, tile_offsets, flags, stamp_out,
-                                 stamp, workspace, workspace_bytes, (hipStream_t)stream, nullptr);
+    uint32_t C, uint32_t N, const float* means2d, const int32_t* radii, uint32_t tile_size, uint32_t tile_width, uint32_t tile_height, int32_t* tiles_per_gauss, int64_t* n_isects,
+    int64_t* max_tile_isects, int32_t* tile_offsets, uint32_t flags, int64_t* stamp_out, int64_t stamp, void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
+    IsectGrid g{}; g.C = C; g.N = N; g.tile_size = tile_size; g.tile_width = tile_width; g.tile_height = tile_height;
+    IsectInputs in{}; in.means2d = means2d; in.radii = radii;
+    IsectCounts c{}; c.tiles_per_gauss = tiles_per_gauss; c.n_isects = n_isects; c.max_tile_isects = max_tile_isects; c.tile_offsets = tile_offsets;
+    c.flags = flags; c.stamp_out = stamp_out; c.stamp = stamp;
+    return lfs::isect_count(g, in, c, Workspace{workspace, workspace_bytes}, (hipStream_t)stream, nullptr);
 }
 
 extern "C" int lfs_intersect_tile_count(
-    uint32_t C, uint32_t N, const float* means2d, const int32_t* radii,
-    uint32_t tile_size, uint32_t tile_width, uint32_t tile_height,
+    uint32_t C, uint32_t N, const float* means2d, const int32_t* radii, uint32_t tile_size, uint32_t tile_width, uint32_t tile_height,
     int32_t* tiles_per_gauss, int64_t* n_isects, void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
     return lfs_intersect_tile_count_ex(C, N, means2d, radii, tile_size, tile_width, tile_height, tiles_per_gauss, n_isects, nullptr, nullptr, 0u, nullptr, 0, workspace,
                                        workspace_bytes, stream);
 }
 
-int lfs::isect_emit_impl(
-    uint32_t C, uint32_t N, const float* means2d, const int32_t* radii, const float* depths,
-    uint32_t tile_size, uint32_t tile_width, uint32_t tile_height, int sort, int64_t n_isects,
-    const int32_t* tiles_per_gauss, int64_t* isect_ids, int32_t* flatten_ids, int32_t* tile_offsets, int64_t* scratch, int64_t max_tile_isects,
-    void* workspace, size_t workspace_bytes, hipStream_t s, const IsectGuard* guard) {
-    if (!workspace || C == 0 || tile_size == 0) return LFS_E_INVALID;
-    IsectWs w = isect_ws(workspace, C, N, tile_width, tile_height);
-    if (workspace_bytes < w.bytes) return LFS_E_WORKSPACE;
-    const uint32_t T = C * tile_width * tile_height;
-    // guarded (speculative) call: the count is on the device. Grids cover the caller's capacity, the kernels read offsets[T]; the sort classes are the ones
-    // tile_scan_kernel was told about (anything longer raised the abort flag and emptied the lists)
-    const bool guarded = guard != nullptr;
-    const int64_t n_grid = guarded ? guard->capacity : n_isects;     // what the launch geometry covers
-    const int64_t n_arg = guarded ? int64_t(-1) : n_isects;          // what the kernels receive
-    if (guarded) {
-        if (!sort || !scratch || guard->capacity < 0) return LFS_E_INVALID;
-        n_isects = guard->capacity;
-        max_tile_isects = int64_t(sort_class_limit(guard->assumed_longest));
-        if (max_tile_isects == int64_t(0xFFFFFFFFu)) max_tile_isects = -1;
-    }
-    if (tile_offsets) {
-        hipError_t e = hipMemcpyAsync(tile_offsets, w.offsets, size_t(T) * 4, hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (n_isects <= 0) return LFS_OK;
-    if (n_isects > 0x7FFFFFFFll) return LFS_E_UNSUPPORTED; // offsets / last_ids are int32 in the reference API
-    if (!means2d || !radii || !depths || !isect_ids || !flatten_ids) return LFS_E_INVALID;
-    const uint32_t tile_n_bits = bit_width_u32(tile_width * tile_height);
-    const size_t total = size_t(C) * N;
-    if (sort) {
-        static bool big_lds_enabled = false; // > 64 KiB of dynamic LDS has to be opted into once per process
-        if (!big_lds_enabled) {
-            hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void*>(&tile_sort_lds_kernel<1024>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8);
-            if (ae != hipSuccess) return (int)ae;
-            ae = hipFuncSetAttribute(reinterpret_cast<const void*>(&tile_sort_bins_kernel<256>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 4096 * 8);
-            if (ae != hipSuccess) return (int)ae;
-            ae = hipFuncSetAttribute(reinterpret_cast<const void*>(&tile_sort_bins_kernel<1024, 1024, false, 64>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8);
-            if (ae != hipSuccess) return (int)ae;
-            ae = hipFuncSetAttribute(reinterpret_cast<const void*>(&isect_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_STAGE * 8);
-            if (ae != hipSuccess) return (int)ae;
-            ae = hipFuncSetAttribute(reinterpret_cast<const void*>(&isect_tiles_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, TILES_CHUNK * 8);
-            if (ae != hipSuccess) return (int)ae;
-            big_lds_enabled = true;
-        }
-        const uint32_t pb = isect_per_block(total);
-        const uint32_t blocks = uint32_t((total + pb - 1) / pb);
-        int tok = lfs::prof_begin("isect_scatter", s);
-        const uint32_t R = C * tile_height;
-        const uint32_t idx_bits = bit_width_u32(uint32_t(total - 1)) ? bit_width_u32(uint32_t(total - 1)) : 1u;
-        const bool two_pass = scratch != nullptr && isect_two_pass_supported(C, N, tile_width, tile_height);
-        if (two_pass) {
-            hipLaunchKernelGGL(isect_rows_kernel, dim3(uint32_t((total + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)), dim3(1024), ROWS_STAGE * 8, s, C, N, means2d, radii,
-                               depths, float(tile_size), tile_width, tile_height, idx_bits, w.offsets, w.row_cursor, reinterpret_cast<uint64_t*>(scratch),
-                               guarded ? guard->abort_flag : nullptr);
-            hipLaunchKernelGGL(isect_tiles_kernel, dim3(uint32_t((n_grid + TILES_CHUNK - 1) / TILES_CHUNK)), dim3(1024), TILES_CHUNK * 8, s, R, tile_width, idx_bits,
-                               n_arg, w.offsets, w.cursor, reinterpret_cast<const uint64_t*>(scratch), isect_ids);
-        } else if (guarded) { lfs::prof_end(tok, s); return LFS_E_UNSUPPORTED; } // (the one-pass scatter does not watch the abort flag)
-        else if (size_t(T) * 8 <= LDS_HIST_LIMIT)
-            hipLaunchKernelGGL(isect_scatter_kernel<true>, dim3(blocks), dim3(1024), size_t(T) * 8, s, C, N, pb, means2d, radii, depths,
-                               float(tile_size), tile_width, tile_height, tile_n_bits, w.offsets, w.cursor, isect_ids, flatten_ids);
-        else
-            hipLaunchKernelGGL(isect_scatter_kernel<false>, dim3(blocks), dim3(1024), 0, s, C, N, pb, means2d, radii, depths,
-                               float(tile_size), tile_width, tile_height, tile_n_bits, w.offsets, w.cursor, isect_ids, flatten_ids);
-        lfs::prof_end(tok, s);
-        lfs::ProfScope prof_sort("isect_tile_sort", s);
-        const uint32_t n_tiles_ = tile_width * tile_height;
-        // size classes (LDS sized to the class so that small tiles do not cap the occupancy): <= 1024 entries with the counting kernel on 256 bins
-        // (256 threads, keys staged in LDS), <= 4096 on 512 bins with 512 threads and only the binned copy in LDS (32 KiB; measured against the staged
-        // 256-thread form: 0.277 -> 0.127 ms per view at 12 M intersections, 0.058 -> 0.042 at 4.4 M; 1024 threads or the same change for the first class:
-        // no further gain), <= 16384 on 1024 bins (1024 threads, 128 KiB LDS; a bin of more than 64 keys falls back to the bitonic network inside the
-        // kernel), larger -> bitonic on global memory
-        // (max_tile_isects >= 0: the longest tile list, from lfs_intersect_tile_count_ex - classes no tile falls into are not launched: ~9 us each at T = 8160)
-        const int64_t longest = max_tile_isects >= 0 ? max_tile_isects : INT64_MAX;
-        // (round 5) both classes in one launch whenever the second one is needed at all: its few long lists then run beside the many short ones instead of after them
-        if (longest > 1024)
-            hipLaunchKernelGGL(tile_sort_bins_2class_kernel, dim3(T), dim3(512), 4096 * 8, s, n_tiles_, tile_n_bits, w.offsets, isect_ids, flatten_ids);
-        else
-            hipLaunchKernelGGL(tile_sort_bins_kernel<256>, dim3(T), dim3(256), 2 * 1024 * 8, s, 1u, 1024u, n_tiles_, tile_n_bits, w.offsets, isect_ids, flatten_ids);
-        if (longest > 4096)
-            hipLaunchKernelGGL((tile_sort_bins_kernel<1024, 1024, false, 64>), dim3(T), dim3(1024), 16384 * 8, s, 4097u, 16384u, n_tiles_, tile_n_bits, w.offsets, isect_ids, flatten_ids);
-        if (longest > 16384)
-            hipLaunchKernelGGL(tile_sort_global_kernel, dim3(T), dim3(1024), 0, s, 16385u, n_tiles_, tile_n_bits, w.offsets, isect_ids, flatten_ids);
-    } else {
-        if (!tiles_per_gauss) return LFS_E_INVALID;
-        const uint32_t nb = uint32_t((total + SCAN_ITEMS - 1) / SCAN_ITEMS);
-        hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nb), dim3(256), 0, s, total, tiles_per_gauss, w.block_sums);
-        hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(1024), 0, s, nb, w.block_sums);
-        hipLaunchKernelGGL(isect_emit_unsorted_kernel, dim3(nb), dim3(256), 0, s, C, N, means2d, radii, depths, tiles_per_gauss,
-                           w.block_sums, float(tile_size), tile_width, tile_height, tile_n_bits, isect_ids, flatten_ids);
-    }
-    return (int)hipGetLastError();
-}
-
 extern "C" int lfs_intersect_tile_emit_ex(
-    uint32_t C, uint32_t N, const float* means2d, const int32_t* radii, const float* depths,
-    uint32_t tile_size, uint32_t tile_width, uint32_t tile_height, int sort, int64_t n_isects,
-    const int32_t* tiles_per_gauss, int64_t* isect_ids, int32_t* flatten_ids, int32_t* tile_offsets, int64_t* scratch, int64_t max_tile_isects,
-    void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
-    return lfs::isect_emit_impl(C, N, means2d, radii, depths, tile_size, tile_width, tile_height, sort, n_isects, tiles_per_gauss, isect_ids, flatten_ids, tile_offsets,
-                                scratch, max_tile_isects, workspace, workspace_bytes, (hipStream_t)stream, nullptr);
+    uint32_t C, uint32_t N, const float* means2d, const int32_t* radii, const float* depths, uint32_t tile_size, uint32_t tile_width, uint32_t tile_height, int sort, int64_t n_isects,
+    const int32_t* tiles_per_gauss, int64_t* isect_ids, int32_t* flatten_ids, int32_t* tile_offsets, int64_t* scratch, int64_t max_tile_isects, void* workspace, size_t workspace_bytes,
+    lfs_stream_t stream) {
+    IsectGrid g{}; g.C = C; g.N = N; g.tile_size = tile_size; g.tile_width = tile_width; g.tile_height = tile_height;
+    IsectInputs in{}; in.means2d = means2d; in.radii = radii; in.depths = depths;
+    IsectLists l{}; l.sort = sort; l.n_isects = n_isects; l.tiles_per_gauss = tiles_per_gauss; l.isect_ids = isect_ids; l.flatten_ids = flatten_ids;
+    l.tile_offsets = tile_offsets; l.scratch = scratch; l.max_tile_isects = max_tile_isects;
+    return lfs::isect_emit(g, in, l, Workspace{workspace, workspace_bytes}, (hipStream_t)stream, nullptr);
 }
 
 extern "C" int lfs_intersect_tile_emit(
-    uint32_t C, uint32_t N, const float* means2d, const int32_t* radii, const float* depths,
-    uint32_t tile_size, uint32_t tile_width, uint32_t tile_height, int sort, int64_t n_isects,
-    const int32_t* tiles_per_gauss, int64_t* isect_ids, int32_t* flatten_ids, int32_t* tile_offsets,
-    void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
+    uint32_t C, uint32_t N, const float* means2d, const int32_t* radii, const float* depths, uint32_t tile_size, uint32_t tile_width, uint32_t tile_height, int sort, int64_t n_isects,
+    const int32_t* tiles_per_gauss, int64_t* isect_ids, int32_t* flatten_ids, int32_t* tile_offsets, void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
     return lfs_intersect_tile_emit_ex(C, N, means2d, radii, depths, tile_size, tile_width, tile_height, sort, n_isects, tiles_per_gauss, isect_ids, flatten_ids,
                                       tile_offsets, nullptr, -1, workspace, workspace_bytes, stream);
 }

@@ -169,71 +169,66 @@ __global__ void __launch_bounds__(256) projection_ut_kernel(
 
 } // namespace lfs
 
+
+using namespace lfs;
+
 static bool simple_camera(const lfs_cameras* c) {
     return c->camera_model == LFS_CAMERA_PINHOLE && c->rs_type == LFS_SHUTTER_GLOBAL && !c->viewmats1 && !c->radial_coeffs && !c->tangential_coeffs && !c->thin_prism_coeffs;
 }
 
-extern "C" int lfs_projection_ut_3dgs_fused(
-    uint32_t N, const float* means, const float* quats, const float* scales, const float* opacities,
-    const lfs_cameras* cams, float eps2d, float near_plane, float far_plane, float radius_clip,
-    const lfs_ut_params* ut_params,
-    int32_t* radii, float* means2d, float* depths, float* conics, float* compensations,
-    lfs_stream_t stream) {
+// what both entries ask of their camera block and their pointers (`present`: the entry's own required ones). LFS_OK with N == 0 or no camera: nothing to do
+static int projection_check(uint32_t N, const lfs_cameras* cams, bool present) {
     if (!cams || !cams->viewmats0 || !cams->Ks) return LFS_E_INVALID;
     if (cams->camera_model != LFS_CAMERA_PINHOLE && cams->camera_model != LFS_CAMERA_FISHEYE) return LFS_E_UNSUPPORTED;
     if (N == 0 || cams->C == 0) return LFS_OK; // ProjectionUT3DGSFused.cu:242-245
-    if (!means || !quats || !scales || !radii || !means2d || !depths || !conics) return LFS_E_INVALID;
+    return present ? LFS_OK : LFS_E_INVALID;
+}
+
+// The instantiation for a call. (Statements in this order, not one nested conditional: the kernels of the code object are laid out in the order they are first named.)
+using ProjectionKernel = decltype(&projection_ut_kernel<false>);
+static ProjectionKernel projection_kernel(bool act, bool simple, bool pack) {
+    if (!act) { if (simple) return projection_ut_kernel<false, true>; return projection_ut_kernel<false, false>; }
+    if (pack) return projection_ut_kernel<true, true, true>;
+    if (simple) return projection_ut_kernel<true, true>;
+    return projection_ut_kernel<true, false>;
+}
+
+// The one launch. act: m holds the RAW parameters, out.quats / scales / opacities receive the activated ones (otherwise m holds activated values under its raw_* names
+// and those three are NULL). r.recs_out given: the PACK instantiation (the training step: one camera, undistorted pinhole, global shutter)
+static int projection_launch(bool act, const char* scope, const ProjModel& m, const ProjCamera& c, const ProjOut& out, float* conics, float* compensations, const ProjRiders& r,
+                             hipStream_t s) {
+    const lfs_cameras* cams = c.cams;
+    const bool simple = simple_camera(cams), pack = r.recs_out != nullptr;
     lfs_ut_params ut = {0.1f, 2.f, 0.f, 0.1f, 1};
-    if (ut_params) ut = *ut_params;
-    dim3 grid((N + 255) / 256, cams->C);
-    lfs::ProfScope prof("projection_ut", (hipStream_t)stream);
-    if (simple_camera(cams))
-        hipLaunchKernelGGL((lfs::projection_ut_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream,
-                           N, means, quats, scales, opacities, *cams, eps2d, near_plane, far_plane, radius_clip, ut,
-                           radii, means2d, depths, conics, compensations, nullptr, nullptr, nullptr);
-    else
-        hipLaunchKernelGGL((lfs::projection_ut_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream,
-                           N, means, quats, scales, opacities, *cams, eps2d, near_plane, far_plane, radius_clip, ut,
-                           radii, means2d, depths, conics, compensations, nullptr, nullptr, nullptr);
+    if (c.ut) ut = *c.ut;
+    lfs::ProfScope prof(scope, s);
+    if (pack && (!act || !simple || cams->C != 1 || !r.cull_out || !r.pack_colors)) return LFS_E_INVALID;
+    hipLaunchKernelGGL(projection_kernel(act, simple, pack),dim3((m.N + 255) / 256, cams->C), dim3(256), 0, s, m.N, m.means, m.raw_quats, m.raw_scales, m.raw_opacities, *cams, c.eps2d, c.near_plane,
+                       c.far_plane, c.radius_clip, ut, out.radii, out.means2d, out.depths, conics, compensations, out.quats, out.scales, out.opacities, r.zero_words, r.zero_n,
+                       static_cast<CamDev*>(r.cams_out), static_cast<GaussRec*>(r.recs_out), static_cast<CullRec*>(r.cull_out), r.pack_colors);
     return (int)hipGetLastError();
 }
 
-int lfs::activations_project_ut_impl(
-    uint32_t N, const float* means, const float* raw_quats, const float* raw_scales, const float* raw_opacities, const lfs_cameras* cams,
-    float eps2d, float near_plane, float far_plane, float radius_clip, const lfs_ut_params* ut_params,
-    float* quats, float* scales, float* opacities, int32_t* radii, float* means2d, float* depths, uint32_t* zero_words, uint32_t zero_n, void* cams_out, hipStream_t stream,
-    void* recs_out, void* cull_out, const float* pack_colors) {
-    if (!cams || !cams->viewmats0 || !cams->Ks) return LFS_E_INVALID;
-    if (cams->camera_model != LFS_CAMERA_PINHOLE && cams->camera_model != LFS_CAMERA_FISHEYE) return LFS_E_UNSUPPORTED;
-    if (N == 0 || cams->C == 0) return LFS_OK;
-    if (!means || !raw_quats || !raw_scales || !raw_opacities || !quats || !scales || !opacities || !radii || !means2d || !depths) return LFS_E_INVALID;
-    lfs_ut_params ut = {0.1f, 2.f, 0.f, 0.1f, 1};
-    if (ut_params) ut = *ut_params;
-    dim3 grid((N + 255) / 256, cams->C);
-    lfs::ProfScope prof("activations_projection_ut", (hipStream_t)stream);
-    if (recs_out != nullptr) { // the training step: records + culling records from the same pass (one camera, undistorted pinhole, global shutter)
-        if (!simple_camera(cams) || cams->C != 1 || !cull_out || !pack_colors) return LFS_E_INVALID;
-        hipLaunchKernelGGL((lfs::projection_ut_kernel<true, true, true>), grid, dim3(256), 0, (hipStream_t)stream,
-                           N, means, raw_quats, raw_scales, raw_opacities, *cams, eps2d, near_plane, far_plane, radius_clip, ut,
-                           radii, means2d, depths, nullptr, nullptr, quats, scales, opacities, zero_words, zero_n, static_cast<lfs::CamDev*>(cams_out),
-                           static_cast<lfs::GaussRec*>(recs_out), static_cast<lfs::CullRec*>(cull_out), pack_colors);
-        return (int)hipGetLastError();
-    }
-    if (simple_camera(cams))
-        hipLaunchKernelGGL((lfs::projection_ut_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream,
-                           N, means, raw_quats, raw_scales, raw_opacities, *cams, eps2d, near_plane, far_plane, radius_clip, ut,
-                           radii, means2d, depths, nullptr, nullptr, quats, scales, opacities, zero_words, zero_n, static_cast<lfs::CamDev*>(cams_out));
-    else
-        hipLaunchKernelGGL((lfs::projection_ut_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream,
-                           N, means, raw_quats, raw_scales, raw_opacities, *cams, eps2d, near_plane, far_plane, radius_clip, ut,
-                           radii, means2d, depths, nullptr, nullptr, quats, scales, opacities, zero_words, zero_n, static_cast<lfs::CamDev*>(cams_out));
-    return (int)hipGetLastError();
+extern "C" int lfs_projection_ut_3dgs_fused(
+    uint32_t N, const float* means, const float* quats, const float* scales, const float* opacities, const lfs_cameras* cams, float eps2d, float near_plane, float far_plane,
+    float radius_clip, const lfs_ut_params* ut_params, int32_t* radii, float* means2d, float* depths, float* conics, float* compensations, lfs_stream_t stream) {
+    const int rc = projection_check(N, cams, means && quats && scales && radii && means2d && depths && conics);
+    if (rc || N == 0 || cams->C == 0) return rc;
+    return projection_launch(false, "projection_ut", ProjModel{N, means, quats, scales, opacities}, ProjCamera{cams, eps2d, near_plane, far_plane, radius_clip, ut_params},
+                             ProjOut{nullptr, nullptr, nullptr, radii, means2d, depths}, conics, compensations, ProjRiders{}, (hipStream_t)stream);
+}
+
+int lfs::activations_project_ut_impl(const ProjModel& m, const ProjCamera& c, const ProjOut& out, const ProjRiders* riders, hipStream_t s) {
+    const int rc = projection_check(m.N, c.cams, m.means && m.raw_quats && m.raw_scales && m.raw_opacities && out.quats && out.scales && out.opacities && out.radii &&
+                                                     out.means2d && out.depths);
+    if (rc || m.N == 0 || c.cams->C == 0) return rc;
+    return projection_launch(true, "activations_projection_ut", m, c, out, nullptr, nullptr, riders ? *riders : ProjRiders{}, s);
 }
 
 extern "C" int lfs_activations_project_ut(
     uint32_t N, const float* means, const float* raw_quats, const float* raw_scales, const float* raw_opacities, const lfs_cameras* cams,
     float eps2d, float near_plane, float far_plane, float radius_clip, const lfs_ut_params* ut_params,
     float* quats, float* scales, float* opacities, int32_t* radii, float* means2d, float* depths, lfs_stream_t stream) {
-    return lfs::activations_project_ut_impl(N, means, raw_quats, raw_scales, raw_opacities, cams, eps2d, near_plane, far_plane, radius_clip, ut_params, quats, scales,
-                                            opacities, radii, means2d, depths, nullptr, 0, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr);
+    return lfs::activations_project_ut_impl(ProjModel{N, means, raw_quats, raw_scales, raw_opacities}, ProjCamera{cams, eps2d, near_plane, far_plane, radius_clip, ut_params},
+                                            ProjOut{quats, scales, opacities, radii, means2d, depths}, nullptr, (hipStream_t)stream);
 }

@@ -98,7 +98,7 @@ static RasterWs raster_ws(void* base, const RasterWsOffsets& at, bool det) {
                     det ? (unsigned long long*)(p + at.det64) : nullptr, at.bytes};
 }
 // a one-camera workspace up to its culling records (camera state, records, accumulator rows): all the finish and tail passes touch. false: `ws` ends before them
-static bool rows_ws(const RasterWorkspace& ws, uint32_t N, RasterWs& w) {
+static bool rows_ws(const Workspace& ws, uint32_t N, RasterWs& w) {
     const RasterWsOffsets at = raster_ws_offsets(1, N, 0, 0, false);
     w = raster_ws(ws.base, at, false);
     return ws.bytes >= at.cull;
@@ -1407,7 +1407,7 @@ static int raster_mode(const lfs_cameras* cams) { return cams->rs_type != LFS_SH
 
 // What both directions check before anything is launched or cleared: the scene's shape, the direction's own operands (`own_ok`, evaluated by the caller), the
 // list sizes and the workspace, which is laid out here.
-static int raster_check(const RasterScene& sc, const RasterLists& l, const RasterWorkspace& ws, bool own_ok, RasterGeom& g, RasterWs& w) {
+static int raster_check(const RasterScene& sc, const RasterLists& l, const Workspace& ws, bool own_ok, RasterGeom& g, RasterWs& w) {
     const lfs_cameras* cams = sc.cams;
     if (!cams || !cams->viewmats0 || !cams->Ks || cams->C == 0) return LFS_E_INVALID;
     if (cams->camera_model != LFS_CAMERA_PINHOLE && cams->camera_model != LFS_CAMERA_FISHEYE) return LFS_E_UNSUPPORTED;
@@ -1447,7 +1447,7 @@ static void raster_prepare(const RasterWs& w, const RasterGeom& g, const RasterS
 #undef LFS_CULL
 }
 
-int lfs::raster_forward(const RasterScene& sc, const RasterLists& l, const RasterWorkspace& ws, const RasterFwdOut& out, hipStream_t s) {
+int lfs::raster_forward(const RasterScene& sc, const RasterLists& l, const Workspace& ws, const RasterFwdOut& out, hipStream_t s) {
     RasterGeom g;
     RasterWs w;
     const int rc = raster_check(sc, l, ws, out.render_colors && out.render_alphas && out.last_ids, g, w);
@@ -1482,7 +1482,7 @@ extern "C" int lfs_rasterize_to_pixels_from_world_3dgs_fwd(
     sc.N = N; sc.channels = channels; sc.means = means; sc.quats = quats; sc.scales = scales; sc.colors = colors; sc.opacities = opacities;
     sc.backgrounds = backgrounds; sc.masks = masks; sc.cams = cams; sc.tile_size = tile_size;
     out.render_colors = render_colors; out.render_alphas = render_alphas; out.last_ids = last_ids;
-    return raster_forward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, RasterWorkspace{workspace, workspace_bytes}, out, (hipStream_t)stream);
+    return raster_forward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, Workspace{workspace, workspace_bytes}, out, (hipStream_t)stream);
 }
 
 // where the records / culling records of a (one-camera) rasterizer workspace live: the training step's projection kernel writes them there (the camera state is its first block)
@@ -1498,7 +1498,7 @@ static bool mse_form_ok(const RasterScene& sc, const RasterBwd& b) {
     return !m || (sc.channels == 3 && sc.cams && sc.cams->C == 1 && !sc.masks && !b.v_render_alphas && m->render && m->target_chw && (b.rows_only || m->loss));
 }
 
-int lfs::raster_backward(const RasterScene& sc, const RasterLists& l, const RasterWorkspace& ws, const RasterBwd& b, hipStream_t s) {
+int lfs::raster_backward(const RasterScene& sc, const RasterLists& l, const Workspace& ws, const RasterBwd& b, hipStream_t s) {
     RasterGeom g;
     RasterWs w;
     const int rc = raster_check(sc, l, ws, mse_form_ok(sc, b), g, w);
@@ -1584,7 +1584,7 @@ extern "C" int lfs_rasterize_to_pixels_from_world_3dgs_bwd_prepared(
     sc.backgrounds = backgrounds; sc.masks = masks; sc.cams = cams; sc.tile_size = tile_size;
     b.render_alphas = render_alphas; b.last_ids = last_ids; b.v_render_colors = v_render_colors; b.v_render_alphas = v_render_alphas;
     b.v_means = v_means; b.v_quats = v_quats; b.v_scales = v_scales; b.v_colors = v_colors; b.v_opacities = v_opacities; b.prepared = true;
-    return raster_backward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, RasterWorkspace{workspace, workspace_bytes}, b, (hipStream_t)stream);
+    return raster_backward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, Workspace{workspace, workspace_bytes}, b, (hipStream_t)stream);
 }
 
 // the self-contained form: camera state, records and cell lists are rebuilt in front of the backward
@@ -1604,7 +1604,7 @@ extern "C" int lfs_rasterize_to_pixels_from_world_3dgs_bwd(
     sc.backgrounds = backgrounds; sc.masks = masks; sc.cams = cams; sc.tile_size = tile_size;
     b.render_alphas = render_alphas; b.last_ids = last_ids; b.v_render_colors = v_render_colors; b.v_render_alphas = v_render_alphas;
     b.v_means = v_means; b.v_quats = v_quats; b.v_scales = v_scales; b.v_colors = v_colors; b.v_opacities = v_opacities;
-    return raster_backward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, RasterWorkspace{workspace, workspace_bytes}, b, (hipStream_t)stream);
+    return raster_backward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, Workspace{workspace, workspace_bytes}, b, (hipStream_t)stream);
 }
 
 // "prepared" backward with the clamped MSE loss of lfs_mse_loss_fwd_bwd folded in (extension): render_colors [H,W,3] = the forward
@@ -1623,7 +1623,7 @@ extern "C" int lfs_rasterize_to_pixels_from_world_3dgs_bwd_prepared_mse(
     b.v_means = v_means; b.v_quats = v_quats; b.v_scales = v_scales; b.v_colors = v_colors; b.v_opacities = v_opacities; b.prepared = true;
     sc.N = N; sc.channels = 3; sc.means = means; sc.quats = quats; sc.scales = scales; sc.colors = colors; sc.opacities = opacities;
     sc.backgrounds = backgrounds; sc.cams = cams; sc.tile_size = tile_size;
-    return raster_backward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, RasterWorkspace{workspace, workspace_bytes}, b, (hipStream_t)stream);
+    return raster_backward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, Workspace{workspace, workspace_bytes}, b, (hipStream_t)stream);
 }
 
 
@@ -1646,7 +1646,7 @@ extern "C" int lfs_rasterize_to_pixels_from_world_3dgs_bwd_prepared_mse_acc(
     b.render_alphas = render_alphas; b.last_ids = last_ids; b.mse = &mse; b.prepared = true; b.rows_only = true;
     sc.N = N; sc.channels = 3; sc.means = means; sc.quats = quats; sc.scales = scales; sc.colors = colors; sc.opacities = opacities;
     sc.backgrounds = backgrounds; sc.cams = cams; sc.tile_size = tile_size;
-    return raster_backward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, RasterWorkspace{workspace, workspace_bytes}, b, (hipStream_t)stream);
+    return raster_backward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, Workspace{workspace, workspace_bytes}, b, (hipStream_t)stream);
 }
 
 // the same for a caller-provided dL/d(render) (any loss): lfs_..._bwd_prepared without its last kernel
@@ -1660,7 +1660,7 @@ extern "C" int lfs_rasterize_to_pixels_from_world_3dgs_bwd_prepared_acc(
     b.render_alphas = render_alphas; b.last_ids = last_ids; b.v_render_colors = v_render_colors; b.v_render_alphas = v_render_alphas; b.prepared = true; b.rows_only = true;
     sc.N = N; sc.channels = 3; sc.means = means; sc.quats = quats; sc.scales = scales; sc.colors = colors; sc.opacities = opacities;
     sc.backgrounds = backgrounds; sc.cams = cams; sc.tile_size = tile_size;
-    return raster_backward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, RasterWorkspace{workspace, workspace_bytes}, b, (hipStream_t)stream);
+    return raster_backward(sc, RasterLists{tile_offsets, flatten_ids, n_isects, 0}, Workspace{workspace, workspace_bytes}, b, (hipStream_t)stream);
 }
 
 // ---- the finish and tail passes over the accumulator rows ----
@@ -1685,7 +1685,7 @@ static const float* loss_slots_of(const RasterWs& w, uint32_t N, const float* lo
 // that need the gradients themselves (multi-GPU all-reduce, several views per step, non-MSE losses). g.* are written or, accumulate != 0, added to;
 // v_colors [N,3] is written (the SH backward consumes it and adds dL/d(dirs) onto g.means). loss (nullable): += the fused MSE partial sums.
 int lfs::gut_finish_grads_impl(const GutParams& p, const GutActivated& act, const GutRegs& regs, const GutGrads& g, const float* v_dirs, float* loss,
-                               const RasterWorkspace& ws, hipStream_t s) {
+                               const Workspace& ws, hipStream_t s) {
     const uint32_t N = p.N;
     if (N == 0) return LFS_OK;
     if (!p.means || !p.raw_quats || !act.quats || !act.scales || !act.opacities || !g.means || !g.raw_scales || !g.raw_quats || !g.raw_opacities || (!g.v_colors && !v_dirs) || !ws.base) return LFS_E_INVALID;
@@ -1709,11 +1709,11 @@ extern "C" int lfs_gut_finish_grads(
     p.N = N; p.means = const_cast<float*>(means); p.raw_quats = const_cast<float*>(raw_quats);
     return lfs::gut_finish_grads_impl(p, GutActivated{quats, scales, opacities}, GutRegs{scale_reg, opacity_reg},
                                       GutGrads{g_means, g_raw_scales, g_raw_quats, g_raw_opacities, v_colors, accumulate}, nullptr, loss,
-                                      RasterWorkspace{workspace, workspace_bytes}, (hipStream_t)stream);
+                                      Workspace{workspace, workspace_bytes}, (hipStream_t)stream);
 }
 
 int lfs::gut_finish_adam_impl(const GutParams& p, const GutActivated& act, const GutAdam& adam, const GutRegs& regs, const float* v_dirs, float* loss,
-                              const RasterWorkspace& ws, hipStream_t s) {
+                              const Workspace& ws, hipStream_t s) {
     const uint32_t N = p.N;
     if (N == 0) return LFS_OK;
     if (!v_dirs) return LFS_E_INVALID;
@@ -1731,7 +1731,7 @@ int lfs::gut_finish_adam_impl(const GutParams& p, const GutActivated& act, const
 // The fused tail of the all-inline step (gut_tail_kernel): SH backward + all six Adam updates (+ the next view's SH colours -> colors [N,3] when next_viewmat is given).
 // LFS_E_UNSUPPORTED for K > 16 (degree 4): the caller enqueues lfs_sh_model_bwd_adam_all + lfs_gut_finish_adam instead.
 int lfs::gut_tail_impl(const GutParams& p, const GutActivated& act, const GutAdam& adam, const GutRegs& regs, const GutTailView& view, float* loss,
-                       const RasterWorkspace& ws, hipStream_t s) {
+                       const Workspace& ws, hipStream_t s) {
     const uint32_t N = p.N, K = p.K;
     if (N == 0) return LFS_OK;
     const uint32_t Kd = (p.sh_degree + 1) * (p.sh_degree + 1);
@@ -1775,5 +1775,5 @@ extern "C" int lfs_gut_finish_adam(
     GutParams p{};
     p.N = N; p.means = means; p.raw_scales = raw_scales; p.raw_quats = raw_quats; p.raw_opacities = raw_opacities;
     return lfs::gut_finish_adam_impl(p, GutActivated{quats, scales, opacities}, GutAdam{m, v, sc, nullptr}, GutRegs{scale_reg, opacity_reg}, v_dirs, loss,
-                                     RasterWorkspace{workspace, workspace_bytes}, (hipStream_t)stream);
+                                     Workspace{workspace, workspace_bytes}, (hipStream_t)stream);
 }

@@ -537,110 +537,105 @@ extern "C" int lfs_spherical_harmonics_bwd(
     return lfs::sh_launch_bwd<false, false>(a, v_colors, v_coeffs, nullptr, nullptr, v_dirs, (hipStream_t)stream);
 }
 
-// radii == NULL (the training step: the colours are evaluated BEFORE the projection, which writes them into the rasterizer's records): every Gaussian
-int lfs::sh_model_fwd_impl(
-    uint32_t n, uint32_t K, uint32_t degrees_to_use, const float* means, const float* viewmat, const float* sh0, const float* shN,
-    const int32_t* radii, float* colors, hipStream_t stream) {
-    const uint32_t Kd = (degrees_to_use + 1) * (degrees_to_use + 1);
-    if (degrees_to_use > 4 || Kd > K || K > 32) return LFS_E_INVALID;
-    if (n == 0) return LFS_OK;
-    if (!means || !viewmat || !sh0 || (K > 1 && !shN) || !colors) return LFS_E_INVALID;
-    lfs::ShArgs a{};
-    a.n = n; a.K = K; a.degree = int(degrees_to_use); a.means = means; a.viewmat = viewmat; a.sh0 = sh0; a.shN = shN; a.radii = radii;
-    return lfs::sh_launch_fwd<true>(a, Kd, colors, stream);
+// ---- the six model-form entries: the three of the training step (lfs_step_internal.h) and the C entries, which put their positional arguments under the same names ----
+using namespace lfs;
+
+static GutParams sh_model(uint32_t n, uint32_t K, uint32_t degree, const float* means, const float* sh0, const float* shN) {
+    GutParams p{};
+    p.N = n; p.K = K; p.sh_degree = degree; p.means = const_cast<float*>(means); p.sh0 = const_cast<float*>(sh0); p.shN = const_cast<float*>(shN);
+    return p;
+}
+struct ShMoments { float *m, *v; const float* scalars; bool given() const { return m && v && scalars; } };   // one Adam group: moments, {lr, beta1, beta2, eps, bc1_rcp, bc2_sqrt_rcp}
+static ShMoments group_of(const GutAdam& adam, int k) { return ShMoments{adam.exp_avg ? adam.exp_avg[k] : nullptr, adam.exp_avg_sq ? adam.exp_avg_sq[k] : nullptr, adam.scalars ? adam.scalars[k] : nullptr}; }
+static AdamScalars scalars_of(const float* t) { return AdamScalars{t[0], t[1], t[2], t[3], t[4], t[5]}; }
+
+// What all six share: the degree / K check (min_K 2: the entry updates shN in place), the operands every one of them needs, and ShArgs. `present`: the entry's own
+// required pointers are there. p.N == 0: LFS_OK and `a` is not filled - the caller returns (nothing to do).
+static int sh_model_args(const GutParams& p, const ShView& v, uint32_t min_K, bool radii_optional, bool present, ShArgs& a) {
+    const uint32_t Kd = (p.sh_degree + 1) * (p.sh_degree + 1);
+    if (p.sh_degree > 4 || Kd > p.K || p.K > 32 || p.K < min_K) return LFS_E_INVALID;
+    if (p.N == 0) return LFS_OK;
+    if (!p.means || !v.viewmat || !p.sh0 || (p.K > 1 && !p.shN) || (!v.radii && !radii_optional) || !v.colors || !present) return LFS_E_INVALID;
+    a = ShArgs{};
+    a.n = p.N; a.K = p.K; a.degree = int(p.sh_degree); a.means = p.means; a.viewmat = v.viewmat; a.sh0 = p.sh0; a.shN = p.shN; a.radii = v.radii; a.colors = v.colors;
+    return LFS_OK;
 }
 
-extern "C" int lfs_sh_model_fwd(
-    uint32_t n, uint32_t K, uint32_t degrees_to_use, const float* means, const float* viewmat, const float* sh0, const float* shN,
-    const int32_t* radii, float* colors, lfs_stream_t stream) {
+int lfs::sh_model_fwd_impl(const GutParams& p, const ShView& v, hipStream_t stream) {
+    ShArgs a;
+    const int rc = sh_model_args(p, v, 1, /*radii_optional=*/true, true, a);
+    if (rc || p.N == 0) return rc;
+    a.colors = nullptr;   // (the forward's output, not an operand)
+    return sh_launch_fwd<true>(a, (p.sh_degree + 1) * (p.sh_degree + 1), v.colors, stream);
+}
+
+extern "C" int lfs_sh_model_fwd(uint32_t n, uint32_t K, uint32_t degrees_to_use, const float* means, const float* viewmat, const float* sh0, const float* shN,
+                                const int32_t* radii, float* colors, lfs_stream_t stream) {
     if (!radii) return LFS_E_INVALID;
-    return lfs::sh_model_fwd_impl(n, K, degrees_to_use, means, viewmat, sh0, shN, radii, colors, (hipStream_t)stream);
+    return lfs::sh_model_fwd_impl(sh_model(n, K, degrees_to_use, means, sh0, shN), ShView{viewmat, radii, colors}, (hipStream_t)stream);
 }
 
-extern "C" int lfs_sh_model_bwd(
-    uint32_t n, uint32_t K, uint32_t degrees_to_use, const float* means, const float* viewmat, const float* sh0, const float* shN,
-    const int32_t* radii, const float* colors, const float* v_colors, int accumulate,
-    float* v_sh0, float* v_shN, float* v_means, lfs_stream_t stream) {
-    const uint32_t Kd = (degrees_to_use + 1) * (degrees_to_use + 1);
-    if (degrees_to_use > 4 || Kd > K || K > 32) return LFS_E_INVALID;
-    if (n == 0) return LFS_OK;
-    if (!means || !viewmat || !sh0 || (K > 1 && (!shN || !v_shN)) || !radii || !colors || !v_colors || !v_sh0 || !v_means) return LFS_E_INVALID;
-    lfs::ShArgs a{};
-    a.n = n; a.K = K; a.degree = int(degrees_to_use); a.means = means; a.viewmat = viewmat; a.sh0 = sh0; a.shN = shN; a.radii = radii; a.colors = colors;
-    if (accumulate) return lfs::sh_launch_bwd<true, true>(a, v_colors, nullptr, v_sh0, v_shN, v_means, (hipStream_t)stream);
-    return lfs::sh_launch_bwd<true, false>(a, v_colors, nullptr, v_sh0, v_shN, v_means, (hipStream_t)stream);
+extern "C" int lfs_sh_model_bwd(uint32_t n, uint32_t K, uint32_t degrees_to_use, const float* means, const float* viewmat, const float* sh0, const float* shN,
+                                const int32_t* radii, const float* colors, const float* v_colors, int accumulate, float* v_sh0, float* v_shN, float* v_means, lfs_stream_t stream) {
+    ShArgs a;
+    const int rc = sh_model_args(sh_model(n, K, degrees_to_use, means, sh0, shN), ShView{viewmat, radii, const_cast<float*>(colors)}, 1, false,
+                                 (K <= 1 || v_shN) && v_colors && v_sh0 && v_means, a);
+    if (rc || n == 0) return rc;
+    if (accumulate) return sh_launch_bwd<true, true>(a, v_colors, nullptr, v_sh0, v_shN, v_means, (hipStream_t)stream);
+    return sh_launch_bwd<true, false>(a, v_colors, nullptr, v_sh0, v_shN, v_means, (hipStream_t)stream);
 }
 
 // lfs_sh_model_bwd with dL/dcolour read from the rasterizer's accumulator rows (slots 13..15 of 16 floats) and dL/d(dirs) WRITTEN to its own [n,3] array:
 // the data-parallel step runs the SH backward BEFORE the finish pass, so that the shN gradient - 45 of a Gaussian's 59 floats - is final (and its
-// all-reduce on the wire) while lfs_gut_finish_grads still runs (csrc/gut_step.hip).
-int lfs::sh_model_bwd_rows_impl(
-    uint32_t n, uint32_t K, uint32_t degrees_to_use, const float* means, const float* viewmat, const float* sh0, const float* shN,
-    const int32_t* radii, const float* colors, const float* acc_rows, int accumulate, float* v_sh0, float* v_shN, float* v_dirs, hipStream_t stream,
-    float* shN_exp_avg, float* shN_exp_avg_sq, const float* shN_scalars) {
-    const uint32_t Kd = (degrees_to_use + 1) * (degrees_to_use + 1);
-    if (degrees_to_use > 4 || Kd > K || K > 32) return LFS_E_INVALID;
-    if (n == 0) return LFS_OK;
-    const bool inline_adam = shN_exp_avg != nullptr;   // shN updated in place by this launch (one view per step): no shN gradient is written
-    if (inline_adam && (accumulate || K < 2 || !shN_exp_avg_sq || !shN_scalars)) return LFS_E_INVALID;
-    if (!means || !viewmat || !sh0 || (K > 1 && (!shN || (!v_shN && !inline_adam))) || !radii || !colors || !acc_rows || !v_sh0 || !v_dirs) return LFS_E_INVALID;
-    lfs::ShArgs a{};
-    a.n = n; a.K = K; a.degree = int(degrees_to_use); a.means = means; a.viewmat = viewmat; a.sh0 = sh0; a.shN = shN; a.radii = radii; a.colors = colors;
+// all-reduce on the wire) while lfs_gut_finish_grads still runs (csrc/gut_step.hip). adam given: shN updated in place by this launch (one view per step) - no shN
+// gradient is written
+int lfs::sh_model_bwd_rows_impl(const GutParams& p, const ShView& v, const float* acc_rows, const ShGrads& g, const GutAdam* adam, hipStream_t stream) {
+    const ShMoments shN = adam ? group_of(*adam, 2) : ShMoments{};
+    ShArgs a;
+    const int rc = sh_model_args(p, v, 1, false, (!adam || (!g.accumulate && p.K >= 2 && shN.given())) && (p.K <= 1 || g.v_shN || adam) && acc_rows && g.v_sh0 && g.v_dirs, a);
+    if (rc || p.N == 0) return rc;
     a.vs = 16; a.dirs_store = true;
-    if (inline_adam) {
-        const float* t = shN_scalars;
-        const lfs::ShAdam adam{shN_exp_avg, shN_exp_avg_sq, lfs::AdamScalars{t[0], t[1], t[2], t[3], t[4], t[5]}};
-        return lfs::sh_launch_bwd_adam(a, acc_rows + 13, v_sh0, v_dirs, adam, stream);
-    }
-    if (accumulate) return lfs::sh_launch_bwd<true, true>(a, acc_rows + 13, nullptr, v_sh0, v_shN, v_dirs, stream);
-    return lfs::sh_launch_bwd<true, false>(a, acc_rows + 13, nullptr, v_sh0, v_shN, v_dirs, stream);
+    if (adam) return sh_launch_bwd_adam(a, acc_rows + 13, g.v_sh0, g.v_dirs, ShAdam{shN.m, shN.v, scalars_of(shN.scalars)}, stream);
+    if (g.accumulate) return sh_launch_bwd<true, true>(a, acc_rows + 13, nullptr, g.v_sh0, g.v_shN, g.v_dirs, stream);
+    return sh_launch_bwd<true, false>(a, acc_rows + 13, nullptr, g.v_sh0, g.v_shN, g.v_dirs, stream);
 }
 
 extern "C" int lfs_sh_model_bwd_adam(
-    uint32_t n, uint32_t K, uint32_t degrees_to_use, const float* means, const float* viewmat, const float* sh0, float* shN,
-    const int32_t* radii, const float* colors, const float* v_colors, float* v_sh0, float* v_means,
-    float* shN_exp_avg, float* shN_exp_avg_sq, float lr, float beta1, float beta2, float eps, float bias_correction1_rcp,
+    uint32_t n, uint32_t K, uint32_t degrees_to_use, const float* means, const float* viewmat, const float* sh0, float* shN, const int32_t* radii, const float* colors,
+    const float* v_colors, float* v_sh0, float* v_means, float* shN_exp_avg, float* shN_exp_avg_sq, float lr, float beta1, float beta2, float eps, float bias_correction1_rcp,
     float bias_correction2_sqrt_rcp, lfs_stream_t stream) {
-    const uint32_t Kd = (degrees_to_use + 1) * (degrees_to_use + 1);
-    if (degrees_to_use > 4 || Kd > K || K > 32 || K < 2) return LFS_E_INVALID;
-    if (n == 0) return LFS_OK;
-    if (!means || !viewmat || !sh0 || !shN || !radii || !colors || !v_colors || !v_sh0 || !v_means || !shN_exp_avg || !shN_exp_avg_sq) return LFS_E_INVALID;
-    lfs::ShArgs a{};
-    a.n = n; a.K = K; a.degree = int(degrees_to_use); a.means = means; a.viewmat = viewmat; a.sh0 = sh0; a.shN = shN; a.radii = radii; a.colors = colors;
-    const lfs::ShAdam adam{shN_exp_avg, shN_exp_avg_sq, lfs::AdamScalars{lr, beta1, beta2, eps, bias_correction1_rcp, bias_correction2_sqrt_rcp}};
-    return lfs::sh_launch_bwd_adam(a, v_colors, v_sh0, v_means, adam, (hipStream_t)stream);
+    ShArgs a;
+    const int rc = sh_model_args(sh_model(n, K, degrees_to_use, means, sh0, shN), ShView{viewmat, radii, const_cast<float*>(colors)}, 2, false,
+                                 v_colors && v_sh0 && v_means && shN_exp_avg && shN_exp_avg_sq, a);
+    if (rc || n == 0) return rc;
+    const ShAdam adam{shN_exp_avg, shN_exp_avg_sq, AdamScalars{lr, beta1, beta2, eps, bias_correction1_rcp, bias_correction2_sqrt_rcp}};
+    return sh_launch_bwd_adam(a, v_colors, v_sh0, v_means, adam, (hipStream_t)stream);
 }
 
 // The all-inline training step (one view, one rank): dL/dcolour is read from the rasterizer's accumulator rows (acc_rows + 13, stride 16 floats),
 // dL/d(dirs) is WRITTEN to v_dirs [n,3] (raster_finish_adam_kernel adds it to the means gradient), and BOTH coefficient tensors
 // are updated in place by their Adam steps: no gradient tensor of the spherical harmonics exists.
-int lfs::sh_model_bwd_adam_all_impl(
-    uint32_t n, uint32_t K, uint32_t degrees_to_use, const float* means, const float* viewmat, float* sh0, float* shN,
-    const int32_t* radii, const float* colors, const float* acc_rows, float* v_dirs,
-    float* sh0_exp_avg, float* sh0_exp_avg_sq, const float* sh0_scalars /* lr, beta1, beta2, eps, bc1_rcp, bc2_sqrt_rcp */,
-    float* shN_exp_avg, float* shN_exp_avg_sq, const float* shN_scalars, hipStream_t stream, const int32_t* abort_flag) {
-    const uint32_t Kd = (degrees_to_use + 1) * (degrees_to_use + 1);
-    if (degrees_to_use > 4 || Kd > K || K > 32 || K < 2) return LFS_E_INVALID;
-    if (n == 0) return LFS_OK;
-    if (!means || !viewmat || !sh0 || !shN || !radii || !colors || !acc_rows || !v_dirs || !sh0_exp_avg || !sh0_exp_avg_sq || !sh0_scalars || !shN_exp_avg ||
-        !shN_exp_avg_sq || !shN_scalars) return LFS_E_INVALID;
-    lfs::ShArgs a{};
-    a.n = n; a.K = K; a.degree = int(degrees_to_use); a.means = means; a.viewmat = viewmat; a.sh0 = sh0; a.shN = shN; a.radii = radii; a.colors = colors;
+static int sh_bwd_adam_all(const GutParams& p, const ShView& v, const float* acc_rows, float* v_dirs, const ShMoments& sh0, const ShMoments& shN, const int32_t* abort_flag,
+                           hipStream_t stream) {
+    ShArgs a;
+    const int rc = sh_model_args(p, v, 2, false, acc_rows && v_dirs && sh0.given() && shN.given(), a);
+    if (rc || p.N == 0) return rc;
     a.abort_flag = abort_flag;
     a.vs = 16; a.dirs_store = true; // dL/dcolour: slots 13..15 of the 16-float rows; dL/d(dirs): its own contiguous [n,3] (partial-row writes into the rows cost more than they save)
-    lfs::ShAdam adam{shN_exp_avg, shN_exp_avg_sq, lfs::AdamScalars{shN_scalars[0], shN_scalars[1], shN_scalars[2], shN_scalars[3], shN_scalars[4], shN_scalars[5]}};
-    adam.m0 = sh0_exp_avg; adam.v0 = sh0_exp_avg_sq;
-    adam.s0 = lfs::AdamScalars{sh0_scalars[0], sh0_scalars[1], sh0_scalars[2], sh0_scalars[3], sh0_scalars[4], sh0_scalars[5]};
-    return lfs::sh_launch_bwd_adam(a, acc_rows + 13, nullptr, v_dirs, adam, stream);
+    ShAdam adam{shN.m, shN.v, scalars_of(shN.scalars)};
+    adam.m0 = sh0.m; adam.v0 = sh0.v; adam.s0 = scalars_of(sh0.scalars);
+    return sh_launch_bwd_adam(a, acc_rows + 13, nullptr, v_dirs, adam, stream);
+}
+
+int lfs::sh_model_bwd_adam_all_impl(const GutParams& p, const ShView& v, const GutAdam& adam, const float* acc_rows, float* v_dirs, hipStream_t stream) {
+    return sh_bwd_adam_all(p, v, acc_rows, v_dirs, group_of(adam, 1), group_of(adam, 2), adam.abort_flag, stream);
 }
 
 extern "C" int lfs_sh_model_bwd_adam_all(
-    uint32_t n, uint32_t K, uint32_t degrees_to_use, const float* means, const float* viewmat, float* sh0, float* shN,
-    const int32_t* radii, const float* colors, const float* acc_rows, float* v_dirs,
-    float* sh0_exp_avg, float* sh0_exp_avg_sq, const float* sh0_scalars /* lr, beta1, beta2, eps, bc1_rcp, bc2_sqrt_rcp */,
-    float* shN_exp_avg, float* shN_exp_avg_sq, const float* shN_scalars, lfs_stream_t stream) {
-    return lfs::sh_model_bwd_adam_all_impl(n, K, degrees_to_use, means, viewmat, sh0, shN, radii, colors, acc_rows, v_dirs, sh0_exp_avg, sh0_exp_avg_sq, sh0_scalars,
-                                           shN_exp_avg, shN_exp_avg_sq, shN_scalars, (hipStream_t)stream, nullptr);
+    uint32_t n, uint32_t K, uint32_t degrees_to_use, const float* means, const float* viewmat, float* sh0, float* shN, const int32_t* radii, const float* colors, const float* acc_rows,
+    float* v_dirs, float* sh0_exp_avg, float* sh0_exp_avg_sq, const float* sh0_scalars, float* shN_exp_avg, float* shN_exp_avg_sq, const float* shN_scalars, lfs_stream_t stream) {
+    return sh_bwd_adam_all(sh_model(n, K, degrees_to_use, means, sh0, shN), ShView{viewmat, radii, const_cast<float*>(colors)}, acc_rows, v_dirs,
+                           ShMoments{sh0_exp_avg, sh0_exp_avg_sq, sh0_scalars}, ShMoments{shN_exp_avg, shN_exp_avg_sq, shN_scalars}, nullptr, (hipStream_t)stream);
 }
 
 static bool sh_views_ok(uint32_t n, uint32_t K, uint32_t degree, uint32_t V, uint32_t stride) {

@@ -105,7 +105,7 @@ def intersect_tile_begin(means2d: Tensor, radii: Tensor, depths: Tensor, C_: int
     ws = workspace(ws_bytes, dev, tag)
     offsets = torch.empty((C_, tile_height, tile_width), dtype=torch.int32, device=dev) if (return_offsets and sort) else None
     # flags = 0: the library zeroes the workspace counters itself on every call (a 4-byte-per-tile memset). The LFS_ISECT_COUNTERS_ZERO elision is for
-    # callers that OWN their workspace memory exclusively (csrc/gut_step.cpp's step context); a Python-side cache of "this buffer is still clean" was
+    # callers that OWN their workspace memory exclusively (csrc/gut_step.hip's step workspace, whose projection kernel clears the counters); a Python-side cache of "this buffer is still clean" was
     # removed in round 3: the ops-level path must not depend on interpreter state to stay inside its buffers.
     flags = 0
     # pinned: the scan kernel writes the counts straight into pinned host memory (no copy kernel) and the host waits for an event recorded behind

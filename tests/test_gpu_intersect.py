@@ -144,3 +144,10 @@ def test_two_pass_scatter_equals_one_pass_over_random_shapes(lfs):
         ids = outs[0][1]
         assert (np.diff(ids) >= 0).all()                       # sorted by (camera | tile | depth)
         assert int(outs[0][0].sum()) == ids.shape[0]
+
+
+def test_every_refused_intersection_call_returns_its_code_and_writes_nothing(lfs):
+    """tests/isect_refusals.py on the real library: each single-fault call of lfs_intersect_tile_count_ex, lfs_intersect_tile_emit_ex and lfs_gut_view_forward returns the
+    code of its row and leaves its outputs and its workspace untouched (the emulated runner: tests/test_emulated_isect_refusals.py)."""
+    import isect_refusals
+    assert isect_refusals.run_all() == len(isect_refusals.ROWS) + len(isect_refusals.STEP_ROWS)
