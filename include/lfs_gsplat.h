@@ -487,6 +487,35 @@ LFS_API int lfs_image_u8_to_chw_f32(const uint8_t* src_hwc, uint32_t src_width, 
  * (255 - value). WRITES sums int64[2] = {sum of dst, sum of dst over the loss's crop}: exact integers, identical on every run. Asynchronous. */
 LFS_API int lfs_mask_prepare(const uint8_t* src_u8, uint32_t src_width, uint32_t src_height, uint8_t* dst_u8, uint32_t dst_width, uint32_t dst_height,
                              uint32_t invert, int32_t threshold, int64_t* sums, lfs_stream_t stream);
+/* ---- undistortion at load (extension). The map of one view: a source image taken through a lens model, and the distortion-free pinhole camera
+ *      the training target is resampled to. Pixel centres are at +0.5 on both sides. A destination pixel (x, y) is normalised with the destination intrinsics,
+ *      distorted by the model and read from the source at
+ *        (sx, sy) = (src_fx * xd + src_cx, src_fy * yd + src_cy).
+ *      model LFS_CAMERA_PINHOLE: the OpenCV terms, radial = k1 k2 k3 (numerator) k4 k5 k6 (denominator), tangential p1 p2, thin s1..s4; the model accepts a pixel
+ *      when its radial factor is > 0.8. model LFS_CAMERA_FISHEYE: theta = atan(r), r_d = theta (1 + k1 theta^2 + .. + k4 theta^8) with radial[0..3]; the model
+ *      accepts a pixel when theta < max_angle (the angle up to which r_d grows; the caller computes it, > 0). A pixel is VALID iff the model accepts it and
+ *      0.5 <= sx <= src_width - 0.5 and 0.5 <= sy <= src_height - 0.5: all four bilinear taps are inside the source, nothing is extrapolated. */
+typedef struct lfs_undistort_map {
+    int32_t model;                       /* LFS_CAMERA_PINHOLE | LFS_CAMERA_FISHEYE */
+    uint32_t src_width, src_height;      /* the decoded file */
+    uint32_t dst_width, dst_height;      /* the training target */
+    float src_fx, src_fy, src_cx, src_cy; /* at the source file's size */
+    float radial[6], tangential[2], thin[4];
+    float max_angle;                     /* fisheye only */
+    float dst_fx, dst_fy, dst_cx, dst_cy;
+} lfs_undistort_map;
+/* All three: asynchronous, one thread per destination pixel, no host read. LFS_E_INVALID before any launch for a NULL map / source (the mask entry excepted) /
+ * destination, a zero size, a size >= 2^30, a model other than the two above, a focal length that is not > 0, a fisheye max_angle that is not > 0.
+ *   lfs_image_undistort_u8_to_chw_f32: src u8 [sh,sw,3] -> dst f32 [3,dh,dw] and valid u8 [dh,dw] (255 | 0). One bilinear tap at (sx, sy) with the arithmetic and
+ *     the 8-bit re-quantisation of lfs_image_u8_to_chw_f32; an invalid pixel is 0 in all three channels.
+ *   lfs_mask_undistort_prepare: lfs_mask_prepare through the same positions: tap, re-quantise, threshold, invert, THEN 0 where the pixel is invalid (an inverted
+ *     mask does not count blank pixels). src_u8 NULL = "no mask file": the output is the validity plane itself (255 | 0; threshold and invert do not apply).
+ *     WRITES sums int64[2] as lfs_mask_prepare does.
+ *   lfs_plane_undistort_nearest_f32: src f32 [sh,sw] -> dst f32 [dh,dw], the texel that contains (sx, sy); NaN where the pixel is invalid. */
+LFS_API int lfs_image_undistort_u8_to_chw_f32(const lfs_undistort_map* map, const uint8_t* src_hwc, float* dst_chw, uint8_t* valid_u8, lfs_stream_t stream);
+LFS_API int lfs_mask_undistort_prepare(const lfs_undistort_map* map, const uint8_t* src_u8, uint8_t* dst_u8, uint32_t invert, int32_t threshold, int64_t* sums,
+                                       lfs_stream_t stream);
+LFS_API int lfs_plane_undistort_nearest_f32(const lfs_undistort_map* map, const float* src_f32, float* dst_f32, lfs_stream_t stream);
 LFS_API int lfs_mean_neighbor_distances(uint32_t N, const float* points, float* out, lfs_stream_t stream);
 LFS_API int lfs_mean_neighbor_distances_exact(uint32_t N, const float* points, float* out, lfs_stream_t stream);
 

@@ -37,6 +37,7 @@ SOURCES = {
     "ssim.hip": ["-ffp-contract=off"],
     "bilateral_grid.hip": ["-ffp-contract=off"],
     "dataprep.hip": ["-ffp-contract=off"],
+    "undistort.hip": ["-ffp-contract=off"],   # undistortion at load: the image / mask / plane resample through a lens model (the tap arithmetic of dataprep.hip, same flags: same bits)
     "fastgs_prep.hip": ["-ffp-contract=off"],
     "filter3d.hip": ["-ffp-contract=off"],   # the 3D smoothing filter's variance from all training cameras (its per-primitive use is in fastgs_prep.hip)
     "sog.hip": ["-ffp-contract=off"],   # SOG export: Morton codes, k-means (the MFMA assignment is an fmaf chain by construction; the flag holds the rest)

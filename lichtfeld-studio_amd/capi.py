@@ -103,6 +103,13 @@ class Filter3dCamera(C.Structure):  # lfs_filter3d_camera (72 bytes: 18 dwords, 
     _fields_ = [("w2c", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("width", C.c_uint32), ("height", C.c_uint32)]
 
 
+class UndistortMapStruct(C.Structure):  # lfs_undistort_map (filled by undistort.UndistortMap.struct)
+    _fields_ = [("model", C.c_int32), ("src_width", C.c_uint32), ("src_height", C.c_uint32), ("dst_width", C.c_uint32), ("dst_height", C.c_uint32),
+                ("src_fx", C.c_float), ("src_fy", C.c_float), ("src_cx", C.c_float), ("src_cy", C.c_float),
+                ("radial", C.c_float * 6), ("tangential", C.c_float * 2), ("thin", C.c_float * 4), ("max_angle", C.c_float),
+                ("dst_fx", C.c_float), ("dst_fy", C.c_float), ("dst_cx", C.c_float), ("dst_cy", C.c_float)]
+
+
 ADAM_MAX_TENSORS = 8
 
 # every symbol include/lfs_gsplat.h declares
@@ -123,6 +130,7 @@ EXPORTS = [
     "lfs_mask_prepare", "lfs_photometric_loss_masked_fwd_bwd", "lfs_mse_loss_masked_fwd_bwd",
     "lfs_depth_prepare", "lfs_depth_l1_loss_fwd_bwd",
     "lfs_fastgs_view_preprocess_ex", "lfs_fastgs_view_backward_ex", "lfs_filter3d_workspace_bytes", "lfs_filter3d_compute",
+    "lfs_image_undistort_u8_to_chw_f32", "lfs_mask_undistort_prepare", "lfs_plane_undistort_nearest_f32",
 ]
 
 

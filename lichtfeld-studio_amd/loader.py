@@ -10,6 +10,8 @@ liblfs_io.so (include/lfs_io.h; C++17, no GPU) plus the two GPU kernels of csrc/
   CameraDataset                          src/training/dataset.hpp:25-75 (every test_every-th image is a validation view)
   colmap_scene                           the Scene the trainer consumes (viewmats [R|t], K scaled to the loaded image size:
                                          src/core/camera.cpp:15-23, :77-98)
+  undistort=True (extension)             views whose camera has lens distortion are resampled at load to a distortion-free pinhole camera
+                                         (undistort.py chooses it, csrc/undistort.hip resamples image, mask and depth target)
 
 liblfs_io decodes PNG, PNM and JPEG itself (baseline and progressive Huffman JPEG, bit-identical to libjpeg-turbo's default pipeline, i.e. to what
 the reference gets through OpenImageIO); what it reports as unsupported (CMYK JPEG, interlaced PNG, TIFF ...) is decoded with Pillow here.
@@ -358,16 +360,86 @@ def u8_to_chw_f32(image_u8: torch.Tensor, out_width: Optional[int] = None, out_h
     return out
 
 
-def load_image(path: str, resize_factor: int = -1, max_width: int = 0, device="cuda:0") -> torch.Tensor:
+def _map_for_source(umap, width: int, height: int, what: str):
+    """the view's map for a source plane of this size: the image's own size as it is, another size (a depth file at its own resolution) with the source
+    intrinsics scaled to it"""
+    if (umap.src_width, umap.src_height) == (width, height):
+        return umap
+    if what == "image":
+        raise LoaderError(f"the undistortion map was built for a {umap.src_width}x{umap.src_height} image, the file is {width}x{height}")
+    return umap.with_source_size(width, height)
+
+
+def undistort_u8_to_chw_f32(image_u8: torch.Tensor, umap) -> Tuple[torch.Tensor, torch.Tensor]:
+    """GPU: u8 [h,w,3] seen through umap's lens model -> (f32 [3,oh,ow] of umap's pinhole camera, validity u8 [oh,ow]: 255 where the source covers the pixel,
+    0 where it does not - the image is 0 there). lfs_image_undistort_u8_to_chw_f32: one bilinear tap, the arithmetic and 8-bit re-quantisation of u8_to_chw_f32."""
+    from .capi import check, load_library, ptr, require_gpu, stream
+    image_u8 = image_u8.contiguous()
+    require_gpu(image_u8)
+    assert image_u8.dtype == torch.uint8 and image_u8.dim() == 3 and image_u8.shape[2] == 3, image_u8.shape
+    umap = _map_for_source(umap, image_u8.shape[1], image_u8.shape[0], "image")
+    out = torch.empty((3, umap.dst_height, umap.dst_width), dtype=torch.float32, device=image_u8.device)
+    valid = torch.empty((umap.dst_height, umap.dst_width), dtype=torch.uint8, device=image_u8.device)
+    s = umap.struct()
+    check(load_library().lfs_image_undistort_u8_to_chw_f32(C.byref(s), ptr(image_u8), ptr(out), ptr(valid), stream()), "image_undistort_u8_to_chw_f32")
+    return out, valid
+
+
+def undistort_mask(mask_u8: Optional[torch.Tensor], umap, invert: bool = False, threshold: int = -1, device=None):
+    """lfs_mask_undistort_prepare -> losses.PreparedMask at umap's destination size: a uint8 [h,w] mask plane through the positions of undistort_u8_to_chw_f32,
+    then threshold, then invert, then 0 where the source does not cover the pixel. mask_u8 None: the view has no mask file - the validity plane is its mask."""
+    from .capi import check, load_library, ptr, require_gpu, stream
+    from .losses import PreparedMask
+    if mask_u8 is not None:
+        mask_u8 = mask_u8.contiguous()
+        require_gpu(mask_u8)
+        assert mask_u8.dtype == torch.uint8 and mask_u8.dim() == 2, mask_u8.shape
+        umap = _map_for_source(umap, mask_u8.shape[1], mask_u8.shape[0], "image")
+        device = mask_u8.device
+    dst = torch.empty((umap.dst_height, umap.dst_width), dtype=torch.uint8, device=device)
+    sums = torch.empty(2, dtype=torch.int64, device=device)
+    s = umap.struct()
+    check(load_library().lfs_mask_undistort_prepare(C.byref(s), ptr(mask_u8), ptr(dst), C.c_uint32(int(bool(invert))), C.c_int32(int(threshold)), ptr(sums), stream()),
+          "mask_undistort_prepare")
+    return PreparedMask(dst, sums)
+
+
+def undistort_plane_nearest(plane_f32: torch.Tensor, umap) -> torch.Tensor:
+    """lfs_plane_undistort_nearest_f32: a float32 [h,w] plane (a depth target at its file's size) -> [oh,ow] of umap's pinhole camera by nearest neighbour, NaN
+    where the source does not cover the pixel."""
+    from .capi import check, load_library, ptr, require_gpu, stream
+    plane_f32 = plane_f32.contiguous()
+    require_gpu(plane_f32)
+    assert plane_f32.dtype == torch.float32 and plane_f32.dim() == 2, plane_f32.shape
+    umap = _map_for_source(umap, plane_f32.shape[1], plane_f32.shape[0], "plane")
+    out = torch.empty((umap.dst_height, umap.dst_width), dtype=torch.float32, device=plane_f32.device)
+    s = umap.struct()
+    check(load_library().lfs_plane_undistort_nearest_f32(C.byref(s), ptr(plane_f32), ptr(out), stream()), "plane_undistort_nearest_f32")
+    return out
+
+
+def _upload_u8(a: np.ndarray, device) -> torch.Tensor:
+    host = torch.from_numpy(a)
+    if torch.cuda.is_available():
+        host = host.pin_memory()
+    return host.to(device, non_blocking=True)
+
+
+def load_image(path: str, resize_factor: int = -1, max_width: int = 0, device="cuda:0", undistort=None, return_valid: bool = False):
     """Camera::load_and_get_image: decode -> [resample] -> f32 [3,h,w] on the device. The upload is the full-size u8 image
-    from pinned memory; resample, layout change and normalisation are one kernel."""
+    from pinned memory; resample, layout change and normalisation are one kernel. undistort (an UndistortMap): the resample goes through the view's lens model
+    (undistort_u8_to_chw_f32); return_valid then returns (image, validity plane) - the plane is None without a map."""
     rgb = decode_rgb8(path)
+    if undistort is not None:
+        img, valid = undistort_u8_to_chw_f32(_upload_u8(rgb, device), undistort)
+        return (img, valid) if return_valid else img
     h, w = rgb.shape[:2]
     ow, oh = image_target_size(w, h, resize_factor, max_width)
     host = torch.from_numpy(rgb)
     if torch.cuda.is_available():
         host = host.pin_memory()
-    return u8_to_chw_f32(host.to(device, non_blocking=True), ow, oh)
+    img = u8_to_chw_f32(host.to(device, non_blocking=True), ow, oh)
+    return (img, None) if return_valid else img
 
 
 def write_png(path: str, rgb: np.ndarray) -> None:
@@ -504,6 +576,24 @@ class CameraDataset:
     data_path: Optional[str] = None     # the scene's directory: where the masks folder is looked for
     masks_folder: Optional[str] = "masks"
     depths_folder: Optional[str] = "depths"
+    undistort: bool = False             # resample every view with lens distortion to a distortion-free pinhole camera at load (undistort.py)
+    undistort_alpha: float = 0.0        # 0: no blank pixels in the output, 1: no source pixel lost (OpenCV's getOptimalNewCameraMatrix alpha)
+    _maps: dict = field(default_factory=dict, repr=False, compare=False)
+
+    def undistort_map(self, index: int):
+        """the view's undistort.UndistortMap, or None: the option is off, or the view's camera has no distortion - it takes the plain resample"""
+        if not self.undistort:
+            return None
+        ci = self.indices[index]
+        if ci not in self._maps:
+            from .undistort import undistorted_camera
+            cam = self.cameras[ci]
+            w, h = (cam.width, cam.height)
+            if os.path.exists(cam.image_path):
+                w, h, _ = get_image_info(cam.image_path)
+            ow, oh = image_target_size(w, h, self.resize_factor, self.max_width)
+            self._maps[ci] = undistorted_camera(cam, w, h, ow, oh, self.undistort_alpha)
+        return self._maps[ci]
 
     def depth_source(self, index: int) -> Optional[str]:
         """the view's depth file (find_depth), or None"""
@@ -531,32 +621,47 @@ class CameraDataset:
         if not 0 <= index < len(self.indices):
             raise IndexError("Dataset index out of range")
         cam = self.cameras[self.indices[index]]
-        return cam, load_image(cam.image_path, self.resize_factor, self.max_width, device)
+        return cam, load_image(cam.image_path, self.resize_factor, self.max_width, device, undistort=self.undistort_map(index))
 
 
-def preload(ds: "CameraDataset", device="cuda:0", workers: int = 8) -> List[torch.Tensor]:
+def preload(ds: "CameraDataset", device="cuda:0", workers: int = 8, return_valid: bool = False):
     """All images of the split as resident f32 [3,h,w] device tensors. Decoding (liblfs_io, outside the GIL) runs on `workers` host threads;
-    upload + resample + layout change stay on the calling thread's stream, in dataset order."""
+    upload + resample + layout change stay on the calling thread's stream, in dataset order. A view with an undistortion map (ds.undistort_map) is resampled
+    through its lens model; return_valid=True returns (images, validity planes) - uint8 [h,w] per such view, None for the others."""
     import concurrent.futures as cf
     paths = [ds.cameras[i].image_path for i in ds.indices]
-    out = []
+    maps = [ds.undistort_map(k) for k in range(len(ds))]   # (before any decode: a camera that cannot be undistorted is refused here)
+    out, valids = [], []
     with cf.ThreadPoolExecutor(max_workers=max(1, workers)) as ex:
-        for rgb in ex.map(decode_rgb8, paths):
+        for k, rgb in enumerate(ex.map(decode_rgb8, paths)):
+            if maps[k] is not None:
+                img, valid = undistort_u8_to_chw_f32(_upload_u8(rgb, device), maps[k])
+                out.append(img)
+                valids.append(valid)
+                continue
             h, w = rgb.shape[:2]
             ow, oh = image_target_size(w, h, ds.resize_factor, ds.max_width)
             host = torch.from_numpy(rgb)
             if torch.cuda.is_available():
                 host = host.pin_memory()
             out.append(u8_to_chw_f32(host.to(device, non_blocking=True), ow, oh))
-    return out
+            valids.append(None)
+    return (out, valids) if return_valid else out
 
 
 def preload_masks(ds: "CameraDataset", device="cuda:0", invert: bool = False, threshold: int = -1) -> list:
-    """The masks of the split, parallel to preload(): a losses.PreparedMask at image_target_size per view that has a mask source, None for the others."""
+    """The masks of the split, parallel to preload(): a losses.PreparedMask at image_target_size per view that has a mask source, None for the others. A view with
+    an undistortion map gets its mask through the same map, 0 where the source does not cover the pixel; with undistort_alpha > 0 such a view WITHOUT a mask
+    file gets the validity plane as its mask (at alpha = 0 every pixel is covered: it stays None)."""
     from .losses import prepare_mask
     out = []
     for i in range(len(ds)):
         src = ds.mask_source(i)
+        umap = ds.undistort_map(i)
+        if umap is not None and (src is not None or ds.undistort_alpha > 0):
+            cam = ds.cameras[ds.indices[i]]
+            out.append(undistort_mask(None if src is None else _upload_u8(load_mask8(cam.image_path, src), device), umap, invert, threshold, device))
+            continue
         if src is None:
             out.append(None)
             continue
@@ -588,7 +693,10 @@ def preload_depths(ds: "CameraDataset", device="cuda:0", kind: str = "invdepth",
             continue
         ow, oh = ds.image_size(i)
         dev = torch.from_numpy(t).to(device)
-        if tuple(dev.shape) != (oh, ow):
+        umap = ds.undistort_map(i)
+        if umap is not None:
+            dev = undistort_plane_nearest(dev.contiguous(), umap)
+        elif tuple(dev.shape) != (oh, ow):
             dev = torch.nn.functional.interpolate(dev[None, None], size=(oh, ow), mode="nearest")[0, 0].contiguous()
         out.append(prepare_depth(dev, None if masks is None else masks[i]))
     return out
@@ -612,20 +720,23 @@ def intrinsics(cam: CameraData, image_width: int, image_height: int) -> np.ndarr
 
 def colmap_scene(base: str, images_folder: str = "images", split: str = "train", test_every: int = 8, resize_factor: int = -1, max_width: int = 0,
                  sh_degree: int = 3, init_scaling: float = 1.0, init_opacity: float = 0.1, text: bool = False, device="cuda:0", masks_folder: Optional[str] = "masks",
-                 depths_folder: Optional[str] = "depths"):
+                 depths_folder: Optional[str] = "depths", undistort: bool = False, undistort_alpha: float = 0.0):
     """COLMAP directory -> (Scene for GutTrainer, CameraDataset, scene_scale). All views must share one image size (the trainer's
-    view batches are rectangular)."""
+    view batches are rectangular). undistort: every view whose camera has lens distortion is resampled at load (preload, preload_masks, preload_depths) to a
+    distortion-free pinhole camera of the same size, and Scene.Ks holds that camera's intrinsics (ds.undistort_map); a view without distortion is untouched."""
     from .scenes import Scene
     cams, center = (read_colmap_cameras_and_images_text if text else read_colmap_cameras_and_images)(base, images_folder)
     pcd = (read_colmap_point_cloud_text if text else read_colmap_point_cloud)(base)
-    ds = CameraDataset(cams, split, test_every, resize_factor, max_width, data_path=base, masks_folder=masks_folder, depths_folder=depths_folder)
+    ds = CameraDataset(cams, split, test_every, resize_factor, max_width, data_path=base, masks_folder=masks_folder, depths_folder=depths_folder,
+                       undistort=undistort, undistort_alpha=undistort_alpha)
     if not len(ds):
         raise LoaderError("the requested split has no images")
     w, h = ds.image_size(0)
     model, scene_scale = init_model_from_pointcloud(pcd, center, sh_degree, init_scaling, init_opacity, device)
     used = [cams[i] for i in ds.indices]
     viewmats = torch.from_numpy(np.stack([world_to_view(c) for c in used]))
-    Ks = torch.from_numpy(np.stack([intrinsics(c, w, h) for c in used]))
+    maps = [ds.undistort_map(k) for k in range(len(ds))]
+    Ks = torch.from_numpy(np.stack([intrinsics(c, w, h) if m is None else m.K() for c, m in zip(used, maps)]))
     means, sh0, shN, scales, quats, opac = [p.detach().clone() for p in model.parameters()]
     scene = Scene(os.path.basename(os.path.normpath(base)), w, h, sh_degree, means, quats, scales, opac, sh0, shN, viewmats, Ks,
                   {"scene_scale": scene_scale, "scene_center": center, "active_sh_degree": 0})   # GutTrainer starts the schedule at degree 0

@@ -15,6 +15,7 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
@@ -67,6 +68,11 @@ def build_parser() -> argparse.ArgumentParser:
                                                          "scale <= 0 trains without a depth target (default: <data>/sparse/0/depth_params.json when it exists)")
     ap.add_argument("--depth-weight-init", type=float, default=1.0, help="weight of the depth loss at the first iteration")
     ap.add_argument("--depth-weight-final", type=float, default=0.01, help="... and at the last: exponential decay between the two")
+    ap.add_argument("--undistort", action="store_true", help="resample every image whose COLMAP camera has lens distortion (SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV, the fisheye "
+                    "models) to a distortion-free pinhole camera of the same size at load, masks and depth targets with it, and train / --eval on that camera (without: the "
+                    "distortion parameters are ignored, as if the images had gone through COLMAP's image_undistorter)")
+    ap.add_argument("--undistort-alpha", type=float, default=0.0, help="with --undistort: 0 = zoom in until no output pixel is blank, 1 = zoom out until no source pixel is lost "
+                    "(OpenCV's getOptimalNewCameraMatrix alpha); above 0 the blank pixels leave the loss (--mask-mode none becomes ignore)")
     return ap
 
 
@@ -88,6 +94,13 @@ def check_args(args) -> None:
         raise SystemExit("--depth-loss is not wired into the 3DGUT route. Please disable the depth loss or disable gut.")
     if args.depth_loss != "none" and not (args.depth_weight_init > 0 and args.depth_weight_final > 0):
         raise SystemExit("--depth-weight-init and --depth-weight-final must be > 0 (the weight is interpolated in the logarithm)")
+    if not 0.0 <= args.undistort_alpha <= 1.0:
+        raise SystemExit("--undistort-alpha must be in [0, 1]")
+    if args.undistort_alpha > 0 and not args.undistort:
+        raise SystemExit("--undistort-alpha needs --undistort")
+    if args.undistort and args.undistort_alpha > 0 and args.mask_mode == "none":
+        args.mask_mode = "ignore"
+        print("undistort: --undistort-alpha > 0 leaves blank pixels in the targets; --mask-mode none becomes ignore (they leave the loss)", file=sys.stderr)
     if args.pose_optimization != "none" and args.eval:   # trainer.cpp:367-370
         raise SystemExit("Evaluating with pose optimization is not supported yet. Please disable pose optimization or evaluation.")
 
@@ -124,7 +137,14 @@ def main():
     split = "train" if args.eval else "all"
     scene, ds, scene_scale = loader.colmap_scene(args.data_path, args.images, split=split, test_every=args.test_every, resize_factor=args.resize_factor,
                                                  max_width=args.max_width, sh_degree=args.sh_degree, init_scaling=init_scaling, init_opacity=init_opacity,
-                                                 text=args.text, device=dev, masks_folder=args.masks_folder, depths_folder=args.depths_folder)
+                                                 text=args.text, device=dev, masks_folder=args.masks_folder, depths_folder=args.depths_folder,
+                                                 undistort=args.undistort, undistort_alpha=args.undistort_alpha)
+    maps = [ds.undistort_map(k) for k in range(len(ds))]
+    if not args.undistort:
+        n_dist = sum(1 for i in ds.indices if ds.cameras[i].camera_model_type != 0 or np.any(ds.cameras[i].radial_distortion) or np.any(ds.cameras[i].tangential_distortion))
+        if n_dist:
+            print(f"warning: {n_dist} of {len(ds)} views have lens distortion, which is being IGNORED (pinhole rendering against distorted images); pass --undistort",
+                  file=sys.stderr)
     masks = loader.preload_masks(ds, dev, args.invert_masks, args.mask_threshold) if args.mask_mode != "none" else None
     depths = None
     if args.depth_loss != "none":
@@ -154,17 +174,21 @@ def main():
         with torch.no_grad():
             scales, opac = filter3d.bake(m, tr.update_filter3d(force=True))
         return SplatModel(m.means.detach(), m.sh0.detach(), m.shN.detach(), scales, m.raw_quats.detach(), opac, m.max_sh_degree, m.active_sh_degree)
+    def val_K(val, k, w, h):
+        """a held-out view's intrinsics: its undistortion map's destination camera, or the plain pinhole K"""
+        m = val.undistort_map(k)
+        return loader.intrinsics(val.cameras[val.indices[k]], w, h) if m is None else m.K()
     os.makedirs(args.output_path, exist_ok=True)
     g = torch.Generator().manual_seed(0)
     val_set = None
     if args.eval and args.eval_every > 0:
         cams_all, _ = (loader.read_colmap_cameras_and_images_text if args.text else loader.read_colmap_cameras_and_images)(args.data_path, args.images)
-        val = loader.CameraDataset(cams_all, "val", args.test_every, args.resize_factor, args.max_width)
+        val = loader.CameraDataset(cams_all, "val", args.test_every, args.resize_factor, args.max_width, undistort=args.undistort, undistort_alpha=args.undistort_alpha)
         vc, vi = [], []
         for k, img in enumerate(loader.preload(val, dev)):
             cam = val.cameras[val.indices[k]]
             h, w = img.shape[1:]
-            vc.append(Camera(torch.from_numpy(loader.world_to_view(cam))[None].to(dev), torch.from_numpy(loader.intrinsics(cam, w, h))[None].to(dev), w, h))
+            vc.append(Camera(torch.from_numpy(loader.world_to_view(cam))[None].to(dev), torch.from_numpy(val_K(val, k, w, h))[None].to(dev), w, h))
             vi.append(img)
         val_set = (vc, vi)
     curve = []
@@ -208,19 +232,23 @@ def main():
            "iters_per_s": round(total / max(t_train, 1e-9), 1)}
     if masks is not None:
         out.update(mask_mode=args.mask_mode, masked_views=sum(m is not None for m in masks))
+    if args.undistort:
+        zs = [m.z for m in maps if m is not None]
+        out.update(undistort_alpha=args.undistort_alpha, undistorted_views=len(zs), undistort_z=[round(min(zs), 5), round(max(zs), 5)] if zs else None)
     if depths is not None:
         out.update(depth_loss=args.depth_loss, depth_views=sum(d is not None for d in depths), depth_weight=[args.depth_weight_init, args.depth_weight_final])
     if args.enable_sparsity:
         out.update(base_iterations=args.iterations, sparsify_steps=args.sparsify_steps, prune_ratio=args.prune_ratio, init_rho=args.init_rho)
     if args.eval:
         cams_all, _ = (loader.read_colmap_cameras_and_images_text if args.text else loader.read_colmap_cameras_and_images)(args.data_path, args.images)
-        val = loader.CameraDataset(cams_all, "val", args.test_every, args.resize_factor, args.max_width, data_path=args.data_path, masks_folder=args.masks_folder)
+        val = loader.CameraDataset(cams_all, "val", args.test_every, args.resize_factor, args.max_width, data_path=args.data_path, masks_folder=args.masks_folder,
+                                   undistort=args.undistort, undistort_alpha=args.undistort_alpha)   # the held-out views through the same kind of map
         val_masks = loader.preload_masks(val, dev, args.invert_masks, args.mask_threshold) if args.mask_mode != "none" else None   # PSNR over the masked pixels; SSIM unmasked
         cameras, images = [], []
         for k, img in enumerate(loader.preload(val, dev)):
             cam = val.cameras[val.indices[k]]
             h, w = img.shape[1:]
-            cameras.append(Camera(torch.from_numpy(loader.world_to_view(cam))[None].to(dev), torch.from_numpy(loader.intrinsics(cam, w, h))[None].to(dev), w, h))
+            cameras.append(Camera(torch.from_numpy(loader.world_to_view(cam))[None].to(dev), torch.from_numpy(val_K(val, k, w, h))[None].to(dev), w, h))
             images.append(img)
         m = evaluate.evaluate(tr.model, cameras, images, total, masks=val_masks, antialiased=args.antialiasing, filter3d=tr.update_filter3d(force=True))
         out.update(psnr=round(m.psnr, 4), ssim=round(m.ssim, 5), val_images=m.n_images)
