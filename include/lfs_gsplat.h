@@ -590,6 +590,21 @@ LFS_API int lfs_gut_view_backward_finish(const lfs_gut_step_args* args, int64_t 
  *   lfs_sh_model_bwd_views over all views on every rank (radii = colors = NULL there: rows pre-masked with colour > 0 by the rank that rendered the view). */
 LFS_API int lfs_gut_view_backward_rows(const lfs_gut_step_args* args, int64_t capacity, const float* v_render, float* const* grads /* [6] host */, int accumulate,
                                        float* v_colors_out, void* workspace, size_t workspace_bytes, lfs_stream_t stream);
+/*   The _ex forms of the gradient-tensor backwards: riders of the view's finish pass. densification_info [2,N] (device; ADC's statistic, default_strategy.cpp): for every
+ *   Gaussian visible in THIS view (both radii > 0) row 0 += 1 and row 1 += s, the screen-equivalent norm of the view's own rasterizer part of dL/dmean,
+ *      g_c = Rinv^T v, z = (Rinv^T (mean - origin)).z, s = sqrt((g_c.x z W / (2 fx))^2 + (g_c.y z H / (2 fy))^2)
+ *   (what dL/dmean2d * 0.5 * (W, H) is on the EWA route: grad_threshold keeps its meaning; the SH direction term of dL/dmean is not in it). The radii are the
+ *   ones lfs_gut_view_forward left in the workspace. ext == NULL or densification_info == NULL: the entry without _ex - the same launches, the same bits (the
+ *   old entries are argument adapters of these). lfs_gut_view_backward_sh has no finish pass and no _ex form. */
+typedef struct lfs_gut_view_ext {
+    float* densification_info;   /* [2,N] device or NULL */
+} lfs_gut_view_ext;
+LFS_API int lfs_gut_view_backward_ex(const lfs_gut_step_args* args, int64_t capacity, const float* v_render, float* const* grads, int accumulate,
+                                     const lfs_gut_view_ext* ext, void* workspace, size_t workspace_bytes, lfs_stream_t stream);
+LFS_API int lfs_gut_view_backward_finish_ex(const lfs_gut_step_args* args, int64_t capacity, float* const* grads, int accumulate,
+                                            const lfs_gut_view_ext* ext, void* workspace, size_t workspace_bytes, lfs_stream_t stream);
+LFS_API int lfs_gut_view_backward_rows_ex(const lfs_gut_step_args* args, int64_t capacity, const float* v_render, float* const* grads /* [6] host */, int accumulate,
+                                          float* v_colors_out, const lfs_gut_view_ext* ext, void* workspace, size_t workspace_bytes, lfs_stream_t stream);
 LFS_API int lfs_gut_step_wait(const int64_t* host_counts, int64_t stamp, double timeout_s, int64_t* n_isects, int64_t* longest);
 /*   lfs_gut_train_step_ex (round 6): lfs_gut_train_step with its three per-Gaussian tail passes (SH backward + Adam on sh0 / shN, finish + Adam on the other four tensors,
  *      and the NEXT step's SH colours) as ONE launch. next_viewmat (device [4,4], nullable): the view the next step will render - its SH colours are then written to the
@@ -657,6 +672,12 @@ LFS_API int lfs_gut_finish_grads(
     uint32_t N, const float* means, const float* raw_quats, const float* quats, const float* scales, const float* opacities, float scale_reg, float opacity_reg,
     int accumulate, float* g_means, float* g_raw_scales, float* g_raw_quats, float* g_raw_opacities, float* v_colors, float* loss,
     void* workspace, size_t workspace_bytes, lfs_stream_t stream);
+/* lfs_gut_finish_grads with the riders of lfs_gut_view_ext (above): radii [N,2] of the view (nullable without a statistic); densification_info without radii is
+ * LFS_E_INVALID before any launch. ext NULL or its pointer NULL: lfs_gut_finish_grads - the same launch, the same bits. */
+LFS_API int lfs_gut_finish_grads_ex(
+    uint32_t N, const float* means, const float* raw_quats, const float* quats, const float* scales, const float* opacities, float scale_reg, float opacity_reg,
+    int accumulate, float* g_means, float* g_raw_scales, float* g_raw_quats, float* g_raw_opacities, float* v_colors, float* loss,
+    const int32_t* radii, const lfs_gut_view_ext* ext, void* workspace, size_t workspace_bytes, lfs_stream_t stream);
 LFS_API int lfs_gut_finish_adam(
     uint32_t N, float* means, float* raw_scales, float* raw_quats, float* raw_opacities, const float* quats, const float* scales, const float* opacities,
     const float* v_dirs /* [N,3] from lfs_sh_model_bwd_adam_all */, float* const* exp_avg /* [4] host: means, raw_scales, raw_quats, raw_opacities */,

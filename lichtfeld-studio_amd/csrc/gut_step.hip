@@ -319,22 +319,32 @@ extern "C" int lfs_gut_view_backward_sh(const lfs_gut_step_args* a, int64_t capa
                                   inline_shN ? &adam : nullptr, s);
 }
 
-extern "C" int lfs_gut_view_backward_finish(const lfs_gut_step_args* a, int64_t capacity, float* const* grads /* [6] host */, int accumulate,
-                                            void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
+// The _ex forms carry the riders of the finish pass (lfs_gut_view_ext: ADC's densification statistic of the view, from the radii the forward left in the workspace);
+// the entries without _ex are their argument adapters (ext = NULL: the same launches, the same bits).
+static GutDensify densify_of(const lfs_gut_view_ext* ext, const StepWs& w) { return GutDensify{w.radii, ext ? ext->densification_info : nullptr}; }
+
+extern "C" int lfs_gut_view_backward_finish_ex(const lfs_gut_step_args* a, int64_t capacity, float* const* grads /* [6] host */, int accumulate,
+                                               const lfs_gut_view_ext* ext, void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
     StepWs w;
     const int rc = open_step(a, Need::Forward, nullptr, capacity, workspace, workspace_bytes, w);
     if (rc) return rc;
     if (!grads || !grads[0] || !grads[3] || !grads[4] || !grads[5] || (a->target_chw && !a->loss)) return LFS_E_INVALID;
+    const GutDensify dens = densify_of(ext, w);
     return gut_finish_grads_impl(params_of(a), activated_of(w), GutRegs{a->scale_reg, a->opacity_reg}, GutGrads{grads[0], grads[3], grads[4], grads[5], nullptr, accumulate},
-                                 w.v_dirs, a->target_chw ? a->loss : nullptr, w.raster, (hipStream_t)stream);
+                                 w.v_dirs, a->target_chw ? a->loss : nullptr, w.raster, (hipStream_t)stream, &dens);
+}
+
+extern "C" int lfs_gut_view_backward_finish(const lfs_gut_step_args* a, int64_t capacity, float* const* grads /* [6] host */, int accumulate,
+                                            void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
+    return lfs_gut_view_backward_finish_ex(a, capacity, grads, accumulate, nullptr, workspace, workspace_bytes, stream);
 }
 
 // The view's backward for the FACTORED gradient exchange of the replicated data-parallel layout (dist.ColorGradExchange): rasterizer backward, then the finish pass -
 // grads[0], grads[3..5] (means WITHOUT the SH direction term, scales, quaternions, opacities), written or added to - and dL/dcolour [N,3] -> v_colors_out. No SH
 // backward here: per view the gradient of the SH coefficients is the outer product basis(direction) x dL/dcolour, every rank knows every rank's camera, so the ranks
 // exchange the 3-float rows and each evaluates the multi-view SH backward (lfs_sh_model_bwd_views) over ALL views itself.
-extern "C" int lfs_gut_view_backward_rows(const lfs_gut_step_args* a, int64_t capacity, const float* v_render, float* const* grads /* [6] host */, int accumulate,
-                                          float* v_colors_out, void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
+extern "C" int lfs_gut_view_backward_rows_ex(const lfs_gut_step_args* a, int64_t capacity, const float* v_render, float* const* grads /* [6] host */, int accumulate,
+                                             float* v_colors_out, const lfs_gut_view_ext* ext, void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     StepWs w;
     int rc = open_step(a, Need::Forward, nullptr, capacity, workspace, workspace_bytes, w);
@@ -344,14 +354,25 @@ extern "C" int lfs_gut_view_backward_rows(const lfs_gut_step_args* a, int64_t ca
     front_of(a, w, capacity, f);
     rc = enqueue_backward(a, w, f, a->target_chw ? nullptr : v_render, s);
     if (rc) return rc;
+    const GutDensify dens = densify_of(ext, w);
     return gut_finish_grads_impl(params_of(a), activated_of(w), GutRegs{a->scale_reg, a->opacity_reg}, GutGrads{grads[0], grads[3], grads[4], grads[5], v_colors_out, accumulate},
-                                 nullptr, a->target_chw ? a->loss : nullptr, w.raster, s);
+                                 nullptr, a->target_chw ? a->loss : nullptr, w.raster, s, &dens);
+}
+
+extern "C" int lfs_gut_view_backward_rows(const lfs_gut_step_args* a, int64_t capacity, const float* v_render, float* const* grads /* [6] host */, int accumulate,
+                                          float* v_colors_out, void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
+    return lfs_gut_view_backward_rows_ex(a, capacity, v_render, grads, accumulate, v_colors_out, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int lfs_gut_view_backward_ex(const lfs_gut_step_args* a, int64_t capacity, const float* v_render, float* const* grads /* [6] host */, int accumulate,
+                                        const lfs_gut_view_ext* ext, void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
+    const int rc = lfs_gut_view_backward_sh(a, capacity, v_render, grads, accumulate, workspace, workspace_bytes, stream);
+    return rc ? rc : lfs_gut_view_backward_finish_ex(a, capacity, grads, accumulate, ext, workspace, workspace_bytes, stream);
 }
 
 extern "C" int lfs_gut_view_backward(const lfs_gut_step_args* a, int64_t capacity, const float* v_render, float* const* grads /* [6] host */, int accumulate,
                                      void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
-    const int rc = lfs_gut_view_backward_sh(a, capacity, v_render, grads, accumulate, workspace, workspace_bytes, stream);
-    return rc ? rc : lfs_gut_view_backward_finish(a, capacity, grads, accumulate, workspace, workspace_bytes, stream);
+    return lfs_gut_view_backward_ex(a, capacity, v_render, grads, accumulate, nullptr, workspace, workspace_bytes, stream);
 }
 
 extern "C" int lfs_gut_view_forward(const lfs_gut_step_args* a, int64_t capacity, int64_t assumed_longest, void* workspace, size_t workspace_bytes,

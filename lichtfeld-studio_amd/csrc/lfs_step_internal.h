@@ -103,8 +103,11 @@ struct ProjOut { float *quats, *scales, *opacities; int32_t* radii; float *means
 struct ProjRiders { uint32_t* zero_words; uint32_t zero_n; void *cams_out, *recs_out, *cull_out; const float* pack_colors; };
 int activations_project_ut_impl(const ProjModel& m, const ProjCamera& c, const ProjOut& out, const ProjRiders* riders /* nullable */, hipStream_t s);
 // lfs_gut_finish_grads with dL/d(dirs) [N,3] (nullable) added to the means gradient; g.v_colors may be NULL then (the SH backward has run already)
+// dens (nullable; lfs_gut_view_ext): ADC's statistic of this view - info [2,N] (visibility count | screen-equivalent gradient norm) is added to by the densifying form of
+// the pass (raster_finish_densify_kernel), which reads the view's radii [N,2]. NULL or info NULL: the pass as it is without it, the same launch and the same bits.
+struct GutDensify { const int32_t* radii; float* info; };
 int gut_finish_grads_impl(const GutParams& p, const GutActivated& act, const GutRegs& regs, const GutGrads& g, const float* v_dirs, float* loss,
-                          const Workspace& ws, hipStream_t s);
+                          const Workspace& ws, hipStream_t s, const GutDensify* dens = nullptr);
 
 // the fused tail of the all-inline step (raster.hip: gut_tail_kernel): SH backward + the six Adam updates in one pass. LFS_E_UNSUPPORTED for K > 16.
 int gut_tail_impl(const GutParams& p, const GutActivated& act, const GutAdam& adam, const GutRegs& regs, const GutTailView& view, float* loss,

@@ -50,9 +50,14 @@
 #include "lfs_cull_conic.cuh"
 #include "lfs_raster_pack.cuh"
 #include "lfs_adam.cuh"
+#include "lfs_raster_finish.cuh"   // finish_geometry, FinishAdam / FinishGrads, LOSS_SLOTS
 #include "lfs_sh.cuh"
 #include "lfs_mcmc_noise.cuh"
 #include "lfs_step_internal.h"
+#ifdef LFS_EMULATE   // (the densifying finish pass is a code object of its own on the GPU; a host build of this file carries it)
+#define LFS_RASTER_DENSIFY_INLINE
+#include "raster_densify.hip"
+#endif
 
 // LFS_BWD_REORTH (default 1 since round 5; -DLFS_BWD_REORTH=0 = the rounds 1 - 4 backward, kept for A/B: tools/build_variant.py noreorth raster.hip -DLFS_BWD_REORTH=0): the backward
 // re-orthogonalises the foot vector against the ray direction before it is used in a gradient - K8's gradients for FLAT Gaussians (tools/aniso_probe.py).
@@ -75,7 +80,6 @@ extern "C" { __attribute__((visibility("default"))) unsigned long long lfs_emul_
 namespace lfs {
 
 static inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
-constexpr uint32_t LOSS_SLOTS = 256; // fused MSE: the wavefronts' partial sums are spread over this many addresses (one hot address costs ~0.08 ms)
 struct RasterWs { CamDev* cams; GaussRec* recs; float* acc; CullRec* cull; int32_t* cell_count; int2* cell_list; unsigned long long* det64; size_t bytes; };
 // cells = C * tiles * (tile_size/8)^2 ; the compacted per-cell lists hold at most (tile_size/8)^2 * n_isects entries
 struct RasterWsOffsets { size_t cams, recs, acc, cull, cell_count, cell_list, det64, bytes; };   // byte offsets of the parts above (det64: only in the deterministic mode)
@@ -664,132 +668,6 @@ __global__ void __launch_bounds__(256) raster_bwd_kernel(
     walk_cell_list<-1>(cl, recs, n_walk - 1, n_walk, eval, []() { return true; });
 }
 
-// dL/d(mean, quaternion, scale) of ONE Gaussian under ONE camera from its accumulator sums A = dL/d(record matrix), G = dL/dg - the vjp tail of Bwd.cu:318-333 through
-// M = S^-1 R^T (global shutter: record matrix M Rinv, g = M (o - mu)). Shared by raster_finish_kernel, raster_finish_adam_kernel and gut_tail_kernel, which are held to
-// each other bit for bit (tests/test_gpu_gut_step.py): the arithmetic is pinned contraction-free here, helpers included (lfs_math.cuh's take the including file's default and
-// this file allows contraction - round 6: a third inlined copy of the fused form came out one ulp off in dL/dmeans, the compiler fuses a*b + c*d differently per context).
-// ADDS to vm / vq / vs (the operator form sums over cameras).
-template <bool UNIFORM_ORIGIN>
-LFS_DI void finish_geometry(const float4 q, const float (&is)[3], const float (&A_in)[9], const f3 G_in, const f3 mu, const CamDev& cam, float (&vm)[3], float (&vq)[4], float (&vs)[3]) {
-#pragma clang fp contract(off)
-    m3 R;
-    float qw = q.x, qx = q.y, qy = q.z, qz = q.w;
-    const float qinv = 1.f / sqrtf(qx * qx + qy * qy + qz * qz + qw * qw);
-    qx *= qinv; qy *= qinv; qz *= qinv; qw *= qinv;
-    {   // quat_to_rotmat
-        const float x2 = qx * qx, y2 = qy * qy, z2 = qz * qz, xy = qx * qy, xz = qx * qz, yz = qy * qz, wx = qw * qx, wy = qw * qy, wz = qw * qz;
-        R.m[0][0] = 1.f - 2.f * (y2 + z2); R.m[1][0] = 2.f * (xy + wz); R.m[2][0] = 2.f * (xz - wy);
-        R.m[0][1] = 2.f * (xy - wz); R.m[1][1] = 1.f - 2.f * (x2 + z2); R.m[2][1] = 2.f * (yz + wx);
-        R.m[0][2] = 2.f * (xz + wy); R.m[1][2] = 2.f * (yz - wx); R.m[2][2] = 1.f - 2.f * (x2 + y2);
-    }
-    m3 M;
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) M.m[r][c] = is[r] * R.m[c][r];
-#if LFS_ACC_SYM
-    if (UNIFORM_ORIGIN) { // the symmetric row (lfs_raster_common.cuh, LFS_ACC_SYM): A_in = B'' (xx, yy, xz, yz, xy, zz) | sum a'', every slot times REC_UNSCALE by the caller; G_in: empty slots
-        const float omx = cam.origin.x - mu.x, omy = cam.origin.y - mu.y, omz = cam.origin.z - mu.z;
-        const f3 gv{M.m[0][0] * omx + M.m[0][1] * omy + M.m[0][2] * omz, M.m[1][0] * omx + M.m[1][1] * omy + M.m[1][2] * omz, M.m[2][0] * omx + M.m[2][1] * omy + M.m[2][2] * omz};
-        m3 U;
-        rot_frame_f32(gv, U);
-        float Bp[3][3];   // B'' = sum a'' (x) w'', two factors of c in it: the second REC_UNSCALE here
-        Bp[0][0] = A_in[0] * REC_UNSCALE; Bp[1][1] = A_in[1] * REC_UNSCALE; Bp[2][2] = A_in[5] * REC_UNSCALE;
-        Bp[0][2] = Bp[2][0] = A_in[2] * REC_UNSCALE; Bp[1][2] = Bp[2][1] = A_in[3] * REC_UNSCALE; Bp[0][1] = Bp[1][0] = A_in[4] * REC_UNSCALE;
-        float T[3][3], B[3][3];   // B = U^T B'' U: the sums in the Gaussian's own frame
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) T[k][c] = Bp[k][0] * U.m[0][c] + Bp[k][1] * U.m[1][c] + Bp[k][2] * U.m[2][c];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) B[r][c] = U.m[0][r] * T[0][c] + U.m[1][r] * T[1][c] + U.m[2][r] * T[2][c];
-        const float as[3] = {U.m[0][0] * A_in[6] + U.m[1][0] * A_in[7] + U.m[2][0] * A_in[8], U.m[0][1] * A_in[6] + U.m[1][1] * A_in[7] + U.m[2][1] * A_in[8],
-                             U.m[0][2] * A_in[6] + U.m[1][2] * A_in[7] + U.m[2][2] * A_in[8]};   // sum a = -dL/dg
-        // mean: g = M (o - mu)  ->  dL/dmu = -M^T dL/dg = M^T sum a
-        vm[0] += M.m[0][0] * as[0] + M.m[1][0] * as[1] + M.m[2][0] * as[2];
-        vm[1] += M.m[0][1] * as[0] + M.m[1][1] * as[1] + M.m[2][1] * as[2];
-        vm[2] += M.m[0][2] * as[0] + M.m[1][2] * as[1] + M.m[2][2] * as[2];
-        // dL/dM = -B M^-T = -B S R^T. Scales: dL/ds_c = -(1 / s_c^2) (dL/dM R)_cc = B_cc / s_c - a sum of like-signed terms, where dL/dA . M + dL/dg . g cancelled to 1e-6.
-        // Rotation: dL/dR[r][c] = dL/dM[c][r] / s_c = -(1 / s_c) sum_k B[c][k] s_k R[r][k]
-        const float sk[3] = {1.f / is[0], 1.f / is[1], 1.f / is[2]};
-        float g[3][3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) g[r][c] = -is[c] * (B[c][0] * sk[0] * R.m[r][0] + B[c][1] * sk[1] * R.m[r][1] + B[c][2] * sk[2] * R.m[r][2]);
-        {   // quat_to_rotmat_vjp on the normalised quaternion
-            const float vw = 2.f * (qx * (g[2][1] - g[1][2]) + qy * (g[0][2] - g[2][0]) + qz * (g[1][0] - g[0][1]));
-            const float vx = 2.f * (-2.f * qx * (g[1][1] + g[2][2]) + qy * (g[1][0] + g[0][1]) + qz * (g[2][0] + g[0][2]) + qw * (g[2][1] - g[1][2]));
-            const float vy = 2.f * (qx * (g[1][0] + g[0][1]) - 2.f * qy * (g[0][0] + g[2][2]) + qz * (g[2][1] + g[1][2]) + qw * (g[0][2] - g[2][0]));
-            const float vz = 2.f * (qx * (g[2][0] + g[0][2]) + qy * (g[2][1] + g[1][2]) - 2.f * qz * (g[0][0] + g[1][1]) + qw * (g[1][0] - g[0][1]));
-            const float dq = vw * qw + vx * qx + vy * qy + vz * qz;
-            vq[0] += (vw - dq * qw) * qinv; vq[1] += (vx - dq * qx) * qinv; vq[2] += (vy - dq * qy) * qinv; vq[3] += (vz - dq * qz) * qinv;
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) vs[c] += B[c][c] * is[c];
-        return;
-    }
-    const float (&A)[9] = A_in; const f3 G = G_in;
-#elif LFS_REC_ROT
-    float Au[9]; f3 Gu = G_in;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) Au[k] = A_in[k];
-    if (UNIFORM_ORIGIN) { // the sums were accumulated in the record's rotated frame (lfs_raster_common.cuh, LFS_REC_ROT): dL/dA = U^T dL/dA'', dL/dg = U^T dL/dg''
-        const float omx = cam.origin.x - mu.x, omy = cam.origin.y - mu.y, omz = cam.origin.z - mu.z;
-        const f3 g{M.m[0][0] * omx + M.m[0][1] * omy + M.m[0][2] * omz, M.m[1][0] * omx + M.m[1][1] * omy + M.m[1][2] * omz, M.m[2][0] * omx + M.m[2][1] * omy + M.m[2][2] * omz};
-        RotFrame F;
-        rot_frame(g, F);   // (the record's frame, bit for bit: lfs_raster_common.cuh)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) rot_apply_t(F, A_in[c], A_in[3 + c], A_in[6 + c], Au[c], Au[3 + c], Au[6 + c]);
-        rot_apply_t(F, G_in.y, G_in.z, G_in.x, Gu.x, Gu.y, Gu.z);   // slots 9 .. 11 arrive as (z, x, y) (raster_bwd_kernel)
-    }
-    const float (&A)[9] = Au; const f3 G = Gu;
-#else
-    const float (&A)[9] = A_in; const f3 G = G_in;
-#endif
-    // dL/dM (math rows r, cols c). Global shutter: the record matrix was M Rinv, so dL/dM = dL/d(M Rinv) Rinv^T
-    m3 vM;
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            if (UNIFORM_ORIGIN) {
-                const m3& Ri = cam.Rinv;
-                vM.m[r][c] = A[3 * r] * Ri.m[c][0] + A[3 * r + 1] * Ri.m[c][1] + A[3 * r + 2] * Ri.m[c][2];
-            } else vM.m[r][c] = A[3 * r + c];
-        }
-    if (UNIFORM_ORIGIN) {
-        const float gv[3] = {G.x, G.y, G.z}, ov[3] = {cam.origin.x - mu.x, cam.origin.y - mu.y, cam.origin.z - mu.z};
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) vM.m[r][c] += gv[r] * ov[c];
-    }
-    // mean: gro = M (o - mu)  ->  dL/dmu = -M^T G
-    vm[0] -= M.m[0][0] * G.x + M.m[1][0] * G.y + M.m[2][0] * G.z;
-    vm[1] -= M.m[0][1] * G.x + M.m[1][1] * G.y + M.m[2][1] * G.z;
-    vm[2] -= M.m[0][2] * G.x + M.m[1][2] * G.y + M.m[2][2] * G.z;
-    // M = S^-1 R^T, i.e. P = M^T = R S^-1 with dL/dP = (dL/dM)^T:  dL/dR[r][c] = dL/dP[r][c] / s_c ;  dL/ds_c = -(1/s_c^2) sum_r R[r][c] dL/dP[r][c]
-    float g[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) g[r][c] = vM.m[c][r] * is[c];
-    {   // quat_to_rotmat_vjp on the normalised quaternion
-        const float vw = 2.f * (qx * (g[2][1] - g[1][2]) + qy * (g[0][2] - g[2][0]) + qz * (g[1][0] - g[0][1]));
-        const float vx = 2.f * (-2.f * qx * (g[1][1] + g[2][2]) + qy * (g[1][0] + g[0][1]) + qz * (g[2][0] + g[0][2]) + qw * (g[2][1] - g[1][2]));
-        const float vy = 2.f * (qx * (g[1][0] + g[0][1]) - 2.f * qy * (g[0][0] + g[2][2]) + qz * (g[2][1] + g[1][2]) + qw * (g[0][2] - g[2][0]));
-        const float vz = 2.f * (qx * (g[2][0] + g[0][2]) + qy * (g[2][1] + g[1][2]) - 2.f * qz * (g[0][0] + g[1][1]) + qw * (g[1][0] - g[0][1]));
-        const float dq = vw * qw + vx * qx + vy * qy + vz * qz;
-        vq[0] += (vw - dq * qw) * qinv; vq[1] += (vx - dq * qx) * qinv; vq[2] += (vy - dq * qy) * qinv; vq[3] += (vz - dq * qz) * qinv;
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-        vs[c] += -is[c] * is[c] * (R.m[0][c] * vM.m[c][0] + R.m[1][c] * vM.m[c][1] + R.m[2][c] * vM.m[c][2]);
-}
-
 // ---------------------------------------------------------------------------
 // finish: accumulator -> dL/d(means, quats, scales, colors, opacities)
 // ---------------------------------------------------------------------------
@@ -847,216 +725,15 @@ __global__ void __launch_bounds__(256) raster_finish_kernel(
     v_scales[3 * gid] = vs[0]; v_scales[3 * gid + 1] = vs[1]; v_scales[3 * gid + 2] = vs[2];
 }
 
-// The all-inline training step (ONE camera, global shutter, one view per step on one rank): raster_finish_kernel + the activation backward
-// (l2_fused.hip: normalize / exp / sigmoid vjp + the MCMC regularisers) + the Adam updates of means, raw scales, raw quaternions and raw
-// opacities (adam.hip) in ONE pass over the Gaussians - no gradient tensor is written or re-read. acc row: dL/dA (9) | -dL/dg (3) | dL/dopacity |
-// dL/dcolour (3: consumed by lfs_sh_model_bwd_adam_all, which hands back dL/d(dirs) in v_dirs). Same operations in the same order as
-// the three separate kernels (the activation and Adam arithmetic is un-fused there: pinned with fp contract(off) here).
-struct FinishAdam { float* m[4]; float* v[4]; AdamScalars s[4]; float scale_reg, opacity_reg; }; // order: means, raw_scales, raw_quats, raw_opacities
-// ADAM = false (multi-GPU / multi-view / non-MSE steps, which need gradient TENSORS): the same pass up to the raw-parameter gradients, written (or added,
-// `accumulate`) to g_* instead of being consumed - raster_finish_kernel + activations_bwd_kernel + the copy of dL/dmeans in one launch; dL/dcolour goes
-// to v_colors for the SH backward, which adds dL/d(dirs) onto g_means afterwards. *loss += the fused MSE (as raster_finish_kernel).
-struct FinishGrads { float* g_means; float* g_scales; float* g_quats; float* g_opac; float* v_colors; int accumulate; };
-constexpr int FINISH_BLOCK = 256;   // threads per workgroup of raster_finish_adam_kernel
-// the fused-loss fold reads LOSS_SLOTS = 256 partial sums with the first four wavefronts of workgroup 0 and adds wave_sum[0..3]: smaller workgroups would drop slots
-static_assert(FINISH_BLOCK >= 256 && FINISH_BLOCK % 64 == 0 && FINISH_BLOCK <= 1024, "FINISH_BLOCK: 256, 320, ..., 1024");
 template <bool ADAM>
 __global__ void __launch_bounds__(FINISH_BLOCK) raster_finish_adam_kernel(
     const uint32_t N, float* __restrict__ means, float* __restrict__ raw_scales, float* __restrict__ raw_quats, float* __restrict__ raw_opacities,
     const float* __restrict__ quats, const float* __restrict__ scales, const float* __restrict__ opacities,
     const CamDev* __restrict__ cams, const float* __restrict__ acc, const float* __restrict__ v_dirs, const FinishAdam ad, const FinishGrads gr,
     const float* __restrict__ loss_slots, float* __restrict__ loss, const int32_t* __restrict__ abort_flag = nullptr) {
-#ifndef LFS_EMULATE
-    // ONE memory round trip per wavefront (round 6). The form before had four in series - abort-flag pointer -> flag -> the accumulator rows (their LDS hand-over
-    // sits behind a scheduling barrier no load may cross) -> the other 21 loads (two of them issued late, behind the first arithmetic) - in a kernel whose 29 streams
-    // reach 5.1 TB/s in a trivial pass (tools/hbm_stream.hip: multi_rmw_32_streams) and that ran at 3.1 - 3.7. Here every load of the pass is issued before the first
-    // wait, through (SGPR base, 32-bit byte offset) addresses - three offset registers instead of a 64-bit address pair per stream - and the abort flag is looked at
-    // where it matters: in front of the stores.
-    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = gid < N;
-    const uint32_t g = live ? gid : (N - 1u);              // (tail lanes read the last row: no branch around the loads)
-    const uint32_t o4 = g << 2, o12 = g * 12u, o16 = g << 4;
-    auto at = [](const void* base, uint32_t byte_off) { return reinterpret_cast<const char*>(base) + byte_off; };
-    auto ld3o = [&](const float* base, float (&dst)[3]) { const V3f t = *reinterpret_cast<const V3f*>(at(base, o12)); dst[0] = t.a[0]; dst[1] = t.a[1]; dst[2] = t.a[2]; };
-    auto ld4o = [&](const float* base) { return *reinterpret_cast<const float4*>(at(base, o16)); };
-    auto ld1o = [&](const float* base) { return *reinterpret_cast<const float*>(at(base, o4)); };
-    int32_t aborted = 0;
-    if (ADAM && abort_flag != nullptr) aborted = *abort_flag; // (scalar load: in flight with everything else)
-    // the 64 accumulator rows of a wavefront (4 KB contiguous) as four fully coalesced 1-KB loads, handed to their lanes through a wave-private LDS block below
-    // (row stride 20 floats: 16-byte aligned, conflict-free on the read side) instead of four 16-byte loads per lane at a 64-byte stride: finish_adam 0.106 / 0.102 -> 0.102 / 0.097 ms
-    // (round 3, profiles/r03/finish_lds_rows_ab.txt)
-    __shared__ float4 s_rows[FINISH_BLOCK / 64][64 * 5];
-    float4* const rows = s_rows[threadIdx.x >> 6];
-    const uint32_t lane = threadIdx.x & 63, g0 = (blockIdx.x * blockDim.x + threadIdx.x) - lane;
-    float4 t_rows[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { // (rows past the end: the last row again - an address clamp instead of a branch around the load)
-        const uint32_t idx = i * 64 + lane, row = min(g0 + (idx >> 2), N - 1u);
-        t_rows[i] = *reinterpret_cast<const float4*>(at(acc, (row << 6) + ((idx & 3u) << 4)));
-    }
-    float mu_a[3], sc[3], vd[3] = {0.f, 0.f, 0.f};
-    ld3o(means, mu_a); ld3o(scales, sc);
-    if (ADAM || v_dirs != nullptr) ld3o(v_dirs, vd);   // (gradient-tensor form: nullable - the SH backward then adds dL/d(dirs) onto g_means afterwards)
-    const float4 q = ld4o(quats), rq = ld4o(raw_quats);
-    const float o = ld1o(opacities);
-    float m0[3] = {0.f, 0.f, 0.f}, v0[3] = {0.f, 0.f, 0.f}, p1[3] = {0.f, 0.f, 0.f}, m1[3] = {0.f, 0.f, 0.f}, v1[3] = {0.f, 0.f, 0.f};
-    float4 mq = make_float4(0.f, 0.f, 0.f, 0.f), vq4 = mq;
-    float po = 0.f, mo = 0.f, vo = 0.f;
-    if (ADAM) {
-        ld3o(ad.m[0], m0); ld3o(ad.v[0], v0); ld3o(raw_scales, p1); ld3o(ad.m[1], m1); ld3o(ad.v[1], v1);
-        mq = ld4o(ad.m[2]); vq4 = ld4o(ad.v[2]);
-        po = ld1o(raw_opacities); mo = ld1o(ad.m[3]); vo = ld1o(ad.v[3]);
-    }
-    float loss_v = 0.f;
-    if (loss_slots != nullptr && blockIdx.x == 0) loss_v = threadIdx.x < LOSS_SLOTS ? loss_slots[threadIdx.x] : 0.f;   // (LOSS_SLOTS = 256: the first four wavefronts carry the slots)
-    // ---- everything is in flight; from here on the pass only consumes (the accumulator rows were requested first and are the first to be waited for) ----
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { const uint32_t idx = i * 64 + lane; rows[(idx >> 2) * 5 + (idx & 3)] = t_rows[i]; }
-    __builtin_amdgcn_wave_barrier();
-    if (loss_slots != nullptr && blockIdx.x == 0) { // *loss = the fused MSE (a store in a fixed order: the step needs no zeroed accumulator)
-        __shared__ float wave_sum[FINISH_BLOCK / 64];
-        float v = loss_v;
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-        if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = v;
-        __syncthreads();
-        if (threadIdx.x == 0 && aborted == 0) {
-            const float total = (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
-            if (ADAM) *loss = total; else if (total != 0.f) unsafeAtomicAdd(loss, total);
-        }
-    }
-    if (!live || aborted != 0) return; // (aborted: uniform) speculative step that did not fit its buffers: no update, the host runs it again
-    float vm[3] = {0.f, 0.f, 0.f}, vq[4] = {0.f, 0.f, 0.f, 0.f}, vs[3] = {0.f, 0.f, 0.f};
-    const float4* a4 = rows + lane * 5;
-    const float4 a0 = a4[0], a1 = a4[1], a2 = a4[2], a3 = a4[3];
-    const float A[9] = {a0.x * REC_UNSCALE, a0.y * REC_UNSCALE, a0.z * REC_UNSCALE, a0.w * REC_UNSCALE, a1.x * REC_UNSCALE, a1.y * REC_UNSCALE, a1.z * REC_UNSCALE,
-                        a1.w * REC_UNSCALE, a2.x * REC_UNSCALE};
-    const f3 G{-a2.y * REC_UNSCALE, -a2.z * REC_UNSCALE, -a2.w * REC_UNSCALE};
-    bool any = G.x != 0.f || G.y != 0.f || G.z != 0.f;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) any |= A[k] != 0.f;
-    const f3 mu{mu_a[0], mu_a[1], mu_a[2]};
-    auto st3a = [&](float* base, const float (&src)[3]) { V3f t; t.a[0] = src[0]; t.a[1] = src[1]; t.a[2] = src[2]; *reinterpret_cast<V3f*>(const_cast<char*>(at(base, o12))) = t; };
-    auto ld3a = [&](const float* base, float (&dst)[3]) { ld3o(base, dst); };
-    const float v_opac = a3.x != 0.f ? a3.x / o : 0.f;
-#else   // LFS_EMULATE: the emulator switches lanes only at cross-lane operations, so it has no wave-private LDS hand-over - the same pass with plain per-lane loads
-    if (ADAM && abort_flag != nullptr && *abort_flag != 0) return; // (uniform) speculative step that did not fit its buffers: no update, the host runs it again
-    if (loss_slots != nullptr && blockIdx.x == 0) { // *loss = the fused MSE (a store in a fixed order: the step needs no zeroed accumulator)
-        __shared__ float wave_sum[FINISH_BLOCK / 64];
-        float v = threadIdx.x < LOSS_SLOTS ? loss_slots[threadIdx.x] : 0.f;   // (LOSS_SLOTS = 256: the first four wavefronts carry the slots whatever the block size)
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-        if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = v;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const float total = (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
-            if (ADAM) *loss = total; else if (total != 0.f) unsafeAtomicAdd(loss, total);
-        }
-    }
-    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= N) return;
-    float vm[3] = {0.f, 0.f, 0.f}, vq[4] = {0.f, 0.f, 0.f, 0.f}, vs[3] = {0.f, 0.f, 0.f};
-    const float4* a4 = reinterpret_cast<const float4*>(acc + size_t(gid) * ACC_STRIDE);
-    const float4 a0 = a4[0], a1 = a4[1], a2 = a4[2], a3 = a4[3];
-    // the row was accumulated against the scaled record (lfs_raster_common.cuh): A' = c A, G' = c G, slot 12 = opac * dL/dopac (divided where `o` is loaded)
-    const float A[9] = {a0.x * REC_UNSCALE, a0.y * REC_UNSCALE, a0.z * REC_UNSCALE, a0.w * REC_UNSCALE, a1.x * REC_UNSCALE, a1.y * REC_UNSCALE, a1.z * REC_UNSCALE,
-                        a1.w * REC_UNSCALE, a2.x * REC_UNSCALE};
-    const f3 G{-a2.y * REC_UNSCALE, -a2.z * REC_UNSCALE, -a2.w * REC_UNSCALE};
-    bool any = G.x != 0.f || G.y != 0.f || G.z != 0.f;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) any |= A[k] != 0.f;
-    // (lfs_math.cuh ld3 / st3: three floats as one 12-byte access)
-    auto ld3a = [&](const float* base, float (&dst)[3]) { const f3 t = ld3(base, gid); dst[0] = t.x; dst[1] = t.y; dst[2] = t.z; };
-    auto st3a = [&](float* base, const float (&src)[3]) { st3(base, gid, f3{src[0], src[1], src[2]}); };
-    float sc[3], vd[3] = {0.f, 0.f, 0.f};
-    const f3 mu = ld3(means, gid);
-    ld3a(scales, sc);
-    if (ADAM || v_dirs != nullptr) ld3a(v_dirs, vd);   // (gradient-tensor form: nullable - the SH backward then adds dL/d(dirs) onto g_means afterwards)
-    // Every operand of the pass is requested HERE, before any arithmetic (round 3): the kernel used to fetch in three dependent phases (rows -> quaternion
-    // inside `if (any)` -> moments), which left each wavefront with 3 - 7 loads in flight and the kernel at 3.5 TB/s. The geometry vjp below now runs for
-    // every Gaussian and is SELECTED by `any` (un-touched Gaussians keep exact zeros; their 1/scale may be inf), so no load hides behind a branch.
-    const float4 q = reinterpret_cast<const float4*>(quats)[gid];
-    const float4 rq = reinterpret_cast<const float4*>(raw_quats)[gid];
-    const float o = opacities[gid];
-    const float v_opac = a3.x != 0.f ? a3.x / o : 0.f;
-    float m0[3] = {0.f, 0.f, 0.f}, v0[3] = {0.f, 0.f, 0.f}, p1[3] = {0.f, 0.f, 0.f}, m1[3] = {0.f, 0.f, 0.f}, v1[3] = {0.f, 0.f, 0.f};
-    float4 mq = make_float4(0.f, 0.f, 0.f, 0.f), vq4 = mq;
-    float po = 0.f, mo = 0.f, vo = 0.f;
-    if (ADAM) {
-        ld3a(ad.m[0], m0); ld3a(ad.v[0], v0); ld3a(raw_scales, p1); ld3a(ad.m[1], m1); ld3a(ad.v[1], v1);
-        mq = reinterpret_cast<const float4*>(ad.m[2])[gid]; vq4 = reinterpret_cast<const float4*>(ad.v[2])[gid];
-        po = raw_opacities[gid]; mo = ad.m[3][gid]; vo = ad.v[3][gid];
-    }
-#endif // LFS_EMULATE
-    { // exactly raster_finish_kernel<true> for C == 1 (selected by `any` at the end)
-        const float is[3] = {1.f / sc[0], 1.f / sc[1], 1.f / sc[2]};
-        finish_geometry<true>(q, is, A, G, mu, cams[0], vm, vq, vs);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { vm[k] = any ? vm[k] : 0.f; vs[k] = any ? vs[k] : 0.f; }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) vq[k] = any ? vq[k] : 0.f;
-    }
-    {
-#pragma clang fp contract(off)
-        // + dL/d(dirs) of the SH backward (sh.hip adds it onto the rasterizer's dL/dmeans in the separate path)
-        float gm[3] = {vm[0] + vd[0], vm[1] + vd[1], vm[2] + vd[2]};
-        // activations_bwd_kernel<false> (l2_fused.hip)
-        const float nrm = sqrtf(rq.x * rq.x + rq.y * rq.y + rq.z * rq.z + rq.w * rq.w);
-        float gq[4];
-        if (nrm > 1e-12f) {
-            const float inv = 1.f / nrm;
-            const float y[4] = {rq.x * inv, rq.y * inv, rq.z * inv, rq.w * inv};
-            const float d = vq[0] * y[0] + vq[1] * y[1] + vq[2] * y[2] + vq[3] * y[3];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) gq[k] = (vq[k] - d * y[k]) * inv;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) gq[k] = vq[k] * 1e12f;
-        }
-        float gs[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) gs[k] = (vs[k] + ad.scale_reg) * sc[k];
-        const float go = (v_opac + ad.opacity_reg) * o * (1.f - o);
-        if (!ADAM) { // gradient tensors out (activations_bwd_kernel's stores; dL/dmeans = the rasterizer's part, the SH backward adds the rest)
-            const float v_col[3] = {a3.y, a3.z, a3.w};
-            if (gr.v_colors != nullptr) st3a(gr.v_colors, v_col);
-            float4* gqo = reinterpret_cast<float4*>(gr.g_quats) + gid;
-            if (gr.accumulate) {
-                float om[3], os[3];
-                ld3a(gr.g_means, om); ld3a(gr.g_scales, os);
-                const float4 oq = *gqo;
-#pragma unroll
-                for (int k2 = 0; k2 < 3; ++k2) { gm[k2] = om[k2] + gm[k2]; gs[k2] = os[k2] + gs[k2]; }
-                gq[0] = oq.x + gq[0]; gq[1] = oq.y + gq[1]; gq[2] = oq.z + gq[2]; gq[3] = oq.w + gq[3];
-                st3a(gr.g_means, gm); st3a(gr.g_scales, gs);
-                *gqo = make_float4(gq[0], gq[1], gq[2], gq[3]);
-                gr.g_opac[gid] += go;
-            } else {
-                st3a(gr.g_means, gm); st3a(gr.g_scales, gs);
-                *gqo = make_float4(gq[0], gq[1], gq[2], gq[3]);
-                gr.g_opac[gid] = go;
-            }
-            return;
-        }
-        // Adam (adam_multi_kernel's per-element update). Every moment is loaded before the first store (the moment arrays hang off a struct: no
-        // __restrict__, a load could not move above an earlier store) and three-float rows move as 12-byte accesses (lfs_math.cuh). Measured on
-        // one box against the element-by-element version: no difference (0.094 - 0.104 ms either way; the kernel walks 29 streams)
-        float p[3] = {mu.x, mu.y, mu.z};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            adam_elem(p[k], m0[k], v0[k], gm[k], ad.s[0]);
-            adam_elem(p1[k], m1[k], v1[k], gs[k], ad.s[1]);
-        }
-        float pq[4] = {rq.x, rq.y, rq.z, rq.w};
-        adam_elem(pq[0], mq.x, vq4.x, gq[0], ad.s[2]); adam_elem(pq[1], mq.y, vq4.y, gq[1], ad.s[2]);
-        adam_elem(pq[2], mq.z, vq4.z, gq[2], ad.s[2]); adam_elem(pq[3], mq.w, vq4.w, gq[3], ad.s[2]);
-        adam_elem(po, mo, vo, go, ad.s[3]);
-        st3a(means, p); st3a(ad.m[0], m0); st3a(ad.v[0], v0);
-        st3a(raw_scales, p1); st3a(ad.m[1], m1); st3a(ad.v[1], v1);
-        reinterpret_cast<float4*>(raw_quats)[gid] = make_float4(pq[0], pq[1], pq[2], pq[3]);
-        reinterpret_cast<float4*>(ad.m[2])[gid] = mq; reinterpret_cast<float4*>(ad.v[2])[gid] = vq4;
-        raw_opacities[gid] = po; ad.m[3][gid] = mo; ad.v[3][gid] = vo;
-    }
+    constexpr bool DENSIFY = false;   // (the densifying form: raster_densify.hip)
+    constexpr const int32_t* radii = nullptr; constexpr float* dens = nullptr;
+#include "lfs_raster_finish_body.cuh"
 }
 
 // ---------------------------------------------------------------------------
@@ -1685,8 +1362,10 @@ static const float* loss_slots_of(const RasterWs& w, uint32_t N, const float* lo
 // that need the gradients themselves (multi-GPU all-reduce, several views per step, non-MSE losses). g.* are written or, accumulate != 0, added to;
 // v_colors [N,3] is written (the SH backward consumes it and adds dL/d(dirs) onto g.means). loss (nullable): += the fused MSE partial sums.
 int lfs::gut_finish_grads_impl(const GutParams& p, const GutActivated& act, const GutRegs& regs, const GutGrads& g, const float* v_dirs, float* loss,
-                               const Workspace& ws, hipStream_t s) {
+                               const Workspace& ws, hipStream_t s, const GutDensify* dens) {
     const uint32_t N = p.N;
+    const bool densify = dens != nullptr && dens->info != nullptr;
+    if (densify && !dens->radii) return LFS_E_INVALID;   // (before anything else: the statistic without the view's radii is refused whatever N is)
     if (N == 0) return LFS_OK;
     if (!p.means || !p.raw_quats || !act.quats || !act.scales || !act.opacities || !g.means || !g.raw_scales || !g.raw_quats || !g.raw_opacities || (!g.v_colors && !v_dirs) || !ws.base) return LFS_E_INVALID;
     RasterWs w;
@@ -1694,22 +1373,38 @@ int lfs::gut_finish_grads_impl(const GutParams& p, const GutActivated& act, cons
     FinishAdam ad;
     fill_finish_adam(ad, N, regs, nullptr);
     const FinishGrads gr{g.means, g.raw_scales, g.raw_quats, g.raw_opacities, g.v_colors, g.accumulate};
+    if (densify) {
+        return finish_densify_launch(N, p.means, p.raw_quats, act.quats, act.scales, act.opacities, w.cams, w.acc, v_dirs, ad, gr, loss_slots_of(w, N, loss), loss, dens->radii,
+                                     dens->info, s);
+    }
     lfs::ProfScope prof("finish_grads", s);
     hipLaunchKernelGGL(raster_finish_adam_kernel<false>, dim3((N + FINISH_BLOCK - 1) / FINISH_BLOCK), dim3(FINISH_BLOCK), 0, s, N, p.means, (float*)nullptr, p.raw_quats,
                        (float*)nullptr, act.quats, act.scales, act.opacities, w.cams, w.acc, v_dirs, ad, gr, loss_slots_of(w, N, loss), loss, (const int32_t*)nullptr);
     return (int)hipGetLastError();
 }
 
+// ext (nullable) with densification_info: the densifying form of the pass, which reads `radii` [N,2] of the view (LFS_E_INVALID without them, before any launch).
+// ext NULL or its pointer NULL: lfs_gut_finish_grads - the same launch, the same bits.
+extern "C" int lfs_gut_finish_grads_ex(
+    uint32_t N, const float* means, const float* raw_quats, const float* quats, const float* scales, const float* opacities, float scale_reg, float opacity_reg,
+    int accumulate, float* g_means, float* g_raw_scales, float* g_raw_quats, float* g_raw_opacities, float* v_colors, float* loss,
+    const int32_t* radii, const lfs_gut_view_ext* ext, void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
+    const GutDensify dens{radii, ext ? ext->densification_info : nullptr};
+    if (dens.info && !radii) return LFS_E_INVALID;
+    if (N != 0 && !v_colors) return LFS_E_INVALID;
+    GutParams p{};   // (read only: the kernel's gradient-tensor forms store no parameter)
+    p.N = N; p.means = const_cast<float*>(means); p.raw_quats = const_cast<float*>(raw_quats);
+    return lfs::gut_finish_grads_impl(p, GutActivated{quats, scales, opacities}, GutRegs{scale_reg, opacity_reg},
+                                      GutGrads{g_means, g_raw_scales, g_raw_quats, g_raw_opacities, v_colors, accumulate}, nullptr, loss,
+                                      Workspace{workspace, workspace_bytes}, (hipStream_t)stream, dens.info ? &dens : nullptr);
+}
+
 extern "C" int lfs_gut_finish_grads(
     uint32_t N, const float* means, const float* raw_quats, const float* quats, const float* scales, const float* opacities, float scale_reg, float opacity_reg,
     int accumulate, float* g_means, float* g_raw_scales, float* g_raw_quats, float* g_raw_opacities, float* v_colors, float* loss,
     void* workspace, size_t workspace_bytes, lfs_stream_t stream) {
-    if (N != 0 && !v_colors) return LFS_E_INVALID;
-    GutParams p{};   // (read only: the kernel's <false> form stores no parameter)
-    p.N = N; p.means = const_cast<float*>(means); p.raw_quats = const_cast<float*>(raw_quats);
-    return lfs::gut_finish_grads_impl(p, GutActivated{quats, scales, opacities}, GutRegs{scale_reg, opacity_reg},
-                                      GutGrads{g_means, g_raw_scales, g_raw_quats, g_raw_opacities, v_colors, accumulate}, nullptr, loss,
-                                      Workspace{workspace, workspace_bytes}, (hipStream_t)stream);
+    return lfs_gut_finish_grads_ex(N, means, raw_quats, quats, scales, opacities, scale_reg, opacity_reg, accumulate, g_means, g_raw_scales, g_raw_quats, g_raw_opacities,
+                                   v_colors, loss, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 int lfs::gut_finish_adam_impl(const GutParams& p, const GutActivated& act, const GutAdam& adam, const GutRegs& regs, const float* v_dirs, float* loss,

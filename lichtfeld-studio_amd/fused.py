@@ -124,11 +124,12 @@ def backward_adam_all(sh_degree: int, means, raw_quats, raw_scales, raw_opac, sh
 
 def backward_grads(means, raw_quats, quats, scales, opac, colors, bg, W: int, H: int, tile: int, viewmat, Kmat, offsets, flatten_ids, render, alpha, last_ids,
                    ws, g_means, g_scales, g_quats, g_opac, accumulate: bool, scale_reg: float, opacity_reg: float, *, target_chw=None, weight: float = 0.0,
-                   loss_acc=None, v_render=None, v_colors_out=None):
+                   loss_acc=None, v_render=None, v_colors_out=None, densification_info=None, radii=None):
     """Rasterizer backward -> gradient tensors of the raw parameters in two launches (the backward kernel, then lfs_gut_finish_grads = raster_finish +
     activations_bwd + the copy of dL/dmeans in one pass). With target_chw the clamped MSE is folded into the backward (loss_acc += it), otherwise
     v_render [1,H,W,3] is the caller's dL/d(render). g_means receives the rasterizer's part of dL/dmeans (the SH backward adds dL/d(dirs) onto it);
-    returns dL/dcolour [1,N,3]."""
+    returns dL/dcolour [1,N,3]. densification_info [2,N] with the view's radii [1,N,2] (ADC's statistic): added to by the densifying form of the finish
+    pass (lfs_gut_finish_grads_ex)."""
     from .capi import cameras_struct
     lib = load_library()
     N = means.shape[0]
@@ -148,9 +149,17 @@ def backward_grads(means, raw_quats, quats, scales, opac, colors, bg, W: int, H:
     v_colors = v_colors_out if v_colors_out is not None else torch.empty((1, N, 3), dtype=means.dtype, device=means.device)
     assert tuple(v_colors.shape) == (1, N, 3) and v_colors.is_contiguous()
     require_gpu(g_means, g_scales, g_quats, g_opac, raw_quats)
-    check(lib.lfs_gut_finish_grads(C.c_uint32(N), ptr(means), ptr(raw_quats), ptr(quats), ptr(scales), ptr(opac), C.c_float(scale_reg), C.c_float(opacity_reg),
-                                   C.c_int(int(accumulate)), ptr(g_means), ptr(g_scales), ptr(g_quats), ptr(g_opac), ptr(v_colors),
-                                   ptr(loss_acc) if target_chw is not None else None, ptr(ws), C.c_size_t(ws.numel()), stream()), "gut_finish_grads")
+    head = (C.c_uint32(N), ptr(means), ptr(raw_quats), ptr(quats), ptr(scales), ptr(opac), C.c_float(scale_reg), C.c_float(opacity_reg), C.c_int(int(accumulate)),
+            ptr(g_means), ptr(g_scales), ptr(g_quats), ptr(g_opac), ptr(v_colors), ptr(loss_acc) if target_chw is not None else None)
+    if densification_info is not None:
+        from .gut_step import ViewExt
+        require_gpu(densification_info, radii)
+        assert tuple(densification_info.shape) == (2, N) and densification_info.dtype == torch.float32 and radii.dtype == torch.int32 and radii.numel() == 2 * N
+        ext = ViewExt()
+        ext.densification_info = densification_info.data_ptr()
+        check(lib.lfs_gut_finish_grads_ex(*head, ptr(radii), C.byref(ext), ptr(ws), C.c_size_t(ws.numel()), stream()), "gut_finish_grads_ex")
+    else:
+        check(lib.lfs_gut_finish_grads(*head, ptr(ws), C.c_size_t(ws.numel()), stream()), "gut_finish_grads")
     return v_colors
 
 
@@ -217,7 +226,8 @@ def render_and_backward(camera: Camera, model: SplatModel, bg_color: Optional[to
                         grads: List[torch.Tensor], loss_acc: torch.Tensor, accumulate: bool, loss: str = "mse",
                         lambda_dssim: float = 0.2, scale_reg: float = 0.0, opacity_reg: float = 0.0, sh_exchange=None, viewmats_all=None, adam_shN: Optional[dict] = None, adam_shard: Optional[dict] = None, bilateral=None, image_idx: int = 0,
                         on_geometry_grads=None, adam_all: Optional[dict] = None, given: Optional[tuple] = None, defer_sh_backward: bool = False,
-                        v_colors_out: Optional[torch.Tensor] = None) -> FusedStepOutput:
+                        v_colors_out: Optional[torch.Tensor] = None, densification_info: Optional[torch.Tensor] = None,
+                        v_dirs_acc: Optional[torch.Tensor] = None) -> FusedStepOutput:
     """One view: forward, loss against `target_chw` ("mse": the rasterizer-only metric of SURVEY.md §8d; "l1_ssim": the reference's
     photometric loss, trainer.cpp:115-128), backward. `grads` = six tensors shaped like model.parameters()
     (means, sh0, shN, raw_scales, raw_quats, raw_opacities); written when accumulate is False, added to otherwise.
@@ -234,7 +244,18 @@ def render_and_backward(camera: Camera, model: SplatModel, bg_color: Optional[to
     every parameter is updated in place by the backward kernels themselves (backward_adam_all).
     `given` = (quats, scales, opacities, radii, means2d, depths, colours) of this view, computed by the caller (render_views_and_backward: projection of
     all views first, then ONE SH launch for all of them); `defer_sh_backward`: the SH backward is the caller's too - dL/dcolour comes back in the
-    output, grads[1] / grads[2] are not touched, grads[0] receives the rasterizer's part of dL/dmeans."""
+    output, grads[1] / grads[2] are not touched, grads[0] receives the rasterizer's part of dL/dmeans.
+    `densification_info` [2,N] (ADC's statistic of the 3DGUT route): visibility count and screen-equivalent gradient norm of this view are added to it
+    by the one-pass finish (backward_grads); ValueError with FUSE_FINISH_GRADS = False (the three-kernel A/B form has no such pass), non-contiguous gradient tensors or
+    the all-inline step (adam_all), which has no gradient-tensor finish pass.
+    `v_dirs_acc` [N,3] (several views of one step, one rank): the SH backward adds its direction term dL/d(dirs) onto this tensor instead of grads[0], which then holds
+    the sum of the rasterizer parts alone; the caller zeroes it before the first view and adds it onto grads[0] after the last - dL/dmeans = (v_0 + v_1 + ..) +
+    (d_0 + d_1 + ..), the association of the batched form (render_views_and_backward), bit for bit."""
+    if v_dirs_acc is not None and (sh_exchange is not None or adam_all is not None or defer_sh_backward):
+        raise ValueError("v_dirs_acc: the replicated gradient-tensor step whose SH backward runs here")
+    if densification_info is not None and (not FUSE_FINISH_GRADS or adam_all is not None or not all(g.is_contiguous() for g in (grads[0], grads[3], grads[4], grads[5]))):
+        raise ValueError("densification_info comes from the one-pass finish (lfs_gut_finish_grads_ex): it needs FUSE_FINISH_GRADS, contiguous gradient tensors and a "
+                         "gradient-tensor step (no adam_all)")
     assert camera.camera_model_type == CameraModelType.PINHOLE and camera.radial_distortion is None and camera.tangential_distortion is None, \
         "the fused path covers the trainer's undistorted pinhole cameras; use rasterizer.rasterize for the rest"
     W, H = int(camera.image_width), int(camera.image_height)
@@ -313,7 +334,7 @@ def render_and_backward(camera: Camera, model: SplatModel, bg_color: Optional[to
             v_colors = backward_grads(means, raw_quats, quats, scales, opac, colors.unsqueeze(0), bg, W, H, tile, viewmat, Kmat, offsets, flatten_ids, render, alpha,
                                       last_ids, ws, g_means, g_scales, g_quats, g_opac, accumulate, scale_reg, opacity_reg,
                                       target_chw=target_chw if fuse_mse else None, weight=weight, loss_acc=loss_acc, v_render=None if fuse_mse else v_render,
-                                      v_colors_out=v_colors_out)
+                                      v_colors_out=v_colors_out, densification_info=densification_info, radii=radii)
             sh_means = g_means          # the SH backward adds dL/d(dirs) straight onto the caller's dL/dmeans
         else:
             if fuse_mse:
@@ -326,6 +347,12 @@ def render_and_backward(camera: Camera, model: SplatModel, bg_color: Optional[to
             # the regularisers of trainer.cpp:132-158 are per step, not per view: the caller passes them with the first view only
             activations_bwd(raw_quats, scales, opac, v_quats, v_scales, v_opac.squeeze(0), g_quats, g_scales, g_opac, accumulate, scale_reg, opacity_reg)
             sh_means = v_means
+            if densification_info is not None:   # (a view without a single intersection: no accumulator rows, every gradient norm is 0 - what is left is the count)
+                densification_info[0] += (radii[0] > 0).all(-1)
+        if v_dirs_acc is not None:
+            if not fused_finish:
+                raise ValueError("v_dirs_acc needs the one-pass finish (FUSE_FINISH_GRADS, contiguous gradient tensors, a view with intersections)")
+            sh_means = v_dirs_acc
         if on_geometry_grads is not None:
             on_geometry_grads()
         if defer_sh_backward:
@@ -361,14 +388,16 @@ def render_and_backward(camera: Camera, model: SplatModel, bg_color: Optional[to
 
 def render_views_and_backward(cameras: List[Camera], model: SplatModel, bg_color: Optional[torch.Tensor], targets: List[torch.Tensor], weight: float,
                               grads: List[torch.Tensor], loss_acc: torch.Tensor, loss: str = "mse", lambda_dssim: float = 0.2, scale_reg: float = 0.0,
-                              opacity_reg: float = 0.0, adam_shN: Optional[dict] = None, bilateral=None, image_idxs: Optional[List[int]] = None) -> List[FusedStepOutput]:
+                              opacity_reg: float = 0.0, adam_shN: Optional[dict] = None, bilateral=None, image_idxs: Optional[List[int]] = None,
+                              densification_info: Optional[torch.Tensor] = None) -> List[FusedStepOutput]:
     """Several views of ONE step on one rank (BASELINE config 4: 8 views per GPU and step): what render_and_backward does view by view, with the
     spherical-harmonics stages batched over the views - the projections of all views first, ONE launch for the colours of all views
     (lfs_sh_model_fwd_views: a Gaussian's coefficient row is read once, not once per view), the rasterizer forward / loss / backward view by view, then
     ONE SH backward over all views (lfs_sh_model_bwd_views) that sums basis x dL/dcolour over the views in registers - the 180 B / Gaussian shN
     gradient is written once instead of read-modify-written per view, or, with `adam_shN` (FusedAdam.prepare_inline), not at all: the kernel applies
     shN's Adam update on the spot. Same arithmetic per (view, Gaussian) as the view-by-view path; the sums over the views are formed in a different
-    order (tests/test_gpu_fused.py). grads are written (not added to). The regularisers count once per step, as in render_and_backward."""
+    order (tests/test_gpu_fused.py). grads are written (not added to). The regularisers count once per step, as in render_and_backward.
+    densification_info: as render_and_backward, every view adds its own statistic."""
     V = len(cameras)
     assert V >= 1 and len(targets) == V
     means, sh0, shN, raw_scales, raw_quats, raw_opac = [p.detach() for p in model.parameters()]
@@ -400,7 +429,7 @@ def render_views_and_backward(cameras: List[Camera], model: SplatModel, bg_color
                                   scale_reg=scale_reg if k == 0 else 0.0, opacity_reg=opacity_reg if k == 0 else 0.0, bilateral=bilateral,
                                   image_idx=image_idxs[k] if image_idxs is not None else k,
                                   given=(quats, scales, opac, radii, means2d, depths, colors_all[k]) + ((isect[k],) if isect else ()), defer_sh_backward=True,
-                                  v_colors_out=v_colors_all[k:k + 1])          # dL/dcolour of the view lands in its slice: no copy
+                                  v_colors_out=v_colors_all[k:k + 1], densification_info=densification_info)          # dL/dcolour of the view lands in its slice: no copy
         out.v_colors = None
         outs.append(out)
     with torch.no_grad():

@@ -39,6 +39,10 @@ class StepOptions(C.Structure):  # lfs_gut_step_options
                 ("loss_workspace", C.c_void_p), ("loss_workspace_bytes", C.c_size_t)]
 
 
+class ViewExt(C.Structure):  # lfs_gut_view_ext
+    _fields_ = [("densification_info", C.c_void_p)]
+
+
 LOSS_KINDS = {"mse": 0, "l1_ssim": 1}
 
 
@@ -242,7 +246,8 @@ class GutStep:
                              lambda a: check(lib.lfs_gut_view_forward(C.byref(a), *self._ws_args()), "gut_view_forward"), "view", after_fit=False)
 
     def _backward_call(self, fn_name: str, params, sh_degree, W, H, viewmat, Kmat, bg, grads, accumulate, target_chw, weight, loss_acc, v_render, scale_reg, opacity_reg,
-                       adam=None, rows_out=None):
+                       adam=None, rows_out=None, densification_info=None):
+        """densification_info [2,N] (ADC's statistic, added to by the view's finish pass): the call goes to the entry's _ex form; None: the entry itself."""
         lib = load_library()
         a = self._args(params, sh_degree, W, H, viewmat, Kmat, bg, target_chw, weight, scale_reg, opacity_reg, loss_acc, adam)
         for g in grads:
@@ -250,22 +255,33 @@ class GutStep:
                 raise LfsError("gut_step: gradient tensors must be contiguous CUDA (HIP) tensors")
         gp = (C.c_void_p * 6)(*[g.data_ptr() if g.numel() else None for g in grads])
         ws, nb = C.c_void_p(self.ws.data_ptr()), C.c_size_t(self.ws.numel())
-        if fn_name == "lfs_gut_view_backward_finish":
-            check(lib.lfs_gut_view_backward_finish(C.byref(a), C.c_int64(self.capacity), gp, C.c_int(int(accumulate)), ws, nb, stream()), fn_name)
+        ext = ()
+        if densification_info is not None:
+            d = densification_info
+            if not d.is_cuda or not d.is_contiguous() or d.dtype != torch.float32 or tuple(d.shape) != (2, params[0].shape[0]):
+                raise LfsError("gut_step: densification_info must be a contiguous float32 CUDA (HIP) tensor [2,N]")
+            e = ViewExt()
+            e.densification_info = d.data_ptr()
+            ext, fn_name = (C.byref(e),), fn_name + "_ex"
+        if fn_name.startswith("lfs_gut_view_backward_finish"):
+            check(getattr(lib, fn_name)(C.byref(a), C.c_int64(self.capacity), gp, C.c_int(int(accumulate)), *ext, ws, nb, stream()), fn_name)
             return
         if v_render is not None:
             v_render = v_render.contiguous()
         rows = () if rows_out is None else (C.c_void_p(rows_out.data_ptr()),)   # (lfs_gut_view_backward_rows: dL/dcolour [N,3], in front of the workspace)
         check(getattr(lib, fn_name)(C.byref(a), C.c_int64(self.capacity), C.c_void_p(v_render.data_ptr()) if v_render is not None else None, gp,
-                                    C.c_int(int(accumulate)), *rows, ws, nb, stream()), fn_name)
+                                    C.c_int(int(accumulate)), *rows, *ext, ws, nb, stream()), fn_name)
 
     def view_backward(self, params: Sequence[torch.Tensor], sh_degree: int, W: int, H: int, viewmat, Kmat, bg, grads: List[torch.Tensor], accumulate: bool, *,
                       target_chw: Optional[torch.Tensor] = None, weight: float = 0.0, loss_acc: Optional[torch.Tensor] = None,
-                      v_render: Optional[torch.Tensor] = None, scale_reg: float = 0.0, opacity_reg: float = 0.0) -> None:
+                      v_render: Optional[torch.Tensor] = None, scale_reg: float = 0.0, opacity_reg: float = 0.0,
+                      densification_info: Optional[torch.Tensor] = None) -> None:
         """Backward of the view view_forward() left in the workspace, into the six gradient tensors (group order): written, or added to with `accumulate`.
-        With target_chw the clamped MSE (weight) is folded into the backward and loss_acc += it; otherwise v_render [H,W,3] is dL/d(render)."""
+        With target_chw the clamped MSE (weight) is folded into the backward and loss_acc += it; otherwise v_render [H,W,3] is dL/d(render).
+        densification_info [2,N] (ADC, strategies.DefaultStrategy): for every Gaussian visible in this view row 0 += 1 and row 1 += the screen-equivalent norm of
+        the view's own rasterizer part of dL/dmeans - by the finish pass, whatever `accumulate` is."""
         self._backward_call("lfs_gut_view_backward", params, sh_degree, W, H, viewmat, Kmat, bg, grads, accumulate, target_chw, weight, loss_acc, v_render,
-                            scale_reg, opacity_reg)
+                            scale_reg, opacity_reg, densification_info=densification_info)
 
     def view_backward_sh(self, params, sh_degree, W, H, viewmat, Kmat, bg, grads, accumulate, *, target_chw=None, weight=0.0, loss_acc=None, v_render=None,
                          adam_shN: Optional[dict] = None) -> None:
@@ -275,18 +291,20 @@ class GutStep:
                             adam=None if adam_shN is None else {"shN": adam_shN})
 
     def view_backward_rows(self, params, sh_degree, W, H, viewmat, Kmat, bg, grads, accumulate, rows_out: torch.Tensor, *, target_chw=None, weight=0.0, loss_acc=None,
-                           v_render=None, scale_reg: float = 0.0, opacity_reg: float = 0.0) -> None:
+                           v_render=None, scale_reg: float = 0.0, opacity_reg: float = 0.0, densification_info: Optional[torch.Tensor] = None) -> None:
         """The view's backward for the factored gradient exchange (dist.ColorGradExchange): grads[0] (means, without the SH direction term), grads[3..5] written / added
-        to, dL/dcolour -> rows_out [N,3], masked with the clamp of the SH colours (colour > 0) - what the multi-view SH backward of every rank takes as it is."""
+        to, dL/dcolour -> rows_out [N,3], masked with the clamp of the SH colours (colour > 0) - what the multi-view SH backward of every rank takes as it is.
+        densification_info: as view_backward."""
         if not rows_out.is_cuda or not rows_out.is_contiguous() or rows_out.numel() != 3 * params[0].shape[0]:
             raise LfsError("gut_step: rows_out must be a contiguous CUDA (HIP) tensor [N,3]")
         self._backward_call("lfs_gut_view_backward_rows", params, sh_degree, W, H, viewmat, Kmat, bg, grads, accumulate, target_chw, weight, loss_acc, v_render,
-                            scale_reg, opacity_reg, rows_out=rows_out)
+                            scale_reg, opacity_reg, rows_out=rows_out, densification_info=densification_info)
         N = params[0].shape[0]
         rows_out.view(N, 3).mul_(self.view("colors", torch.float32, (N, 3)) > 0)   # clamp_min backward of rasterizer.cpp:262 (colours of invisible Gaussians: rows are 0 anyway)
 
     def view_backward_finish(self, params, sh_degree, W, H, viewmat, Kmat, bg, grads, accumulate, *, target_chw=None, weight=0.0, loss_acc=None,
-                             scale_reg: float = 0.0, opacity_reg: float = 0.0) -> None:
-        """Second half: accumulator rows + dL/d(dirs) -> grads[0], grads[3..5]; loss_acc += the fused MSE of the first half (when target_chw was given)."""
+                             scale_reg: float = 0.0, opacity_reg: float = 0.0, densification_info: Optional[torch.Tensor] = None) -> None:
+        """Second half: accumulator rows + dL/d(dirs) -> grads[0], grads[3..5]; loss_acc += the fused MSE of the first half (when target_chw was given).
+        densification_info: as view_backward (the SH direction term this half adds to grads[0] does not enter it)."""
         self._backward_call("lfs_gut_view_backward_finish", params, sh_degree, W, H, viewmat, Kmat, bg, grads, accumulate, target_chw, weight, loss_acc, None,
-                            scale_reg, opacity_reg)
+                            scale_reg, opacity_reg, densification_info=densification_info)

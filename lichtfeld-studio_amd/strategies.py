@@ -10,8 +10,10 @@ Differences from the reference, all about data parallelism (the reference is sin
   * parameters are replaced through `SplatModel` + `FusedAdam.replace_param`, and the trainer is told (`on_resize`) to
     rebuild its flat gradient bucket.
 `DefaultStrategy` needs `densification_info` [2,N] (visibility count, accumulated screen-space gradient norm): in the reference
-it is produced by the fastgs rasterizer's backward (kernels_backward.cuh:233-236, SURVEY.md §8f row 1, not built yet); here it
-is an input of `grow_gs` so the state surgery is testable on its own.
+it is produced by the fastgs rasterizer's backward only (kernels_backward.cuh:233-236; under --gut nothing fills it and ADC never
+densifies). Here two producers fill it: the fastgs backward (fastgs.py) and, on the 3DGUT route, the densifying finish pass of the
+fused gradient-tensor steps (gut_step.py / fused.py `densification_info=`: the screen-equivalent norm of the view's dL/dmean,
+DESIGN.md 8k). It is an input of `grow_gs`, so the state surgery is testable on its own.
 """
 from __future__ import annotations
 

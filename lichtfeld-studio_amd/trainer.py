@@ -142,7 +142,8 @@ class GutTrainer:
             raise ValueError("filter3d is not wired into the 3DGUT route (rasterizer='gut'): its step forms render the unfiltered scales and opacities. "
                              "Use rasterizer='fastgs'.")
         if absgrad and rasterizer == "gut":
-            raise ValueError("absgrad is not wired into the 3DGUT route (rasterizer='gut'): its backward has no densification_info. Use rasterizer='fastgs'.")
+            raise ValueError("absgrad is not wired into the 3DGUT route (rasterizer='gut'): its densification_info comes from the finish pass, the per-pixel absolute "
+                             "sums would have to come from the rasterizer backward itself. Use rasterizer='fastgs'.")
         if absgrad and strategy != "default":
             raise ValueError("absgrad changes what ADC reads from densification_info: it needs strategy='default'")
         self.absgrad = bool(absgrad)
@@ -204,12 +205,16 @@ class GutTrainer:
         self.strategy_kind = strategy
         self._resize_suspended, self._resize_pending = False, False
         self.batch_views = True          # one rank, several views per step: SH forward / backward once over all views (False: view by view, A/B and tests)
-        self.densification_info = None   # [2,N]: fastgs backward's (visibility count, screen-space gradient norm) for ADC
+        # [2,N] for ADC: (visibility count, screen-space gradient norm) - from the fastgs backward (kernels_backward.cuh:233-236), or, on the 3DGUT route, the
+        # screen-equivalent norm from the densifying finish pass of the fused step forms (the reference's --gut leaves it unfilled and never densifies)
+        self.densification_info = None
+        self._dens_step = None           # the fused 3DGUT step in flight: the tensor its views add to (None: no ADC, or past stop_refine)
         self.scale_reg = self.opacity_reg = 0.0
-        if strategy == "default" and rasterizer != "fastgs":
-            # ADC reads densification_info (per-Gaussian visibility counts and screen-space gradient norms), which only the fastgs backward
-            # produces (kernels_backward.cuh:233-236); on the 3DGUT path grow / prune would silently never run. The reference pairs --gut with MCMC.
-            raise ValueError("strategy='default' (ADC) needs rasterizer='fastgs': the 3DGUT backward has no densification_info")
+        if strategy == "default" and rasterizer != "fastgs" and not fused_l2:
+            # the statistic is computed by the finish pass of the fused gradient-tensor step forms; torch autograd over the op-by-op mirror (fused_l2=False) has no such
+            # pass, and grow / prune would silently never run
+            raise ValueError("strategy='default' (ADC) with rasterizer='gut' needs the fused step (fused_l2=True): densification_info comes from its finish pass, "
+                             "which the autograd form does not have. Use fused_l2=True or rasterizer='fastgs'.")
         if strategy is not None:
             from . import strategies
             op = opt_params or strategies.OptimizationParameters.for_strategy(strategy, iterations=iterations, **({"absgrad": True} if self.absgrad else {}))
@@ -614,6 +619,9 @@ class GutTrainer:
             return self._step_autograd(targets, views, total_views)
         if not plan.inline_all:
             self.loss_acc.zero_()   # (the all-inline step stores the loss: no fill launch)
+        self._dens_step = self._densification_target()
+        if self._dens_step is not None and (plan.path == "cxx_all" or plan.inline_all or plan.inline_shard):
+            raise ValueError(f"ADC on the 3DGUT route needs a gradient-tensor step form, plan_step chose {plan.path}")   # (plan_step keeps strategy='default' out of them)
         if plan.path == "cxx_all":
             self._step_cxx_all(plan, targets, views, total_views)
         elif plan.path == "cxx_views":
@@ -625,6 +633,16 @@ class GutTrainer:
         else:
             self._step_py_views(plan, targets, views, total_views)
         return self._finish_fused_step(plan)
+
+    def _densification_target(self) -> Optional[torch.Tensor]:
+        """ADC on the 3DGUT route: the [2,N] tensor this step's views add their statistic to, (re-)allocated zeroed at the current N as _train_step_fastgs does
+        (default_strategy.cpp:312-314); None without ADC and from stop_refine on."""
+        if self.strategy is None or self.strategy_kind != "default" or self._past_base() or self.iteration >= self.strategy.params.stop_refine:
+            return None
+        N = self.model.means.shape[0]
+        if self.densification_info is None or self.densification_info.shape[1] != N:
+            self.densification_info = torch.zeros((2, N), device=self.device)
+        return self.densification_info
 
     def _cxx_supported(self) -> bool:
         """Shapes the speculative C++ step does not take (more than 512 tile rows, the index-bit limit, debug bit 5: csrc/intersect.hip would return
@@ -731,7 +749,7 @@ class GutTrainer:
                 self.bucket.all_reduce_early([2], chunks=4)
             gs.view_backward_finish(ps, deg, sc.width, sc.height, vm, Km, self.bg, self.bucket.views, k > 0, target_chw=fold, weight=weight,
                                     loss_acc=self.loss_acc, scale_reg=self.scale_reg / self.world if k == 0 else 0.0,
-                                    opacity_reg=self.opacity_reg / self.world if k == 0 else 0.0)
+                                    opacity_reg=self.opacity_reg / self.world if k == 0 else 0.0, densification_info=self._dens_step)
         self._last_radii = gs.view("radii", torch.int32, (1, N, 2))
 
     def _step_cxx_factored(self, plan, targets, views, total_views) -> None:
@@ -754,7 +772,7 @@ class GutTrainer:
             v_render, fold = self._view_loss(gs, v, tgt, weight, self._mask_of(k))
             gs.view_backward_rows(ps, deg, sc.width, sc.height, vm, Km, self.bg, self.bucket.views, k > 0, ex.send[k], target_chw=fold, weight=weight,
                                   loss_acc=self.loss_acc, v_render=v_render, scale_reg=self.scale_reg / self.world if k == 0 else 0.0,
-                                  opacity_reg=self.opacity_reg / self.world if k == 0 else 0.0)
+                                  opacity_reg=self.opacity_reg / self.world if k == 0 else 0.0, densification_info=self._dens_step)
         self._last_radii = gs.view("radii", torch.int32, (1, N, 2))
         # Round 6: the all-gather goes FIRST. Collectives of one communicator execute in issue order on RCCL's stream; the multi-view SH backward below waits for the
         # gathered rows and for nothing else, the 11-float all-reduce is only needed by the optimizer afterwards - issued second it travels UNDER the SH backward
@@ -781,7 +799,7 @@ class GutTrainer:
         outs = render_views_and_backward([self.camera(v) for v in views], self.model, self.bg, [targets[k % len(targets)] for k in range(len(views))],
                                          1.0 / total_views, self.bucket.views, self.loss_acc, loss=self.loss_kind, lambda_dssim=self.lambda_dssim,
                                          scale_reg=self.scale_reg, opacity_reg=self.opacity_reg, adam_shN=inline_v, bilateral=self.bilateral,
-                                         image_idxs=list(views))
+                                         image_idxs=list(views), densification_info=self._dens_step)
         self.last_n_isects, self._last_radii = outs[-1].n_isects, outs[-1].radii
 
     def _step_py_views(self, plan, targets, views, total_views) -> None:
@@ -796,6 +814,11 @@ class GutTrainer:
         every = None
         if self.sh_exchange is not None:  # what every rank renders at sub-step k (the owners evaluate SH for all of them)
             every = self._views_all or [lfs_dist.views_for_step(self.iteration - 1, j, self.world, self.scene.viewmats.shape[0], len(views)) for j in range(self.world)]
+        # ADC, several views on one rank: the SH direction terms of dL/dmeans are summed apart from the rasterizer parts and added once, as the batched form adds them -
+        # the two single-rank forms then take the same refinement decisions from bit-equal parameters (tests/test_gpu_gut_densify.py)
+        dirs = None
+        if self._dens_step is not None and len(views) > 1 and self.sh_exchange is None and self.world == 1:
+            dirs = torch.zeros_like(self.bucket.views[0])
         for k, v in enumerate(views):
             vm_all = None if every is None else [self.scene.viewmats[e[k]:e[k] + 1].contiguous() for e in every]
             out = render_and_backward(self.camera(v), self.model, self.bg, targets[k % len(targets)], 1.0 / total_views,
@@ -804,11 +827,13 @@ class GutTrainer:
                                       scale_reg=self.scale_reg / self.world if k == 0 else 0.0,
                                       opacity_reg=self.opacity_reg / self.world if k == 0 else 0.0,
                                       sh_exchange=self.sh_exchange, viewmats_all=vm_all, adam_shN=inline, adam_shard=inline_shard, adam_all=inline_all,
-                                      bilateral=self.bilateral, image_idx=v,
+                                      bilateral=self.bilateral, image_idx=v, densification_info=self._dens_step, v_dirs_acc=dirs,
                                       # last view: scales / quats / opacities gradients are final before the SH backward starts - their all-reduce overlaps with it
                                       # (the ADMM term goes into the opacity gradient before it leaves)
                                       on_geometry_grads=(lambda: (self._add_sparsity_term(), self.bucket.all_reduce_early([3, 4, 5]))) if (self.world > 1 and k == len(views) - 1) else None)
             self.last_n_isects, self._last_radii = out.n_isects, out.radii
+        if dirs is not None:
+            self.bucket.views[0].add_(dirs)
 
     def _finish_fused_step(self, plan):
         """What follows the backward of every fused step form: all-reduce of the flat bucket, the bilateral grid's own optimizer, strategy / optimizer step."""
@@ -826,6 +851,11 @@ class GutTrainer:
                 pass
             elif plan.path == "cxx_all":   # (one_call: the noise went into the tail - what is left of post_backward is the SH schedule)
                 self.strategy.post_backward_schedule(self.iteration)
+            elif self.strategy_kind == "default":   # ADC fed by the finish pass's statistic, as _train_step_fastgs feeds it from the fastgs backward
+                dens, self._dens_step = self._dens_step, None
+                if dens is not None and plan.multi and self.strategy.is_refining(self.iteration):
+                    lfs_dist.all_reduce_sum(dens)   # replicas must take the same densification decisions
+                self.densification_info = self.strategy.post_backward(self.iteration, dens)
             elif self.sh_exchange is not None and self.strategy.is_refining(self.iteration):
                 self._refine_with_full_shN(lambda: self.strategy.post_backward(self.iteration))
             else:
