@@ -723,6 +723,26 @@ typedef struct lfs_adam_tensor {
 #define LFS_ADAM_MAX_TENSORS 8
 LFS_API int lfs_adam_step_multi(const lfs_adam_tensor* tensors /* host array */, int32_t n_tensors, lfs_stream_t stream);
 
+/* ---- Visible-only Adam (extension; csrc/adam_visible.hip): gsplat's SelectiveAdam / the official 3DGS code's sparse_adam. A step has a
+ *      visibility set V of Gaussians, given as bits: bit i of a uint32 array of lfs_visibility_words(N) = ceil(N / 32) words, bits >= N zero.
+ *        i in V:     the rows of i get exactly lfs_adam_step's update - the same bits, with the scalars of the tensor's entry (the caller computes the bias
+ *                    corrections from its global step count, as for lfs_adam_step_multi).
+ *        i not in V: param, exp_avg and exp_avg_sq of its rows are neither read nor written and grad is not read - a NaN in such a gradient row has no effect -
+ *                    except where a 16-byte access of a narrow row straddles into a visible neighbour's row (those elements are stored back as loaded).
+ *      Consequence: a gradient term that reaches every Gaussian (a regulariser) does not move the Gaussians outside V.
+ *   lfs_fastgs_view_visibility: bit i = (n_touched[i] != 0) of the view's primitive workspace as lfs_fastgs_view_preprocess left it - the predicate under which
+ *      lfs_fastgs_view_backward adds 1 to densification_info[0][i]. Reads N, width, height and the workspace of the view. accumulate != 0: ORed into bits (the
+ *      union over a step's views); 0: bits is overwritten, bits >= N of the last word with 0. One lane per Gaussian, one ballot per wave, each wave stores its own
+ *      two words: no atomics, no host read. N == 0: LFS_OK, nothing launched. LFS_E_INVALID before any launch: NULL view / primitive workspace / bits, a zero image
+ *      size; LFS_E_WORKSPACE: a workspace shorter than lfs_fastgs_primitive_workspace_bytes.
+ *   lfs_adam_step_multi_visible: lfs_adam_step_multi over the rows of V, ONE launch. Every tensor is [N, width] with width = n_elements / N; tensors with 0
+ *      elements are skipped. LFS_E_INVALID before any launch: n_elements % N != 0 (N == 0 with a non-empty tensor included), NULL visible_bits with N > 0, a NULL
+ *      tensor pointer, more than LFS_ADAM_MAX_TENSORS tensors. Bits at or past N are ignored. */
+LFS_API uint32_t lfs_visibility_words(uint32_t N);
+LFS_API int lfs_fastgs_view_visibility(const lfs_fastgs_view* view, uint32_t* bits, int accumulate, lfs_stream_t stream);
+LFS_API int lfs_adam_step_multi_visible(const lfs_adam_tensor* tensors /* host array */, int32_t n_tensors, const uint32_t* visible_bits, uint32_t N,
+                                        lfs_stream_t stream);
+
 /* ---- SOG export (csrc/sog.hip): Morton codes (kernels/morton_encoding.cu:21-97) and the three kernels of Lloyd's iteration (kernels/kmeans.cu:18-122).
  *      All entry points are asynchronous on `stream`, validate on the host before any launch (LFS_E_INVALID: NULL pointer, negative count, k or D of 0, a
  *      workspace that is not 16-byte aligned; LFS_E_UNSUPPORTED: k > 65536 or D > 64; LFS_E_WORKSPACE: workspace short), use no float atomics (same bits on every

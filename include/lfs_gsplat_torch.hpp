@@ -74,6 +74,18 @@ void adam_step_wrapper(torch::Tensor& param, torch::Tensor& exp_avg, torch::Tens
                        const float bias_correction2_sqrt_rcp);
 } // namespace fast_gs::optimizer
 
+// Visible-only Adam (extension; lfs_adam_step_multi_visible of lfs_gsplat.h): ONE launch updates, with adam_step's arithmetic, the rows of the
+// Gaussians whose bit is set in visible_bits (int32 [ceil(N / 32)], bit i of word i / 32; bits >= N zero) and neither reads nor writes the rows of the others -
+// parameters, moments and gradients. Every tensor of a group is a contiguous float32 device tensor with leading dimension N; at most 8 groups. The caller
+// computes the bias corrections from its global step count, as for adam_step_wrapper. Launches on the current stream.
+namespace lfs {
+struct AdamVisibleGroup {
+    torch::Tensor param, exp_avg, exp_avg_sq, grad;
+    float lr, beta1, beta2, eps, bias_correction1_rcp, bias_correction2_sqrt_rcp;
+};
+void adam_step_multi_visible(std::vector<AdamVisibleGroup>& groups, const torch::Tensor& visible_bits, int64_t N);
+} // namespace lfs
+
 // The forward -> backward staging slot of the rasterizer wrappers (csrc/torch_ops.cpp; Ops.h has no argument through which a forward could hand its records and
 // per-cell lists to its backward, so the last forward's workspace is parked, keyed on the identity of its operands). Control surface (extension, not in Ops.h):
 //   torch_raster_staging_clear()     drop the parked workspace NOW - a viewer at the end of a render, a module before it is unloaded;

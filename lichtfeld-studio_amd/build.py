@@ -33,6 +33,7 @@ SOURCES = {
     "intersect.hip": ["-ffp-contract=off"],
     "mcmc.hip": ["-ffp-contract=off"],
     "adam.hip": ["-ffp-contract=off"],
+    "adam_visible.hip": ["-ffp-contract=off"],   # visible-only Adam + the visibility bits of a fastgs view: adam.hip's arithmetic and flags (same bits), its own code object
     "l2_fused.hip": ["-ffp-contract=off"],
     "ssim.hip": ["-ffp-contract=off"],
     "bilateral_grid.hip": ["-ffp-contract=off"],

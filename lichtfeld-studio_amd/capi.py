@@ -131,6 +131,7 @@ EXPORTS = [
     "lfs_depth_prepare", "lfs_depth_l1_loss_fwd_bwd",
     "lfs_fastgs_view_preprocess_ex", "lfs_fastgs_view_backward_ex", "lfs_filter3d_workspace_bytes", "lfs_filter3d_compute",
     "lfs_image_undistort_u8_to_chw_f32", "lfs_mask_undistort_prepare", "lfs_plane_undistort_nearest_f32",
+    "lfs_visibility_words", "lfs_fastgs_view_visibility", "lfs_adam_step_multi_visible",
 ]
 
 
@@ -167,7 +168,8 @@ def load_library():
         for name in ("lfs_select_kth_workspace_bytes", "lfs_admm_update_workspace_bytes", "lfs_admm_loss_grad_workspace_bytes", "lfs_admm_prune_mask_workspace_bytes"):
             getattr(lib, name).restype = C.c_size_t
         lib.lfs_version.restype = C.c_char_p
-        for name in ("lfs_fastgs_view_preprocess", "lfs_fastgs_view_render", "lfs_fastgs_view_backward", "lfs_fastgs_view_preprocess_ex", "lfs_fastgs_view_backward_ex",
+        lib.lfs_visibility_words.restype = C.c_uint32
+        for name in ("lfs_fastgs_view_visibility", "lfs_adam_step_multi_visible", "lfs_fastgs_view_preprocess","lfs_fastgs_view_render", "lfs_fastgs_view_backward", "lfs_fastgs_view_preprocess_ex", "lfs_fastgs_view_backward_ex",
                      "lfs_filter3d_compute"):
             getattr(lib, name).restype = C.c_int
         if os.environ.get("LFS_DEBUG_FLAGS"):   # measurement / debugging only (tools/*.sh): e.g. 64 = the reference's tile lists + pack + cull kernels inside the step

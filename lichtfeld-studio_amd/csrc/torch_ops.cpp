@@ -369,6 +369,30 @@ void adam_step_wrapper(torch::Tensor& param, torch::Tensor& exp_avg, torch::Tens
 }
 } // namespace fast_gs::optimizer
 
+namespace lfs {
+void adam_step_multi_visible(std::vector<AdamVisibleGroup>& groups, const torch::Tensor& visible_bits, int64_t N) {
+    if (groups.empty()) return;
+    TORCH_CHECK(groups.size() <= LFS_ADAM_MAX_TENSORS, "adam_step_multi_visible: at most ", LFS_ADAM_MAX_TENSORS, " groups per launch");
+    TORCH_CHECK(N >= 0 && N <= int64_t(UINT32_MAX), "adam_step_multi_visible: N out of range");
+    LFS_CHECK_INPUT(visible_bits);
+    TORCH_CHECK(visible_bits.scalar_type() == at::kInt && visible_bits.numel() >= (N + 31) / 32, "visible_bits must be an int32 tensor of ceil(N / 32) words");
+    LFS_DEVICE_GUARD(visible_bits);
+    lfs_adam_tensor t[LFS_ADAM_MAX_TENSORS];
+    for (size_t i = 0; i < groups.size(); ++i) {
+        AdamVisibleGroup& g = groups[i];
+        LFS_CHECK_INPUT(g.param); LFS_CHECK_INPUT(g.exp_avg); LFS_CHECK_INPUT(g.exp_avg_sq); LFS_CHECK_INPUT(g.grad);
+        TORCH_CHECK(g.param.dim() >= 1 && g.param.size(0) == N, "adam_step_multi_visible: the leading dimension of every parameter must be N");
+        TORCH_CHECK(g.exp_avg.numel() == g.param.numel() && g.exp_avg_sq.numel() == g.param.numel() && g.grad.numel() == g.param.numel(),
+                    "adam_step_multi_visible: moments and gradient must have the parameter's size");
+        t[i] = lfs_adam_tensor{g.param.data_ptr<float>(), g.exp_avg.data_ptr<float>(), g.exp_avg_sq.data_ptr<float>(), g.grad.data_ptr<float>(), g.param.numel(),
+                               g.lr, g.beta1, g.beta2, g.eps, g.bias_correction1_rcp, g.bias_correction2_sqrt_rcp};
+    }
+    check_rc(lfs_adam_step_multi_visible(t, (int32_t)groups.size(), reinterpret_cast<const uint32_t*>(visible_bits.data_ptr<int32_t>()), (uint32_t)N, cur_stream()),
+             "adam_step_multi_visible");
+    for (AdamVisibleGroup& g : groups) { bump(g.param); bump(g.exp_avg); bump(g.exp_avg_sq); }
+}
+} // namespace lfs
+
 // ---------------------------------------------------------------------------------------------------------
 // lfs::GutTrainStep: the C++ training step (csrc/gut_step.hip) for a libtorch caller
 // ---------------------------------------------------------------------------------------------------------

@@ -51,6 +51,20 @@ PYBIND11_MODULE(_lfs_torch_ops, m) {
                                           py::dict d; d["stores"] = s.stores; d["hits"] = s.hits; d["misses"] = s.misses; d["skipped_forwards"] = s.skipped_forwards; d["parked_bytes"] = s.parked_bytes; return d; });
     m.def("adam_step_wrapper", [](at::Tensor param, at::Tensor exp_avg, at::Tensor exp_avg_sq, at::Tensor grad, float lr, float b1, float b2,
                                   float eps, float bc1, float bc2) { fast_gs::optimizer::adam_step_wrapper(param, exp_avg, exp_avg_sq, grad, lr, b1, b2, eps, bc1, bc2); });
+    // lfs::adam_step_multi_visible: the groups travel as parallel lists; scalars[i] = (lr, beta1, beta2, eps, bias_correction1_rcp, bias_correction2_sqrt_rcp)
+    m.def("adam_step_multi_visible",
+          [](std::vector<at::Tensor> params, std::vector<at::Tensor> exp_avgs, std::vector<at::Tensor> exp_avg_sqs, std::vector<at::Tensor> grads,
+             std::vector<std::vector<float>> scalars, at::Tensor visible_bits, int64_t N) {
+              TORCH_CHECK(exp_avgs.size() == params.size() && exp_avg_sqs.size() == params.size() && grads.size() == params.size() && scalars.size() == params.size(),
+                          "adam_step_multi_visible: lists of different lengths");
+              std::vector<lfs::AdamVisibleGroup> groups;
+              for (size_t i = 0; i < params.size(); ++i) {
+                  TORCH_CHECK(scalars[i].size() == 6, "adam_step_multi_visible: six scalars per group");
+                  groups.push_back(lfs::AdamVisibleGroup{params[i], exp_avgs[i], exp_avg_sqs[i], grads[i], scalars[i][0], scalars[i][1], scalars[i][2], scalars[i][3],
+                                                         scalars[i][4], scalars[i][5]});
+              }
+              lfs::adam_step_multi_visible(groups, visible_bits, N);
+          });
     m.def("fastgs_forward_wrapper",
           [](at::Tensor means, at::Tensor scales_raw, at::Tensor rotations_raw, at::Tensor opacities_raw, at::Tensor sh0, at::Tensor sh_rest, at::Tensor w2c,
              at::Tensor cam_position, int active_sh_bases, int width, int height, float fx, float fy, float cx, float cy, float near_plane, float far_plane) {

@@ -254,7 +254,7 @@ def mse_loss_chw_fwd_bwd(render_chw: torch.Tensor, target_chw: torch.Tensor, wei
 def render_and_backward(settings: FastGSSettings, w2c: torch.Tensor, model: SplatModel, target_chw: torch.Tensor, weight: float, grads, loss_acc: torch.Tensor,
                         densification_info: Optional[torch.Tensor] = None, loss: str = "mse", lambda_dssim: float = 0.2, bilateral=None, image_idx: int = 0,
                         adam_shN: Optional[dict] = None, grad_w2c: Optional[torch.Tensor] = None, mask=None, mask_alpha_weight: float = 0.0,
-                        depth_target=None, depth_weight: float = 0.0):
+                        depth_target=None, depth_weight: float = 0.0, visibility_bits: Optional[torch.Tensor] = None, accumulate_visibility: bool = False):
     """One training view without an autograd graph (black background; loss "mse" or the trainer's "l1_ssim", trainer.cpp:122-125):
     forward, [bilateral-grid slice, trainer.cpp:662-664,] loss, backward; the gradients of (means, sh0, shN, raw_scales, raw_quats,
     raw_opacities) are WRITTEN into `grads` (param-group order); the bilateral grid's gradient is accumulated into its .grad;
@@ -262,7 +262,9 @@ def render_and_backward(settings: FastGSSettings, w2c: torch.Tensor, model: Spla
     mask (a losses.PreparedMask): the masked loss on `shown`; with mask_alpha_weight > 0 ("segment", l1_ssim) the opacity penalty outside the mask, whose
     gradient replaces the zero alpha gradient of the backward.
     depth_target (a losses.PreparedDepth; settings.depth "depth" | "invdepth" says what it holds): loss_acc += weight * depth_weight * the masked L1 between the
-    accumulated depth map and the target (lfs_depth_l1_loss_fwd_bwd), and the backward is the depth one. None: everything as before."""
+    accumulated depth map and the target (lfs_depth_l1_loss_fwd_bwd), and the backward is the depth one. None: everything as before.
+    visibility_bits (int32 [ceil(N / 32)], visible-only Adam): bit i is written - with accumulate_visibility ORed - from the view's n_touched column right after
+    the forward (ops.fastgs_view_visibility): set exactly where the backward counts Gaussian i as visible. None: nothing is launched."""
     means, sh0, shN, raw_scales, raw_quats, raw_opac = [p.detach() for p in model.parameters()]
     g_means, g_sh0, g_shN, g_scales, g_quats, g_opac = grads
     with torch.no_grad():
@@ -273,6 +275,9 @@ def render_and_backward(settings: FastGSSettings, w2c: torch.Tensor, model: Spla
             v_depth = depth_l1_loss_fwd_bwd(depth, depth_target, weight * depth_weight, loss_acc)
         else:
             image, alpha, pws, iws, n_inst = forward_wrapper(means, raw_scales, raw_quats, raw_opac, sh0, shN, w2c, settings)
+        if visibility_bits is not None:
+            from .ops import fastgs_view_visibility
+            fastgs_view_visibility(pws, means.shape[0], settings.width, settings.height, visibility_bits, accumulate_visibility)
         shown = image if bilateral is None else bilateral.apply_fused(image, image_idx, chw=True)
         v_alpha = None
         if mask is not None:

@@ -6,6 +6,10 @@ reciprocals computed in double on the host and cast to float (fused_adam.cpp:78-
 "skip the higher-degree SH group while iteration <= 1000" shortcut (:68-70; step_count still
 advances, :66).  `fused=True` issues ONE multi-tensor launch for all groups instead of the
 reference's one launch per tensor; the per-element arithmetic is identical.
+
+Extension, visible-only Adam (gsplat's SelectiveAdam): `set_visibility(bits, N)` makes the NEXT step() update only
+the Gaussians whose bit is set - parameters and moments of the others are neither read nor written, the step counts advance for
+every parameter as always (the bias corrections come from the global step count).
 """
 from __future__ import annotations
 
@@ -28,6 +32,15 @@ class FusedAdam:
         self.state = {}
         self.fused = fused
         self._inline_done = set()
+        self._visibility = None
+
+    def set_visibility(self, bits: torch.Tensor, N: int) -> None:
+        """The next step() - and only that one - updates the rows of the Gaussians whose bit is set in `bits` (int32 [ceil(N / 32)], bit i of word i // 32;
+        ops.fastgs_view_visibility writes them) through ONE ops.adam_step_multi_visible launch. Every parameter that step updates must have leading dimension N.
+        Gradient terms that reach every Gaussian (MCMC's scale / opacity regularisers, the ADMM penalty) do not move the Gaussians outside the set."""
+        if not self.fused:
+            raise ValueError("set_visibility needs fused=True: the visible-only update is the one multi-tensor launch (use FusedAdam(..., fused=True))")
+        self._visibility = (bits, int(N))
 
     def _state(self, p: torch.Tensor) -> dict:
         st = self.state.get(id(p))
@@ -52,6 +65,15 @@ class FusedAdam:
 
     @torch.no_grad()
     def step(self, iteration: int) -> None:
+        visibility, self._visibility = self._visibility, None   # consumed by this step, whatever it updates
+        if visibility is not None:
+            if not self.fused:
+                raise ValueError("set_visibility needs fused=True: the visible-only update is the one multi-tensor launch (use FusedAdam(..., fused=True))")
+            for group in self.param_groups:
+                for p in group["params"]:
+                    if p.dim() < 1 or p.shape[0] != visibility[1]:
+                        raise ValueError(f"set_visibility(bits, N = {visibility[1]}): a parameter of shape {tuple(p.shape)} does not have N rows "
+                                         "(visible-only Adam covers per-Gaussian parameters; keep other tensors in an optimizer of their own)")
         entries = []
         for i, group in enumerate(self.param_groups, start=1):
             lr, eps = group["lr"], group["eps"]
@@ -71,7 +93,9 @@ class FusedAdam:
                 entries.append((p, st["exp_avg"], st["exp_avg_sq"], p.grad.contiguous(), float(lr), float(beta1), float(beta2),
                                 float(eps), float(bc1_rcp), float(bc2_sqrt_rcp)))
         self._inline_done.clear()   # (ids of tensors replaced meanwhile must not linger: Python reuses ids)
-        if self.fused:
+        if visibility is not None:
+            ops.adam_step_multi_visible(entries, *visibility)
+        elif self.fused:
             ops.adam_step_multi(entries)
         else:
             for e in entries:

@@ -393,3 +393,45 @@ def adam_step_multi(entries) -> None:
         require_gpu(p, m, v, g)
         arr[i] = capi.AdamTensor(p.data_ptr(), m.data_ptr(), v.data_ptr(), g.data_ptr(), p.numel(), lr, b1, b2, eps, bc1, bc2)
     check(load_library().lfs_adam_step_multi(arr, C.c_int32(len(entries)), stream()), "adam_step_multi")
+
+
+# -----------------------------------------------------------------------------------------
+# visible-only Adam (extension; csrc/adam_visible.hip): gsplat's SelectiveAdam over visibility BITS
+# -----------------------------------------------------------------------------------------
+def visibility_words(N: int) -> int:
+    """ceil(N / 32): the int32 words of a visibility bit buffer for N Gaussians (lfs_visibility_words)."""
+    return int(load_library().lfs_visibility_words(C.c_uint32(int(N))))
+
+
+def _check_bits(bits: Tensor, N: int, what: str) -> None:
+    require_gpu(bits)
+    if bits.dtype != torch.int32 or bits.numel() < (int(N) + 31) // 32:
+        raise LfsError(f"{what}: the visibility bits must be an int32 tensor of at least ceil(N / 32) = {(int(N) + 31) // 32} words "
+                       f"(got {bits.dtype}, {bits.numel()} elements)")
+
+
+def fastgs_view_visibility(primitive_workspace: Tensor, N: int, width: int, height: int, bits: Tensor, accumulate: bool = False) -> None:
+    """bit i of `bits` (int32 [ceil(N / 32)]) = Gaussian i touched a tile of the view whose forward filled `primitive_workspace` (n_touched != 0: the predicate of
+    the backward's visibility count). accumulate: OR into bits (the union over a step's views) instead of overwriting. No host read."""
+    require_gpu(primitive_workspace)
+    _check_bits(bits, N, "fastgs_view_visibility")
+    view = capi.FastgsView()
+    view.N, view.width, view.height = int(N), int(width), int(height)
+    view.primitive_workspace, view.primitive_workspace_bytes = primitive_workspace.data_ptr(), primitive_workspace.numel()
+    check(load_library().lfs_fastgs_view_visibility(C.byref(view), ptr(bits), C.c_int(int(bool(accumulate))), stream()), "fastgs_view_visibility")
+
+
+def adam_step_multi_visible(entries, bits: Tensor, N: int) -> None:
+    """adam_step_multi for the Gaussians whose bit is set: entries as there, every tensor [N, ...]; the rows of the others - parameters, moments, gradients -
+    are neither read nor written. One launch."""
+    entries = list(entries)
+    if not entries:
+        return
+    if len(entries) > capi.ADAM_MAX_TENSORS:
+        raise LfsError("too many tensors for one adam_step_multi_visible launch")
+    _check_bits(bits, N, "adam_step_multi_visible")
+    arr = (capi.AdamTensor * len(entries))()
+    for i, (p, m, v, g, lr, b1, b2, eps, bc1, bc2) in enumerate(entries):
+        require_gpu(p, m, v, g)
+        arr[i] = capi.AdamTensor(p.data_ptr(), m.data_ptr(), v.data_ptr(), g.data_ptr(), p.numel(), lr, b1, b2, eps, bc1, bc2)
+    check(load_library().lfs_adam_step_multi_visible(arr, C.c_int32(len(entries)), ptr(bits), C.c_uint32(int(N)), stream()), "adam_step_multi_visible")

@@ -91,7 +91,7 @@ class GutTrainer:
                  sh_sharded: Optional[bool] = None, factored_sh: bool = False, one_call: bool = False, pose_optimization: str = "none", pose_lr: float = 1e-5,
                  enable_sparsity: bool = False, sparsify_steps: int = 15000, init_rho: float = 0.0005, prune_ratio: float = 0.6, sparsity_update_every: int = 50,
                  mask_mode: str = "none", mask_alpha_weight: float = 1.0, antialiasing: bool = False, depth_loss: str = "none", depth_weight=(1.0, 0.01),
-                 filter3d: bool = False, filter3d_every: int = 100, filter3d_variance: float = 0.2, absgrad: bool = False):
+                 filter3d: bool = False, filter3d_every: int = 100, filter3d_variance: float = 0.2, absgrad: bool = False, visible_adam: bool = False):
         """strategy: None (fixed set of Gaussians: the benchmark), "mcmc" (strategies.MCMC: relocation + growth + SGLD noise, with
         the scale / opacity regularisers of trainer.cpp:132-158) or "default" (ADC; needs densification_info, see strategies.py).
         `seed` seeds the strategy's generator: the same on every rank, so replicas densify identically.
@@ -121,7 +121,28 @@ class GutTrainer:
         depth_loss: "none" | "invdepth" | "depth" (DESIGN.md 8g): what train_step(depths=...) supervises - the accumulated inverse depth (the Inria trainer's
         convention: monocular depth, scale and offset fitted per image) or the accumulated depth of the view against a losses.PreparedDepth, by a masked L1 whose weight
         decays exponentially from depth_weight[0] (first iteration) to depth_weight[1] (iteration `iterations`) - the log-linear interpolation of the Inria trainer's
-        depth_l1_weight. fastgs rasterizer, one rank. With "none" (and on steps without depths) the trainer plans and computes what it always did."""
+        depth_l1_weight. fastgs rasterizer, one rank. With "none" (and on steps without depths) the trainer plans and computes what it always did.
+        visible_adam (gsplat's visible_adam / SelectiveAdam, the official code's sparse_adam): the optimizer step updates only the Gaussians that at least
+        one view of the step projected onto a tile (n_touched != 0 after the preprocess - the predicate of the backward's visibility count); parameters and Adam moments
+        of the others are neither read nor written, so they keep their values instead of drifting along a stale momentum, and the step streams 1652 B per VISIBLE
+        Gaussian. The step counts, and with them the bias corrections, stay global. Consequence: gradient terms that reach every Gaussian - MCMC's scale and opacity
+        regularisers - do not move Gaussians outside the step's views. On an iteration in which the strategy refines (rows are replaced before the optimizer runs) the
+        step is the dense one. fastgs rasterizer, one rank, without enable_sparsity and one_call. Off: the trainer plans and computes what it always did."""
+        if visible_adam:
+            if rasterizer == "gut":
+                raise ValueError("visible_adam is not wired into the 3DGUT route (rasterizer='gut'): nothing on that route produces the visibility bits yet, and its "
+                                 "fused tail applies Adam itself. Use rasterizer='fastgs'.")
+            if world > 1:
+                raise ValueError("visible_adam is implemented for one rank (world == 1): the visibility bits would need an OR-reduction across ranks. Use world=1.")
+            if enable_sparsity:
+                raise ValueError("visible_adam cannot be combined with enable_sparsity: the ADMM penalty must reach every opacity. Use visible_adam=False for a "
+                                 "sparsifying run.")
+            if one_call:
+                raise ValueError("visible_adam cannot be combined with one_call: the one-call C++ step applies Adam inside its own kernels. Use one_call=False.")
+            if not fused_adam:
+                raise ValueError("visible_adam needs fused_adam=True: the visible-only update is the one multi-tensor launch")
+        self.visible_adam = bool(visible_adam)
+        self._vis_bits = None           # int32 [ceil(N / 32)]: the union of the step's views, rebuilt when N changes
         if depth_loss not in ("none", "invdepth", "depth"):
             raise ValueError(f"Invalid depth loss: {depth_loss}")
         if depth_loss != "none":
@@ -413,8 +434,14 @@ class GutTrainer:
         inline = None   # one view on one rank, Adam reading shN: the SH backward inside lfs_fastgs_view_backward (args.adam) updates shN itself
         if (self.inline_shN_adam and self.world == 1 and len(views) == 1 and self.strategy is None and self.iteration > 1000 and self.model.shN.shape[1] > 0
                 and getattr(self.optimizer, "fused", False) and self.pose_module is None   # (the optimizer-fused backward has no camera gradient)
-                and self._depths is None):                                                   # (... and no depth gradient)
+                and self._depths is None                                                    # (... and no depth gradient)
+                and not self.visible_adam):                                                  # (... and it updates every row of shN)
             inline = self.optimizer.prepare_inline(self.model.shN)
+        vis = None
+        if self.visible_adam:
+            if self._vis_bits is None or self._vis_bits.numel() != (N + 31) // 32:
+                self._vis_bits = torch.zeros((N + 31) // 32, dtype=torch.int32, device=self.device)
+            vis = self._vis_bits
         for k, v in enumerate(views):
             dst = self.bucket.views if k == 0 else self._fg_tmp
             w2c, w2c_adj, g_w2c = self.scene.viewmats[v:v + 1].contiguous(), None, None
@@ -430,7 +457,8 @@ class GutTrainer:
             _, _, self.last_n_isects = fg_step(st, w2c, self.model, targets[k % len(targets)],
                                                1.0 / total_views, dst, self.loss_acc, densification_info=dens, loss=self.loss_kind,
                                                lambda_dssim=self.lambda_dssim, bilateral=self.bilateral, image_idx=v, adam_shN=inline, grad_w2c=g_w2c,
-                                               **self._fastgs_mask_args(k), **depth_args)
+                                               **self._fastgs_mask_args(k), **depth_args,
+                                               **({"visibility_bits": vis, "accumulate_visibility": k > 0} if vis is not None else {}))
             if w2c_adj is not None:
                 w2c_adj.backward(g_w2c)   # accumulates into the module's parameters over the views of the step
                 self.last_grad_w2c = g_w2c
@@ -462,8 +490,14 @@ class GutTrainer:
                 self.densification_info = self.strategy.post_backward(self.iteration, dens)
             else:
                 self.strategy.post_backward(self.iteration)
+            # (a refinement has replaced rows since the bits were written: that step stays the dense one; so does none at all past the strategy's step limit)
+            if (vis is not None and self.iteration < self.strategy.step_limit and self.model.means.shape[0] == N
+                    and (self._past_base() or not self.strategy.is_refining(self.iteration))):
+                self.optimizer.set_visibility(vis, N)
             self.strategy.step(self.iteration)
         else:
+            if vis is not None:
+                self.optimizer.set_visibility(vis, N)
             self.optimizer.step(self.iteration)
             self.scheduler.step()
         if self.pose_optimizer is not None:   # trainer.cpp:763-765: after the model's optimizer step

@@ -59,6 +59,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--absgrad", action="store_true", help="ADC densifies by the per-pixel ABSOLUTE screen-space gradients (AbsGS; fastgs rasterizer, --strategy default): large "
                     "Gaussians over fine texture, whose signed gradients cancel, get split. Without --grad-threshold the threshold becomes 8e-4")
     ap.add_argument("--grad-threshold", type=float, default=None, help="ADC's screen-space gradient threshold for splitting / cloning (default 2e-4; 8e-4 with --absgrad)")
+    ap.add_argument("--visible-adam", action="store_true", help="the optimizer updates only the Gaussians the step's views saw (gsplat's visible_adam, the official code's "
+                    "sparse_adam; fastgs rasterizer): the others keep parameters and Adam moments untouched, and the step streams only the visible rows")
     ap.add_argument("--depth-loss", default="none", choices=["none", "invdepth", "depth"],
                     help="depth-regularised training (fastgs rasterizer): L1 between the accumulated inverse depth (invdepth: monocular depth, the Inria convention) or depth of a view "
                          "and <data>/<depths folder>/<image stem>.npy (float32 [H,W]) or .png (16-bit greyscale, value / 65536). With --eval, every held-out render is then saved as "
@@ -88,6 +90,10 @@ def check_args(args) -> None:
         raise SystemExit("--absgrad is not wired into the 3DGUT route. Please disable absgrad or disable gut.")
     if args.absgrad and args.strategy != "default":
         raise SystemExit("--absgrad changes what ADC densifies by: it needs --strategy default.")
+    if args.visible_adam and args.gut:
+        raise SystemExit("--visible-adam is not wired into the 3DGUT route. Please disable visible-adam or disable gut.")
+    if args.visible_adam and args.enable_sparsity:
+        raise SystemExit("--visible-adam cannot be combined with --enable-sparsity: the ADMM penalty must reach every opacity.")
     if args.grad_threshold is not None and not args.grad_threshold > 0:
         raise SystemExit("--grad-threshold must be > 0")
     if args.depth_loss != "none" and args.gut:
@@ -161,7 +167,7 @@ def main():
                     enable_sparsity=args.enable_sparsity, sparsify_steps=args.sparsify_steps, init_rho=args.init_rho, prune_ratio=args.prune_ratio,
                     mask_mode=args.mask_mode, mask_alpha_weight=args.mask_alpha_weight, antialiasing=args.antialiasing,
                     depth_loss=args.depth_loss, depth_weight=(args.depth_weight_init, args.depth_weight_final),
-                    filter3d=args.filter3d, filter3d_every=args.filter3d_every, absgrad=args.absgrad)
+                    filter3d=args.filter3d, filter3d_every=args.filter3d_every, absgrad=args.absgrad, visible_adam=args.visible_adam)
     total = tr.total_iterations                                             # --iterations, plus the sparsification phase
 
     def export():
@@ -228,7 +234,7 @@ def main():
     torch.cuda.synchronize()
     t_train = time.time() - t0 - t_eval
     out = {"data": args.data_path, "images": len(ds), "size": [scene.width, scene.height], "iterations": total, "rasterizer": rast,
-           "strategy": args.strategy, "antialiasing": bool(args.antialiasing), "filter3d": bool(args.filter3d), "absgrad": bool(args.absgrad), "pose_optimization": args.pose_optimization, "gaussians": int(tr.model.means.shape[0]), "load_s": round(t_load, 1), "train_s": round(t_train, 1),
+           "strategy": args.strategy, "antialiasing": bool(args.antialiasing), "filter3d": bool(args.filter3d), "absgrad": bool(args.absgrad), "visible_adam": bool(args.visible_adam), "pose_optimization": args.pose_optimization, "gaussians": int(tr.model.means.shape[0]), "load_s": round(t_load, 1), "train_s": round(t_train, 1),
            "iters_per_s": round(total / max(t_train, 1e-9), 1)}
     if masks is not None:
         out.update(mask_mode=args.mask_mode, masked_views=sum(m is not None for m in masks))
