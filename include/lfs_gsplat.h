@@ -743,6 +743,26 @@ LFS_API int lfs_fastgs_view_visibility(const lfs_fastgs_view* view, uint32_t* bi
 LFS_API int lfs_adam_step_multi_visible(const lfs_adam_tensor* tensors /* host array */, int32_t n_tensors, const uint32_t* visible_bits, uint32_t N,
                                         lfs_stream_t stream);
 
+/* ---- Contribution statistic of the EWA rasterizer (extension; csrc/fastgs_contrib.hip): what a Gaussian contributes to a view's image.
+ *      For Gaussian i, over exactly the pixels p into which lfs_fastgs_view_render blends i (the alpha test passed and the pixel did not terminate AT i: an instance
+ *      that terminates a pixel is not in the image and not in the statistic), with w = T alpha, T the transmittance in front of the instance, the 16-byte row
+ *      stats[i] is UPDATED (never cleared: the caller zero-fills a buffer once and accumulates views into it):
+ *        dword 0    bit pattern of max w       unsigned integer maximum (non-negative floats order like their bits)
+ *        dword 1    number of pixels blended   uint32 add - wraps after 2^32 (pixel, view) pairs: keep W * H * views < 2^32 per buffer (contribution.py folds into
+ *                                              64-bit tensors before that)
+ *        dword 2-3  sum w, unsigned 64-bit fixed point with 24 fraction bits (little endian): every wavefront sums the weights of its 8x8 cell in float in a fixed
+ *                   order, rounds sum * 2^24 to nearest once and adds the integer
+ *      There are no float atomics: the rows are bit-reproducible from run to run and do not depend on the order in which views are accumulated.
+ *      Call it after lfs_fastgs_view_preprocess[_ex] AND lfs_fastgs_view_render on the same two workspaces with the same n_instances (the render builds the instance
+ *      and cell lists); the mode of the preprocess - antialiased, 3D filter, depth - is in the records, so there is no flag. Reads N, width, height, the intrinsics and
+ *      the primitive workspace of the view; writes nothing but stats (device, [N,4] uint32, 8-byte aligned).
+ *      Before any launch: LFS_E_INVALID for a NULL view / primitive workspace / stats, a zero image size, a negative n_instances, a misaligned stats; LFS_E_WORKSPACE
+ *      for a primitive workspace shorter than lfs_fastgs_primitive_workspace_bytes or an instance workspace that is NULL or shorter than
+ *      lfs_fastgs_instance_workspace_bytes; LFS_E_UNSUPPORTED beyond the record walker's limits (as lfs_fastgs_view_render). n_instances == 0 or N == 0: LFS_OK,
+ *      nothing launched, stats untouched. */
+LFS_API int lfs_fastgs_view_contribution(const lfs_fastgs_view* view, int64_t n_instances, void* instance_workspace, size_t instance_workspace_bytes,
+                                         uint32_t* stats /* device [N,4], ADDED TO */, lfs_stream_t stream);
+
 /* ---- SOG export (csrc/sog.hip): Morton codes (kernels/morton_encoding.cu:21-97) and the three kernels of Lloyd's iteration (kernels/kmeans.cu:18-122).
  *      All entry points are asynchronous on `stream`, validate on the host before any launch (LFS_E_INVALID: NULL pointer, negative count, k or D of 0, a
  *      workspace that is not 16-byte aligned; LFS_E_UNSUPPORTED: k > 65536 or D > 64; LFS_E_WORKSPACE: workspace short), use no float atomics (same bits on every

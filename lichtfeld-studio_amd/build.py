@@ -44,6 +44,9 @@ SOURCES = {
     "sog.hip": ["-ffp-contract=off"],   # SOG export: Morton codes, k-means (the MFMA assignment is an fmaf chain by construction; the flag holds the rest)
     "sparsity.hip": ["-ffp-contract=off"],   # ADMM sparsity: radix select, state update, loss + gradient (the sigmoid of l2_fused.hip, same flags: same bits)
     "fastgs_blend.hip": ["-fno-slp-vectorize"],
+    # the contribution statistic (max / count / sum of the blending weights per Gaussian): the forward's walk and alphas (fastgs_blend.hip's flags: the same bits), its own code object
+    # (no atomic optimizer: lane 0 issues the row's three atomics with wave-uniform values - the pass's scan loops over the one active lane are pure overhead)
+    "fastgs_contrib.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
     "prof.hip": [],
     # no SLP packing: v_pk_* operand pairing forces SGPR shuffles right after the scalar record
     # load and defeats the software prefetch (measured on the ISA); plain v_fma with SGPR operands

@@ -132,6 +132,7 @@ EXPORTS = [
     "lfs_fastgs_view_preprocess_ex", "lfs_fastgs_view_backward_ex", "lfs_filter3d_workspace_bytes", "lfs_filter3d_compute",
     "lfs_image_undistort_u8_to_chw_f32", "lfs_mask_undistort_prepare", "lfs_plane_undistort_nearest_f32",
     "lfs_visibility_words", "lfs_fastgs_view_visibility", "lfs_adam_step_multi_visible",
+    "lfs_fastgs_view_contribution",
 ]
 
 

@@ -30,8 +30,6 @@ LFS_DI bool cell_reachable(float mx, float my, float A, float B, float C, float 
     return !(A * ddx * ddx + C * ddy * ddy + B * ddx * ddy > thr); // NaN -> keep
 }
 
-constexpr uint32_t WPT = 4; // 8x8 cells per 16x16 tile
-
 __global__ void __launch_bounds__(256) fg_cull_kernel(
     const uint32_t gw, const uint32_t gh, const uint32_t width, const uint32_t height, const uint32_t cull_enabled,
     const GaussRec* __restrict__ recs, const int32_t* __restrict__ offsets, const int32_t* __restrict__ ids,
@@ -88,18 +86,7 @@ __global__ void __launch_bounds__(256) fg_cull_kernel(
     if (lane == 0) cell_count[cell] = count;
 }
 
-struct Frag { float dx, dy, alpha; bool ok; };
-// one primitive against this lane's pixel: sigma' = A dx^2 + B dx dy + C dy^2 (bits), alpha = min(opacity 2^-sigma', 0.999)
-LFS_DI Frag frag_eval(const GaussRec& rec, const float px, const float py) {
-    Frag f;
-    f.dx = rec.r0.x - px; f.dy = rec.r0.y - py;
-    const float u = __builtin_fmaf(rec.r0.w, f.dy, rec.r0.z * f.dx);
-    const float s = __builtin_fmaf(rec.r1.x * f.dy, f.dy, f.dx * u);
-    f.alpha = fminf(rec.r1.z * __builtin_amdgcn_exp2f(-s), MAX_ALPHA);
-    f.ok = !(s < 0.f); // kernels_forward.cuh:425-426
-    return f;
-}
-
+// (Frag / frag_eval - one primitive against one pixel - and WPT live in lfs_fastgs.cuh: fastgs_contrib.hip evaluates the same alphas)
 // fwd / bwd: ONE wavefront per workgroup (the cells of a tile never cooperate here; a finished cell frees its slot at once - as raster.hip's wave_geom)
 // DEPTH (lfs_fastgs_view_render with a depth plane): one more accumulator D += r2.w T alpha over exactly the instances the colour takes, stored to depth_map [1,H,W]; r2.w arrives with
 // the record. The default form does not read r2.w or depth_map.

@@ -94,6 +94,20 @@ inline InstWs inst_ws(void* base, uint32_t width, uint32_t height, uint64_t n_in
 //   0,1 sum h (dx, dy) | 2,3,4 sum h (dx dx, dx dy, dy dy), h = -alpha dL/dalpha | 5,6,7 dL/d(clamped colour) | 8 sum alpha dL/dalpha |
 //   9 dL/dd = sum w g_depth (depth form of the backward only; 0 otherwise) | 10,11 sum |k gx_p|, sum |k gy_p| (abs form only; 0 otherwise) | 12..15 unused
 
+// The per-pixel evaluation shared by the blend kernels (fastgs_blend.hip) and the contribution statistic (fastgs_contrib.hip): one definition, the same alpha bits.
+constexpr uint32_t WPT = 4; // 8x8 cells per 16x16 tile
+struct Frag { float dx, dy, alpha; bool ok; };
+// one primitive against this lane's pixel: sigma' = A dx^2 + B dx dy + C dy^2 (bits), alpha = min(opacity 2^-sigma', 0.999)
+LFS_DI Frag frag_eval(const GaussRec& rec, const float px, const float py) {
+    Frag f;
+    f.dx = rec.r0.x - px; f.dy = rec.r0.y - py;
+    const float u = __builtin_fmaf(rec.r0.w, f.dy, rec.r0.z * f.dx);
+    const float s = __builtin_fmaf(rec.r1.x * f.dy, f.dy, f.dx * u);
+    f.alpha = fminf(rec.r1.z * __builtin_amdgcn_exp2f(-s), MAX_ALPHA);
+    f.ok = !(s < 0.f); // kernels_forward.cuh:425-426
+    return f;
+}
+
 // What the host remembers of the preprocess that last filled a primitive workspace (fastgs_prep.hip: remember_flags), as render and the backward use it: ONE lookup per
 // call, so every form a call picks comes from the same state of the table. All zero: a default (or antialiased-only) workspace, or one the table no longer holds.
 uint32_t remembered_flags(const void* primitive_workspace);

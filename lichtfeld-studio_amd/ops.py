@@ -435,3 +435,19 @@ def adam_step_multi_visible(entries, bits: Tensor, N: int) -> None:
         require_gpu(p, m, v, g)
         arr[i] = capi.AdamTensor(p.data_ptr(), m.data_ptr(), v.data_ptr(), g.data_ptr(), p.numel(), lr, b1, b2, eps, bc1, bc2)
     check(load_library().lfs_adam_step_multi_visible(arr, C.c_int32(len(entries)), ptr(bits), C.c_uint32(int(N)), stream()), "adam_step_multi_visible")
+
+
+# -----------------------------------------------------------------------------------------
+# contribution statistic of a fastgs view (extension; csrc/fastgs_contrib.hip): max / count / sum of the blending weights per Gaussian
+# -----------------------------------------------------------------------------------------
+def fastgs_view_contribution(primitive_workspace: Tensor, instance_workspace: Tensor, n_instances: int, N: int, width: int, height: int, stats: Tensor) -> None:
+    """ADD the view's statistic to `stats` (int32 [N,4]: bits of max w | blended pixels | sum w as 40.24 fixed point in two dwords; contribution.py unpacks it). The two
+    workspaces are those of a forward of the view (preprocess AND render) with `n_instances`. Integer atomics only: the same bits in any order of views. No host read."""
+    require_gpu(primitive_workspace, instance_workspace, stats)
+    if stats.dtype != torch.int32 or stats.dim() != 2 or tuple(stats.shape) != (int(N), 4):
+        raise LfsError(f"fastgs_view_contribution: stats must be a contiguous int32 [N, 4] = [{int(N)}, 4] tensor (got {stats.dtype}, {tuple(stats.shape)})")
+    view = capi.FastgsView()
+    view.N, view.width, view.height = int(N), int(width), int(height)
+    view.primitive_workspace, view.primitive_workspace_bytes = primitive_workspace.data_ptr(), primitive_workspace.numel()
+    check(load_library().lfs_fastgs_view_contribution(C.byref(view), C.c_int64(int(n_instances)), ptr(instance_workspace), C.c_size_t(instance_workspace.numel()), ptr(stats),
+                                                      stream()), "fastgs_view_contribution")

@@ -91,7 +91,8 @@ class GutTrainer:
                  sh_sharded: Optional[bool] = None, factored_sh: bool = False, one_call: bool = False, pose_optimization: str = "none", pose_lr: float = 1e-5,
                  enable_sparsity: bool = False, sparsify_steps: int = 15000, init_rho: float = 0.0005, prune_ratio: float = 0.6, sparsity_update_every: int = 50,
                  mask_mode: str = "none", mask_alpha_weight: float = 1.0, antialiasing: bool = False, depth_loss: str = "none", depth_weight=(1.0, 0.01),
-                 filter3d: bool = False, filter3d_every: int = 100, filter3d_variance: float = 0.2, absgrad: bool = False, visible_adam: bool = False):
+                 filter3d: bool = False, filter3d_every: int = 100, filter3d_variance: float = 0.2, absgrad: bool = False, visible_adam: bool = False,
+                 contribution_prune_at=(), contribution_threshold: float = 0.01):
         """strategy: None (fixed set of Gaussians: the benchmark), "mcmc" (strategies.MCMC: relocation + growth + SGLD noise, with
         the scale / opacity regularisers of trainer.cpp:132-158) or "default" (ADC; needs densification_info, see strategies.py).
         `seed` seeds the strategy's generator: the same on every rank, so replicas densify identically.
@@ -127,7 +128,34 @@ class GutTrainer:
         of the others are neither read nor written, so they keep their values instead of drifting along a stale momentum, and the step streams 1652 B per VISIBLE
         Gaussian. The step counts, and with them the bias corrections, stay global. Consequence: gradient terms that reach every Gaussian - MCMC's scale and opacity
         regularisers - do not move Gaussians outside the step's views. On an iteration in which the strategy refines (rows are replaced before the optimizer runs) the
-        step is the dense one. fastgs rasterizer, one rank, without enable_sparsity and one_call. Off: the trainer plans and computes what it always did."""
+        step is the dense one. fastgs rasterizer, one rank, without enable_sparsity and one_call. Off: the trainer plans and computes what it always did.
+        contribution_prune_at (contribution.py): at the end of each listed iteration (1-based, after the optimizer step) the blending-weight statistic
+        is computed over ALL training views with the trainer's own render settings (antialiasing, the current 3D filter, camera(v)), and every Gaussian whose
+        maximum blending weight over all training rays is below contribution_threshold (RadSplat's 0.01) is removed - parameters, both Adam moments and the
+        strategy's accumulators follow as in every other removal; the 3D filter is recomputed and the visibility words are rebuilt. The statistic follows the image:
+        an instance that only terminates pixels counts as 0, so a prune is a training-time operation that the remaining iterations heal. fastgs rasterizer, one
+        rank, not with strategy="mcmc" (it holds the count), sh_sharded or one_call. Empty (default): the trainer plans and computes what it always did."""
+        contribution_prune_at = tuple(int(i) for i in contribution_prune_at)
+        if contribution_prune_at:
+            if rasterizer == "gut":
+                raise ValueError("contribution_prune_at is not wired into the 3DGUT route (rasterizer='gut'): the blending-weight statistic is a kernel of the EWA "
+                                 "blend path. Use rasterizer='fastgs'.")
+            if world > 1:
+                raise ValueError("contribution_prune_at is implemented for one rank (world == 1): every rank would have to reduce the statistic over all views. Use world=1.")
+            if sh_sharded:
+                raise ValueError("contribution_prune_at cannot be combined with sh_sharded: that layout belongs to the fused 3DGUT step. Use sh_sharded=False.")
+            if strategy == "mcmc":
+                raise ValueError("contribution_prune_at cannot be combined with strategy='mcmc': MCMC holds the Gaussian count and would relocate onto the freed rows. "
+                                 "Use strategy='default' or no strategy.")
+            if one_call:
+                raise ValueError("contribution_prune_at cannot be combined with one_call: the one-call C++ step keeps its own view of the model's size. Use one_call=False.")
+            bad = [i for i in contribution_prune_at if not 1 <= i <= int(iterations)]
+            if bad:
+                raise ValueError(f"contribution_prune_at names iterations outside 1..{int(iterations)}: {bad}")
+            if not 0.0 < float(contribution_threshold) < 1.0:
+                raise ValueError(f"contribution_threshold must lie in (0, 1) (got {contribution_threshold}): it is compared with a blending weight")
+        self.contribution_prune_at, self.contribution_threshold = frozenset(contribution_prune_at), float(contribution_threshold)
+        self.contribution_log = []      # (iteration, N before, N after) of every contribution prune
         if visible_adam:
             if rasterizer == "gut":
                 raise ValueError("visible_adam is not wired into the 3DGUT route (rasterizer='gut'): nothing on that route produces the visibility bits yet, and its "
@@ -331,6 +359,25 @@ class GutTrainer:
             mask = sp.get_prune_mask(self.model.raw_opacities.detach())
             self._remove_gaussians(mask)
             self.sparsity = None   # (trainer.cpp:240: the optimiser object is dropped after the prune)
+
+    def _contribution_after_step(self) -> None:
+        """contribution_prune_at: after the optimizer step of a listed iteration, the statistic over all training views and the RadSplat prune (contribution.py)."""
+        if self.iteration not in self.contribution_prune_at:
+            return
+        from .contribution import compute_contribution, prune_mask
+        n_before = int(self.model.means.shape[0])
+        cameras = [self.camera(v) for v in range(int(self.scene.viewmats.shape[0]))]
+        stats = compute_contribution(self.model, cameras, antialiased=self.antialiasing, filter3d=self.update_filter3d())
+        mask = prune_mask(stats, threshold=self.contribution_threshold)
+        self._remove_gaussians(mask)
+        n_after = int(self.model.means.shape[0])
+        if n_after != n_before:   # as after a refinement: the filter belongs to the rows that are left, the visibility words are rebuilt for the new count
+            self.update_filter3d(force=True)
+            self._vis_bits = None
+            if self.densification_info is not None and self.densification_info.shape[1] == n_before:   # ADC's accumulators keep the rows of the Gaussians that stay
+                self.densification_info = self.densification_info[:, mask.logical_not()].contiguous()
+        self.contribution_log.append((self.iteration, n_before, n_after))
+        print(f"[contribution prune] iteration {self.iteration}: N {n_before} -> {n_after} (max blending weight < {self.contribution_threshold:g})")
 
     @torch.no_grad()
     def _remove_gaussians(self, mask: torch.Tensor) -> None:
@@ -617,6 +664,7 @@ class GutTrainer:
                 and not self._past_base()):
             self.model.active_sh_degree += 1
         self._sparsity_after_step()
+        self._contribution_after_step()
         return out
 
     def _train_step(self, targets: List[torch.Tensor], views: Optional[List[int]] = None, views_all: Optional[List[List[int]]] = None) -> float:

@@ -61,6 +61,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--grad-threshold", type=float, default=None, help="ADC's screen-space gradient threshold for splitting / cloning (default 2e-4; 8e-4 with --absgrad)")
     ap.add_argument("--visible-adam", action="store_true", help="the optimizer updates only the Gaussians the step's views saw (gsplat's visible_adam, the official code's "
                     "sparse_adam; fastgs rasterizer): the others keep parameters and Adam moments untouched, and the step streams only the visible rows")
+    ap.add_argument("--contribution-prune-at", type=int, nargs="+", default=[], metavar="ITER",
+                    help="contribution pruning (fastgs rasterizer): at the end of each listed iteration, compute every Gaussian's maximum blending weight over ALL training "
+                         "views and remove the ones below --contribution-threshold (RadSplat). Training goes on and heals what the prune disturbed")
+    ap.add_argument("--contribution-threshold", type=float, default=0.01, help="a Gaussian no training ray weights this much is removed (RadSplat: 0.01)")
     ap.add_argument("--depth-loss", default="none", choices=["none", "invdepth", "depth"],
                     help="depth-regularised training (fastgs rasterizer): L1 between the accumulated inverse depth (invdepth: monocular depth, the Inria convention) or depth of a view "
                          "and <data>/<depths folder>/<image stem>.npy (float32 [H,W]) or .png (16-bit greyscale, value / 65536). With --eval, every held-out render is then saved as "
@@ -94,6 +98,16 @@ def check_args(args) -> None:
         raise SystemExit("--visible-adam is not wired into the 3DGUT route. Please disable visible-adam or disable gut.")
     if args.visible_adam and args.enable_sparsity:
         raise SystemExit("--visible-adam cannot be combined with --enable-sparsity: the ADMM penalty must reach every opacity.")
+    if args.contribution_prune_at:
+        if args.gut:
+            raise SystemExit("--contribution-prune-at is not wired into the 3DGUT route. Please disable contribution pruning or disable gut.")
+        if args.strategy == "mcmc":
+            raise SystemExit("--contribution-prune-at cannot be combined with --strategy mcmc: MCMC holds the Gaussian count and would relocate onto the freed rows.")
+        bad = [i for i in args.contribution_prune_at if not 1 <= i <= args.iterations]
+        if bad:
+            raise SystemExit(f"--contribution-prune-at names iterations outside 1..{args.iterations}: {bad}")
+        if not 0.0 < args.contribution_threshold < 1.0:
+            raise SystemExit("--contribution-threshold must lie in (0, 1): it is compared with a blending weight")
     if args.grad_threshold is not None and not args.grad_threshold > 0:
         raise SystemExit("--grad-threshold must be > 0")
     if args.depth_loss != "none" and args.gut:
@@ -167,7 +181,8 @@ def main():
                     enable_sparsity=args.enable_sparsity, sparsify_steps=args.sparsify_steps, init_rho=args.init_rho, prune_ratio=args.prune_ratio,
                     mask_mode=args.mask_mode, mask_alpha_weight=args.mask_alpha_weight, antialiasing=args.antialiasing,
                     depth_loss=args.depth_loss, depth_weight=(args.depth_weight_init, args.depth_weight_final),
-                    filter3d=args.filter3d, filter3d_every=args.filter3d_every, absgrad=args.absgrad, visible_adam=args.visible_adam)
+                    filter3d=args.filter3d, filter3d_every=args.filter3d_every, absgrad=args.absgrad, visible_adam=args.visible_adam,
+                    contribution_prune_at=tuple(args.contribution_prune_at), contribution_threshold=args.contribution_threshold)
     total = tr.total_iterations                                             # --iterations, plus the sparsification phase
 
     def export():
