@@ -763,6 +763,39 @@ LFS_API int lfs_adam_step_multi_visible(const lfs_adam_tensor* tensors /* host a
 LFS_API int lfs_fastgs_view_contribution(const lfs_fastgs_view* view, int64_t n_instances, void* instance_workspace, size_t instance_workspace_bytes,
                                          uint32_t* stats /* device [N,4], ADDED TO */, lfs_stream_t stream);
 
+/* ---- Scene transform (extension; csrc/splat_transform.hip): move a splat by a similarity x' = s R x + t, the view-dependent colour included.
+ *      The reference's SplatData::transform (src/core/splat_data.cpp:288) leaves shN untouched and averages a non-uniform scale; neither is reproduced.
+ *   lfs_sh_rotation_matrices (pure host function): R row-major proper rotation, degree <= 4; out receives M_1 .. M_degree, row-major, packed back to back (9, 25, 49,
+ *      81 doubles). a'_l = M_l a_l for band l of one colour channel in the coefficient order and signs of the SH kernels: for every unit d,
+ *      sum_k a'_k Y_k(d) = sum_k a_k Y_k(R^T d). An exactly-identity R gives exactly-identity matrices. LFS_E_INVALID: NULL, degree > 4, non-finite entries.
+ *   lfs_splat_transform_from_matrix (pure host function): decomposes a row-major 4x4 and fills the float32 record the kernels take - sR, t, the unit quaternion of R
+ *      (wxyz, w >= 0), log s rounded once, and ALL four band matrices rounded from float64 (sh_degree only says how many of them lfs_splat_transform_apply uses). R is
+ *      re-orthonormalised in float64 first. LFS_E_INVALID: NULL, non-finite entries, a last row other than (0,0,0,1), det <= 0 (s <= 0, reflections), a linear part A
+ *      that is not a similarity (max |A^T A / s^2 - I| > 1e-5 with s = cbrt(det A): non-uniform scale and shear are refused, not averaged), sh_degree > 4.
+ *   lfs_splat_transform_apply: xf is a HOST pointer (passed to the kernels by value). Each of the four in / out pairs may be NULL together (skipped); an output may be
+ *      the same pointer as its input (in place), any other overlap is the caller's error. shN is [N, shN_rows, 3], shN_rows >= (sh_degree + 1)^2 - 1; rows beyond the
+ *      rotated bands are copied through. Single-precision operations in exactly this order (no fused multiply-adds):
+ *        means       ((sR[i][0] x + sR[i][1] y) + sR[i][2] z) + t[i]
+ *        quats       q_R (x) q on the raw quaternion, no normalisation: w = ((w1 w2 - x1 x2) - y1 y2) - z1 z2, x = ((w1 x2 + x1 w2) + y1 z2) - z1 y2,
+ *                    y = ((w1 y2 - x1 z2) + y1 w2) + z1 x2, z = ((w1 z2 + x1 y2) - y1 x2) + z1 w2 (1 = q_R, 2 = the Gaussian's)
+ *        raw_scales  raw + log_s
+ *        shN         per channel and band: a'_i = sum_k M[i][k] a_k, ascending k, left to right
+ *      sh0 and the opacities are invariant. N == 0: LFS_OK. LFS_E_INVALID before any launch: NULL xf, sh_degree > 4, a half-NULL pair, shN_rows too small;
+ *      LFS_E_UNSUPPORTED: shN_rows > 511. No workspace, no host read, no atomics. */
+typedef struct lfs_splat_transform {
+    float sR[9];          /* s R, row-major */
+    float t[3];
+    float q[4];           /* unit quaternion of R, wxyz, w >= 0 */
+    float log_s;
+    uint32_t sh_degree;   /* bands 1 .. sh_degree of shN are rotated */
+    float m1[9], m2[25], m3[49], m4[81];   /* the band matrices, row-major */
+} lfs_splat_transform;    /* 728 bytes */
+LFS_API int lfs_sh_rotation_matrices(const double* R /* [9] */, uint32_t degree, double* out);
+LFS_API int lfs_splat_transform_from_matrix(const double* m /* [16] */, uint32_t sh_degree, lfs_splat_transform* out);
+LFS_API int lfs_splat_transform_apply(uint32_t N, const lfs_splat_transform* xf /* host */, const float* means /* [N,3] */, const float* quats /* [N,4] */,
+                                      const float* raw_scales /* [N,3] */, const float* shN /* [N,shN_rows,3] */, uint32_t shN_rows, float* means_o, float* quats_o,
+                                      float* raw_scales_o, float* shN_o, lfs_stream_t stream);
+
 /* ---- SOG export (csrc/sog.hip): Morton codes (kernels/morton_encoding.cu:21-97) and the three kernels of Lloyd's iteration (kernels/kmeans.cu:18-122).
  *      All entry points are asynchronous on `stream`, validate on the host before any launch (LFS_E_INVALID: NULL pointer, negative count, k or D of 0, a
  *      workspace that is not 16-byte aligned; LFS_E_UNSUPPORTED: k > 65536 or D > 64; LFS_E_WORKSPACE: workspace short), use no float atomics (same bits on every

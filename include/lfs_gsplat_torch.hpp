@@ -86,6 +86,17 @@ struct AdamVisibleGroup {
 void adam_step_multi_visible(std::vector<AdamVisibleGroup>& groups, const torch::Tensor& visible_bits, int64_t N);
 } // namespace lfs
 
+// Scene transform (extension; lfs_splat_transform_from_matrix / lfs_splat_transform_apply of lfs_gsplat.h): move a splat by the similarity
+// x' = s R x + t given as a row-major 4x4 - means [N,3], raw quaternions [N,4] (wxyz, q_R (x) q), log-scales [N,3] (+ log s) and the SH bands of shN [N,K,3]
+// (every band K holds: degree = floor(sqrt(K + 1)) - 1, at most 4; further rows are carried over). This is what replaces the body of gs::SplatData::transform
+// (src/core/splat_data.cpp:288), which leaves shN unrotated and averages a non-uniform scale: here a matrix that is no proper similarity throws. Contiguous float32
+// device tensors; undefined tensors are skipped. inplace: the tensors are overwritten and returned; otherwise new tensors. sh0 and the opacities are invariant.
+namespace lfs {
+struct SplatTransformed { torch::Tensor means, quats, raw_scales, shN; };
+SplatTransformed splat_transform(const torch::Tensor& means, const torch::Tensor& quats, const torch::Tensor& raw_scales, const torch::Tensor& shN, const double m[16],
+                                 bool inplace);
+} // namespace lfs
+
 // The forward -> backward staging slot of the rasterizer wrappers (csrc/torch_ops.cpp; Ops.h has no argument through which a forward could hand its records and
 // per-cell lists to its backward, so the last forward's workspace is parked, keyed on the identity of its operands). Control surface (extension, not in Ops.h):
 //   torch_raster_staging_clear()     drop the parked workspace NOW - a viewer at the end of a render, a module before it is unloaded;

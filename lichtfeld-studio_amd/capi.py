@@ -110,6 +110,11 @@ class UndistortMapStruct(C.Structure):  # lfs_undistort_map (filled by undistort
                 ("dst_fx", C.c_float), ("dst_fy", C.c_float), ("dst_cx", C.c_float), ("dst_cy", C.c_float)]
 
 
+class SplatTransformStruct(C.Structure):  # lfs_splat_transform (728 bytes: 182 dwords; filled by lfs_splat_transform_from_matrix)
+    _fields_ = [("sR", C.c_float * 9), ("t", C.c_float * 3), ("q", C.c_float * 4), ("log_s", C.c_float), ("sh_degree", C.c_uint32),
+                ("m1", C.c_float * 9), ("m2", C.c_float * 25), ("m3", C.c_float * 49), ("m4", C.c_float * 81)]
+
+
 ADAM_MAX_TENSORS = 8
 
 # every symbol include/lfs_gsplat.h declares
@@ -133,6 +138,7 @@ EXPORTS = [
     "lfs_image_undistort_u8_to_chw_f32", "lfs_mask_undistort_prepare", "lfs_plane_undistort_nearest_f32",
     "lfs_visibility_words", "lfs_fastgs_view_visibility", "lfs_adam_step_multi_visible",
     "lfs_fastgs_view_contribution",
+    "lfs_sh_rotation_matrices", "lfs_splat_transform_from_matrix", "lfs_splat_transform_apply",
 ]
 
 
@@ -171,7 +177,7 @@ def load_library():
         lib.lfs_version.restype = C.c_char_p
         lib.lfs_visibility_words.restype = C.c_uint32
         for name in ("lfs_fastgs_view_visibility", "lfs_adam_step_multi_visible", "lfs_fastgs_view_preprocess","lfs_fastgs_view_render", "lfs_fastgs_view_backward", "lfs_fastgs_view_preprocess_ex", "lfs_fastgs_view_backward_ex",
-                     "lfs_filter3d_compute"):
+                     "lfs_filter3d_compute", "lfs_sh_rotation_matrices", "lfs_splat_transform_from_matrix", "lfs_splat_transform_apply"):
             getattr(lib, name).restype = C.c_int
         if os.environ.get("LFS_DEBUG_FLAGS"):   # measurement / debugging only (tools/*.sh): e.g. 64 = the reference's tile lists + pack + cull kernels inside the step
             lib.lfs_set_debug_flags(C.c_uint32(int(os.environ["LFS_DEBUG_FLAGS"], 0)))

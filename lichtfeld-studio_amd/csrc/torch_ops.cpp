@@ -393,6 +393,43 @@ void adam_step_multi_visible(std::vector<AdamVisibleGroup>& groups, const torch:
 }
 } // namespace lfs
 
+namespace lfs {
+SplatTransformed splat_transform(const torch::Tensor& means, const torch::Tensor& quats, const torch::Tensor& raw_scales, const torch::Tensor& shN, const double m[16],
+                                 bool inplace) {
+    const torch::Tensor* in[4] = {&means, &quats, &raw_scales, &shN};
+    const int64_t width[3] = {3, 4, 3};
+    int64_t N = -1;
+    for (int i = 0; i < 4; ++i) {
+        if (!in[i]->defined()) continue;
+        LFS_CHECK_INPUT(*in[i]);
+        TORCH_CHECK(in[i]->scalar_type() == at::kFloat, "splat_transform: float32 tensors are needed");
+        TORCH_CHECK(i < 3 ? (in[i]->dim() == 2 && in[i]->size(1) == width[i]) : (in[i]->dim() == 3 && in[i]->size(2) == 3),
+                    "splat_transform: means [N,3], quats [N,4], raw_scales [N,3], shN [N,K,3] are needed");
+        TORCH_CHECK(N < 0 || in[i]->size(0) == N, "splat_transform: the tensors differ in N");
+        N = in[i]->size(0);
+    }
+    SplatTransformed out;
+    if (N < 0) return out;
+    TORCH_CHECK(N <= int64_t(UINT32_MAX), "splat_transform: N out of range");
+    const int64_t rows = shN.defined() ? shN.size(1) : 0;
+    uint32_t degree = 0;
+    while (degree < 4 && int64_t(degree + 2) * int64_t(degree + 2) - 1 <= rows) ++degree;
+    lfs_splat_transform xf;
+    check_rc(lfs_splat_transform_from_matrix(m, degree, &xf), "splat_transform(from_matrix)");
+    torch::Tensor* o[4] = {&out.means, &out.quats, &out.raw_scales, &out.shN};
+    for (int i = 0; i < 4; ++i)
+        if (in[i]->defined()) *o[i] = inplace ? *in[i] : (i == 3 && rows == 0 ? in[i]->clone() : torch::empty_like(*in[i]));
+    const bool sh = shN.defined() && rows > 0;
+    auto p = [](const torch::Tensor& t, bool use) -> float* { return (use && t.defined() && t.numel() > 0) ? t.data_ptr<float>() : nullptr; };
+    const torch::Tensor& first = means.defined() ? means : quats.defined() ? quats : raw_scales.defined() ? raw_scales : shN;
+    LFS_DEVICE_GUARD(first);
+    check_rc(lfs_splat_transform_apply((uint32_t)N, &xf, p(means, true), p(quats, true), p(raw_scales, true), p(shN, sh), (uint32_t)rows, p(out.means, true),
+                                       p(out.quats, true), p(out.raw_scales, true), p(out.shN, sh), cur_stream()), "splat_transform");
+    if (inplace) for (int i = 0; i < 4; ++i) if (o[i]->defined()) bump(*o[i]);
+    return out;
+}
+} // namespace lfs
+
 // ---------------------------------------------------------------------------------------------------------
 // lfs::GutTrainStep: the C++ training step (csrc/gut_step.hip) for a libtorch caller
 // ---------------------------------------------------------------------------------------------------------

@@ -65,6 +65,16 @@ PYBIND11_MODULE(_lfs_torch_ops, m) {
               }
               lfs::adam_step_multi_visible(groups, visible_bits, N);
           });
+    // lfs::splat_transform: None = an undefined tensor (the pair is skipped); matrix: 16 numbers, row-major
+    m.def("splat_transform",
+          [](OptT means, OptT quats, OptT raw_scales, OptT shN, std::vector<double> matrix, bool inplace) {
+              TORCH_CHECK(matrix.size() == 16, "splat_transform: a 4x4 matrix (16 numbers) is needed");
+              const lfs::SplatTransformed r = lfs::splat_transform(means.value_or(at::Tensor()), quats.value_or(at::Tensor()), raw_scales.value_or(at::Tensor()),
+                                                                   shN.value_or(at::Tensor()), matrix.data(), inplace);
+              auto opt = [](const at::Tensor& t) -> py::object { return t.defined() ? py::cast(t) : py::none(); };
+              return py::make_tuple(opt(r.means), opt(r.quats), opt(r.raw_scales), opt(r.shN));
+          },
+          py::arg("means"), py::arg("quats"), py::arg("raw_scales"), py::arg("shN"), py::arg("matrix"), py::arg("inplace") = false);
     m.def("fastgs_forward_wrapper",
           [](at::Tensor means, at::Tensor scales_raw, at::Tensor rotations_raw, at::Tensor opacities_raw, at::Tensor sh0, at::Tensor sh_rest, at::Tensor w2c,
              at::Tensor cam_position, int active_sh_bases, int width, int height, float fx, float fy, float cx, float cy, float near_plane, float far_plane) {
