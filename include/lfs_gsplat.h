@@ -551,7 +551,9 @@ LFS_API int lfs_activations_project_ut(
  *      means, sh0, shN, raw_scales, raw_quats, raw_opacities; adam[k] = {lr, beta1, beta2, eps, 1/(1-beta1^t), 1/sqrt(1-beta2^t)} (fused_adam.cpp:78-92).
  *      viewmat [4,4], Kmat [3,3], background [3] (nullable), target_chw [3,H,W] on the device; *loss = loss_weight * mse(clamp(render,0,1), target) (stored).
  *   workspace: lfs_gut_step_layout_for(...).bytes; the layout names the byte offsets of what a caller may want to look at afterwards (the render
- *      [H,W,3], alpha [H,W], radii int32 [N,2], ...). tile_offsets has T + 1 entries (the last one is n_isects).
+ *      [H,W,3], alpha [H,W], radii int32 [N,2], ...). tile_offsets has T + 1 entries (the last one is n_isects). After a fused-tail one-call
+ *      step (lfs_gut_train_step_ex / _opt) the key form of isect_ids and - K <= 16 - the quats / scales / opacities blocks are not written: the step reads neither.
+ *      The split form (lfs_gut_view_forward) and the three-pass lfs_gut_train_step still write them.
  *   lfs_gut_view_forward / lfs_gut_view_backward: the same step split for callers that need GRADIENT TENSORS (data-parallel ranks, several views per step,
  *      losses other than MSE): forward into the workspace, then backward into grads[6] (group order; written or, accumulate != 0, added to). */
 typedef struct lfs_gut_step_args {

@@ -58,7 +58,7 @@ SOURCES = {
     "gut_step.hip": [],   # host code only: the C++ training-step driver
     "version.hip": [],    # lfs_version(): carries the hash of the sources (recompiled whenever any of them changed)
 }
-HEADERS = ["lfs_math.cuh", "lfs_sh.cuh", "lfs_adam.cuh", "lfs_camera.cuh", "lfs_prof.h", "lfs_raster_common.cuh", "lfs_raster_finish.cuh", "lfs_raster_finish_body.cuh", "lfs_cull_conic.cuh", "lfs_raster_pack.cuh", "lfs_tilelists.cuh", "lfs_fastgs.cuh", "lfs_mcmc_noise.cuh", "lfs_step_internal.h", os.path.join("..", "..", "include", "lfs_gsplat.h")]
+HEADERS = ["lfs_math.cuh", "lfs_sh.cuh", "lfs_adam.cuh", "lfs_camera.cuh", "lfs_prof.h", "lfs_raster_common.cuh", "lfs_raster_finish.cuh", "lfs_raster_finish_body.cuh", "lfs_cull_conic.cuh", "lfs_raster_pack.cuh", "lfs_tilelists.cuh", "lfs_fastgs.cuh", "lfs_mcmc_noise.cuh", "lfs_activations.cuh", "lfs_step_internal.h", os.path.join("..", "..", "include", "lfs_gsplat.h")]
 
 
 def source_hash() -> str:

@@ -127,8 +127,17 @@ int open_step(const lfs_gut_step_args* a, Need need, const lfs_gut_step_options*
 }
 
 // everything up to and including the rasterizer forward; shared by the Adam-inline step and the gradient-tensor step
+// What a one-call training step leaves out of its forward (FwdLean; the split forward lfs_gut_view_forward passes none of it): work whose result the step never reads.
+//   no_activations : the projection kernel does not store the activated quaternions / scales / opacities - the fused tail recomputes them from the raw values
+//                    (lfs_activations.cuh). Only with the records packed by the projection kernel: raster_pack_kernel (debug bit 6) reads them.
+//   no_keys        : the per-tile sort does not write the reference's keys back into isect_ids (the rasterizer reads flatten_ids and the offsets), and the count does
+//                    not write tiles_per_gauss (only the unsorted emit reads it)
+// (Measured and left out, profiles/r20/lean_step: the backward's accumulator memset as a rider of the scan launch - the 64 MB of zero lines then drain under the
+// cull and the forward, which lose more than the memset launch costs.)
+struct FwdLean { bool no_activations, no_keys; };
+
 int enqueue_forward(const lfs_gut_step_args* a, const StepWs& w, int64_t capacity, int64_t assumed_longest, int64_t* host_counts, int64_t stamp, hipStream_t s, Front& f,
-                    bool colors_ready = false) {   // colors_ready: w.colors holds this view's SH colours already (the previous step's fused tail wrote them)
+                    bool colors_ready = false, const FwdLean& lean = FwdLean{}) {   // colors_ready: w.colors holds this view's SH colours already (the previous step's fused tail wrote them)
     front_of(a, w, capacity, f);
     const lfs_ut_params ut{0.1f, 2.f, 0.f, 0.1f, 1};   // Cameras.h:27-61 defaults, as the trainer passes them (rasterizer_autograd.cpp:223-234)
     // trainer constants of rasterizer.cpp:176-181: eps2d 0.3, near 0.01, far 1e4, radius_clip 0
@@ -147,14 +156,15 @@ int enqueue_forward(const lfs_gut_step_args* a, const StepWs& w, int64_t capacit
     }
     const ProjCamera cam{&f.cams, /*eps2d=*/0.3f, /*near_plane=*/0.01f, /*far_plane=*/10000.f, /*radius_clip=*/0.f, &ut};
     const ProjRiders riders{w.isect_totals, w.grid.tiles(), /*cams_out=*/w.raster.base, pack_here ? recs : nullptr, pack_here ? cull : nullptr, pack_here ? w.colors : nullptr};
-    rc = activations_project_ut_impl(ProjModel{a->N, a->means, a->raw_quats, a->raw_scales, a->raw_opacities}, cam, ProjOut{w.quats, w.scales, w.opacities, w.radii, w.means2d, w.depths},
-                                     &riders, s);
+    const bool store_act = !(lean.no_activations && pack_here);
+    rc = activations_project_ut_impl(ProjModel{a->N, a->means, a->raw_quats, a->raw_scales, a->raw_opacities}, cam,
+                                     ProjOut{store_act ? w.quats : nullptr, store_act ? w.scales : nullptr, store_act ? w.opacities : nullptr, w.radii, w.means2d, w.depths}, &riders, s);
     if (rc) return rc;
     const IsectGuard guard{capacity, assumed_longest, w.abort_flag};
     const IsectInputs in{w.means2d, w.radii, w.depths};
     int64_t* counts = host_counts ? host_counts : w.dev_counts;   // [n_isects, longest tile list, stamp]
     IsectCounts cnt{};   // (no tile_offsets copy: the rasterizer reads the workspace's own; the projection kernel has cleared the totals)
-    cnt.tiles_per_gauss = w.tiles_per_gauss; cnt.n_isects = counts; cnt.max_tile_isects = counts + 1; cnt.stamp_out = counts + 2; cnt.stamp = stamp; cnt.flags = LFS_ISECT_COUNTERS_ZERO;
+    cnt.tiles_per_gauss = lean.no_keys ? nullptr : w.tiles_per_gauss; cnt.n_isects = counts; cnt.max_tile_isects = counts + 1; cnt.stamp_out = counts + 2; cnt.stamp = stamp; cnt.flags = LFS_ISECT_COUNTERS_ZERO;
     rc = isect_count(w.grid, in, cnt, w.isect, s, &guard);
     if (rc) return rc;
     if (!pack_here && !colors_ready) { // the SH colours need the projection's radii only: enqueued between the count and the binning passes, as the Python step did with its `overlap` hook
@@ -162,7 +172,8 @@ int enqueue_forward(const lfs_gut_step_args* a, const StepWs& w, int64_t capacit
         if (rc) return rc;
     }
     IsectLists lists{};   // (guarded: the count and the longest list are the guard's)
-    lists.sort = 1; lists.n_isects = -1; lists.max_tile_isects = -1; lists.tiles_per_gauss = w.tiles_per_gauss; lists.isect_ids = w.isect_ids; lists.flatten_ids = w.flatten_ids; lists.scratch = w.binned;
+    lists.sort = 1; lists.n_isects = -1; lists.max_tile_isects = -1; lists.tiles_per_gauss = lean.no_keys ? nullptr : w.tiles_per_gauss; lists.isect_ids = w.isect_ids; lists.flatten_ids = w.flatten_ids; lists.scratch = w.binned;
+    lists.keep_keys = !lean.no_keys;
     rc = isect_emit(w.grid, in, lists, w.isect, s, &guard);
     if (rc) return rc;
     return raster_forward(f.scene, f.lists, f.ws, RasterFwdOut{w.render, w.alpha, w.last_ids, /*cams_ready=*/true, /*records_ready=*/pack_here}, s);
@@ -194,7 +205,7 @@ int three_pass_tail(const lfs_gut_step_args* a, const StepWs& w, float* loss, hi
 int enqueue_tail(const lfs_gut_step_args* a, const StepWs& w, const lfs_gut_step_options& o, const float* next_viewmat, float* loss, hipStream_t s) {
     if (a->K > 16) return three_pass_tail(a, w, loss, s);
     const GutTailView view{a->viewmat, next_viewmat, w.radii, w.colors, o.freeze_shN != 0, o.noise, o.noise_lr};
-    return gut_tail_impl(params_of(a), activated_of(w), adam_of(a, w), GutRegs{a->scale_reg, a->opacity_reg}, view, loss, w.raster, s);
+    return gut_tail_impl(params_of(a), adam_of(a, w), GutRegs{a->scale_reg, a->opacity_reg}, view, loss, w.raster, s);
 }
 
 // ---- the training step: ONE sequence (open -> forward -> [loss kernels] -> backward -> tail) in two forms ----------------------------------------------------
@@ -228,8 +239,11 @@ int train_step_impl(Form form, const lfs_gut_step_args* a, const lfs_gut_step_op
     StepWs w;
     int rc = open_step(a, o.freeze_shN ? Need::AdamFrozenShN : Need::Adam, &o, capacity, workspace, workspace_bytes, w);
     if (rc) return rc;
+    FwdLean lean{};
+    lean.no_keys = form == Form::FusedTail;   // (the three-pass form keeps writing what it wrote)
+    lean.no_activations = form == Form::FusedTail && a->K <= 16;   // (K > 16: the fused-tail form runs the three passes, which read the stored values)
     Front f;
-    rc = enqueue_forward(a, w, capacity, assumed_longest, host_counts, stamp, s, f, colors_ready != 0);
+    rc = enqueue_forward(a, w, capacity, assumed_longest, host_counts, stamp, s, f, colors_ready != 0, lean);
     if (rc) return rc;
     float* v_render = nullptr;
     if (ssim) {

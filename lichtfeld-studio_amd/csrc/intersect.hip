@@ -84,7 +84,7 @@ __global__ void __launch_bounds__(1024) isect_count_kernel(
                     else atomicAdd(&totals[base + i * tw + j], 1u);
                 }
         }
-        tiles_per_gauss[idx] = n;
+        if (tiles_per_gauss != nullptr) tiles_per_gauss[idx] = n;   // (uniform; NULL: the guarded step - only the unsorted emit reads them)
     }
     if (LDS_HIST) {
         __syncthreads();
@@ -425,7 +425,7 @@ static int count_check(const IsectGrid& g, const IsectInputs& in, const IsectCou
     if (!c.n_isects || !ws.base || !grid_ok(g)) return LFS_E_INVALID;
     if (bit_width_u32(g.tile_width * g.tile_height) + bit_width_u32(g.C) > 32) return LFS_E_UNSUPPORTED; // IntersectTile.cu:154
     if (ws.bytes < isect_layout(g).bytes) return LFS_E_WORKSPACE;
-    if (size_t(g.C) * g.N > 0 && (!in.means2d || !in.radii || !c.tiles_per_gauss)) return LFS_E_INVALID;
+    if (size_t(g.C) * g.N > 0 && (!in.means2d || !in.radii || (!c.tiles_per_gauss && !guard))) return LFS_E_INVALID;   // (a guarded emit always sorts: it reads no tiles_per_gauss)
     return guard_ok(guard) ? LFS_OK : LFS_E_INVALID;
 }
 
@@ -560,13 +560,14 @@ int lfs::isect_emit(const IsectGrid& g, const IsectInputs& in, const IsectLists&
         const int64_t known = guard ? int64_t(sort_class_limit(guard->assumed_longest)) : l.max_tile_isects;
         const int64_t longest = known >= 0 ? known : INT64_MAX;
         const SortClass &c0 = SORT_CLASSES[0], &c1 = SORT_CLASSES[1], &c2 = SORT_CLASSES[2];
+        int64_t* const keys_out = l.keep_keys ? l.isect_ids : nullptr;   // NULL: the LDS classes write flatten_ids only (the global-memory network sorts isect_ids in place)
         // (round 5) both first classes in one launch whenever the second one is needed at all: its few long lists then run beside the many short ones instead of after them
         if (longest > c0.limit)
-            hipLaunchKernelGGL(tile_sort_bins_2class_kernel, dim3(T), dim3(c1.block), c1.lds_bytes, s, n_tiles_, tile_n_bits, w.offsets, l.isect_ids, l.flatten_ids);
+            hipLaunchKernelGGL(tile_sort_bins_2class_kernel, dim3(T), dim3(c1.block), c1.lds_bytes, s, n_tiles_, tile_n_bits, w.offsets, l.isect_ids, l.flatten_ids, keys_out);
         else
-            hipLaunchKernelGGL(c0.kernel, dim3(T), dim3(c0.block), c0.lds_bytes, s, 1u, c0.limit, n_tiles_, tile_n_bits, w.offsets, l.isect_ids, l.flatten_ids);
+            hipLaunchKernelGGL(c0.kernel, dim3(T), dim3(c0.block), c0.lds_bytes, s, 1u, c0.limit, n_tiles_, tile_n_bits, w.offsets, l.isect_ids, l.flatten_ids, keys_out);
         if (longest > c1.limit)
-            hipLaunchKernelGGL(c2.kernel, dim3(T), dim3(c2.block), c2.lds_bytes, s, c1.limit + 1, c2.limit, n_tiles_, tile_n_bits, w.offsets, l.isect_ids, l.flatten_ids);
+            hipLaunchKernelGGL(c2.kernel, dim3(T), dim3(c2.block), c2.lds_bytes, s, c1.limit + 1, c2.limit, n_tiles_, tile_n_bits, w.offsets, l.isect_ids, l.flatten_ids, keys_out);
         if (longest > c2.limit)
             hipLaunchKernelGGL(tile_sort_global_kernel, dim3(T), dim3(1024), 0, s, c2.limit + 1, n_tiles_, tile_n_bits, w.offsets, l.isect_ids, l.flatten_ids);
     } else {

@@ -21,9 +21,14 @@ struct IsectGrid {
 };
 inline IsectGrid isect_grid_of_image(uint32_t N, uint32_t W, uint32_t H, uint32_t tile) { return IsectGrid{1, N, tile, (W + tile - 1) / tile, (H + tile - 1) / tile}; }   // one camera; tile > 0
 struct IsectInputs { const float* means2d; const int32_t* radii; const float* depths; };   // (the count reads no depths)
+// tiles_per_gauss: nullable in a guarded call (only the unsorted emit reads it, and a guarded emit always sorts)
 struct IsectCounts { int32_t* tiles_per_gauss; int64_t *n_isects, *max_tile_isects; int32_t* tile_offsets; uint32_t flags; int64_t* stamp_out; int64_t stamp; };   // (as lfs_intersect_tile_count_ex)
 // guarded: n_isects and max_tile_isects are ignored (the count is read from the workspace offsets on the device, the sort classes are the guard's), scratch is required
-struct IsectLists { int sort; int64_t n_isects; const int32_t* tiles_per_gauss; int64_t* isect_ids; int32_t* flatten_ids; int32_t* tile_offsets; int64_t* scratch; int64_t max_tile_isects; };
+// keep_keys (default true): the per-tile sort also writes the reference's (camera | tile | depth) keys back into isect_ids. false (the training step, whose rasterizer reads
+// flatten_ids and the offsets only): isect_ids keeps the parked (depth bits << 32 | flatten id) entries in bucket order - 8 B per intersection less to store. (Lists
+// longer than the last LDS class are ordered in place by tile_sort_global_kernel, which rewrites isect_ids either way.)
+struct IsectLists { int sort; int64_t n_isects; const int32_t* tiles_per_gauss; int64_t* isect_ids; int32_t* flatten_ids; int32_t* tile_offsets; int64_t* scratch; int64_t max_tile_isects;
+                    bool keep_keys = true; };
 // The workspace as byte offsets from its base: totals [T], cursor [T], row_cursor [C * tile_height] (two-pass scatter), offsets [T + 1] (offsets[T] = n_isects:
 // what the guarded rasterizer calls take as tile_offsets), block_sums [ceil(C N / 2048) + 1] (the unsorted emit's scan)
 struct IsectLayout { size_t totals, cursor, row_cursor, offsets, block_sums, bytes; };
@@ -110,7 +115,7 @@ int gut_finish_grads_impl(const GutParams& p, const GutActivated& act, const Gut
                           const Workspace& ws, hipStream_t s, const GutDensify* dens = nullptr);
 
 // the fused tail of the all-inline step (raster.hip: gut_tail_kernel): SH backward + the six Adam updates in one pass. LFS_E_UNSUPPORTED for K > 16.
-int gut_tail_impl(const GutParams& p, const GutActivated& act, const GutAdam& adam, const GutRegs& regs, const GutTailView& view, float* loss,
-                  const Workspace& ws, hipStream_t s);
+// (no GutActivated: the kernel recomputes the activated values from the raw ones it holds - lfs_activations.cuh)
+int gut_tail_impl(const GutParams& p, const GutAdam& adam, const GutRegs& regs, const GutTailView& view, float* loss, const Workspace& ws, hipStream_t s);
 
 } // namespace lfs

@@ -1,7 +1,8 @@
 // Per-tile list machinery shared by intersect.hip (gsplat::intersect_tile) and fastgs.hip (the EWA rasterizer's instance lists):
 // the exclusive scan of per-tile counts and the per-tile sort of (depth bits << 32 | id) keys that a scatter kernel parked in
-// a 64-bit array. The sort kernels write the reference's (camera | tile | depth) key back into that array and the id into a
-// 32-bit array. See intersect.hip for the design notes.
+// a 64-bit array. The sort kernels write the id into a 32-bit array and the reference's (camera | tile | depth) key into keys_out - the
+// parked array itself for every caller that wants the keys (the kernels read a bucket completely before they write any of it), NULL
+// (a uniform branch around the store) for the training step, which reads the ids only. See intersect.hip for the design notes.
 #pragma once
 #include "lfs_math.cuh"
 
@@ -131,7 +132,7 @@ LFS_DI void bitonic_sort_lds(uint64_t* __restrict__ keys, const uint32_t n_pad) 
 // (the body: one workgroup of THREADS threads sorts the bucket [start, start + n) of tile t; lds64 = the workgroup's dynamic LDS block)
 template <int THREADS, int NBINS, bool COPY, uint32_t BIN_LIMIT>
 LFS_DI void tile_sort_bins_body(const uint32_t t, const uint32_t start, const uint32_t n, const uint32_t n_tiles, const uint32_t tile_n_bits,
-                                int64_t* __restrict__ isect_ids, int32_t* __restrict__ flatten_ids, uint64_t* __restrict__ lds64) {
+                                const int64_t* isect_ids, int32_t* __restrict__ flatten_ids, int64_t* keys_out, uint64_t* __restrict__ lds64) {
     __shared__ uint32_t s_hist[NBINS], s_off[NBINS + 1], s_minmax[2], s_big;
     static_assert(NBINS % 64 == 0, "one wave scans the bin counts");
     constexpr int PER = NBINS / 64;
@@ -185,7 +186,7 @@ LFS_DI void tile_sort_bins_body(const uint32_t t, const uint32_t start, const ui
         bitonic_sort_lds<THREADS>(B, n_pad);
         for (uint32_t i = threadIdx.x; i < n; i += THREADS) {
             const uint64_t k = B[i];
-            isect_ids[start + i] = int64_t(hi_bits | (k >> 32));
+            if (keys_out != nullptr) keys_out[start + i] = int64_t(hi_bits | (k >> 32));
             flatten_ids[start + i] = int32_t(uint32_t(k));
         }
         return;
@@ -198,7 +199,7 @@ LFS_DI void tile_sort_bins_body(const uint32_t t, const uint32_t start, const ui
         const uint32_t o = s_off[b], m = s_off[b + 1] - o;
         uint32_t rank = 0;
         for (uint32_t j = 0; j < m; ++j) rank += B[o + j] < k ? 1u : 0u;
-        isect_ids[start + o + rank] = int64_t(hi_bits | (k >> 32));
+        if (keys_out != nullptr) keys_out[start + o + rank] = int64_t(hi_bits | (k >> 32));
         flatten_ids[start + o + rank] = int32_t(uint32_t(k));
     }
 }
@@ -206,13 +207,13 @@ LFS_DI void tile_sort_bins_body(const uint32_t t, const uint32_t start, const ui
 template <int THREADS, int NBINS = 256, bool COPY = true, uint32_t BIN_LIMIT = 32>
 __global__ void __launch_bounds__(THREADS) tile_sort_bins_kernel(
     const uint32_t n_min, const uint32_t n_max, const uint32_t n_tiles, const uint32_t tile_n_bits, const int32_t* __restrict__ offsets,
-    int64_t* __restrict__ isect_ids, int32_t* __restrict__ flatten_ids) {
+    const int64_t* isect_ids, int32_t* __restrict__ flatten_ids, int64_t* keys_out) {
     LFS_DYN_LDS(uint64_t, lds64);
     const uint32_t t = blockIdx.x;
     const uint32_t start = uint32_t(offsets[t]);
     const uint32_t n = uint32_t(offsets[t + 1]) - start;
     if (n < n_min || n > n_max) return;
-    tile_sort_bins_body<THREADS, NBINS, COPY, BIN_LIMIT>(t, start, n, n_tiles, tile_n_bits, isect_ids, flatten_ids, lds64);
+    tile_sort_bins_body<THREADS, NBINS, COPY, BIN_LIMIT>(t, start, n, n_tiles, tile_n_bits, isect_ids, flatten_ids, keys_out, lds64);
 }
 
 // The two size classes that hold every tile of a typical view - 1 .. 1024 entries (256 bins, keys staged in LDS) and 1025 .. 4096 (512 bins, only the binned copy in LDS) -
@@ -220,14 +221,14 @@ __global__ void __launch_bounds__(THREADS) tile_sort_bins_kernel(
 // it the tail of its longest tiles on a mostly idle chip; in one launch those tiles overlap with the thousands of short ones. Same bodies, same results (the body does not
 // depend on which other tiles run beside it); 32 KiB of dynamic LDS per workgroup (the larger class) = 5 workgroups per CU.
 static __global__ void __launch_bounds__(512) tile_sort_bins_2class_kernel(
-    const uint32_t n_tiles, const uint32_t tile_n_bits, const int32_t* __restrict__ offsets, int64_t* __restrict__ isect_ids, int32_t* __restrict__ flatten_ids) {
+    const uint32_t n_tiles, const uint32_t tile_n_bits, const int32_t* __restrict__ offsets, const int64_t* isect_ids, int32_t* __restrict__ flatten_ids, int64_t* keys_out) {
     LFS_DYN_LDS(uint64_t, lds64);
     const uint32_t t = blockIdx.x;
     const uint32_t start = uint32_t(offsets[t]);
     const uint32_t n = uint32_t(offsets[t + 1]) - start;
     if (n < 1u || n > 4096u) return;   // (longer lists: the 1024-thread class / the global-memory network, launched separately when a tile needs them)
-    if (n <= 1024u) tile_sort_bins_body<512, 256, true, 32>(t, start, n, n_tiles, tile_n_bits, isect_ids, flatten_ids, lds64);
-    else tile_sort_bins_body<512, 512, false, 32>(t, start, n, n_tiles, tile_n_bits, isect_ids, flatten_ids, lds64);
+    if (n <= 1024u) tile_sort_bins_body<512, 256, true, 32>(t, start, n, n_tiles, tile_n_bits, isect_ids, flatten_ids, keys_out, lds64);
+    else tile_sort_bins_body<512, 512, false, 32>(t, start, n, n_tiles, tile_n_bits, isect_ids, flatten_ids, keys_out, lds64);
 }
 
 // ---------------------------------------------------------------------------
@@ -238,7 +239,7 @@ static __global__ void __launch_bounds__(512) tile_sort_bins_2class_kernel(
 template <int THREADS>
 __global__ void __launch_bounds__(THREADS) tile_sort_lds_kernel(
     const uint32_t n_min, const uint32_t n_max, const uint32_t n_tiles, const uint32_t tile_n_bits, const int32_t* __restrict__ offsets,
-    int64_t* __restrict__ isect_ids, int32_t* __restrict__ flatten_ids) {
+    const int64_t* isect_ids, int32_t* __restrict__ flatten_ids, int64_t* keys_out) {
     LFS_DYN_LDS(uint64_t, keys);
     const uint32_t t = blockIdx.x;
     const uint32_t start = uint32_t(offsets[t]);
@@ -252,7 +253,7 @@ __global__ void __launch_bounds__(THREADS) tile_sort_lds_kernel(
     bitonic_sort_lds<THREADS>(keys, n_pad);
     for (uint32_t i = threadIdx.x; i < n; i += THREADS) {
         const uint64_t k = keys[i];
-        isect_ids[start + i] = int64_t(hi_bits | (k >> 32));
+        if (keys_out != nullptr) keys_out[start + i] = int64_t(hi_bits | (k >> 32));
         flatten_ids[start + i] = int32_t(uint32_t(k));
     }
 }

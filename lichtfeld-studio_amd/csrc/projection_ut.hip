@@ -7,6 +7,7 @@
 // compiled with -ffp-contract=off: it has VALU headroom to spare and un-fused
 // arithmetic keeps the sigma-point cancellation (weights -99 / +16.67) on the
 // same rounding path as the oracle.
+#include "lfs_activations.cuh"
 #include "lfs_camera.cuh"
 #include "lfs_prof.h"
 #include "lfs_raster_pack.cuh"
@@ -16,7 +17,8 @@ namespace lfs {
 
 // ACT (fused training step): quats / scales / opacities are the RAW parameters; the kernel applies gs::SplatData's activations first (the arithmetic of
 // activations_fwd_kernel, l2_fused.hip: x / max(|x|, 1e-12), exp, sigmoid), stores the activated values (act_*) and projects those - bit for bit what the
-// two separate kernels compute. conics are not needed by the world-space rasterizer and not written then.
+// two separate kernels compute. conics are not needed by the world-space rasterizer and not written then. act_* may be NULL (all three): nothing is stored - the
+// fused-tail training step, whose tail kernel evaluates the same function (lfs_activations.cuh) on the raw values it holds anyway.
 // SIMPLE (round 3): the camera block is KNOWN to be an undistorted pinhole with a global shutter - what the trainer renders (rasterizer.cpp:176-181 with the
 // COLMAP PINHOLE / SIMPLE_PINHOLE models and every synthetic scene). The camera-model, distortion and shutter branches of lfs_camera.cuh - all wave-uniform,
 // but all compiled into the generic kernel: 125 VGPRs and ~70 000 lines of ISA for the worst case, a fisheye camera under a rolling shutter - become
@@ -65,11 +67,11 @@ __global__ void __launch_bounds__(256) projection_ut_kernel(
         float4 qin = reinterpret_cast<const float4*>(quats)[gid];
         float opac_in = opacities != nullptr ? opacities[gid] : 0.f;
         if (ACT) {
-            const float den = fmaxf(sqrtf(qin.x * qin.x + qin.y * qin.y + qin.z * qin.z + qin.w * qin.w), 1e-12f);
-            qin = make_float4(qin.x / den, qin.y / den, qin.z / den, qin.w / den);
-            scale = {expf(scale.x), expf(scale.y), expf(scale.z)};
-            opac_in = 1.f / (1.f + expf(-opac_in));
-            if (cid == 0) {
+            const float raw_sc[3] = {scale.x, scale.y, scale.z};
+            float act_sc[3];
+            splat_activations(qin, raw_sc, opac_in, qin, act_sc, opac_in);
+            scale = {act_sc[0], act_sc[1], act_sc[2]};
+            if (cid == 0 && act_quats != nullptr) {   // (uniform) NULL: the fused-tail step - its tail recomputes the three from the raw values (gut_tail_kernel)
                 reinterpret_cast<float4*>(act_quats)[gid] = qin;
                 st3(act_scales, gid, scale);
                 act_opacities[gid] = opac_in;
@@ -219,7 +221,9 @@ extern "C" int lfs_projection_ut_3dgs_fused(
 }
 
 int lfs::activations_project_ut_impl(const ProjModel& m, const ProjCamera& c, const ProjOut& out, const ProjRiders* riders, hipStream_t s) {
-    const int rc = projection_check(m.N, c.cams, m.means && m.raw_quats && m.raw_scales && m.raw_opacities && out.quats && out.scales && out.opacities && out.radii &&
+    const bool act_out = out.quats && out.scales && out.opacities, act_none = !out.quats && !out.scales && !out.opacities;   // all three, or (PACK riders only) none
+    const bool pack = riders && riders->recs_out;
+    const int rc = projection_check(m.N, c.cams, m.means && m.raw_quats && m.raw_scales && m.raw_opacities && (act_out || (act_none && pack)) && out.radii &&
                                                      out.means2d && out.depths);
     if (rc || m.N == 0 || c.cams->C == 0) return rc;
     return projection_launch(true, "activations_projection_ut", m, c, out, nullptr, nullptr, riders ? *riders : ProjRiders{}, s);

@@ -53,6 +53,7 @@
 #include "lfs_raster_finish.cuh"   // finish_geometry, FinishAdam / FinishGrads, LOSS_SLOTS
 #include "lfs_sh.cuh"
 #include "lfs_mcmc_noise.cuh"
+#include "lfs_activations.cuh"
 #include "lfs_step_internal.h"
 #ifdef LFS_EMULATE   // (the densifying finish pass is a code object of its own on the GPU; a host build of this file carries it)
 #define LFS_RASTER_DENSIFY_INLINE
@@ -756,7 +757,6 @@ __global__ void __launch_bounds__(FINISH_BLOCK) raster_finish_adam_kernel(
 struct GutTail {
     uint32_t N, K; int degree;
     float *means, *sh0, *shN, *raw_scales, *raw_quats, *raw_opacities;
-    const float *quats, *scales, *opacities;       // activated values (the projection kernel wrote them)
     const float* viewmat; const float* next_viewmat;   // next_viewmat: NULL = no colours for the next step
     const int32_t* radii; float* colors;             // in: this step's colours (clamp mask); out (next_viewmat given): the next step's, for EVERY Gaussian
     const float* acc;
@@ -836,10 +836,8 @@ __global__ void __launch_bounds__(64) gut_tail_kernel(const GutTail t, const Cam
     auto ld4o = [&](const float* base) { return *reinterpret_cast<const float4*>(at(base, o16)); };
     auto ld1o = [&](const float* base) { return *reinterpret_cast<const float*>(at(base, o4)); };
     const float4 a0 = a4[0], a1 = a4[1], a2 = a4[2];
-    float sc[3], m0[3], v0m[3], p1[3], m1[3], v1[3];
-    ld3o(t.scales, sc);
-    const float4 q = ld4o(t.quats), rq = ld4o(t.raw_quats);
-    const float o = ld1o(t.opacities);
+    float m0[3], v0m[3], p1[3], m1[3], v1[3];
+    const float4 rq = ld4o(t.raw_quats);
     const FinishAdam& ad = t.fin;
     ld3o(ad.m[0], m0); ld3o(ad.v[0], v0m); ld3o(t.raw_scales, p1); ld3o(ad.m[1], m1); ld3o(ad.v[1], v1);
     float4 mq = ld4o(ad.m[2]), vq4 = ld4o(ad.v[2]);
@@ -909,6 +907,10 @@ __global__ void __launch_bounds__(64) gut_tail_kernel(const GutTail t, const Cam
         vd[0] = (gx - dd * d.x) * inorm; vd[1] = (gy - dd * d.y) * inorm; vd[2] = (gz - dd * d.z) * inorm;
     }
     float pm[3] = {mu.x, mu.y, mu.z};   // the mean: updated below, read again by phase 4
+    // the activated quaternion / scales / opacity, from the raw values as loaded: what the projection kernel computed for the forward (lfs_activations.cuh, the same
+    // function: the same bits) - the fused-tail step does not store them, and this kernel does not read them back (32 B per Gaussian each way)
+    float4 q; float sc[3], o;
+    splat_activations(rq, p1, po, q, sc, o);
     {   // raster_finish_adam_kernel<true> from its "everything is in flight" line on, statement by statement
         const float A[9] = {a0.x * REC_UNSCALE, a0.y * REC_UNSCALE, a0.z * REC_UNSCALE, a0.w * REC_UNSCALE, a1.x * REC_UNSCALE, a1.y * REC_UNSCALE, a1.z * REC_UNSCALE,
                             a1.w * REC_UNSCALE, a2.x * REC_UNSCALE};
@@ -1425,14 +1427,14 @@ int lfs::gut_finish_adam_impl(const GutParams& p, const GutActivated& act, const
 
 // The fused tail of the all-inline step (gut_tail_kernel): SH backward + all six Adam updates (+ the next view's SH colours -> colors [N,3] when next_viewmat is given).
 // LFS_E_UNSUPPORTED for K > 16 (degree 4): the caller enqueues lfs_sh_model_bwd_adam_all + lfs_gut_finish_adam instead.
-int lfs::gut_tail_impl(const GutParams& p, const GutActivated& act, const GutAdam& adam, const GutRegs& regs, const GutTailView& view, float* loss,
-                       const Workspace& ws, hipStream_t s) {
+// The activated quaternions / scales / opacities are not an input: the kernel recomputes them from the raw values (lfs_activations.cuh).
+int lfs::gut_tail_impl(const GutParams& p, const GutAdam& adam, const GutRegs& regs, const GutTailView& view, float* loss, const Workspace& ws, hipStream_t s) {
     const uint32_t N = p.N, K = p.K;
     if (N == 0) return LFS_OK;
     const uint32_t Kd = (p.sh_degree + 1) * (p.sh_degree + 1);
     if (p.sh_degree > 3 || Kd > K || K < 2) return LFS_E_INVALID;
     if (K > 16) return LFS_E_UNSUPPORTED;
-    if (!p.means || !p.sh0 || !p.shN || !p.raw_scales || !p.raw_quats || !p.raw_opacities || !act.quats || !act.scales || !act.opacities || !view.viewmat || !view.radii ||
+    if (!p.means || !p.sh0 || !p.shN || !p.raw_scales || !p.raw_quats || !p.raw_opacities || !view.viewmat || !view.radii ||
         !view.colors || !adam.exp_avg || !adam.exp_avg_sq || !adam.scalars || !ws.base) return LFS_E_INVALID;
     for (int k = 0; k < 6; ++k) if ((!adam.exp_avg[k] || !adam.exp_avg_sq[k]) && !(view.freeze_shN && k == 2)) return LFS_E_INVALID;
     RasterWs w;
@@ -1440,7 +1442,6 @@ int lfs::gut_tail_impl(const GutParams& p, const GutActivated& act, const GutAda
     GutTail t{};
     t.N = N; t.K = K; t.degree = int(p.sh_degree);
     t.means = p.means; t.sh0 = p.sh0; t.shN = p.shN; t.raw_scales = p.raw_scales; t.raw_quats = p.raw_quats; t.raw_opacities = p.raw_opacities;
-    t.quats = act.quats; t.scales = act.scales; t.opacities = act.opacities;
     t.viewmat = view.viewmat; t.next_viewmat = view.next_viewmat; t.radii = view.radii; t.colors = view.colors; t.acc = w.acc;
     t.m0 = adam.exp_avg[1]; t.v0 = adam.exp_avg_sq[1]; t.s0 = adam_scalars(adam.scalars[1]);
     t.mN = adam.exp_avg[2]; t.vN = adam.exp_avg_sq[2]; t.sN = adam_scalars(adam.scalars[2]);
