@@ -798,6 +798,37 @@ LFS_API int lfs_splat_transform_apply(uint32_t N, const lfs_splat_transform* xf 
                                       const float* raw_scales /* [N,3] */, const float* shN /* [N,shN_rows,3] */, uint32_t shN_rows, float* means_o, float* quats_o,
                                       float* raw_scales_o, float* shN_o, lfs_stream_t stream);
 
+/* ---- Background colour on the EWA route (extension; csrc/background.hip): the compose stage between lfs_fastgs_view_render and the loss, its
+ *      backward, and the RGBA target. The reference blends the background in torch outside its rasterizer (fast_rasterizer.cpp:60-66). Planes are contiguous
+ *      [.,H,W] float32 device tensors; bg is passed BY VALUE (kernel arguments: no device tensor, no host read). Single-precision operations in exactly this order,
+ *      no fused multiply-adds.
+ *   lfs_background_compose: one launch, up to two jobs; either group's three pointers may be NULL together.
+ *      render group   shown_c = image_c + (1.0f - alpha) * bg_c              image [3,H,W], alpha [1,H,W] -> shown [3,H,W]; shown == image (in place) is allowed
+ *      target group   a = (float)u8 / 255.0f; out_c = a * t_c + (1.0f - a) * bg_c     target_rgb [3,H,W], target_alpha [H,W] uint8 -> target_out [3,H,W]
+ *                     (a == 0: out == bg bit for bit; a == 255: out == t). target_out must not be target_rgb: LFS_E_INVALID.
+ *   lfs_background_compose_bwd: d = (v_0 bg_0 + v_1 bg_1) + v_2 bg_2; v_alpha = v_alpha_in ? v_alpha_in - d : -d. v_shown [3,H,W], v_alpha_in NULL or [H,W],
+ *      v_alpha [H,W] (may be v_alpha_in). dL/d(image) is v_shown itself: the caller hands the same tensor on.
+ *   Any other overlap of the operands is the caller's error. LFS_E_INVALID before any launch: a NULL struct, both groups NULL, half a group, a NULL v_shown / v_alpha,
+ *   a zero extent, H * W >= 2^31, a non-finite bg. 16-byte accesses are used when H * W % 4 == 0 and every float pointer involved is 16-byte aligned (the uint8 plane:
+ *   4-byte); any 4-byte-aligned float tensors are accepted otherwise. No workspace, no atomics. */
+typedef struct lfs_background_compose_args {
+    uint32_t height, width;
+    float bg[3];
+    const float *image, *alpha;
+    float* shown;
+    const float* target_rgb;
+    const uint8_t* target_alpha;
+    float* target_out;
+} lfs_background_compose_args;       /* 72 bytes */
+typedef struct lfs_background_compose_bwd_args {
+    uint32_t height, width;
+    float bg[3];
+    const float *v_shown, *v_alpha_in;
+    float* v_alpha;
+} lfs_background_compose_bwd_args;   /* 48 bytes */
+LFS_API int lfs_background_compose(const lfs_background_compose_args* args, lfs_stream_t stream);
+LFS_API int lfs_background_compose_bwd(const lfs_background_compose_bwd_args* args, lfs_stream_t stream);
+
 /* ---- SOG export (csrc/sog.hip): Morton codes (kernels/morton_encoding.cu:21-97) and the three kernels of Lloyd's iteration (kernels/kmeans.cu:18-122).
  *      All entry points are asynchronous on `stream`, validate on the host before any launch (LFS_E_INVALID: NULL pointer, negative count, k or D of 0, a
  *      workspace that is not 16-byte aligned; LFS_E_UNSUPPORTED: k > 65536 or D > 64; LFS_E_WORKSPACE: workspace short), use no float atomics (same bits on every

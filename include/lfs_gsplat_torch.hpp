@@ -97,6 +97,18 @@ SplatTransformed splat_transform(const torch::Tensor& means, const torch::Tensor
                                  bool inplace);
 } // namespace lfs
 
+// Background colour on the EWA route (extension; lfs_background_compose / lfs_background_compose_bwd of lfs_gsplat.h): what replaces the torch
+// expression `image + (1 - alpha) * bg` after fast_gs's forward (fast_rasterizer.cpp:60-66) on a training step, bit for bit, with the colour passed by value - and
+// composites an RGBA target over the same colour in the same launch. Contiguous device tensors: image / shown / target_rgb / target_out float32 [3,H,W], alpha
+// float32 [1,H,W] or [H,W], target_alpha uint8 [H,W]. Either group may be left undefined as a whole. inplace: shown IS image. The target is never composited in place.
+// background_compose_bwd: v_alpha = (v_alpha_in or 0) - sum_c bg_c v_shown_c, [1,H,W]; inplace: written into v_alpha_in. dL/d(image) is v_shown itself.
+namespace lfs {
+struct BackgroundComposed { torch::Tensor shown, target; };
+BackgroundComposed background_compose(const float bg[3], const torch::Tensor& image, const torch::Tensor& alpha, const torch::Tensor& target_rgb,
+                                      const torch::Tensor& target_alpha, bool inplace);
+torch::Tensor background_compose_bwd(const float bg[3], const torch::Tensor& v_shown, const torch::Tensor& v_alpha_in, bool inplace);
+} // namespace lfs
+
 // The forward -> backward staging slot of the rasterizer wrappers (csrc/torch_ops.cpp; Ops.h has no argument through which a forward could hand its records and
 // per-cell lists to its backward, so the last forward's workspace is parked, keyed on the identity of its operands). Control surface (extension, not in Ops.h):
 //   torch_raster_staging_clear()     drop the parked workspace NOW - a viewer at the end of a render, a module before it is unloaded;

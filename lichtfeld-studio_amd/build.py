@@ -43,6 +43,8 @@ SOURCES = {
     "filter3d.hip": ["-ffp-contract=off"],   # the 3D smoothing filter's variance from all training cameras (its per-primitive use is in fastgs_prep.hip)
     # scene transform: similarity move of means / quaternions / log-scales and the SH band rotation (streaming; un-fused so a float32 host model repeats every bit), its own code object
     "splat_transform.hip": ["-ffp-contract=off"],
+    # background colour on the EWA route: render / RGBA-target compose and its alpha backward (streaming; un-fused so torch's expression repeats every bit), its own code object
+    "background.hip": ["-ffp-contract=off"],
     "sog.hip": ["-ffp-contract=off"],   # SOG export: Morton codes, k-means (the MFMA assignment is an fmaf chain by construction; the flag holds the rest)
     "sparsity.hip": ["-ffp-contract=off"],   # ADMM sparsity: radix select, state update, loss + gradient (the sigmoid of l2_fused.hip, same flags: same bits)
     "fastgs_blend.hip": ["-fno-slp-vectorize"],

@@ -115,6 +115,15 @@ class SplatTransformStruct(C.Structure):  # lfs_splat_transform (728 bytes: 182 
                 ("m1", C.c_float * 9), ("m2", C.c_float * 25), ("m3", C.c_float * 49), ("m4", C.c_float * 81)]
 
 
+class BackgroundComposeArgs(C.Structure):  # lfs_background_compose_args (72 bytes)
+    _fields_ = [("height", C.c_uint32), ("width", C.c_uint32), ("bg", C.c_float * 3), ("image", C.c_void_p), ("alpha", C.c_void_p), ("shown", C.c_void_p),
+                ("target_rgb", C.c_void_p), ("target_alpha", C.c_void_p), ("target_out", C.c_void_p)]
+
+
+class BackgroundComposeBwdArgs(C.Structure):  # lfs_background_compose_bwd_args (48 bytes)
+    _fields_ = [("height", C.c_uint32), ("width", C.c_uint32), ("bg", C.c_float * 3), ("v_shown", C.c_void_p), ("v_alpha_in", C.c_void_p), ("v_alpha", C.c_void_p)]
+
+
 ADAM_MAX_TENSORS = 8
 
 # every symbol include/lfs_gsplat.h declares
@@ -139,6 +148,7 @@ EXPORTS = [
     "lfs_visibility_words", "lfs_fastgs_view_visibility", "lfs_adam_step_multi_visible",
     "lfs_fastgs_view_contribution",
     "lfs_sh_rotation_matrices", "lfs_splat_transform_from_matrix", "lfs_splat_transform_apply",
+    "lfs_background_compose", "lfs_background_compose_bwd",
 ]
 
 
@@ -177,8 +187,10 @@ def load_library():
         lib.lfs_version.restype = C.c_char_p
         lib.lfs_visibility_words.restype = C.c_uint32
         for name in ("lfs_fastgs_view_visibility", "lfs_adam_step_multi_visible", "lfs_fastgs_view_preprocess","lfs_fastgs_view_render", "lfs_fastgs_view_backward", "lfs_fastgs_view_preprocess_ex", "lfs_fastgs_view_backward_ex",
-                     "lfs_filter3d_compute", "lfs_sh_rotation_matrices", "lfs_splat_transform_from_matrix", "lfs_splat_transform_apply"):
-            getattr(lib, name).restype = C.c_int
+                     "lfs_filter3d_compute", "lfs_sh_rotation_matrices", "lfs_splat_transform_from_matrix", "lfs_splat_transform_apply",
+                     "lfs_background_compose", "lfs_background_compose_bwd"):
+            if name in EXPORTS:   # (always, but for a timing tool that loads the PARENT commit's library beside this one with the new entries taken off the list)
+                getattr(lib, name).restype = C.c_int
         if os.environ.get("LFS_DEBUG_FLAGS"):   # measurement / debugging only (tools/*.sh): e.g. 64 = the reference's tile lists + pack + cull kernels inside the step
             lib.lfs_set_debug_flags(C.c_uint32(int(os.environ["LFS_DEBUG_FLAGS"], 0)))
         _LIB = lib

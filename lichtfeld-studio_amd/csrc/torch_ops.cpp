@@ -430,6 +430,63 @@ SplatTransformed splat_transform(const torch::Tensor& means, const torch::Tensor
 }
 } // namespace lfs
 
+namespace lfs {
+static void check_bg_plane(const torch::Tensor& t, int64_t channels, int64_t H, int64_t W, at::ScalarType type, const char* what) {
+    LFS_CHECK_INPUT(t);
+    TORCH_CHECK(t.scalar_type() == type && t.dim() >= 2 && t.size(-2) == H && t.size(-1) == W && t.numel() == channels * H * W, "background_compose: ", what, " has the wrong type or shape");
+}
+
+BackgroundComposed background_compose(const float bg[3], const torch::Tensor& image, const torch::Tensor& alpha, const torch::Tensor& target_rgb,
+                                      const torch::Tensor& target_alpha, bool inplace) {
+    const bool render = image.defined() || alpha.defined(), target = target_rgb.defined() || target_alpha.defined();
+    TORCH_CHECK(render || target, "background_compose: neither a render group nor a target group was given");
+    TORCH_CHECK(!render || (image.defined() && alpha.defined()), "background_compose: image and alpha are given together");
+    TORCH_CHECK(!target || (target_rgb.defined() && target_alpha.defined()), "background_compose: target_rgb and target_alpha are given together");
+    const torch::Tensor& first = render ? image : target_rgb;
+    TORCH_CHECK(first.dim() == 3, "background_compose: [3,H,W] tensors are needed");
+    const int64_t H = first.size(1), W = first.size(2);
+    TORCH_CHECK(H > 0 && W > 0 && H <= int64_t(UINT32_MAX) && W <= int64_t(UINT32_MAX), "background_compose: image size out of range");
+    BackgroundComposed out;
+    lfs_background_compose_args a = {};
+    a.height = (uint32_t)H; a.width = (uint32_t)W;
+    for (int i = 0; i < 3; ++i) a.bg[i] = bg[i];
+    if (render) {
+        check_bg_plane(image, 3, H, W, at::kFloat, "image"); check_bg_plane(alpha, 1, H, W, at::kFloat, "alpha");
+        out.shown = inplace ? image : torch::empty_like(image);
+        a.image = image.data_ptr<float>(); a.alpha = alpha.data_ptr<float>(); a.shown = out.shown.data_ptr<float>();
+    }
+    if (target) {
+        check_bg_plane(target_rgb, 3, H, W, at::kFloat, "target_rgb"); check_bg_plane(target_alpha, 1, H, W, at::kByte, "target_alpha");
+        out.target = torch::empty_like(target_rgb);
+        a.target_rgb = target_rgb.data_ptr<float>(); a.target_alpha = target_alpha.data_ptr<uint8_t>(); a.target_out = out.target.data_ptr<float>();
+    }
+    LFS_DEVICE_GUARD(first);
+    check_rc(lfs_background_compose(&a, cur_stream()), "background_compose");
+    if (render && inplace) bump(out.shown);
+    return out;
+}
+
+torch::Tensor background_compose_bwd(const float bg[3], const torch::Tensor& v_shown, const torch::Tensor& v_alpha_in, bool inplace) {
+    TORCH_CHECK(v_shown.defined() && v_shown.dim() == 3, "background_compose_bwd: v_shown [3,H,W] is needed");
+    const int64_t H = v_shown.size(1), W = v_shown.size(2);
+    TORCH_CHECK(H > 0 && W > 0 && H <= int64_t(UINT32_MAX) && W <= int64_t(UINT32_MAX), "background_compose_bwd: image size out of range");
+    check_bg_plane(v_shown, 3, H, W, at::kFloat, "v_shown");
+    if (v_alpha_in.defined()) check_bg_plane(v_alpha_in, 1, H, W, at::kFloat, "v_alpha_in");
+    TORCH_CHECK(!inplace || v_alpha_in.defined(), "background_compose_bwd: inplace needs v_alpha_in");
+    torch::Tensor out = inplace ? v_alpha_in : torch::empty({1, H, W}, v_shown.options());
+    lfs_background_compose_bwd_args a = {};
+    a.height = (uint32_t)H; a.width = (uint32_t)W;
+    for (int i = 0; i < 3; ++i) a.bg[i] = bg[i];
+    a.v_shown = v_shown.data_ptr<float>();
+    a.v_alpha_in = v_alpha_in.defined() ? v_alpha_in.data_ptr<float>() : nullptr;
+    a.v_alpha = out.data_ptr<float>();
+    LFS_DEVICE_GUARD(v_shown);
+    check_rc(lfs_background_compose_bwd(&a, cur_stream()), "background_compose_bwd");
+    if (inplace) bump(out);
+    return out;
+}
+} // namespace lfs
+
 // ---------------------------------------------------------------------------------------------------------
 // lfs::GutTrainStep: the C++ training step (csrc/gut_step.hip) for a libtorch caller
 // ---------------------------------------------------------------------------------------------------------

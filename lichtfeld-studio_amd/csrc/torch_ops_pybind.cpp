@@ -75,6 +75,22 @@ PYBIND11_MODULE(_lfs_torch_ops, m) {
               return py::make_tuple(opt(r.means), opt(r.quats), opt(r.raw_scales), opt(r.shN));
           },
           py::arg("means"), py::arg("quats"), py::arg("raw_scales"), py::arg("shN"), py::arg("matrix"), py::arg("inplace") = false);
+    // lfs::background_compose / _bwd: None = an undefined tensor (the group is skipped); background: 3 numbers
+    m.def("background_compose",
+          [](std::vector<float> background, OptT image, OptT alpha, OptT target_rgb, OptT target_alpha, bool inplace) {
+              TORCH_CHECK(background.size() == 3, "background_compose: a colour (3 numbers) is needed");
+              const lfs::BackgroundComposed r = lfs::background_compose(background.data(), image.value_or(at::Tensor()), alpha.value_or(at::Tensor()),
+                                                                        target_rgb.value_or(at::Tensor()), target_alpha.value_or(at::Tensor()), inplace);
+              auto opt = [](const at::Tensor& t) -> py::object { return t.defined() ? py::cast(t) : py::none(); };
+              return py::make_tuple(opt(r.shown), opt(r.target));
+          },
+          py::arg("background"), py::arg("image"), py::arg("alpha"), py::arg("target_rgb") = py::none(), py::arg("target_alpha") = py::none(), py::arg("inplace") = false);
+    m.def("background_compose_bwd",
+          [](std::vector<float> background, at::Tensor v_shown, OptT v_alpha_in, bool inplace) {
+              TORCH_CHECK(background.size() == 3, "background_compose_bwd: a colour (3 numbers) is needed");
+              return lfs::background_compose_bwd(background.data(), v_shown, v_alpha_in.value_or(at::Tensor()), inplace);
+          },
+          py::arg("background"), py::arg("v_shown"), py::arg("v_alpha_in") = py::none(), py::arg("inplace") = false);
     m.def("fastgs_forward_wrapper",
           [](at::Tensor means, at::Tensor scales_raw, at::Tensor rotations_raw, at::Tensor opacities_raw, at::Tensor sh0, at::Tensor sh_rest, at::Tensor w2c,
              at::Tensor cam_position, int active_sh_bases, int width, int height, float fx, float fy, float cx, float cy, float near_plane, float far_plane) {

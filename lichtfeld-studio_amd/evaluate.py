@@ -50,7 +50,7 @@ class EvalMetrics:
 @torch.no_grad()
 def evaluate(model, cameras: List, images: List[torch.Tensor], iteration: int = 0, background: Optional[torch.Tensor] = None,
              rasterizer: str = "fastgs", masks: Optional[List] = None, antialiased: bool = False,
-             filter3d: Optional[torch.Tensor] = None) -> EvalMetrics:
+             filter3d: Optional[torch.Tensor] = None, alphas: Optional[List] = None) -> EvalMetrics:
     """cameras: rasterizer.Camera per validation view; images: the ground truth [3,H,W] in [0,1]. rasterizer="fastgs" is the reference's protocol
     (metrics.cpp:430 renders with fast_rasterize whatever was trained with); "gut" renders with the 3DGUT rasterizer instead - what a model trained with
     --gut was optimised for: 3DGUT has no screen-space dilation, the EWA renderer adds its 0.3-pixel low-pass to Gaussians the training shrank below a
@@ -59,7 +59,9 @@ def evaluate(model, cameras: List, images: List[torch.Tensor], iteration: int = 
     per-pixel form that a mask could weight without printing the mask's edge into the statistics.
     antialiased: the fastgs renders run in the antialiased mode (fastgs.FastGSSettings.antialiased) - for a model trained with GutTrainer(antialiasing=True).
     filter3d: the [N] variances of the 3D smoothing filter the model was trained with (GutTrainer.update_filter3d(); fastgs.FastGSSettings.filter3d): the renders are
-    the filtered ones. A model whose parameters were baked (filter3d.bake) is evaluated without it."""
+    the filtered ones. A model whose parameters were baked (filter3d.bake) is evaluated without it.
+    alphas (parallel to images; uint8 [H,W] planes of RGBA ground truth, loader.preload_alphas, or None entries): each such ground-truth image is composited over
+    `background` (a * gt + (1 - a) * bg, a = u8 / 255: ops.background_compose) before PSNR and SSIM - the render is composited over the same colour."""
     from .fastgs import fast_rasterize
     from .rasterizer import rasterize
     if rasterizer not in ("fastgs", "gut"):
@@ -74,9 +76,16 @@ def evaluate(model, cameras: List, images: List[torch.Tensor], iteration: int = 
     ps, ss = [], []
     if masks is not None and len(masks) != len(images):
         raise ValueError("masks must be parallel to images")
+    if alphas is not None and len(alphas) != len(images):
+        raise ValueError("alphas must be parallel to images")
+    bg_floats = tuple(float(v) for v in bg.detach().cpu().reshape(-1)) if alphas is not None and any(a is not None for a in alphas) else None
     for i, (cam, gt) in enumerate(zip(cameras, images)):
         img = torch.clamp(render(cam, model, bg).image, 0.0, 1.0)
-        ps.append(psnr(img, gt.to(dev), mask=masks[i] if masks is not None else None))
-        ss.append(ssim(img, gt.to(dev)))
+        gt = gt.to(dev)
+        if alphas is not None and alphas[i] is not None:
+            from .ops import background_compose
+            gt = background_compose(bg_floats, target_rgb=gt.contiguous(), target_alpha=alphas[i].to(dev).contiguous())[1]
+        ps.append(psnr(img, gt, mask=masks[i] if masks is not None else None))
+        ss.append(ssim(img, gt))
     n = max(len(ps), 1)
     return EvalMetrics(sum(ps) / n, sum(ss) / n, int(model.means.shape[0]), iteration, len(ps))

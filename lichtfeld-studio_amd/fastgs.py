@@ -254,8 +254,9 @@ def mse_loss_chw_fwd_bwd(render_chw: torch.Tensor, target_chw: torch.Tensor, wei
 def render_and_backward(settings: FastGSSettings, w2c: torch.Tensor, model: SplatModel, target_chw: torch.Tensor, weight: float, grads, loss_acc: torch.Tensor,
                         densification_info: Optional[torch.Tensor] = None, loss: str = "mse", lambda_dssim: float = 0.2, bilateral=None, image_idx: int = 0,
                         adam_shN: Optional[dict] = None, grad_w2c: Optional[torch.Tensor] = None, mask=None, mask_alpha_weight: float = 0.0,
-                        depth_target=None, depth_weight: float = 0.0, visibility_bits: Optional[torch.Tensor] = None, accumulate_visibility: bool = False):
-    """One training view without an autograd graph (black background; loss "mse" or the trainer's "l1_ssim", trainer.cpp:122-125):
+                        depth_target=None, depth_weight: float = 0.0, visibility_bits: Optional[torch.Tensor] = None, accumulate_visibility: bool = False,
+                        background=None, target_alpha: Optional[torch.Tensor] = None):
+    """One training view without an autograd graph (black background unless `background` says otherwise; loss "mse" or the trainer's "l1_ssim", trainer.cpp:122-125):
     forward, [bilateral-grid slice, trainer.cpp:662-664,] loss, backward; the gradients of (means, sh0, shN, raw_scales, raw_quats,
     raw_opacities) are WRITTEN into `grads` (param-group order); the bilateral grid's gradient is accumulated into its .grad;
     `grad_w2c` (optional out buffer, pose optimisation): the camera gradient is written into it (backward_wrapper).
@@ -264,7 +265,26 @@ def render_and_backward(settings: FastGSSettings, w2c: torch.Tensor, model: Spla
     depth_target (a losses.PreparedDepth; settings.depth "depth" | "invdepth" says what it holds): loss_acc += weight * depth_weight * the masked L1 between the
     accumulated depth map and the target (lfs_depth_l1_loss_fwd_bwd), and the backward is the depth one. None: everything as before.
     visibility_bits (int32 [ceil(N / 32)], visible-only Adam): bit i is written - with accumulate_visibility ORed - from the view's n_touched column right after
-    the forward (ops.fastgs_view_visibility): set exactly where the backward counts Gaussian i as visible. None: nothing is launched."""
+    the forward (ops.fastgs_view_visibility): set exactly where the backward counts Gaussian i as visible. None: nothing is launched.
+    background (three Python floats, passed to the kernels by value; None = black): the image the bilateral grid and the loss see is image + (1 - alpha) * bg
+    (ops.background_compose right after the forward and the visibility bits, trainer.cpp:656-664 - fast_rasterize's expression, the same bits), and after the loss
+    and the bilateral backward ops.background_compose_bwd turns dL/d(shown) into the alpha gradient of the backward (on top of segment mode's). dL/d(image) is
+    dL/d(shown) itself.
+    target_alpha (uint8 [H,W] on the device): the target the loss sees is a * target + (1 - a) * bg, a = u8 / 255 - composited over THIS step's background, black
+    included - written into a scratch tensor kept across steps, in the launch that composes the render (target_chw itself is never written).
+    With background None or (0, 0, 0) and target_alpha None nothing new is launched: the step is the one without the two arguments, bit for bit.
+    -> (image, alpha, n_instances): the rasterizer's own image, before the background."""
+    bg = None
+    if background is not None:
+        bg = tuple(float(v) for v in background)
+        if len(bg) != 3 or not all(v == v and abs(v) != float("inf") for v in bg):
+            raise LfsError(f"background must be three finite floats (got {background!r})")
+        if bg == (0.0, 0.0, 0.0):
+            bg = None
+    if target_alpha is not None:
+        if target_alpha.dtype != torch.uint8 or tuple(target_alpha.shape) != (settings.height, settings.width):
+            raise LfsError(f"target_alpha must be a uint8 [{settings.height},{settings.width}] tensor (got {target_alpha.dtype}, {tuple(target_alpha.shape)})")
+        target_alpha = target_alpha.contiguous()
     means, sh0, shN, raw_scales, raw_quats, raw_opac = [p.detach() for p in model.parameters()]
     g_means, g_sh0, g_shN, g_scales, g_quats, g_opac = grads
     with torch.no_grad():
@@ -278,7 +298,22 @@ def render_and_backward(settings: FastGSSettings, w2c: torch.Tensor, model: Spla
         if visibility_bits is not None:
             from .ops import fastgs_view_visibility
             fastgs_view_visibility(pws, means.shape[0], settings.width, settings.height, visibility_bits, accumulate_visibility)
-        shown = image if bilateral is None else bilateral.apply_fused(image, image_idx, chw=True)
+        composed = image
+        if bg is not None or target_alpha is not None:
+            from .ops import background_compose
+            t_out = None
+            if target_alpha is not None:
+                target_chw = target_chw.contiguous()
+                t_out = getattr(render_and_backward, "_target", None)
+                if t_out is None or t_out.shape != target_chw.shape or t_out.device != target_chw.device:
+                    t_out = render_and_backward._target = torch.empty_like(target_chw)
+            if bg is not None:   # out of place: `image` stays the rasterizer's (it is returned)
+                composed, t_out = background_compose(bg, image, alpha, None, target_chw if t_out is not None else None, target_alpha, t_out)
+            else:                # black: the render is its own composite, only the target is
+                _, t_out = background_compose((0.0, 0.0, 0.0), target_rgb=target_chw, target_alpha=target_alpha, target_out=t_out)
+            if t_out is not None:
+                target_chw = t_out
+        shown = composed if bilateral is None else bilateral.apply_fused(composed, image_idx, chw=True)
         v_alpha = None
         if mask is not None:
             from .losses import loss_fwd_bwd
@@ -295,7 +330,10 @@ def render_and_backward(settings: FastGSSettings, w2c: torch.Tensor, model: Spla
         else:
             raise ValueError(f"unknown loss {loss!r}")
         if bilateral is not None:
-            v_image = bilateral.apply_fused_backward(image, image_idx, v_image, chw=True)
+            v_image = bilateral.apply_fused_backward(composed, image_idx, v_image, chw=True)
+        if bg is not None:   # d(shown)/d(alpha) = -bg: into the alpha gradient of the backward, in place on segment mode's
+            from .ops import background_compose_bwd
+            v_alpha = background_compose_bwd(bg, v_image, v_alpha, v_alpha)
         if not hasattr(render_and_backward, "_zero") or render_and_backward._zero.shape != alpha.shape or render_and_backward._zero.device != alpha.device:
             render_and_backward._zero = torch.zeros_like(alpha)
         backward_wrapper(densification_info, v_image, render_and_backward._zero if v_alpha is None else v_alpha, image, alpha, means, raw_scales, raw_quats, sh0, shN, pws, iws, w2c, settings, n_inst,

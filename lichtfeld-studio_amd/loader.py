@@ -675,6 +675,30 @@ def preload_masks(ds: "CameraDataset", device="cuda:0", invert: bool = False, th
     return out
 
 
+def preload_alphas(ds: "CameraDataset", device="cuda:0") -> list:
+    """The alpha channels of the split's RGBA images, parallel to preload(): a uint8 [h,w] device plane at image_target_size per view whose file has 2 or 4
+    channels (get_image_info), None for the others - what GutTrainer.train_step(alphas=...) and evaluate(alphas=...) composite the target with.
+    The plane goes through prepare_mask(threshold=-1): the image's own sample positions, re-quantised to 8 bits, no threshold and no inversion; a view with an
+    undistortion map through undistort_mask, alpha 0 where the source does not cover the pixel. The file's alpha is straight (un-premultiplied) and is resampled
+    apart from the colour: when an image is downscaled, a pixel on the object's edge takes its colour from the unweighted mean of object and matte colour - a
+    fringe of the matte colour that premultiplied resampling would not leave. A known limit, like the plain resample's missing prefilter."""
+    from .losses import prepare_mask
+    out = []
+    for i in range(len(ds)):
+        cam = ds.cameras[ds.indices[i]]
+        if not os.path.isfile(cam.image_path) or get_image_info(cam.image_path)[2] not in (2, 4):
+            out.append(None)
+            continue
+        a = load_mask8(cam.image_path, (cam.image_path, True))
+        umap = ds.undistort_map(i)
+        if umap is not None:
+            out.append(undistort_mask(_upload_u8(a, device), umap, False, -1, device).mask_u8)
+            continue
+        ow, oh = image_target_size(a.shape[1], a.shape[0], ds.resize_factor, ds.max_width)
+        out.append(prepare_mask(_upload_u8(a, device), ow, oh, False, -1).mask_u8)
+    return out
+
+
 def preload_depths(ds: "CameraDataset", device="cuda:0", kind: str = "invdepth", params: Optional[dict] = None, masks: Optional[list] = None) -> list:
     """The depth targets of the split, parallel to preload(): a losses.PreparedDepth at image_target_size per view that has a depth file (and, with a params
     table, a reliable scale), None for the others. The file holds what `kind` names ("invdepth": the Inria convention; "depth"); params = load_depth_params(...)

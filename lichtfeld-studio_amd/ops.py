@@ -451,3 +451,66 @@ def fastgs_view_contribution(primitive_workspace: Tensor, instance_workspace: Te
     view.primitive_workspace, view.primitive_workspace_bytes = primitive_workspace.data_ptr(), primitive_workspace.numel()
     check(load_library().lfs_fastgs_view_contribution(C.byref(view), C.c_int64(int(n_instances)), ptr(instance_workspace), C.c_size_t(instance_workspace.numel()), ptr(stats),
                                                       stream()), "fastgs_view_contribution")
+
+
+# -----------------------------------------------------------------------------------------
+# background colour on the EWA route (extension; csrc/background.hip): the compose stage, its alpha backward and the RGBA target
+# -----------------------------------------------------------------------------------------
+background_launches = {"compose": 0, "compose_bwd": 0}   # how often each entry was called (tests: the default step calls neither)
+
+
+def _bg_triple(background) -> Tuple[float, float, float]:
+    bg = tuple(float(v) for v in background)
+    if len(bg) != 3:
+        raise LfsError(f"background must be three floats (got {background!r})")
+    return bg
+
+
+def _bg_plane(t: Tensor, channels: int, H: int, W: int, dtype, what: str) -> None:
+    if t.dtype != dtype or t.numel() != channels * H * W or tuple(t.shape[-2:]) != (H, W):
+        raise LfsError(f"background compose: {what} must be a {dtype} [{channels},{H},{W}] tensor (got {t.dtype}, {tuple(t.shape)})")
+
+
+def background_compose(background, image: Optional[Tensor] = None, alpha: Optional[Tensor] = None, shown: Optional[Tensor] = None,
+                       target_rgb: Optional[Tensor] = None, target_alpha: Optional[Tensor] = None, target_out: Optional[Tensor] = None):
+    """ONE launch, up to two jobs (lfs_background_compose) -> (shown, target_out); `background`: three Python floats, passed by value.
+    render group (image [3,H,W], alpha [1,H,W] or [H,W]): shown = image + (1 - alpha) * bg - torch's expression in fastgs.fast_rasterize, the same bits. shown: None
+    allocates, `image` itself composes in place. target group (target_rgb [3,H,W] float32, target_alpha [H,W] uint8): target_out = a * t + (1 - a) * bg with
+    a = u8 / 255; target_out: None allocates; target_rgb itself is refused (the resident image is reused every epoch). A group left out is None throughout."""
+    bg = _bg_triple(background)
+    render, target = image is not None, target_rgb is not None
+    if not render and not target:
+        raise LfsError("background_compose: neither a render group (image, alpha) nor a target group (target_rgb, target_alpha) was given")
+    if render != (alpha is not None) or target != (target_alpha is not None) or (shown is not None and not render) or (target_out is not None and not target):
+        raise LfsError("background_compose: a group is given as a whole (image + alpha [+ shown]; target_rgb + target_alpha [+ target_out])")
+    H, W = (image if render else target_rgb).shape[-2:]
+    H, W = int(H), int(W)
+    if render:
+        shown = torch.empty_like(image) if shown is None else shown
+        _bg_plane(image, 3, H, W, torch.float32, "image"), _bg_plane(alpha, 1, H, W, torch.float32, "alpha"), _bg_plane(shown, 3, H, W, torch.float32, "shown")
+    if target:
+        target_out = torch.empty_like(target_rgb) if target_out is None else target_out
+        _bg_plane(target_rgb, 3, H, W, torch.float32, "target_rgb"), _bg_plane(target_alpha, 1, H, W, torch.uint8, "target_alpha")
+        _bg_plane(target_out, 3, H, W, torch.float32, "target_out")
+    require_gpu(image, alpha, shown, target_rgb, target_alpha, target_out)
+    args = capi.BackgroundComposeArgs(H, W, (C.c_float * 3)(*bg), ptr(image), ptr(alpha), ptr(shown), ptr(target_rgb), ptr(target_alpha), ptr(target_out))
+    check(load_library().lfs_background_compose(C.byref(args), stream()), "background_compose")
+    background_launches["compose"] += 1
+    return shown, target_out
+
+
+def background_compose_bwd(background, v_shown: Tensor, v_alpha_in: Optional[Tensor] = None, v_alpha: Optional[Tensor] = None) -> Tensor:
+    """-> v_alpha [1,H,W] = (v_alpha_in or 0) - sum_c bg_c v_shown_c (lfs_background_compose_bwd): the alpha gradient of the compose stage added to the one the loss
+    already has (segment mode). v_alpha: None allocates; v_alpha_in itself is allowed (in place). dL/d(image) is v_shown: hand the same tensor on."""
+    bg = _bg_triple(background)
+    H, W = int(v_shown.shape[-2]), int(v_shown.shape[-1])
+    if v_alpha is None:
+        v_alpha = torch.empty((1, H, W), dtype=torch.float32, device=v_shown.device)
+    _bg_plane(v_shown, 3, H, W, torch.float32, "v_shown"), _bg_plane(v_alpha, 1, H, W, torch.float32, "v_alpha")
+    if v_alpha_in is not None:
+        _bg_plane(v_alpha_in, 1, H, W, torch.float32, "v_alpha_in")
+    require_gpu(v_shown, v_alpha_in, v_alpha)
+    args = capi.BackgroundComposeBwdArgs(H, W, (C.c_float * 3)(*bg), ptr(v_shown), ptr(v_alpha_in), ptr(v_alpha))
+    check(load_library().lfs_background_compose_bwd(C.byref(args), stream()), "background_compose_bwd")
+    background_launches["compose_bwd"] += 1
+    return v_alpha

@@ -92,7 +92,8 @@ class GutTrainer:
                  enable_sparsity: bool = False, sparsify_steps: int = 15000, init_rho: float = 0.0005, prune_ratio: float = 0.6, sparsity_update_every: int = 50,
                  mask_mode: str = "none", mask_alpha_weight: float = 1.0, antialiasing: bool = False, depth_loss: str = "none", depth_weight=(1.0, 0.01),
                  filter3d: bool = False, filter3d_every: int = 100, filter3d_variance: float = 0.2, absgrad: bool = False, visible_adam: bool = False,
-                 contribution_prune_at=(), contribution_threshold: float = 0.01):
+                 contribution_prune_at=(), contribution_threshold: float = 0.01, background=(0.0, 0.0, 0.0), background_mode: str = "constant",
+                 background_jitter: bool = True):
         """strategy: None (fixed set of Gaussians: the benchmark), "mcmc" (strategies.MCMC: relocation + growth + SGLD noise, with
         the scale / opacity regularisers of trainer.cpp:132-158) or "default" (ADC; needs densification_info, see strategies.py).
         `seed` seeds the strategy's generator: the same on every rank, so replicas densify identically.
@@ -134,7 +135,24 @@ class GutTrainer:
         maximum blending weight over all training rays is below contribution_threshold (RadSplat's 0.01) is removed - parameters, both Adam moments and the
         strategy's accumulators follow as in every other removal; the 3D filter is recomputed and the visibility words are rebuilt. The statistic follows the image:
         an instance that only terminates pixels counts as 0, so a prune is a training-time operation that the remaining iterations heal. fastgs rasterizer, one
-        rank, not with strategy="mcmc" (it holds the count), sh_sharded or one_call. Empty (default): the trainer plans and computes what it always did."""
+        rank, not with strategy="mcmc" (it holds the count), sh_sharded or one_call. Empty (default): the trainer plans and computes what it always did.
+        background, background_mode (background.py): the colour every step composites its render - and, with train_step(alphas=...), its RGBA targets -
+        over. background: "black" | "white" | a triple in [0,1] (the official trainer's --white_background). background_mode "constant": that colour; "random": one
+        colour per step, shared by the step's views, from torch.rand(3) on a CPU generator seeded with `seed` (the same on every rank and in every rerun, no device
+        read; the official trainer's random_background); "modulated": the reference's bg_modulation - a sine-modulated colour mixed into `background` for the first
+        three quarters of the run (background_jitter: its +-0.03 jitter, from the same CPU generator). The fastgs route hands the three floats to its compose kernels
+        by value (fastgs.render_and_backward(background=)); on the 3DGUT route, whose kernels read the colour from device memory, it is copied into self.bg before
+        the step. Every step form of both routes takes it. `last_background` is the colour of the last step. With the defaults nothing new is launched, self.bg is
+        never written and every plan is what it was."""
+        from . import background as lfs_background
+        self.background = lfs_background.parse_background(background)
+        if background_mode not in lfs_background.MODES:
+            raise ValueError(f"Invalid background mode: {background_mode} (one of {lfs_background.MODES})")
+        self.background_mode, self.background_jitter = background_mode, bool(background_jitter)
+        self._bg_generator = torch.Generator().manual_seed(int(seed))   # CPU: every rank draws the same colours, nothing is read back
+        self.last_background = self.background
+        self._step_bg = None            # the colour of the step in flight when it is not black (None: the step composes nothing)
+        self._alphas = None             # the step's RGBA planes (fastgs route; the other routes composite their targets before the step)
         contribution_prune_at = tuple(int(i) for i in contribution_prune_at)
         if contribution_prune_at:
             if rasterizer == "gut":
@@ -279,6 +297,8 @@ class GutTrainer:
             self.scheduler = ExponentialLR(self.optimizer, gamma=0.01 ** (1.0 / iterations), param_group_index=0)
         self.sh_degree_interval = 1000     # without a strategy the trainer keeps the SH schedule itself (strategies do it in post_backward)
         self.bg = torch.zeros(3, device=device)
+        if self.background != (0.0, 0.0, 0.0):   # a constant colour is written here, once; the per-step modes write it before every step (_set_step_background)
+            self.bg = torch.tensor(self.background, dtype=torch.float32, device=device)
         # appearance model of BASELINE config 5 (trainer.cpp:66-99: Adam(lr, eps 1e-15) + warm-up exponential schedule), fastgs path only
         self.bilateral, self.tv_loss_weight = None, tv_loss_weight
         if use_bilateral_grid:
@@ -463,7 +483,8 @@ class GutTrainer:
         """The same step through the fastgs (EWA) rasterizer - the reference's default training path (trainer.cpp:656-760): fused
         preprocess -> blend -> [bilateral grid] -> loss ("mse" | "l1_ssim") -> blend backward -> preprocess backward (raw-parameter
         gradients straight into the flat bucket) -> all-reduce -> strategy.post_backward (ADC fed by the rasterizer's
-        densification_info, or MCMC) -> fused Adam. Black background."""
+        densification_info, or MCMC) -> fused Adam. The step's background colour (background.py) and RGBA planes go to the compose kernels by value / pointer;
+        with the defaults (black, no alphas) nothing of that is launched."""
         from .fastgs import render_and_backward as fg_step
         self.update_filter3d()
         if self.bucket is None:
@@ -504,7 +525,7 @@ class GutTrainer:
             _, _, self.last_n_isects = fg_step(st, w2c, self.model, targets[k % len(targets)],
                                                1.0 / total_views, dst, self.loss_acc, densification_info=dens, loss=self.loss_kind,
                                                lambda_dssim=self.lambda_dssim, bilateral=self.bilateral, image_idx=v, adam_shN=inline, grad_w2c=g_w2c,
-                                               **self._fastgs_mask_args(k), **depth_args,
+                                               **self._fastgs_mask_args(k), **depth_args, **self._fastgs_background_args(k),
                                                **({"visibility_bits": vis, "accumulate_visibility": k > 0} if vis is not None else {}))
             if w2c_adj is not None:
                 w2c_adj.backward(g_w2c)   # accumulates into the module's parameters over the views of the step
@@ -564,6 +585,44 @@ class GutTrainer:
         if m is None:
             return {}
         return {"mask": m, "mask_alpha_weight": self.mask_alpha_weight if self.mask_mode == "segment" else 0.0}
+
+    def _fastgs_background_args(self, k: int) -> dict:
+        """the background colour and the RGBA plane of the step's k-th view for fastgs.render_and_backward - {} on a black step without alphas: the parent's call"""
+        out = {}
+        if self._step_bg is not None:
+            out["background"] = self._step_bg
+        a = None if self._alphas is None else self._alphas[k % len(self._alphas)]
+        if a is not None:
+            out["target_alpha"] = a
+        return out
+
+    def background_for_step(self, iteration: int):
+        """The colour of (1-based) `iteration` -> three Python floats (background.background_for_step with this trainer's base colour, mode and generator). The random
+        and the jittered modes DRAW from the generator: train_step calls this once per step."""
+        from .background import background_for_step
+        return background_for_step(iteration, self.base_iterations, self.background, self.background_mode, self._bg_generator, self.background_jitter)
+
+    def _set_step_background(self) -> None:
+        """Before a step: its colour -> last_background, _step_bg (fastgs route: by value) and, on the other routes, self.bg. The copy is stream-ordered from a FRESH
+        host tensor: a pinned buffer reused across steps with non_blocking=True would be read when the copy executes, not when it is enqueued - by then the host may
+        hold the next step's colour. A constant colour was written at construction: nothing is copied, and with the defaults nothing ever is."""
+        if self.background_mode == "constant":
+            bg = self.background
+        else:
+            bg = self.background_for_step(self.iteration + 1)
+            if self.rasterizer != "fastgs":
+                self.bg.copy_(torch.tensor(bg, dtype=torch.float32))
+        self.last_background = bg
+        self._step_bg = None if bg == (0.0, 0.0, 0.0) else bg
+
+    def _composite_targets(self, targets, alphas):
+        """RGBA targets on the routes other than fastgs: each target with a plane is composited over the step's colour by a target-only call of the compose entry
+        before the step form sees it (a new tensor: the resident image is reused every epoch)"""
+        from .ops import background_compose
+        out = []
+        for t, a in zip(targets, alphas):
+            out.append(t if a is None else background_compose(self.last_background, target_rgb=t.contiguous(), target_alpha=a)[1])
+        return out
 
     def _bilateral_step(self) -> None:
         """trainer.cpp:699-705, :758-761: TV regulariser (1/world of it per rank), sum of the ranks' grid gradients, Adam + warm-up schedule."""
@@ -626,8 +685,12 @@ class GutTrainer:
         return Camera(sc.viewmats[view:view + 1].contiguous(), sc.Ks[view:view + 1].contiguous(), sc.width, sc.height)
 
     def train_step(self, targets: List[torch.Tensor], views: Optional[List[int]] = None, views_all: Optional[List[List[int]]] = None,
-                   next_views: Optional[List[int]] = None, masks: Optional[List] = None, depths: Optional[List] = None) -> float:
-        """depths: a list parallel to `targets` of losses.PreparedDepth (at the training resolution; what depth_loss names: inverse depth or depth) or None (that
+                   next_views: Optional[List[int]] = None, masks: Optional[List] = None, depths: Optional[List] = None, alphas: Optional[List] = None) -> float:
+        """alphas: a list parallel to `targets` of uint8 [H,W] device planes (the alpha channel of an RGBA target, loader.preload_alphas) or None (that view is opaque):
+        the target the loss sees is a * target + (1 - a) * background, a = u8 / 255, over THIS step's colour, black included. fastgs route: composited inside the step
+        (fastgs.render_and_backward(target_alpha=)); every other route: by a target-only call of the compose entry before the step form sees the target, so every
+        form takes it. A step whose alphas are all None is the step without the argument.
+        depths: a list parallel to `targets` of losses.PreparedDepth (at the training resolution; what depth_loss names: inverse depth or depth) or None (that
         view has no depth target); needs depth_loss "invdepth" or "depth". A step whose depths are all None is the step without the argument.
         masks: a list parallel to `targets` of losses.PreparedMask (at the training resolution) or None (that view is unmasked); needs mask_mode "ignore" or
         "segment". A step whose masks are all None is the unmasked step.
@@ -646,6 +709,19 @@ class GutTrainer:
             if len(masks) != len(targets):
                 raise ValueError("masks must be parallel to targets")
             self._masks = list(masks)
+        self._alphas = None
+        if alphas is not None and any(a is not None for a in alphas):
+            if len(alphas) != len(targets):
+                raise ValueError("alphas must be parallel to targets")
+            sc = self.scene
+            for a in alphas:
+                if a is not None and (not torch.is_tensor(a) or a.dtype != torch.uint8 or tuple(a.shape) != (int(sc.height), int(sc.width))):
+                    raise ValueError(f"train_step(alphas=...): every plane is a uint8 [{int(sc.height)},{int(sc.width)}] tensor or None (got "
+                                     f"{(a.dtype, tuple(a.shape)) if torch.is_tensor(a) else type(a).__name__})")
+            self._alphas = [None if a is None else a.contiguous() for a in alphas]
+        self._set_step_background()
+        if self._alphas is not None and self.rasterizer != "fastgs":
+            targets, self._alphas = self._composite_targets(targets, self._alphas), None
         self._depths = None
         if depths is not None and any(d is not None for d in depths):
             if self.depth_loss == "none":
@@ -658,6 +734,7 @@ class GutTrainer:
         finally:
             self._masks = None
             self._depths = None
+            self._alphas = None
         # the SH schedule, AFTER the backward / optimizer step of the iteration, where the strategies keep it (post_backward: mcmc.cpp:366-368,
         # default_strategy.cpp) - iteration 1000, 2000, ... still renders with the old degree, as the reference does; without a strategy the trainer does it
         if (self.strategy is None and self.iteration % self.sh_degree_interval == 0 and self.model.active_sh_degree < self.model.max_sh_degree

@@ -79,6 +79,13 @@ def build_parser() -> argparse.ArgumentParser:
                     "distortion parameters are ignored, as if the images had gone through COLMAP's image_undistorter)")
     ap.add_argument("--undistort-alpha", type=float, default=0.0, help="with --undistort: 0 = zoom in until no output pixel is blank, 1 = zoom out until no source pixel is lost "
                     "(OpenCV's getOptimalNewCameraMatrix alpha); above 0 the blank pixels leave the loss (--mask-mode none becomes ignore)")
+    ap.add_argument("--background", type=float, nargs=3, default=None, metavar=("R", "G", "B"), help="the colour training renders (and RGBA targets) are composited over, in [0,1] (default black)")
+    ap.add_argument("--white-background", action="store_true", help="--background 1 1 1 (the official trainer's --white_background)")
+    ap.add_argument("--random-background", action="store_true", help="one random colour per step (seeded, CPU generator; the official trainer's random_background): with "
+                    "--alpha-targets, transparent becomes the only consistent explanation of a pixel whose alpha is 0")
+    ap.add_argument("--bg-modulation", action="store_true", help="the reference's bg_modulation: a sine-modulated colour mixed into the background for the first three quarters of the run")
+    ap.add_argument("--alpha-targets", action="store_true", help="images with an alpha channel (2 or 4 channels) are composited over the step's background colour "
+                    "before the loss, and over the evaluation background by --eval")
     return ap
 
 
@@ -121,6 +128,14 @@ def check_args(args) -> None:
     if args.undistort and args.undistort_alpha > 0 and args.mask_mode == "none":
         args.mask_mode = "ignore"
         print("undistort: --undistort-alpha > 0 leaves blank pixels in the targets; --mask-mode none becomes ignore (they leave the loss)", file=sys.stderr)
+    if args.random_background and args.bg_modulation:
+        raise SystemExit("--random-background and --bg-modulation both choose the colour of every step: pass one of them.")
+    if args.white_background and args.background is not None:
+        raise SystemExit("--white-background is --background 1 1 1: pass one of them.")
+    if args.white_background:
+        args.background = [1.0, 1.0, 1.0]
+    if args.background is not None and not all(v == v and 0.0 <= v <= 1.0 for v in args.background):
+        raise SystemExit("--background takes three numbers in [0, 1]")
     if args.pose_optimization != "none" and args.eval:   # trainer.cpp:367-370
         raise SystemExit("Evaluating with pose optimization is not supported yet. Please disable pose optimization or evaluation.")
 
@@ -171,6 +186,11 @@ def main():
         depths = loader.preload_depths(ds, dev, args.depth_loss, loader.load_depth_params(depth_params_path(args)), masks)
         if not any(d is not None for d in depths):
             raise SystemExit(f"--depth-loss {args.depth_loss}: no view has a usable depth target under {os.path.join(args.data_path, args.depths_folder)}")
+    alphas = loader.preload_alphas(ds, dev) if args.alpha_targets else None
+    if alphas is not None and not any(a is not None for a in alphas):
+        raise SystemExit("--alpha-targets: no image of the split has an alpha channel")
+    background = tuple(args.background) if args.background is not None else (0.0, 0.0, 0.0)
+    background_mode = "random" if args.random_background else "modulated" if args.bg_modulation else "constant"
     targets = loader.preload(ds, dev, workers=os.cpu_count() or 8)          # resident in HBM: 288 GB hold a Mip-NeRF360 scene at full resolution
     t_load = time.time() - t0
     rast = "gut" if args.gut else "fastgs"
@@ -182,7 +202,8 @@ def main():
                     mask_mode=args.mask_mode, mask_alpha_weight=args.mask_alpha_weight, antialiasing=args.antialiasing,
                     depth_loss=args.depth_loss, depth_weight=(args.depth_weight_init, args.depth_weight_final),
                     filter3d=args.filter3d, filter3d_every=args.filter3d_every, absgrad=args.absgrad, visible_adam=args.visible_adam,
-                    contribution_prune_at=tuple(args.contribution_prune_at), contribution_threshold=args.contribution_threshold)
+                    contribution_prune_at=tuple(args.contribution_prune_at), contribution_threshold=args.contribution_threshold,
+                    background=background, background_mode=background_mode)
     total = tr.total_iterations                                             # --iterations, plus the sparsification phase
 
     def export():
@@ -220,7 +241,8 @@ def main():
         if not order:
             order = torch.randperm(len(ds), generator=g).tolist()          # infinite random sampler, one view per step
         v = order.pop()
-        tr.train_step([targets[v]], views=[v], masks=None if masks is None else [masks[v]], depths=None if depths is None else [depths[v]])
+        tr.train_step([targets[v]], views=[v], masks=None if masks is None else [masks[v]], depths=None if depths is None else [depths[v]],
+                      alphas=None if alphas is None else [alphas[v]])
         if args.enable_sparsity and it + 1 == args.iterations:              # the model of the base run, before sparsification touches it
             loader.save_ply(export(), os.path.join(args.output_path, f"splat_{args.iterations}.ply"))
         if val_set is not None and (it + 1) % args.eval_every == 0:
@@ -256,6 +278,8 @@ def main():
     if args.undistort:
         zs = [m.z for m in maps if m is not None]
         out.update(undistort_alpha=args.undistort_alpha, undistorted_views=len(zs), undistort_z=[round(min(zs), 5), round(max(zs), 5)] if zs else None)
+    if background_mode != "constant" or background != (0.0, 0.0, 0.0) or alphas is not None:
+        out.update(background=list(background), background_mode=background_mode, alpha_views=None if alphas is None else sum(a is not None for a in alphas))
     if depths is not None:
         out.update(depth_loss=args.depth_loss, depth_views=sum(d is not None for d in depths), depth_weight=[args.depth_weight_init, args.depth_weight_final])
     if args.enable_sparsity:
@@ -271,7 +295,10 @@ def main():
             h, w = img.shape[1:]
             cameras.append(Camera(torch.from_numpy(loader.world_to_view(cam))[None].to(dev), torch.from_numpy(val_K(val, k, w, h))[None].to(dev), w, h))
             images.append(img)
-        m = evaluate.evaluate(tr.model, cameras, images, total, masks=val_masks, antialiased=args.antialiasing, filter3d=tr.update_filter3d(force=True))
+        val_alphas = loader.preload_alphas(val, dev) if args.alpha_targets else None
+        eval_bg = torch.tensor(background, dtype=torch.float32, device=dev)   # (the base colour: the per-step modes end on it)
+        m = evaluate.evaluate(tr.model, cameras, images, total, background=eval_bg, masks=val_masks, antialiased=args.antialiasing,
+                              filter3d=tr.update_filter3d(force=True), alphas=val_alphas)
         out.update(psnr=round(m.psnr, 4), ssim=round(m.ssim, 5), val_images=m.n_images)
         if args.depth_loss != "none":   # the held-out renders and, beside each, its expected depth map (D / alpha; grey, scaled to the view's own range)
             from lichtfeld_studio_amd import fastgs
@@ -290,7 +317,7 @@ def main():
                 loader.write_png(os.path.join(rdir, f"val_{k:04d}_depth.png"), grey[..., None].repeat(3, axis=2))
             out["renders"] = rdir
         if args.gut:   # the reference's protocol above renders with the EWA rasterizer; this is the renderer the model was trained with
-            mg = evaluate.evaluate(tr.model, cameras, images, total, rasterizer="gut", masks=val_masks)
+            mg = evaluate.evaluate(tr.model, cameras, images, total, background=eval_bg, rasterizer="gut", masks=val_masks, alphas=val_alphas)
             out.update(psnr_gut=round(mg.psnr, 4), ssim_gut=round(mg.ssim, 5))
     if curve:
         out["psnr_curve"] = curve
